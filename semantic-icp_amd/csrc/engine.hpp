@@ -358,7 +358,6 @@ struct TickSet {
   bool static_ranges = false;  // the next ticks' large accumulate launches keep equal chunk ranges (a stream while scans are being uploaded)
   std::vector<int> tick_act;  // the pairs whose arguments d_batch currently holds
   bool tick_valid = false;
-  unsigned epoch_host = 0;    // mirror of d_bhdr->epoch_base: tick_prepare_kernel adds kMaxBatchLen per tick, and so does the host
 };
 
 }  // namespace host
@@ -406,7 +405,6 @@ struct sicp_context {
   // state per pair, pinned mirrors, and the captured [accumulate_batch, lm_step_batch] x lm_batch graph
   TickSet ts[2];  // two sets: the halves of a batch alternate, one's tick runs while the host turns the other around
   DevBuf<sicp::LmState> d_bstates;
-  DevBuf<sicp::EvalIn> d_ein;         // [2 per pair]: what an evaluation reads of its pair when the accumulate launch steps the machine itself
   DevBuf<unsigned> d_solo_sync;       // the last pair still iterating: hand-off words of the persistent solve (solve_one_kernel)
   unsigned solo_tag = 0;              // its tags so far (a launch uses solo_tag + 1 ...: the words are never zeroed in between)
   int solo_seq = 0, solo_pair = 0;    // launch counter (the state's pad_ word echoes it at a regular end) and the pair's state slot
@@ -572,7 +570,7 @@ bool weights_from_histograms(const sicp_params& P, int K);
 int run_weights(sicp_context* h, const double* qt);
 int run_correspondences(sicp_context* h, const double* qt, int K, bool weights);
 void fill_acc(sicp_context* h, sicp::AccArgs& a);
-extern const int kMaxActivePairs;  // pairs one launch evaluates (12 bytes of LDS each in the accumulate kernel)
+constexpr int kMaxActivePairs = 256;  // pairs one launch evaluates (12 bytes of LDS each in the accumulate kernel)
 int eval28(sicp_context* h, const double* qt, double* out28);
 // ---- pieces of align() shared by the single-pair and the lock-step batch drivers ---------------
 struct OuterState {
@@ -594,11 +592,10 @@ struct SolveResult {
   double cost = 0;
 };
 
-hipError_t create_side_stream(hipStream_t* st);  // the stream of a batch's / a stream's searches and feature kernels (SICP_SIDE_PRIORITY: A/B aid)
+hipError_t create_side_stream(hipStream_t* st);  // the stream of a batch's / a stream's searches and feature kernels
 bool solo_allowed(sicp_context* h);
 bool general_covariances(const sicp_context* h);  // either cloud carries caller covariances of general form
 int align_host_loop(sicp_context* h, const double* init_qt, double* out_qt, int32_t* outer_iters, sicp_stats* stats);
-bool lm_step_in_launch();
 int run_solve(sicp_context* h, const double* init_qt, double* out_qt, SolveResult* res);
 bool same_solver(const sicp_params& a, const sicp_params& b);
 int tickset_reserve(sicp_context* h, TickSet& S, int n);

@@ -346,141 +346,16 @@ __global__ __launch_bounds__(256) void nn_merge_kernel(MergeArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
-// exact kNN through the Hilbert-ordered 4-ary box tree (bvh.hpp): one query per lane, seed leaf
-// for a first bound, then a stackless fixed-order depth-first walk pruned by the float32 box
-// distance.  Result sets are order independent (keys), so the output equals brute force bit for
-// bit.
+// exact kNN through the Hilbert-ordered 4-ary box tree (bvh.hpp): seed leaf for a first bound, then
+// a stackless fixed-order depth-first walk pruned by the float32 box distance.  Result sets are
+// order independent (keys), so the output equals brute force bit for bit.  (The walk with one query
+// per lane is gone: the quad variant below says what it measured.)
 // ------------------------------------------------------------------------------------------
-template <int K>
-__device__ __forceinline__ void scan_leaf(const float4* __restrict__ pts, float px, float py, float pz, u64 (&bk)[K], float& wd) {
-  float4 t[kLeaf];
-#pragma unroll
-  for (int p = 0; p < kLeaf; ++p) t[p] = pts[p];  // padded with (+inf, +inf, +inf, -1): no bounds test
-#pragma unroll
-  for (int p = 0; p < kLeaf; ++p) consider<K>(bk, wd, l2_simple(px, py, pz, t[p].x, t[p].y, t[p].z), __float_as_uint(t[p].w));
-}
-
 __device__ __forceinline__ float box_lb(const float4 lo, const float4 hi, float px, float py, float pz) {
   const float ex = fmaxf(fmaxf(lo.x - px, px - hi.x), 0.f);
   const float ey = fmaxf(fmaxf(lo.y - py, py - hi.y), 0.f);
   const float ez = fmaxf(fmaxf(lo.z - pz, pz - hi.z), 0.f);
   return (ex * ex + ey * ey) + ez * ez;  // lower bound of l2_simple over the box (monotone rounding)
-}
-
-// 4-bit mask of the children of node (level, parent) whose box can still hold a neighbour
-__device__ __forceinline__ unsigned child_mask(const float4* __restrict__ blo, const float4* __restrict__ bhi, int child_off,
-                                               int child_cnt, int parent, float px, float py, float pz, float wd) {
-  const int c0 = parent * kFan;
-  unsigned m = 0;
-  float4 lo[kFan], hi[kFan];
-#pragma unroll
-  for (int c = 0; c < kFan; ++c) {  // 8 independent loads; indices clamped, validity applied below
-    const int node = child_off + min(c0 + c, child_cnt - 1);
-    lo[c] = blo[node];
-    hi[c] = bhi[node];
-  }
-#pragma unroll
-  for (int c = 0; c < kFan; ++c) {
-    const float lb = box_lb(lo[c], hi[c], px, py, pz);
-    // lb == wd may still hide an equal distance with a lower caller index: keep it
-    if (c0 + c < child_cnt && !(lb > wd)) m |= 1u << c;
-  }
-  return m;
-}
-
-template <int K>
-__global__ __launch_bounds__(64) void bvh_knn_kernel(KnnArgs a) {
-  __shared__ int s_off[kMaxLevels], s_cnt[kMaxLevels];
-  if (threadIdx.x < kMaxLevels) { s_off[threadIdx.x] = a.tree.lv.off[threadIdx.x]; s_cnt[threadIdx.x] = a.tree.lv.cnt[threadIdx.x]; }
-  __syncthreads();
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= a.q_count) return;
-  float px, py, pz;
-  load_query(a.qx, a.qy, a.qz, a.q_begin + q, a.do_xform, a.M, px, py, pz);
-  u64 bk[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) bk[k] = KEY_EMPTY;
-  float wd = key_dist(KEY_EMPTY);
-  const float4* __restrict__ pts = a.tree.pts4 + a.tree.pt_begin;
-  const float4* __restrict__ blo = a.tree.box_lo + a.tree.node_begin;
-  const float4* __restrict__ bhi = a.tree.box_hi + a.tree.node_begin;
-  const int top = a.tree.lv.n_levels - 1;
-  const int n_leaf = s_cnt[0];
-  int dbg_nodes = 0, dbg_leaves = 0;
-
-  // --- seed: a level-1 node (<= 4 leaves, 64 points) next to the query gives the first bound:
-  // the query's own node for the covariance self-query, the node of its curve index otherwise.
-  int seed = 0;  // index at level min(1, top)
-  if (top >= 1) {
-    if (a.self) {
-      seed = (q / kLeaf) / kFan;
-    } else {
-      // locate the query's curve index among the leaves' first indices (last leaf with code <= qc)
-      const u64 qc = curve_code(px, py, pz, a.tree.lo[0], a.tree.lo[1], a.tree.lo[2], a.tree.scale);
-      const u64* __restrict__ codes = a.tree.leaf_code + a.tree.code_begin;
-      int lo_i = 0, hi_i = n_leaf - 1;
-      while (lo_i < hi_i) {
-        const int mid = (lo_i + hi_i + 1) >> 1;
-        if (codes[mid] <= qc) lo_i = mid; else hi_i = mid - 1;
-      }
-      seed = lo_i / kFan;
-    }
-    const int l0 = seed * kFan, l1 = min(l0 + kFan, n_leaf);
-    for (int l = l0; l < l1; ++l) { scan_leaf<K>(pts + (size_t)l * kLeaf, px, py, pz, bk, wd); ++dbg_leaves; }
-  } else {
-    scan_leaf<K>(pts, px, py, pz, bk, wd);
-  }
-
-  // --- depth-first walk of everything else.  State: the level L whose nodes are being iterated,
-  // the index `base` of the first sibling of the current group at L, and one 4-bit mask per level
-  // of the siblings still to visit.  "while-while": each lane walks boxes until it holds a leaf,
-  // then the wave scans leaves together (the scan is the expensive, divergence-sensitive part).
-  if (top >= 2) {
-    unsigned masks = 0;  // 4 bits per level, levels 0..top-1 (top <= 13 needs two words)
-    unsigned masks_hi = 0;
-    auto get = [&](int L) -> unsigned { return L < 8 ? (masks >> (4 * L)) & 15u : (masks_hi >> (4 * (L - 8))) & 15u; };
-    auto put = [&](int L, unsigned m) {
-      if (L < 8) masks = (masks & ~(15u << (4 * L))) | (m << (4 * L));
-      else masks_hi = (masks_hi & ~(15u << (4 * (L - 8)))) | (m << (4 * (L - 8)));
-    };
-    int L = top - 1, base = 0;
-    put(L, child_mask(blo, bhi, s_off[L], s_cnt[L], 0, px, py, pz, wd));
-    ++dbg_nodes;
-    bool done = false;
-    while (!done) {
-      int leaf = -1;
-      while (leaf < 0 && !done) {
-        const unsigned m = get(L);
-        if (m == 0) {  // this sibling group is exhausted: back to the parent's group
-          if (L == top - 1) { done = true; break; }
-          ++L;
-          base = (base / kFan) & ~(kFan - 1);
-          continue;
-        }
-        const int c = __ffs(m) - 1;
-        put(L, m & (m - 1));
-        const int node = base + c;
-        if (L == 1 && node == seed) continue;  // already scanned as the seed group
-        if (L == 0) {
-          leaf = node;
-        } else {
-          put(L - 1, child_mask(blo, bhi, s_off[L - 1], s_cnt[L - 1], node, px, py, pz, wd));
-          ++dbg_nodes;
-          --L;
-          base = node * kFan;
-        }
-      }
-      if (leaf >= 0) {
-        // the bound may have tightened since the mask was computed: re-test before paying for the scan
-        const int bn = s_off[0] + leaf;
-        if (!(box_lb(blo[bn], bhi[bn], px, py, pz) > wd)) { scan_leaf<K>(pts + (size_t)leaf * kLeaf, px, py, pz, bk, wd); ++dbg_leaves; }
-      }
-    }
-  } else if (top == 1) {
-    // two levels: the seed group was one level-1 node == the root; nothing else exists
-  }
-  emit<K>(bk, a.inv, a.gate_sq, a.out_i, a.out_d, (size_t)(a.q_begin + q) * a.k_out, a.k_out);
-  if (a.dbg) { a.dbg[2 * q] = dbg_nodes; a.dbg[2 * q + 1] = dbg_leaves; }
 }
 
 // Quad-per-query variant of the tree search (the default).  With one query per lane a 100 K-point
@@ -1113,31 +988,15 @@ hipError_t launch_bvh_knn_quad(int K, const KnnArgs& a, hipStream_t st) {
 hipError_t launch_bvh_knn_packet(int K, const KnnArgs& a, hipStream_t st) {
   if (a.q_count <= 0) return hipSuccess;
   const int packets = (a.q_count + 15) / 16;
-  static const int wpb_small = [] { const char* e = getenv("SICP_KNN_WPB"); return e ? atoi(e) : 4; }();  // tuning aid
-  static const int wpb_big = [] { const char* e = getenv("SICP_KNN_WPB20"); return e ? atoi(e) : 2; }();
-  auto grid = [&](int wpb) { return dim3((packets + wpb - 1) / wpb); };
-#define SICP_PK(KK, W) hipLaunchKernelGGL((bvh_knn_packet_kernel<KK, W>), grid(W), dim3(64 * W), 0, st, a)
+#define SICP_PK(KK, W) hipLaunchKernelGGL((bvh_knn_packet_kernel<KK, W>), dim3((packets + W - 1) / W), dim3(64 * W), 0, st, a)
   switch (K) {
-    case 1: if (wpb_small == 1) SICP_PK(1, 1); else if (wpb_small == 2) SICP_PK(1, 2); else SICP_PK(1, 4); break;
-    case 4: if (wpb_small == 1) SICP_PK(4, 1); else if (wpb_small == 2) SICP_PK(4, 2); else SICP_PK(4, 4); break;
-    case 20: if (wpb_big == 1) SICP_PK(20, 1); else if (wpb_big == 2) SICP_PK(20, 2); else SICP_PK(20, 4); break;
+    case 1: SICP_PK(1, 4); break;
+    case 4: SICP_PK(4, 4); break;
+    case 20: SICP_PK(20, 2); break;
     case 32: SICP_PK(32, 2); break;
     default: return hipErrorInvalidValue;
   }
 #undef SICP_PK
-  return hipGetLastError();
-}
-
-hipError_t launch_bvh_knn(int K, const KnnArgs& a, hipStream_t st) {
-  if (a.q_count <= 0) return hipSuccess;
-  dim3 grid((a.q_count + 63) / 64);
-  switch (K) {
-    case 1: hipLaunchKernelGGL((bvh_knn_kernel<1>), grid, dim3(64), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((bvh_knn_kernel<4>), grid, dim3(64), 0, st, a); break;
-    case 20: hipLaunchKernelGGL((bvh_knn_kernel<20>), grid, dim3(64), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((bvh_knn_kernel<32>), grid, dim3(64), 0, st, a); break;
-    default: return hipErrorInvalidValue;
-  }
   return hipGetLastError();
 }
 
@@ -1156,11 +1015,7 @@ hipError_t launch_bvh_knn_packet_jobs(int K, const KnnArgs* jobs, int n, hipStre
     switch (K) {
       case 1: SICP_PKJ(1, 4); break;
       case 4: SICP_PKJ(4, 4); break;
-#if defined(SICP_EXPERIMENT_K20_LISTS)  // timing experiment only: the k = 20 self-search with SHORTER per-lane lists -- wrong beyond that many entries
-      case 20: SICP_PKJ(SICP_EXPERIMENT_K20_LISTS, 2); break;
-#else
       case 20: SICP_PKJ(20, 2); break;
-#endif
       case 32: SICP_PKJ(32, 2); break;
       default: return hipErrorInvalidValue;
     }

@@ -197,8 +197,7 @@ int sicp_destroy(sicp_handle h) {
     if (!h) return SICP_OK;
     // park it: everything it queued has ended, its clouds go back to their pool (or stay with whoever shares them), and
     // what remains is a handle as sicp_create makes them -- with its streams, mirrors, buffers and graphs in place
-    static const bool no_pool = std::getenv("SICP_NO_HANDLE_POOL") != nullptr;  // A/B aid
-    bool clean = !no_pool && h->stream && h->stream2 && hipSetDevice(h->device) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess &&
+    bool clean = h->stream && h->stream2 && hipSetDevice(h->device) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess &&
                  hipStreamSynchronize(h->stream2) == hipSuccess;
     if (clean && h->side_stream) clean = hipStreamSynchronize(h->side_stream) == hipSuccess;
     if (clean && h->feat_stream) clean = hipStreamSynchronize(h->feat_stream) == hipSuccess;
@@ -472,13 +471,7 @@ int sicp_accumulate_batch(sicp_handle* hs, int32_t n, const double* qt, double* 
       h->ts[0].h_batch[p].nb = nb;
       HIPCHECK(hipStreamSynchronize(g->stream));  // the pair's correspondences are complete
     }
-#ifdef SICP_DEV_PROBES
-    // (developer build only: SICP_ACC_INNER_REPEAT makes the kernel repeat its range that many times inside one launch)
-    static const int inner = [] { const char* e = std::getenv("SICP_ACC_INNER_REPEAT"); return e ? std::atoi(e) : 0; }();
-#else
-    const int inner = 0;
-#endif
-    *h->ts[0].h_bhdr = sicp::BatchHeader{n, h->ts[0].epoch_host, {inner, 0}};
+    *h->ts[0].h_bhdr = sicp::BatchHeader{n, 0u, 0u, 0};
     HIPCHECK(hipMemcpyAsync(h->ts[0].d_bhdr.p, h->ts[0].h_bhdr, sizeof(sicp::BatchHeader), hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(h->ts[0].d_batch.p, h->ts[0].h_batch, sizeof(sicp::BatchArgs) * n, hipMemcpyHostToDevice, h->stream));
     if (repeat < 1) repeat = 1;

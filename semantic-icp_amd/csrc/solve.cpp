@@ -100,11 +100,6 @@ int batch_reserve(sicp_context* h, int n) {
   SICPCHECK(tickset_reserve(h, h->ts[0], n));
   n = std::max(32, (n + 31) / 32 * 32);
   HIPCHECK(h->d_bstates.reserve(n));
-  if (h->d_ein.cap < (size_t)2 * n) {  // (zeroed: epoch 0 never is a launch's epoch)
-    HIPCHECK(h->d_ein.reserve((size_t)2 * n));
-    HIPCHECK(hipMemsetAsync(h->d_ein.p, 0, sizeof(sicp::EvalIn) * h->d_ein.cap, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-  }
   HIPCHECK(h->d_bout28.reserve((size_t)28 * n));
   if (h->h_batch_cap < n) {
     if (h->h_bstates) (void)hipHostFree(h->h_bstates);
@@ -117,27 +112,9 @@ int batch_reserve(sicp_context* h, int n) {
   return SICP_OK;
 }
 
-// Build-time experiment of round 6 (-DSICP_LM_STEP_IN_LAUNCH, then SICP_LM_STEP_IN_LAUNCH=1): the LM step of a tick inside its
-// accumulate launches (solve_kernels.hip says what it measured: slower).  The product's tick is [accumulate, lm_step_batch] x len.
-// The searches / weights / feature kernels of the pairs between two solves run on a stream of their own beside the ticks.
-// SICP_SIDE_PRIORITY=low|high (developer A/B aid): that stream with the device's lowest / highest queue priority.
-hipError_t create_side_stream(hipStream_t* st) {
-  static const int mode = [] { const char* e = std::getenv("SICP_SIDE_PRIORITY"); return !e ? 0 : (e[0] == 'l' ? 1 : (e[0] == 'h' ? 2 : 0)); }();
-  if (mode == 0) return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-  int least = 0, greatest = 0;  // (numerically: greatest priority is the smaller number)
-  hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-  if (e != hipSuccess) return e;
-  return hipStreamCreateWithPriority(st, hipStreamNonBlocking, mode == 1 ? least : greatest);
-}
-
-bool lm_step_in_launch() {
-#if defined(SICP_LM_STEP_IN_LAUNCH)
-  static const bool on = std::getenv("SICP_LM_STEP_IN_LAUNCH") != nullptr;
-  return on;
-#else
-  return false;
-#endif
-}
+// The searches / weights / feature kernels of the pairs between two solves run on a stream of their own beside the ticks
+// (with the device's lowest or highest queue priority it measured 10-13 % slower: DESIGN.md 3.1).
+hipError_t create_side_stream(hipStream_t* st) { return hipStreamCreateWithFlags(st, hipStreamNonBlocking); }
 
 // One TICK of a batch: `len` LM evaluations of every pair in `act` (pair indices), in one graph launch:
 // the accumulate kernel evaluates all of them at their current LM poses, lm_step_batch_kernel
@@ -194,16 +171,15 @@ int tick_launch(sicp_context* h, TickSet& S, hipStream_t M, sicp_handle* hs, int
       HIPCHECK(hipHostMalloc((void**)&h->h_solo_flag, kSoloFallbackOffset + sizeof(sicp::LmState), hipHostMallocCoherent));
       *h->h_solo_flag = 0;
     }
-    static const bool no_poll = std::getenv("SICP_SOLO_NO_HOST_POLL") != nullptr;  // A/B aid: wait for the read-back copy as before
-    A.host_state = no_poll ? nullptr : static_cast<sicp::LmCore*>(h->h_bstates + p);
-    A.host_flag = no_poll ? nullptr : h->h_solo_flag;
+    A.host_state = static_cast<sicp::LmCore*>(h->h_bstates + p);
+    A.host_flag = h->h_solo_flag;
     h->solo_pair = p;
     h->solo_was_init = A.init != 0;
     S.tick_valid = false;  // (the argument array in HBM was not refreshed)
     HIPCHECK(sicp::launch_solve_one(g->corr_K, h->params.use_sqloss, A, nb, M));
     // The fallback read-back lands in an area of its OWN: the host reads h_bstates[p] as soon as the polled word has changed,
     // while this copy may still be in flight behind the kernel -- it must not rewrite what the host is reading (solo_wait
-    // moves it over when the poll did not see the word: a launch that gave up, polling switched off).
+    // moves it over when the poll did not see the word: a launch that gave up).
     HIPCHECK(hipMemcpyAsync(reinterpret_cast<char*>(h->h_solo_flag) + kSoloFallbackOffset, h->d_bstates.p + p, sizeof(sicp::LmState), hipMemcpyDeviceToHost, M));
     return SICP_OK;
   }
@@ -219,11 +195,10 @@ int tick_launch(sicp_context* h, TickSet& S, hipStream_t M, sicp_handle* hs, int
     if (g->partials.reserve((size_t)nb * 28) != hipSuccess) return SICP_ERR_OUT_OF_MEMORY;
     fill_acc(g, B.a);
     B.a.lm = B.a.lm_step = h->d_bstates.p + p;
-    B.a.ein = lm_step_in_launch() ? h->d_ein.p + 2 * (size_t)p : nullptr;
     B.nb = nb;
   }
   if (!same_set) {
-    *S.h_bhdr = sicp::BatchHeader{(int)act.size(), S.epoch_host, {0, 0}};
+    *S.h_bhdr = sicp::BatchHeader{(int)act.size(), 0u, 0u, 0};
     HIPCHECK(hipMemcpyAsync(S.d_bhdr.p, S.h_bhdr, sizeof(sicp::BatchHeader), hipMemcpyHostToDevice, M));
     HIPCHECK(hipMemcpyAsync(S.d_batch.p, S.h_batch, sizeof(sicp::BatchArgs) * act.size(), hipMemcpyHostToDevice, M));
     S.tick_act = act;
@@ -236,23 +211,20 @@ int tick_launch(sicp_context* h, TickSet& S, hipStream_t M, sicp_handle* hs, int
   // fault when a thread other than the main one launches graphs while it traces kernels (tools/r04/two_thread_dispatch.hip
   // reproduces it without this library), and a stream's ticks are launched by its worker thread.  Same kernels, same bits.
   static const bool no_graph = std::getenv("SICP_NO_GRAPH") != nullptr;
-  const bool fold = lm_step_in_launch();
   if (no_graph) {
     const int cap = std::min(S.cap, kMaxActivePairs);
-    if (fold) HIPCHECK(sicp::launch_tick_prepare(S.d_bhdr.p, S.d_batch.p, M));
     for (int b = 0; b < len; ++b) {
-      HIPCHECK(sicp::launch_accumulate_batch(hs[act[0]]->corr_K, h->params.use_sqloss, S.d_bhdr.p, S.d_batch.p, cap, M, b | (S.static_ranges ? sicp::kAccStaticRanges : 0)));
-      if (!fold) HIPCHECK(sicp::launch_lm_step_batch(S.d_bhdr.p, S.d_batch.p, cap, M));
+      HIPCHECK(sicp::launch_accumulate_batch(hs[act[0]]->corr_K, h->params.use_sqloss, S.d_bhdr.p, S.d_batch.p, cap, M, S.static_ranges ? sicp::kAccStaticRanges : 0));
+      HIPCHECK(sicp::launch_lm_step_batch(S.d_bhdr.p, S.d_batch.p, cap, M));
     }
   } else {
     int built = 0;
     sicp::BatchGraph& graph = S.graph[S.static_ranges ? 1 : 0];
     HIPCHECK(sicp::batch_graph_prepare(graph, hs[act[0]]->corr_K, h->params.use_sqloss, S.d_bhdr.p, S.d_batch.p, std::min(S.cap, kMaxActivePairs),
-                                       len, &built, fold ? 1 : 0, S.static_ranges ? 1 : 0));
+                                       len, &built, S.static_ranges ? 1 : 0));
     h->st.graph_builds += built;
     HIPCHECK(hipGraphLaunch(graph.exec, M));
   }
-  if (fold) S.epoch_host += (unsigned)sicp::kMaxBatchLen;  // (what tick_prepare_kernel has just been queued to do)
   HIPCHECK(hipMemcpyAsync(h->h_bstates + lo, h->d_bstates.p + lo, sizeof(sicp::LmState) * (hi - lo), hipMemcpyDeviceToHost, M));
   return SICP_OK;
 }
@@ -266,7 +238,7 @@ int tick_wait(sicp_context* h, hipStream_t M) {
 
 // Wait for a persistent solve: its master writes the state into the pinned mirror and then the launch number into a pinned
 // word (SoloArgs::host_flag) -- the host polls that word (bounded) instead of waiting for the read-back copy queued behind
-// the kernel; whatever the poll does not see (a launch that gave up, polling switched off) the stream wait catches.
+// the kernel; whatever the poll does not see (a launch that gave up) the stream wait catches.
 int solo_wait(sicp_context* h, hipStream_t M) {
   if (h->h_solo_flag) {
     volatile int* flag = h->h_solo_flag;
@@ -505,7 +477,7 @@ int align_batch(sicp_handle* hs, int32_t n, const double* init_qt, double* out_q
   // fills the ramp: 2.09 -> 2.12 G corr/s at 256 pairs (chunks of 8 ... 32 alike, 64 and more lose it again).
   const bool staged = one_launch && n > 48;
   const bool early_first = one_launch && n <= 4;  // (never staged: that starts at 49 pairs)
-  static const int kStartChunk = [] { const char* e = std::getenv("SICP_START_CHUNK"); const int v = e ? std::atoi(e) : 32; return v > 0 ? v : 32; }();  // tuning aid
+  constexpr int kStartChunk = 32;
   if (!staged) {  // (a staged batch queues its start-up pipelines below, once the run exists)
     for (int p = 0; p < n; ++p) {
       hs[p]->epoch = epoch;

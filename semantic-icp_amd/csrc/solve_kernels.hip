@@ -228,14 +228,9 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v2i __attribute__((ext_vector_type(2)));
 
-// The streams of a pass (indices, weights, source records) are read once; loading them non-temporal
-// (-DSICP_STREAM_NT), so that they would not push the gathered target records out of L2, measured SLOWER:
-// 110.5 vs 108.0 us over 32 pairs, 876 vs 810 us over 256.
-#if defined(SICP_STREAM_NT)
-#define SICP_STREAM_LOAD(p) __builtin_nontemporal_load(p)
-#else
+// The streams of a pass (indices, weights, source records) are read once; loading them non-temporal, so that they would
+// not push the gathered target records out of L2, measured SLOWER: 110.5 vs 108.0 us over 32 pairs, 876 vs 810 us over 256.
 #define SICP_STREAM_LOAD(p) (*(p))
-#endif
 struct RecMid { double nz; float x, y; };
 __device__ __forceinline__ void load_rec(const SICP_GLOBAL PointRec* r, float& x, float& y, float& z, double& nx, double& ny, double& nz) {
   const SICP_GLOBAL char* p = (const SICP_GLOBAL char*)r;
@@ -499,11 +494,7 @@ __device__ __forceinline__ void accumulate_segment(const LoadCtx& L, const MathC
     __builtin_amdgcn_s_barrier();
     for (int e = threadIdx.x; e < parked * 28; e += BS) {
       const int c = e / 28, k = e - 28 * c;
-#if defined(SICP_LM_STEP_IN_LAUNCH)  // (write-through: the workgroup that finishes a pair LAST sums the columns of all of them inside this launch)
-      coherent_store_f64(partials + (size_t)k * n_chunks + (chunk - parked + c), (comb[c][0][k] + comb[c][1][k]) + (comb[c][2][k] + comb[c][3][k]));
-#else
       partials[(size_t)k * n_chunks + (chunk - parked + c)] = (comb[c][0][k] + comb[c][1][k]) + (comb[c][2][k] + comb[c][3][k]);
-#endif
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -663,41 +654,11 @@ __device__ __forceinline__ int sums_all_finite(const double (&s_part)[4][28]) {
   return __all(v - v == 0.0) ? 1 : 0;
 }
 
-// ---- build-time experiment of round 6 (-DSICP_LM_STEP_IN_LAUNCH + SICP_LM_STEP_IN_LAUNCH=1 in the environment): the LM step
-// INSIDE the accumulate launch -- the workgroup that delivers a pair's last columns sums them all and advances the pair's
-// trust-region machine, the tick is [tick_prepare, accumulate x len] instead of [accumulate, lm_step_batch] x len.  Built,
-// bit-identical to the product (all GPU tests), and SLOWER everywhere: 256-pair stream step 184.2 against 183.1 ms, 16 full-size
-// pairs 59.5 against 48.9 ms per step, SE3-GICP 144 against 129 (profiles/r06/lm_step_in_launch_ab.json).  Every workgroup's range
-// is about half a pair, so every pair completes at the END of the launch and its step (reduce 44 KB + ~9 us of one lane) extends
-// the launch by what the separate kernel took; the drain + two barriers + one agent-scope add per segment and the 532 bytes of
-// scratch lm_feed's 310 registers cost the kernel come on top.  The step's kernel was never the loss it looked like in the
-// trace (55 us "present" per launch): while it waits for a SIMD the searches that share the chip make progress.
-// Not part of the product build.
-#if defined(SICP_LM_STEP_IN_LAUNCH)
-// One LM step of a pair from inside the accumulate launch (one lane).  Not inlined: lm_feed wants ~310 registers, the
-// accumulate kernel is compiled for two waves per SIMD (256), and this runs once per pair and evaluation -- whatever it
-// spills must stay out of the kernel's hot loop.
-__device__ __attribute__((noinline)) void lm_step_in_launch(LmState* lm, EvalIn* next, unsigned next_epoch, const double (&o)[28]) {
-  LmCore st = *lm;
-  lm_feed(st, lm->opt, o);
-  st.pending = 0;  // the arrival counter of the NEXT launch starts from zero
-  *static_cast<LmCore*>(lm) = st;
-#pragma unroll
-  for (int k = 0; k < 7; ++k) next->pose[k] = st.pose[k];
-  next->status = st.status;
-  next->epoch = next_epoch;
-}
-
-#endif
-
 template <int K, bool SQLOSS, int BS>
-__global__ __launch_bounds__(BS, SICP_ACC_OCC) void accumulate_staged_kernel(const BatchHeader* __restrict__ hdr, const BatchArgs* __restrict__ batch, int node) {
+__global__ __launch_bounds__(BS, SICP_ACC_OCC) void accumulate_staged_kernel(BatchHeader* __restrict__ hdr, const BatchArgs* __restrict__ batch, int flags) {
   constexpr int SG = GroupShape<K>::SG, NS = GroupShape<K>::NS, NW = BS / 64;
   extern __shared__ __attribute__((aligned(16))) double smem[];  // ONE shared object: [reduction tiles | staging | logarithm table | per-pair walk state]
   __shared__ int total_running;
-#if defined(SICP_LM_STEP_IN_LAUNCH)
-  __shared__ int s_last;
-#endif
   __shared__ double comb[COMB_CHUNKS][NW][28];
   static_assert(COMB_CHUNKS * NW >= 4 && BS == REDUCE_THREADS, "comb[] doubles as reduce_partials_block's scratch; the workgroup is its block");
   char* stage_all = reinterpret_cast<char*>(smem + NW * RED_ROWS * RED_STRIDE);
@@ -705,19 +666,10 @@ __global__ __launch_bounds__(BS, SICP_ACC_OCC) void accumulate_staged_kernel(con
   PairSlot* ctx = reinterpret_cast<PairSlot*>(log_tab + LOG_TABLE_BYTES);
   const int n_pairs = hdr->n_pairs;
   if (n_pairs <= 0) return;
-  // this launch's epoch (pairs whose LM machine is stepped inside the launch: AccArgs::ein, see EvalIn in kernels.h)
-  const unsigned epoch = (unsigned)uniform_i32((int)(hdr->epoch_base + (unsigned)(node & 0xffff)));
-  (void)epoch;
   for (int k = threadIdx.x; k < kLogTableEntries; k += BS) reinterpret_cast<v2d*>(log_tab)[k] = reinterpret_cast<const v2d*>(kLogTable)[k];
   for (int p = threadIdx.x; p < n_pairs; p += BS) {
     const AccArgs& a = batch[p].a;
     PairSlot c;
-#if defined(SICP_LM_STEP_IN_LAUNCH)
-    if (a.ein) {  // (never the state itself: another workgroup of this launch may already have stepped it)
-      const EvalIn& in = a.ein[epoch & 1u];
-      c.running = in.epoch == epoch && in.status == LM_RUNNING;
-    } else
-#endif
     c.running = a.lm ? a.lm->status == LM_RUNNING : 1;
     c.n_chunks = acc_geometry(a.n_s * a.K, SG).n_chunks;
     c.item_begin = 0;
@@ -751,7 +703,6 @@ __global__ __launch_bounds__(BS, SICP_ACC_OCC) void accumulate_staged_kernel(con
   const unsigned T = (unsigned)total_running, G = gridDim.x, b = blockIdx.x;
   SICP_LDS char* stage = (SICP_LDS char*)stage_all + wave * (SG * STAGE_SLOT_BYTES);
   SICP_LDS double* tile = (SICP_LDS double*)smem + wave * (RED_ROWS * RED_STRIDE);
-#if !defined(SICP_ACC_STATIC_RANGES) && !defined(SICP_DEV_PROBES)
   // Work split (round 6): the chunks of the running pairs are handed out in RUNS of consecutive chunks by an agent-scope
   // counter, not as equal static ranges.  In a tick the accumulate workgroups are dispatched beside the search kernels of the
   // side stream and start up to hundreds of microseconds apart (an 80 KB / 4 x 196-register workgroup only gets onto a CU as
@@ -762,16 +713,16 @@ __global__ __launch_bounds__(BS, SICP_ACC_OCC) void accumulate_staged_kernel(con
   // the pipeline fill).  ONLY launches with at least 8 runs per workgroup are split this way: every run pays a pipeline fill and
   // two barriers, and with few runs per workgroup their granularity unbalances the launch -- shorter runs were measured too
   // (T / 4G chunks): 16 full-size pairs 56.9 against 44.4 ms per step, the open stream's ramp-up 1.9 K against 2.0 K pairs/s --
-  // so smaller launches keep the equal contiguous ranges of rounds 2-5.  The two counters live in the header
-  // (BatchHeader::pad_) and are reset by the last workgroup to leave -- everyone has made its last fetch by then.
-  // (-DSICP_ACC_STATIC_RANGES: the equal contiguous ranges of rounds 2-5, for A/B.)
-  unsigned* const next_run = reinterpret_cast<unsigned*>(const_cast<int*>(&hdr->pad_[0]));
-  unsigned* const left = reinterpret_cast<unsigned*>(const_cast<int*>(&hdr->pad_[1]));
+  // so smaller launches keep the equal contiguous ranges of rounds 2-5.  The two counters are BatchHeader::next_run and
+  // BatchHeader::runs_left: the host uploads them as zeros with the header, and the last workgroup to leave resets them --
+  // everyone has made its last fetch by then (kernels.h: which launches share a header).
+  unsigned* const next_run = &hdr->next_run;
+  unsigned* const left = &hdr->runs_left;
   constexpr unsigned run = (unsigned)COMB_CHUNKS;
-  // (the same for every workgroup of the launch; kAccStaticRanges in `node`: the host asks for equal ranges -- a stream while scans
+  // (the same for every workgroup of the launch; kAccStaticRanges in `flags`: the host asks for equal ranges -- a stream while scans
   //  are being uploaded: a launch whose workgroups all stay to the end leaves the tree-build kernels of the upload stream, whose sorts
   //  need LDS, no CU to get onto except between launches: 1.9 K instead of 2.0 K pairs/s end to end)
-  const bool by_runs = !(node & kAccStaticRanges) && T >= kRunsPerWorkgroupForDynamic * run * G;
+  const bool by_runs = !(flags & kAccStaticRanges) && T >= kRunsPerWorkgroupForDynamic * run * G;
   __shared__ unsigned s_run;
   unsigned fetched = 0u;
   if (by_runs && threadIdx.x == 0) fetched = __hip_atomic_fetch_add(next_run, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -792,21 +743,6 @@ __global__ __launch_bounds__(BS, SICP_ACC_OCC) void accumulate_staged_kernel(con
     item_end = T < G ? (b < T ? (int)b + 1 : (int)b) : (int)((b + 1) * T / G);
     if (item >= item_end) break;
   }
-#else
-  int item = T < G ? (int)b : (int)(b * T / G);
-  const int item_end = T < G ? (b < T ? (int)b + 1 : (int)b) : (int)((b + 1) * T / G);
-  if (item >= item_end) return;
-#endif
-
-#ifdef SICP_DEV_PROBES
-  // developer build only (-DSICP_DEV_PROBES, tools/corun_probe.py): hdr->pad_[0] > 1 repeats the workgroup's whole range
-  // that many times inside ONE launch -- the same sums every time -- which keeps the persistent workgroups resident the
-  // way a fused multi-evaluation kernel would, so that what co-resides with them can be measured.  The product kernel
-  // has neither the loop nor the header read.
-  const int item_first = item;
-  for (int rep = uniform_i32(hdr->pad_[0] > 1 ? hdr->pad_[0] : 1); rep > 0; --rep) {
-  item = item_first;
-#endif
   while (item < item_end) {
     // the pair this item belongs to: the last one that begins at or before it (always a running one)
     int lo = 0, hi = n_pairs - 1;
@@ -833,13 +769,6 @@ __global__ __launch_bounds__(BS, SICP_ACC_OCC) void accumulate_staged_kernel(con
     MathCtx M;
     {
       Pose P;
-#if defined(SICP_LM_STEP_IN_LAUNCH)
-      if (a.ein) {
-        const double* q = a.ein[epoch & 1u].pose;
-        se3::rotation(q, P.R);
-        P.t[0] = q[4]; P.t[1] = q[5]; P.t[2] = q[6];
-      } else
-#endif
       if (a.lm) {
         se3::rotation(a.lm->pose, P.R);
         P.t[0] = a.lm->pose[4]; P.t[1] = a.lm->pose[5]; P.t[2] = a.lm->pose[6];
@@ -858,39 +787,7 @@ __global__ __launch_bounds__(BS, SICP_ACC_OCC) void accumulate_staged_kernel(con
 
     accumulate_segment<K, SQLOSS, BS>(L, M, chunk_lo, n_here, n_chunks, steps, uniform_i32(geo.chunk_groups), partials, stage, tile, comb, lane, wave);
     item += n_here;
-#if defined(SICP_LM_STEP_IN_LAUNCH)
-    // ---- the LM step, inside this launch: the workgroup that delivers a pair's LAST columns sums them all and advances the
-    // pair's trust-region machine (csrc/lm.hpp: the code lm_step_batch_kernel runs, in the order it runs it: the same bits)
-    // while the other workgroups are still evaluating other pairs -- no second launch per evaluation, and nothing waits for
-    // a 312-register block to find a SIMD between the search waves that share the chip with a tick.
-    // Hand-off (cdna_hip_programming.md recipe R1): the columns were stored write-through, every wave drains its stores,
-    // ONE agent-scope add on the pair's arrival counter (LmCore::pending) tells who is last; the last one reads the
-    // columns with agent-scope loads.  The stepped state goes to the pair's LmState (what the host reads back after the tick)
-    // and, as pose + status + epoch, to the OTHER EvalIn entry: the next launch's input, never this one's.
-    EvalIn* const ein = uniform_ptr(a.ein);
-    if (ein != nullptr) {
-      LmState* const lm = uniform_ptr(a.lm_step);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (threadIdx.x == 0) {
-        const int before = __hip_atomic_fetch_add(&lm->pending, n_here, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = before + n_here == n_chunks;
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (s_last) {
-        double o[28];
-        reduce_partials_block<true>((const double*)partials, n_chunks, *reinterpret_cast<double (*)[4][28]>(&comb[0][0][0]), o);
-        if (threadIdx.x == 0) lm_step_in_launch(lm, ein + ((epoch + 1u) & 1u), epoch + 1u, o);
-        __syncthreads();  // (comb[] is the next segment's again)
-      }
-    }
-#endif
   }
-#ifdef SICP_DEV_PROBES
-  }
-#endif
-#if !defined(SICP_ACC_STATIC_RANGES) && !defined(SICP_DEV_PROBES)
   __syncthreads();  // (s_run is rewritten at the top)
   }
   if (by_runs && threadIdx.x == 0) {
@@ -900,13 +797,13 @@ __global__ __launch_bounds__(BS, SICP_ACC_OCC) void accumulate_staged_kernel(con
       __hip_atomic_store(left, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-#endif
 }
 
 // device-resident solve: reduce the partial columns and advance the LM machine by one evaluation
 // (lm.hpp: the same lm_feed the host loop runs).  One workgroup per pair; the grid is the capacity of
 // the batch buffers, the blocks beyond the number of active pairs leave at once.  Thread 0 takes the
-// trust-region step (serial: ~10 us, the longest link of a pair-alone evaluation).
+// trust-region step (serial: ~10 us, the longest link of a pair-alone evaluation).  (Stepping the machine inside the
+// accumulate launch instead, by the workgroup that delivers a pair's last columns, measured slower: DESIGN.md 3.1.)
 #ifndef SICP_LM_STEP_WAVES
 #define SICP_LM_STEP_WAVES 1  // waves per SIMD the LM step is compiled for (1: lm_feed gets the 312 VGPRs it wants)
 #endif
@@ -1385,10 +1282,8 @@ static void* accumulate_fn(int K, int use_sqloss) {
 }
 
 int accumulate_grid() {
-  // persistent workgroups: two per CU (two waves per SIMD).  SICP_ACC_GRID is a tuning aid.
+  // persistent workgroups: two per CU (two waves per SIMD)
   static const int grid = [] {
-    const char* e = getenv("SICP_ACC_GRID");
-    if (e && atoi(e) > 0) return atoi(e);
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     return SICP_ACC_OCC * (cus > 0 ? cus : 256);
@@ -1401,10 +1296,10 @@ static size_t stream_smem_bytes(int capacity, int K) {
   return sizeof(double) * 4 * RED_ROWS * RED_STRIDE + staging + LOG_TABLE_BYTES + sizeof(PairSlot) * (size_t)capacity;
 }
 
-hipError_t launch_accumulate_batch(int K, int use_sqloss, const BatchHeader* hdr, const BatchArgs* batch, int capacity, hipStream_t st, int node) {
+hipError_t launch_accumulate_batch(int K, int use_sqloss, BatchHeader* hdr, const BatchArgs* batch, int capacity, hipStream_t st, int flags) {
   void* fn = accumulate_fn(K, use_sqloss);
   if (!fn) return hipErrorInvalidValue;
-  void* args[] = {(void*)&hdr, (void*)&batch, (void*)&node};
+  void* args[] = {(void*)&hdr, (void*)&batch, (void*)&flags};
   return hipLaunchKernel(fn, dim3(accumulate_grid()), dim3(256), args, stream_smem_bytes(capacity, K), st);
 }
 
@@ -1418,8 +1313,7 @@ bool solve_one_fits(int total, int K) {
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n > 0 ? n : 256;
   }();
-  static const bool off = getenv("SICP_NO_SOLO") != nullptr;  // developer switch: always the [accumulate, LM step] graph
-  return !off && total > 0 && accumulate_blocks(total, K) + 1 <= (cus < 257 ? cus : 257) && acc_geometry(total, acc_slots_per_group(K)).steps == 8 / acc_slots_per_group(K);
+  return total > 0 && accumulate_blocks(total, K) + 1 <= (cus < 257 ? cus : 257) && acc_geometry(total, acc_slots_per_group(K)).steps == 8 / acc_slots_per_group(K);
 }
 
 // How long a wait of the persistent solve may last before it gives up, in ticks of the 100 MHz constant clock: 5 ms
@@ -1446,35 +1340,6 @@ hipError_t launch_solve_one(int K, int use_sqloss, const SoloArgs& args, int n_c
 hipError_t launch_lm_step_batch(const BatchHeader* hdr, const BatchArgs* batch, int capacity, hipStream_t st) {
   if (capacity <= 0) return hipSuccess;
   hipLaunchKernelGGL(lm_step_batch_kernel, dim3(capacity), dim3(REDUCE_THREADS), 0, st, hdr, batch);
-  return hipGetLastError();
-}
-
-// First kernel of a tick whose accumulate launches step the LM machines themselves: a new epoch range for the tick, and every
-// pair's pose / status -- from its LmState, whoever wrote it last: lm_init_kernel for a pair that joins, the previous tick's
-// last step, a persistent solve that gave up -- as the input of the tick's first evaluation.  ONE workgroup (it owns the
-// header word it advances).
-__global__ __launch_bounds__(256) void tick_prepare_kernel(BatchHeader* __restrict__ hdr, const BatchArgs* __restrict__ batch) {
-  __shared__ unsigned s_epoch;
-  if (threadIdx.x == 0) {
-    s_epoch = hdr->epoch_base + (unsigned)kMaxBatchLen;  // (an even stride: a tick's first evaluation always has the same parity)
-    hdr->epoch_base = s_epoch;
-  }
-  __syncthreads();
-  const unsigned e0 = s_epoch;
-  for (int p = threadIdx.x; p < hdr->n_pairs; p += blockDim.x) {
-    const AccArgs& a = batch[p].a;
-    if (!a.ein || !a.lm_step) continue;
-    EvalIn& in = a.ein[e0 & 1u];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) in.pose[k] = a.lm_step->pose[k];
-    in.status = a.lm_step->status;
-    in.epoch = e0;
-    a.lm_step->pending = 0;
-  }
-}
-
-hipError_t launch_tick_prepare(BatchHeader* hdr, const BatchArgs* batch, hipStream_t st) {
-  hipLaunchKernelGGL(tick_prepare_kernel, dim3(1), dim3(256), 0, st, hdr, batch);
   return hipGetLastError();
 }
 
@@ -1509,17 +1374,17 @@ void batch_graph_destroy(BatchGraph& g) {
   g.exec = nullptr; g.graph = nullptr; g.len = 0;
 }
 
-hipError_t batch_graph_prepare(BatchGraph& g, int K, int use_sqloss, const BatchHeader* hdr, const BatchArgs* batch, int capacity, int len,
-                               int* built, int fold, int static_ranges) {
+hipError_t batch_graph_prepare(BatchGraph& g, int K, int use_sqloss, BatchHeader* hdr, const BatchArgs* batch, int capacity, int len,
+                               int* built, int static_ranges) {
   *built = 0;
   void* fn = accumulate_fn(K, use_sqloss);
   if (capacity <= 0 || len < 1 || len > kMaxBatchLen || !fn) return hipErrorInvalidValue;
-  if (g.exec && g.K == K && g.sqloss == use_sqloss && g.len == len && g.batch == batch && g.hdr == hdr && g.capacity == capacity && g.fold == fold &&
+  if (g.exec && g.K == K && g.sqloss == use_sqloss && g.len == len && g.batch == batch && g.hdr == hdr && g.capacity == capacity &&
       g.static_ranges == static_ranges)
     return hipSuccess;
   batch_graph_destroy(g);
-  int node = 0;
-  void* args[] = {(void*)&hdr, (void*)&batch, (void*)&node};  // (kernel parameters are copied when a node is added)
+  int flags = static_ranges ? kAccStaticRanges : 0;
+  void* args[] = {(void*)&hdr, (void*)&batch, (void*)&flags};  // (kernel parameters are copied when a node is added)
   hipKernelNodeParams pa, ps;
   memset(&pa, 0, sizeof pa);
   pa.func = fn;
@@ -1528,32 +1393,23 @@ hipError_t batch_graph_prepare(BatchGraph& g, int K, int use_sqloss, const Batch
   pa.sharedMemBytes = (unsigned)stream_smem_bytes(capacity, K);
   pa.kernelParams = args;
   memset(&ps, 0, sizeof ps);
-  ps.func = fold ? (void*)tick_prepare_kernel : (void*)lm_step_batch_kernel;
-  ps.gridDim = dim3(fold ? 1 : capacity);
-  ps.blockDim = dim3(fold ? 256 : REDUCE_THREADS);
+  ps.func = (void*)lm_step_batch_kernel;
+  ps.gridDim = dim3(capacity);
+  ps.blockDim = dim3(REDUCE_THREADS);
   ps.kernelParams = args;
   hipError_t e = hipGraphCreate(&g.graph, 0);
   if (e != hipSuccess) return e;
   hipGraphNode_t prev = nullptr, acc = nullptr, step = nullptr;
-  if (fold) {  // [tick_prepare, accumulate x len]: the accumulate launches step the machines themselves
-    e = hipGraphAddKernelNode(&step, g.graph, nullptr, 0, &ps);
+  for (int b = 0; b < len; ++b) {
+    e = hipGraphAddKernelNode(&acc, g.graph, prev ? &prev : nullptr, prev ? 1 : 0, &pa);
+    if (e != hipSuccess) return e;
+    e = hipGraphAddKernelNode(&step, g.graph, &acc, 1, &ps);
     if (e != hipSuccess) return e;
     prev = step;
   }
-  for (int b = 0; b < len; ++b) {
-    node = b | (static_ranges ? kAccStaticRanges : 0);
-    e = hipGraphAddKernelNode(&acc, g.graph, prev ? &prev : nullptr, prev ? 1 : 0, &pa);
-    if (e != hipSuccess) return e;
-    prev = acc;
-    if (!fold) {
-      e = hipGraphAddKernelNode(&step, g.graph, &acc, 1, &ps);
-      if (e != hipSuccess) return e;
-      prev = step;
-    }
-  }
   e = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
   if (e != hipSuccess) return e;
-  g.K = K; g.sqloss = use_sqloss; g.len = len; g.batch = batch; g.hdr = hdr; g.capacity = capacity; g.fold = fold; g.static_ranges = static_ranges;
+  g.K = K; g.sqloss = use_sqloss; g.len = len; g.batch = batch; g.hdr = hdr; g.capacity = capacity; g.static_ranges = static_ranges;
   *built = 1;
   return hipSuccess;
 }

@@ -51,11 +51,9 @@ int run_nn(sicp_context* h, int K, const Cloud& Qc, int q_begin, int q_count, co
     static const bool want_dbg = debug_enabled() && std::getenv("SICP_KNN_STATS") != nullptr;  // developer aid (prints: needs SICP_DEBUG)
     DevBuf<int> dbg;
     if (want_dbg) { HIPCHECK(dbg.reserve((size_t)2 * q_count)); a.dbg = dbg.p; }
-    static const bool lane_per_query = std::getenv("SICP_KNN_LANE_PER_QUERY") != nullptr;  // A/B aid
     // statistics: the packet kernel counts the neighbours that pass the gate as it writes them (spread over
     // kLiveCounters partial counters); every other engine leaves it to a kernel of its own (count_active)
-    static const bool count_kernel = std::getenv("SICP_COUNT_KERNEL") != nullptr;  // A/B aid: always the separate kernel
-    if (h->count_stats && !self && out_i == h->idx.p && !lane_per_query && !count_kernel && h->params.nn_method == 1) {
+    if (h->count_stats && !self && out_i == h->idx.p && h->params.nn_method == 1) {
       a.live_cnt = (unsigned long long*)h->d_count.p;
       h->counted_in_search = true;
     }
@@ -70,8 +68,7 @@ int run_nn(sicp_context* h, int K, const Cloud& Qc, int q_begin, int q_count, co
       return SICP_OK;
     }
     KernelTimer kt(h, stream == h->stream ? timer_bit : 0);
-    if (lane_per_query) HIPCHECK(sicp::launch_bvh_knn(L, a, stream));
-    else if (h->params.nn_method == 2) HIPCHECK(sicp::launch_bvh_knn_quad(L, a, stream));
+    if (h->params.nn_method == 2) HIPCHECK(sicp::launch_bvh_knn_quad(L, a, stream));
     else HIPCHECK(sicp::launch_bvh_knn_packet(L, a, stream));
     account(kt.stop());
     if (want_dbg) {
@@ -183,9 +180,9 @@ int compute_features(sicp_context* h, Cloud& c, bool with_hist, hipStream_t stre
   HIPCHECK(c.nn.reserve(m * k));
   if (with_hist) HIPCHECK(c.hist.reserve(m * (size_t)sicp::hist_stride(P.num_classes)));
   // the packet search writes the lists rank-major ([k][n]): coalesced stores there and coalesced
-  // loads in the covariance kernel; the other engines keep [n][k]
-  static const bool no_lane_per_query = std::getenv("SICP_KNN_LANE_PER_QUERY") == nullptr && !(debug_enabled() && std::getenv("SICP_KNN_STATS") != nullptr);
-  const int nn_stride = (P.nn_method == 1 && no_lane_per_query) ? (int)m : 0;
+  // loads in the covariance kernel; the other engines keep [n][k], and so do the walk statistics' runs (SICP_KNN_STATS)
+  static const bool knn_stats = debug_enabled() && std::getenv("SICP_KNN_STATS") != nullptr;
+  const int nn_stride = (P.nn_method == 1 && !knn_stats) ? (int)m : 0;
   for (int s = 0; s < c.n_seg(); ++s) {
     const int o = c.seg_off[s], cnt = c.seg_off[s + 1] - o;
     SICPCHECK(run_nn(h, k, c, o, cnt, nullptr, c, s, true, std::numeric_limits<float>::infinity(), c.nn.p, nullptr,
@@ -210,12 +207,11 @@ int compute_features(sicp_context* h, Cloud& c, bool with_hist, hipStream_t stre
   a.float_products = P.quirk_float_products;
   a.rec = c.rec.p;
   a.hist = with_hist ? c.hist.p : nullptr;
-  // (SICP_NO_DENSE_SRC: developer switch; with it the accumulate kernel streams the 48-byte records: 814 instead of
-  //  800 us per 256-pair launch, 2.18 instead of 2.22 G corr/s)
-  static const bool dense_on = std::getenv("SICP_NO_DENSE_SRC") == nullptr;
+  // the records also as dense arrays (without them the accumulate kernel streams the 48-byte records: 814 instead of
+  // 800 us per 256-pair launch, 2.18 instead of 2.22 G corr/s)
   a.rec_dense = nullptr; a.rec_dense_n = 0;
   c.rec_dense_n = 0;
-  if (dense_on && n > 0) {
+  if (n > 0) {
     HIPCHECK(c.rec_dense.reserve(sicp::dense_rec_bytes(n)));
     a.rec_dense = c.rec_dense.p; a.rec_dense_n = n;
     c.rec_dense_n = n;
@@ -283,20 +279,16 @@ int run_correspondences(sicp_context* h, const double* qt, int K, bool weights) 
   // (knn_kernels.hip: KnnArgs::w_*; the same operations as em_weight_rows4_kernel, which then does not run) -- for a handle
   // on its own and in batches of at most 4 pairs (JobCollector::fold_weights says why not in larger ones).  Only when
   // the projections it reads are already there -- computed by an EARLIER flush, not waiting in this one (a flush launches
-  // its searches first) -- and not for the developer variants that have a weight kernel of their own.
-  // SICP_NO_WEIGHT_FOLD / SICP_WEIGHT_FOLD_ALWAYS (A/B aids): never / also in large batches and streams.
+  // its searches first).
   WeightFold fold_args;
   const WeightFold* fold = nullptr;
   {
-    static const bool no_fold = std::getenv("SICP_NO_WEIGHT_FOLD") != nullptr;
-    static const bool lane_per_query = std::getenv("SICP_KNN_LANE_PER_QUERY") != nullptr;
     const unsigned long long want_id = h->cm_id * 1099511628211ull + (unsigned long long)P.k_cov;
-    bool ok = weights && !no_fold && !lane_per_query && P.mode == SICP_MODE_EM && K == 4 && P.nn_method == 1 && P.profile == 0 &&
+    bool ok = weights && P.mode == SICP_MODE_EM && K == 4 && P.nn_method == 1 && P.profile == 0 &&
               P.num_classes >= 1 && P.num_classes <= 16 && !weights_from_histograms(P, K) && S.n_seg() == 1 &&
               S.proj_valid && T.proj_valid && S.proj_cm_id == want_id && T.proj_cm_id == want_id;
     if (ok && h->collect) {
-      static const bool always = std::getenv("SICP_WEIGHT_FOLD_ALWAYS") != nullptr;  // A/B aid: also in large batches and streams
-      ok = h->collect->fold_weights || always;
+      ok = h->collect->fold_weights;
       for (int s = 0; s < kParts; ++s) ok = ok && h->collect->cov[s].empty() && h->collect->proj[s].empty();
     }
     if (ok) {
@@ -407,9 +399,6 @@ void fill_acc(sicp_context* h, sicp::AccArgs& a) {
   a.partials = h->partials.p;
 }
 
-// pairs one launch evaluates (12 bytes of LDS each in the accumulate kernel).  SICP_MAX_ACTIVE: tuning aid.
-const int kMaxActivePairs = [] { const char* e = std::getenv("SICP_MAX_ACTIVE"); const int v = e ? std::atoi(e) : 256; return std::min(std::max(v, 1), 512); }();
-
 // One evaluation sweep at pose qt: the batched kernel on a batch of one (every path -- a pair alone, a
 // lock-step batch, the host-loop solve, this hook -- runs the SAME accumulate kernel, so they agree bit
 // for bit), then the fixed-order sum of the chunk partials.
@@ -425,7 +414,7 @@ int eval28(sicp_context* h, const double* qt, double* out28) {
   fill_acc(h, B.a);
   fill_pose(qt, B.a.pose);
   B.nb = nb;
-  *h->ts[0].h_bhdr = sicp::BatchHeader{1, h->ts[0].epoch_host, {0, 0}};
+  *h->ts[0].h_bhdr = sicp::BatchHeader{1, 0u, 0u, 0};
   HIPCHECK(hipMemcpyAsync(h->ts[0].d_bhdr.p, h->ts[0].h_bhdr, sizeof(sicp::BatchHeader), hipMemcpyHostToDevice, h->stream));
   HIPCHECK(hipMemcpyAsync(h->ts[0].d_batch.p, h->ts[0].h_batch, sizeof(sicp::BatchArgs), hipMemcpyHostToDevice, h->stream));
   if (general_covariances(h)) {
@@ -529,15 +518,13 @@ int align_end(sicp_context* h, const OuterState& o, double t_begin, int32_t* out
   return SICP_OK;
 }
 
-// slice of the batch a pair belongs to: SICP_BATCH_PARTS contiguous slices of >= 2 pairs (default: 2 for
-// K > 1, 4 for K = 1).  Measured at the end of round 2 (100K-point pairs; G corr/s at 1 / 2 / 3 / 4 slices):
-// EM-ICP K = 4: 16 pairs 1.22 / 1.26 / 1.09 / 1.04, 64 pairs 1.49 / 1.55 / 1.55 / 1.46, 256 pairs 1.71 / 1.81 /
-// 1.81 / 1.74 -- two streams of job launches overlap one slice's small kernels with the other's search
-// tails, more of them only split the search launches into smaller, tail-bound ones; SE3-GICP K = 1 (cheap
-// searches, short accumulate launches) at 256 pairs: 0.71 with 2 slices, 0.78 with 4.
+// slice of the batch a pair belongs to: contiguous slices of >= 2 pairs (2 for K > 1, 4 for K = 1).  Measured at the
+// end of round 2 (100K-point pairs; G corr/s at 1 / 2 / 3 / 4 slices): EM-ICP K = 4: 16 pairs 1.22 / 1.26 / 1.09 / 1.04,
+// 64 pairs 1.49 / 1.55 / 1.55 / 1.46, 256 pairs 1.71 / 1.81 / 1.81 / 1.74 -- two streams of job launches overlap one
+// slice's small kernels with the other's search tails, more of them only split the search launches into smaller,
+// tail-bound ones; SE3-GICP K = 1 (cheap searches, short accumulate launches) at 256 pairs: 0.71 with 2 slices, 0.78 with 4.
 int batch_slice(int p, int n, int knn) {
-  static const int env = [] { const char* e = std::getenv("SICP_BATCH_PARTS"); return e ? std::atoi(e) : 0; }();
-  const int want = env > 0 ? env : knn <= 1 ? 4 : 2;
+  const int want = knn <= 1 ? 4 : 2;
   const int parts = std::max(1, std::min(std::min(want, kParts), n / 2));
   return (int)((long long)p * parts / n);
 }
