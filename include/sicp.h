@@ -350,6 +350,50 @@ int sicp_transform_source(sicp_handle h, const double qt[7], float* ox, float* o
 /* getFusedLabels (em_icp.hpp:202-268): out_labels[n_source] */
 int sicp_fused_labels(sicp_handle h, const double qt[7], uint32_t* out_labels);
 
+/* ---- initial alignment without a pose prior ------------------------------------------------------
+ * The reference's Bootstrap (exec/bootstrap.h): box filter -> VoxelGrid -> NormalEstimation -> FPFHEstimation on the
+ * keypoints of both clouds -> SampleConsensusInitialAlignment.  Registers the handle's current source onto its current
+ * target from no initial guess; the result is a coarse pose for sicp_align's init_qt.  Works in every mode, ignores
+ * labels, uses the finite points the handle holds.  Orders, precisions and the deviations from PCL: INTEGRATION.md. */
+typedef struct sicp_bootstrap_params {
+  double box_max;              /* keep a point when x < box_max && y < box_max && z < box_max: 35 (bootstrap.h:24-28) */
+  double leaf_size;            /* VoxelGrid leaf: 0.4 (bootstrap.h:29-33)                                              */
+  double normal_radius;        /* NormalEstimation radius: 3 (bootstrap.h:105)                                         */
+  double feature_radius;       /* FPFHEstimation radius: 3 (bootstrap.h:112)                                           */
+  double min_sample_distance;  /* 0.4 (bootstrap.h:57)                                                                 */
+  double max_corr_distance;    /* TruncatedError threshold: 0.8 (bootstrap.h:58)                                       */
+  int32_t max_iterations;      /* hypotheses: 500 (bootstrap.h:59)                                                     */
+  int32_t nr_samples;          /* points per hypothesis: 3 (PCL default), 3..8                                         */
+  int32_t k_correspondences;   /* feature neighbours one is drawn from: 10 (PCL default), 1..16                        */
+  int32_t reserved_;
+  uint64_t seed;               /* splitmix64 state of the sampling: 1                                                  */
+} sicp_bootstrap_params;
+typedef struct sicp_bootstrap_info {
+  int32_t n_source_keypoints, n_target_keypoints;  /* voxel centroids of the box-filtered clouds              */
+  int32_t max_neighbours;      /* largest radius neighbourhood of either cloud (the point itself included)    */
+  int32_t best_iteration;      /* hypothesis that won (0-based)                                               */
+  double best_error;           /* its summed truncated error                                                  */
+  double t_keypoints_ms, t_features_ms, t_match_ms, t_score_ms, t_total_ms;  /* host wall clock per stage    */
+} sicp_bootstrap_info;
+int sicp_default_bootstrap_params(sicp_bootstrap_params* p);
+/* out_qt[7]: the coarse pose source -> target; info may be NULL.  SICP_ERR_TOO_FEW_POINTS when the source has fewer
+ * than nr_samples keypoints with features or the target none; SICP_ERR_INVALID_ARGUMENT for a bad parameter or a voxel
+ * grid whose cell count overflows int32 (PCL silently returns the input there).  Nothing on the handle changes. */
+int sicp_bootstrap(sicp_handle h, const sicp_bootstrap_params* p, double out_qt[7], sicp_bootstrap_info* info);
+/* test / bench hook: the keypoints of cloud `which` with their normals, FPFH features and feature-radius
+ * neighbour lists (CSR: nbr_offsets[n + 1], nbr_idx sorted by (d^2, index)).  Counts are always written; an output
+ * array is written when it is non-NULL and its capacity (points / neighbour entries) suffices, otherwise the call
+ * answers SICP_ERR_INVALID_ARGUMENT.  xyz3: n*3, normal3: n*3 (NaN with < 3 neighbours), fpfh33: n*33 (NaN likewise). */
+int sicp_bootstrap_keypoints(sicp_handle h, int which, const sicp_bootstrap_params* p, int32_t capacity,
+                             int64_t nbr_capacity, int32_t* n_keypoints, int64_t* n_nbrs, float* xyz3,
+                             double* normal3, float* fpfh33, int64_t* nbr_offsets, int32_t* nbr_idx);
+/* test / bench hook: the hypotheses of n caller-supplied samples (keypoint indices of both clouds, nr_samples per
+ * hypothesis, row-major), scored as sicp_bootstrap scores its own: M12 n*12 (rows 0..2 of the 4x4 matrix, nullable),
+ * err n.  feat_knn (nullable, n_source_keypoints * k_correspondences): the feature neighbours of every source
+ * keypoint, target keypoint indices, -1 where there are fewer or the keypoint has no feature. */
+int sicp_bootstrap_score(sicp_handle h, const sicp_bootstrap_params* p, int32_t n, const int32_t* src_idx,
+                         const int32_t* tgt_idx, double* M12, double* err, int32_t knn_capacity, int32_t* feat_knn);
+
 /* ---- test / bench hooks: the individual stages -------------------------------- */
 /* ComputeCovariances (em_icp.hpp:270-343 = gicp.hpp:177-239 =
  * semantic_point_cloud.hpp:25-84) for one cloud.  Any output may be NULL.

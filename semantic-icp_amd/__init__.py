@@ -110,6 +110,40 @@ class SicpStreamResult(C.Structure):
     ]
 
 
+class SicpBootstrapParams(C.Structure):
+    _fields_ = [
+        ("box_max", C.c_double),
+        ("leaf_size", C.c_double),
+        ("normal_radius", C.c_double),
+        ("feature_radius", C.c_double),
+        ("min_sample_distance", C.c_double),
+        ("max_corr_distance", C.c_double),
+        ("max_iterations", C.c_int32),
+        ("nr_samples", C.c_int32),
+        ("k_correspondences", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
+class SicpBootstrapInfo(C.Structure):
+    _fields_ = [
+        ("n_source_keypoints", C.c_int32),
+        ("n_target_keypoints", C.c_int32),
+        ("max_neighbours", C.c_int32),
+        ("best_iteration", C.c_int32),
+        ("best_error", C.c_double),
+        ("t_keypoints_ms", C.c_double),
+        ("t_features_ms", C.c_double),
+        ("t_match_ms", C.c_double),
+        ("t_score_ms", C.c_double),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class SicpError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -196,6 +230,11 @@ def lib():
             "sicp_stream_poll": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SicpStreamResult), C.POINTER(C.c_int32)],
             "sicp_stream_counters": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
             "sicp_synchronize": [C.c_void_p],
+            "sicp_default_bootstrap_params": [C.POINTER(SicpBootstrapParams)],
+            "sicp_bootstrap": [C.c_void_p, C.POINTER(SicpBootstrapParams), _dp, C.POINTER(SicpBootstrapInfo)],
+            "sicp_bootstrap_keypoints": [C.c_void_p, C.c_int, C.POINTER(SicpBootstrapParams), C.c_int32, C.c_int64, _ip,
+                                         C.POINTER(C.c_int64), _fp, _dp, _fp, C.POINTER(C.c_int64), _ip],
+            "sicp_bootstrap_score": [C.c_void_p, C.POINTER(SicpBootstrapParams), C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, _ip],
         }.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
@@ -237,6 +276,19 @@ def default_params(mode: int) -> SicpParams:
     st = lib().sicp_default_params(mode, C.byref(p))
     if st != OK:
         raise SicpError(st, "sicp_default_params")
+    return p
+
+
+def default_bootstrap_params(**overrides) -> SicpBootstrapParams:
+    """the constants of exec/bootstrap.h (sicp_default_bootstrap_params), with any field overridden by keyword"""
+    p = SicpBootstrapParams()
+    st = lib().sicp_default_bootstrap_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_bootstrap_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
     return p
 
 
@@ -367,6 +419,46 @@ class Engine:
         out = np.empty(self.n[SOURCE], dtype=np.uint32)
         self._check(lib().sicp_fused_labels(self._h, _ptr(qt, _dp), _ptr(out, _up)), "sicp_fused_labels")
         return out
+
+    # ---- initial alignment without a pose prior (exec/bootstrap.h) ------------------------
+    def bootstrap(self, params: SicpBootstrapParams | None = None):
+        """coarse pose source -> target from no initial guess (qt[7], ready for align()) and the run's info dict"""
+        p = params if params is not None else default_bootstrap_params()
+        qt = np.empty(7)
+        info = SicpBootstrapInfo()
+        self._check(lib().sicp_bootstrap(self._h, C.byref(p), _ptr(qt, _dp), C.byref(info)), "sicp_bootstrap")
+        return qt, info.as_dict()
+
+    def bootstrap_keypoints(self, which: int, params: SicpBootstrapParams | None = None):
+        """keypoints of one cloud: xyz (n,3) f32, normals (n,3), fpfh (n,33) f32, neighbour lists as CSR (offsets, idx)"""
+        p = params if params is not None else default_bootstrap_params()
+        n, nn = C.c_int32(0), C.c_int64(0)
+        self._check(lib().sicp_bootstrap_keypoints(self._h, which, C.byref(p), 0, 0, C.byref(n), C.byref(nn), None, None, None, None, None),
+                    "sicp_bootstrap_keypoints")
+        xyz = np.empty((n.value, 3), dtype=np.float32)
+        nrm = np.empty((n.value, 3))
+        f = np.empty((n.value, 33), dtype=np.float32)
+        off = np.empty(n.value + 1, dtype=np.int64)
+        idx = np.empty(max(nn.value, 1), dtype=np.int32)
+        self._check(lib().sicp_bootstrap_keypoints(self._h, which, C.byref(p), n.value, nn.value, C.byref(n), C.byref(nn), _ptr(xyz, _fp),
+                                                   _ptr(nrm, _dp), _ptr(f, _fp), off.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(idx, _ip)),
+                    "sicp_bootstrap_keypoints")
+        return xyz, nrm, f, off, idx[:nn.value]
+
+    def bootstrap_score(self, src_idx, tgt_idx, params: SicpBootstrapParams | None = None, n_source_keypoints: int | None = None):
+        """hypotheses of given samples (keypoint indices, (n, nr_samples) each): M (n,3,4), truncated errors (n,), and -- when
+        n_source_keypoints is given -- the feature neighbours of every source keypoint (n_source_keypoints, k)"""
+        p = params if params is not None else default_bootstrap_params()
+        a = np.ascontiguousarray(src_idx, dtype=np.int32).reshape(-1, p.nr_samples)
+        b = np.ascontiguousarray(tgt_idx, dtype=np.int32).reshape(-1, p.nr_samples)
+        n = a.shape[0]
+        M = np.empty((n, 3, 4))
+        err = np.empty(n)
+        knn = None if n_source_keypoints is None else np.empty((n_source_keypoints, p.k_correspondences), dtype=np.int32)
+        cap = 0 if knn is None else knn.size
+        self._check(lib().sicp_bootstrap_score(self._h, C.byref(p), n, _ptr(a, _ip), _ptr(b, _ip), _ptr(M, _dp), _ptr(err, _dp), cap,
+                                               _ptr(knn, _ip)), "sicp_bootstrap_score")
+        return M, err, knn
 
     # ---- stage hooks -----------------------------------------------------------------
     def covariances(self, which: int, want_hist: bool = False, want_nn: bool = False):

@@ -1,0 +1,31 @@
+// bootstrap.hpp -- internal interface of the initial alignment without a pose prior (bootstrap.cpp; entry points in
+// sicp_api.cpp).
+#ifndef SICP_BOOTSTRAP_HPP_
+#define SICP_BOOTSTRAP_HPP_
+
+#include "engine.hpp"
+
+namespace sicp {
+namespace host {
+
+constexpr int kBootMaxSamples = 8;  // nr_samples
+
+// splitmix64 from `state`; index(n) = floor(n * u), u = (next() >> 11) * 2^-53: the hypothesis sequence is a pure function
+// of the seed (tests/bootstrap_ref.py restates it)
+struct BootRng {
+  uint64_t state;
+  uint64_t next();
+  int index(int n);
+};
+
+void bootstrap_default_params(sicp_bootstrap_params* p);
+int bootstrap_run(sicp_context* h, const sicp_bootstrap_params* p, double* out_qt, sicp_bootstrap_info* info);
+int bootstrap_keypoints(sicp_context* h, int which, const sicp_bootstrap_params* p, int32_t capacity, int64_t nbr_capacity,
+                        int32_t* n_keypoints, int64_t* n_nbrs, float* xyz3, double* normal3, float* fpfh33,
+                        int64_t* nbr_offsets, int32_t* nbr_idx);
+int bootstrap_score(sicp_context* h, const sicp_bootstrap_params* p, int32_t n, const int32_t* src_idx, const int32_t* tgt_idx,
+                    double* M12, double* err, int32_t knn_capacity, int32_t* feat_knn);
+
+}  // namespace host
+}  // namespace sicp
+#endif

@@ -6,6 +6,34 @@
 
 namespace sicp {
 
+// one rotation of the cyclic Jacobi eigensolver of a symmetric 3x3 matrix (A := J^T A J, V := V J): the normal
+// estimation of cov_kernel and of the bootstrap's normal kernel
+__device__ __forceinline__ void jacobi_rotate(double (&A)[3][3], double (&V)[3][3], int p, int q) {
+  const double apq = A[p][q];
+  if (apq == 0.0) return;
+  const double tau = (A[q][q] - A[p][p]) / (2.0 * apq);
+  const double t = (tau >= 0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+  const double c = 1.0 / sqrt(1.0 + t * t), s = t * c;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double akp = A[k][p], akq = A[k][q];
+    A[k][p] = c * akp - s * akq;
+    A[k][q] = s * akp + c * akq;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double apk = A[p][k], aqk = A[q][k];
+    A[p][k] = c * apk - s * aqk;
+    A[q][k] = s * apk + c * aqk;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double vkp = V[k][p], vkq = V[k][q];
+    V[k][p] = c * vkp - s * vkq;
+    V[k][q] = s * vkp + c * vkq;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // per-correspondence math (closed form of gicp_cost_function.h:31-70
 // chained with Sophus' Dx_this_mul_exp_x_at_0, for C = I - (1-eps) n n^T)

@@ -348,5 +348,44 @@ hipError_t launch_se3_ops(int op, int n, const double* in, double* out, hipStrea
 hipError_t launch_transform_float(int n, const float* x, const float* y, const float* z, const Mat4f& M,
                                   float* ox, float* oy, float* oz, hipStream_t st);
 
+// ---- initial alignment without a pose prior (bootstrap_kernels.hip; driver: bootstrap.cpp) ----
+// The sort / scan wrappers follow rocPRIM's convention: temp == nullptr asks for the bytes.
+constexpr int kBootMaxK = 16;  // feature neighbours per source keypoint (k_correspondences)
+int boot_bounds_blocks(int n);
+// per workgroup of 256 points: min xyz, max xyz and count of the box-filtered points -> blk[block * 8 + 0..6]
+hipError_t launch_boot_bounds(int n, const float* x, const float* y, const float* z, double box_max, float* blk, hipStream_t st);
+// key[i] = voxel index << 32 | i for a kept point, ~0 otherwise
+hipError_t launch_boot_voxel_keys(int n, const float* x, const float* y, const float* z, double box_max, float inv_leaf,
+                                  const int* min_b, int dx, int dxy, unsigned long long* key, hipStream_t st);
+hipError_t boot_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, int n, hipStream_t st);
+hipError_t boot_sort_pairs(void* temp, size_t& bytes, const unsigned long long* kin, unsigned long long* kout, const int* vin,
+                           int* vout, int n, hipStream_t st);
+hipError_t boot_scan_int(void* temp, size_t& bytes, const int* in, int* out, int n, hipStream_t st);
+hipError_t boot_scan_ll(void* temp, size_t& bytes, const long long* in, long long* out, int n, hipStream_t st);
+hipError_t boot_segmented_sort(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long total,
+                               int segments, const long long* off, hipStream_t st);
+// sorted voxel keys -> first entry of every voxel (heads[n_out]) and the keypoint count *n_out
+hipError_t launch_boot_voxel_compact(int n_kept, const unsigned long long* key, int* flag, int* pos, int* heads, int* n_out,
+                                     void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t launch_boot_centroids(int n_kp, int n_kept, const int* heads, const unsigned long long* key, const float* x,
+                                 const float* y, const float* z, float* kx, float* ky, float* kz, hipStream_t st);
+// radius neighbourhoods on a uniform grid: cell keys + point ids (to be sorted by key), then count (fill = 0) or write the
+// unsorted lists of (d^2 bits << 32 | index) at off[i] (fill = 1); split: sorted lists -> index / d^2 arrays
+hipError_t launch_boot_cell_keys(int m, const float* x, const float* y, const float* z, float inv_cell, unsigned long long* key,
+                                 int* val, hipStream_t st);
+hipError_t launch_boot_radius(int fill, int m, const float* x, const float* y, const float* z, float inv_cell,
+                              const unsigned long long* skey, const int* sval, float r2, long long* count, const long long* off,
+                              unsigned long long* list, hipStream_t st);
+hipError_t launch_boot_split(long long total, const unsigned long long* list, int* idx, float* d2, hipStream_t st);
+hipError_t launch_boot_normals(int m, const float* x, const float* y, const float* z, const long long* off, const int* idx,
+                               double* n3, hipStream_t st);
+// SPFH (spfh: m * 33 doubles of scratch) and FPFH (fpfh: m * 33 floats)
+hipError_t launch_boot_fpfh(int m, const float* x, const float* y, const float* z, const double* n3, const long long* off,
+                            const int* idx, const float* d2, double* spfh, float* fpfh, hipStream_t st);
+// out[ns][k]: the k nearest target features of every source feature (-1: none / no feature)
+hipError_t launch_boot_feature_knn(int ns, const float* sf, int nt, const float* tf, int k, int* out, hipStream_t st);
+// err[h] = sum over the nq squared distances d2[h][.] of (e <= t ? e / t : 1)
+hipError_t launch_boot_error(int n_hyp, int nq, const float* d2, double t, double* err, hipStream_t st);
+
 }  // namespace sicp
 #endif

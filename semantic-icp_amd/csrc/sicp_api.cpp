@@ -1,6 +1,7 @@
 // sicp_api.cpp -- the C ABI of include/sicp.h (handles, clouds, align, test / bench hooks) on top of the engine
 // (engine.hpp).  There is no CPU fallback: every stage runs on the GPU and every entry point fails with
 // SICP_ERR_NO_DEVICE / SICP_ERR_HIP if it cannot.  Registration streams: streams.cpp.
+#include "bootstrap.hpp"
 #include "engine.hpp"
 
 using namespace sicp::host;
@@ -900,6 +901,39 @@ int sicp_synchronize(sicp_handle h) {
     SICPCHECK(set_device(h));
     HIPCHECK(hipStreamSynchronize(h->stream));
     return SICP_OK;
+  });
+}
+
+// ---- initial alignment without a pose prior (exec/bootstrap.h; bootstrap.cpp) ----------------------------------------
+int sicp_default_bootstrap_params(sicp_bootstrap_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    bootstrap_default_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_bootstrap(sicp_handle h, const sicp_bootstrap_params* p, double out_qt[7], sicp_bootstrap_info* info) {
+  return abi_guard(h, [&]() -> int {
+    if (!h) return SICP_ERR_INVALID_ARGUMENT;
+    return bootstrap_run(h, p, out_qt, info);
+  });
+}
+
+int sicp_bootstrap_keypoints(sicp_handle h, int which, const sicp_bootstrap_params* p, int32_t capacity, int64_t nbr_capacity,
+                             int32_t* n_keypoints, int64_t* n_nbrs, float* xyz3, double* normal3, float* fpfh33,
+                             int64_t* nbr_offsets, int32_t* nbr_idx) {
+  return abi_guard(h, [&]() -> int {
+    if (!h) return SICP_ERR_INVALID_ARGUMENT;
+    return bootstrap_keypoints(h, which, p, capacity, nbr_capacity, n_keypoints, n_nbrs, xyz3, normal3, fpfh33, nbr_offsets, nbr_idx);
+  });
+}
+
+int sicp_bootstrap_score(sicp_handle h, const sicp_bootstrap_params* p, int32_t n, const int32_t* src_idx, const int32_t* tgt_idx,
+                         double* M12, double* err, int32_t knn_capacity, int32_t* feat_knn) {
+  return abi_guard(h, [&]() -> int {
+    if (!h) return SICP_ERR_INVALID_ARGUMENT;
+    return bootstrap_score(h, p, n, src_idx, tgt_idx, M12, err, knn_capacity, feat_knn);
   });
 }
 
