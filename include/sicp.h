@@ -380,6 +380,20 @@ int sicp_default_bootstrap_params(sicp_bootstrap_params* p);
  * than nr_samples keypoints with features or the target none; SICP_ERR_INVALID_ARGUMENT for a bad parameter or a voxel
  * grid whose cell count overflows int32 (PCL silently returns the input there).  Nothing on the handle changes. */
 int sicp_bootstrap(sicp_handle h, const sicp_bootstrap_params* p, double out_qt[7], sicp_bootstrap_info* info);
+/* sicp_bootstrap for n pairs at once: pair i = handle hs[i]'s current source onto its current target, with the same
+ * params for every pair.  Per pair bit-identical to sicp_bootstrap(hs[i], p, ...): pose, info counts, best_iteration
+ * and best_error (the t_*_ms fields hold the batch's stage times, the same in every info).  status[n] (nullable)
+ * gets each pair's own code; the call returns SICP_OK when every pair succeeded, else the first failing pair's code.
+ * A pair that fails (SICP_ERR_NOT_READY: a handle without both clouds; SICP_ERR_TOO_FEW_POINTS; SICP_ERR_INVALID_ARGUMENT:
+ * a voxel grid that overflows int32) does not stop the others; its out_qt row and info are not written, and the message
+ * (sicp_last_error of its handle, and of hs[0] for the first failing pair) names the pair's index.  A failure of the call
+ * itself (HIP, memory) is every unfinished pair's status.  out_qt n*7; infos nullable.  Handles may be in any mode, may
+ * repeat, and may share clouds (sicp_share_cloud): a cloud's keypoints and features are computed once per call.  n has no
+ * upper bound (the work runs in groups of bounded scratch).  Refused before any work, with SICP_ERR_INVALID_ARGUMENT and
+ * nothing written: n < 1, a NULL array or handle, handles on different devices, bad params.  Nothing on any handle
+ * changes. */
+int sicp_bootstrap_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* p, double* out_qt, int32_t* status,
+                         sicp_bootstrap_info* infos);
 /* test / bench hook: the keypoints of cloud `which` with their normals, FPFH features and feature-radius
  * neighbour lists (CSR: nbr_offsets[n + 1], nbr_idx sorted by (d^2, index)).  Counts are always written; an output
  * array is written when it is non-NULL and its capacity (points / neighbour entries) suffices, otherwise the call

@@ -232,6 +232,8 @@ def lib():
             "sicp_synchronize": [C.c_void_p],
             "sicp_default_bootstrap_params": [C.POINTER(SicpBootstrapParams)],
             "sicp_bootstrap": [C.c_void_p, C.POINTER(SicpBootstrapParams), _dp, C.POINTER(SicpBootstrapInfo)],
+            "sicp_bootstrap_batch": [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(SicpBootstrapParams), _dp, _ip,
+                                     C.POINTER(SicpBootstrapInfo)],
             "sicp_bootstrap_keypoints": [C.c_void_p, C.c_int, C.POINTER(SicpBootstrapParams), C.c_int32, C.c_int64, _ip,
                                          C.POINTER(C.c_int64), _fp, _dp, _fp, C.POINTER(C.c_int64), _ip],
             "sicp_bootstrap_score": [C.c_void_p, C.POINTER(SicpBootstrapParams), C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, _ip],
@@ -535,6 +537,28 @@ def align_batch(engines, init_qts=None, want_stats: bool = True):
         msgs = "; ".join(m for m in (lib().sicp_last_error(e._h).decode() for e in engines) if m)
         raise RuntimeError(f"sicp_align_batch failed: {_strerror(rc)} ({rc}) {msgs}")
     return [(out[p].copy(), (sts[p].as_dict() if want_stats else {"outer_iters": int(its[p])})) for p in range(n)]
+
+
+def bootstrap_batch(engines, params: SicpBootstrapParams | None = None):
+    """sicp_bootstrap_batch: Engine.bootstrap for every engine's pair in one call (the same params for all).
+    Returns [(status, qt, info)] in the order of `engines`: per pair identical to Engine.bootstrap, qt None and info
+    {"error": message} for a pair that failed.  Raises SicpError only when the whole call is refused."""
+    n = len(engines)
+    p = params if params is not None else default_bootstrap_params()
+    out = np.empty((max(n, 1), 7))
+    unset = -(2 ** 31)
+    status = np.full(max(n, 1), unset, dtype=np.int32)
+    infos = (SicpBootstrapInfo * max(n, 1))()
+    rc = lib().sicp_bootstrap_batch(_handles(engines) if n else None, n, C.byref(p), _ptr(out, _dp), _ptr(status, _ip), infos)
+    if rc != OK and (n == 0 or status[0] == unset):
+        raise SicpError(rc, "sicp_bootstrap_batch", lib().sicp_last_error(engines[0]._h).decode() if n else "")
+    res = []
+    for i in range(n):
+        if status[i] == OK:
+            res.append((OK, out[i].copy(), infos[i].as_dict()))
+        else:
+            res.append((int(status[i]), None, {"error": lib().sicp_last_error(engines[i]._h).decode()}))
+    return res
 
 
 def accumulate_batch(engines, qts, repeat: int = 1):

@@ -4,6 +4,15 @@
 // transforms solved on the host in f64, and all of them are scored on the device at once -- one K = 1 box-tree search per
 // hypothesis over a tree of the target keypoints, collected into the packet kernel's job launches, then one
 // truncated-error reduction.  Orders and precisions: INTEGRATION.md ("Bootstrap").
+//
+// Every call is a batch of pairs (sicp_bootstrap = a batch of one): each stage runs over all clouds / pairs of a group at
+// once -- the hot kernels as one job launch (kernels.h: BootCloudJob / BootPairJob), the rocPRIM sorts and scans queued
+// cloud after cloud -- with one host synchronisation per stage for the whole group.  A cloud shared by several pairs
+// (sicp_share_cloud) gets its keypoints and features once per call.
+#include <map>
+#include <set>
+#include <thread>
+
 #include "bootstrap.hpp"
 
 namespace sicp {
@@ -12,6 +21,14 @@ namespace host {
 namespace {
 
 typedef unsigned long long u64;
+
+// pairs and new cloud points per group: what bounds the scratch of a call whatever its number of pairs
+constexpr int kGroupPairs = 64;
+constexpr long long kGroupPoints = 16ll << 20;
+// search outputs (one per source keypoint and hypothesis) in flight per scoring chunk
+constexpr long long kScoreOutputs = 32ll << 20;
+// host threads drawing the hypotheses of a group's pairs (a GPU host command gets 16 CPUs: never sized by the machine)
+constexpr int kGenThreads = 8;
 
 // the keypoints of one cloud and their features, device-resident (keypoint order)
 struct BootCloud {
@@ -28,7 +45,7 @@ struct BootCloud {
   DevBuf<float> fpfh;
 };
 
-// every scratch buffer of one call (arena blocks: recycled between calls)
+// every scratch buffer of one cloud (arena blocks: recycled between calls)
 struct BootScratch {
   DevBuf<float> x, y, z, blk;
   DevBuf<u64> key, key2;
@@ -43,14 +60,82 @@ struct BootScratch {
   DevBuf<float> nd2;
 };
 
+// one distinct cloud of a call: its keypoints, features and what the stages hand each other
+struct CloudWork {
+  const Cloud* c = nullptr;
+  int status = SICP_OK;
+  std::string msg;  // why status != SICP_OK (without the entry point's name)
+  BootCloud k;
+  BootScratch s;
+  std::vector<char> valid;      // keypoints with a feature
+  std::shared_ptr<Cloud> tree;  // the keypoints as an engine cloud: query set and search tree of the scoring
+  // stage hand-over
+  std::vector<float> blk;
+  long long n_kept = 0;
+  int n_kp = 0;
+  size_t scan_bytes = 0;
+  std::vector<long long> cnt;
+  long long total = 0;
+  std::vector<double> n3;
+  bool live() const { return status == SICP_OK; }
+  void fail(int st, std::string why) { status = st; msg = std::move(why); }
+};
+
+// one pair of a call
+struct PairWork {
+  int index = 0;
+  CloudWork *S = nullptr, *T = nullptr;
+  int status = SICP_OK;
+  bool done = false;  // its pose and info are written
+  std::string msg;
+  std::vector<int> knn;  // [n_source][k]
+  int k_eff = 0;         // k clamped to the target keypoints with a feature
+  std::vector<int> src_valid;
+  int tgt_valid = 0;
+  int n_hyp = 0;
+  std::vector<double> M, Q, err;  // [n_hyp][12], [n_hyp][4], [n_hyp]
+  size_t knn_at = 0, err_at = 0;  // places in the stage buffers
+};
+
+// one launch's job table: the jobs and the inclusive prefix of their block counts, uploaded as one block of device memory.
+// The host copy stays alive with the table (a table lives until its stage synchronises).
+template <class J>
+struct JobTable {
+  std::vector<J> jobs;
+  std::vector<int> end;
+  int blocks = 0;
+  std::vector<unsigned char> host;
+  DevBuf<unsigned char> dev;
+  size_t end_at = 0;
+  void add(const J& j, long long nblocks) {
+    if (nblocks <= 0) return;
+    jobs.push_back(j);
+    blocks += (int)nblocks;
+    end.push_back(blocks);
+  }
+  int nj() const { return (int)jobs.size(); }
+  hipError_t upload(hipStream_t st) {
+    if (jobs.empty()) return hipSuccess;
+    end_at = (sizeof(J) * jobs.size() + 255) & ~(size_t)255;
+    host.assign(end_at + sizeof(int) * end.size(), 0);
+    std::memcpy(host.data(), jobs.data(), sizeof(J) * jobs.size());
+    std::memcpy(host.data() + end_at, end.data(), sizeof(int) * end.size());
+    hipError_t e = dev.reserve(host.size());
+    if (e != hipSuccess) return e;
+    return hipMemcpyAsync(dev.p, host.data(), host.size(), hipMemcpyHostToDevice, st);
+  }
+  const J* d_jobs() const { return reinterpret_cast<const J*>(dev.p); }
+  const int* d_end() const { return reinterpret_cast<const int*>(dev.p + end_at); }
+};
+
 int temp_reserve(sicp_context* h, BootScratch& s, size_t bytes) {
   HIPCHECK(s.temp.reserve(bytes + 256));
   return SICP_OK;
 }
 
-int check_params(sicp_context* h, const sicp_bootstrap_params& p) {
+int check_params(sicp_context* h, const sicp_bootstrap_params& p, const char* who) {
   auto bad = [&](const char* what) {
-    h->last_error = std::string("sicp_bootstrap: ") + what;
+    h->last_error = std::string(who) + ": " + what;
     return SICP_ERR_INVALID_ARGUMENT;
   };
   if (std::isnan(p.box_max)) return bad("box_max is NaN");
@@ -62,135 +147,6 @@ int check_params(sicp_context* h, const sicp_bootstrap_params& p) {
   if (p.max_iterations < 1) return bad("max_iterations must be >= 1");
   if (p.nr_samples < 3 || p.nr_samples > kBootMaxSamples) return bad("nr_samples must be in 3..8");
   if (p.k_correspondences < 1 || p.k_correspondences > kBootMaxK) return bad("k_correspondences must be in 1..16");
-  return SICP_OK;
-}
-
-// box filter + voxel grid: keypoints = centroids of the occupied voxels in ascending voxel index
-int voxel_keypoints(sicp_context* h, const Cloud& c, const sicp_bootstrap_params& p, BootScratch& s, BootCloud& out) {
-  const int n = c.n;
-  const hipStream_t st = h->stream;
-  out.n = 0;
-  if (n <= 0) return SICP_OK;
-  if (c.hx.size() < (size_t)n) return SICP_ERR_NOT_READY;
-  HIPCHECK(s.x.reserve(n)); HIPCHECK(s.y.reserve(n)); HIPCHECK(s.z.reserve(n));
-  HIPCHECK(hipMemcpyAsync(s.x.p, c.hx.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
-  HIPCHECK(hipMemcpyAsync(s.y.p, c.hy.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
-  HIPCHECK(hipMemcpyAsync(s.z.p, c.hz.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
-  const int nb = boot_bounds_blocks(n);
-  HIPCHECK(s.blk.reserve((size_t)nb * 8));
-  HIPCHECK(launch_boot_bounds(n, s.x.p, s.y.p, s.z.p, p.box_max, s.blk.p, st));
-  std::vector<float> blk((size_t)nb * 8);
-  HIPCHECK(hipMemcpyAsync(blk.data(), s.blk.p, sizeof(float) * blk.size(), hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipStreamSynchronize(st));
-  const float inf = std::numeric_limits<float>::infinity();
-  float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
-  long long n_kept = 0;
-  for (int b = 0; b < nb; ++b) {
-    for (int d = 0; d < 3; ++d) { lo[d] = std::min(lo[d], blk[b * 8 + d]); hi[d] = std::max(hi[d], blk[b * 8 + 3 + d]); }
-    n_kept += (long long)blk[b * 8 + 6];
-  }
-  if (n_kept == 0) return SICP_OK;
-  // PCL VoxelGrid::applyFilter: min_b / max_b = floor(min_p / max_p * (1 / leaf)) in f32
-  const float inv_leaf = 1.0f / (float)p.leaf_size;
-  int min_b[3];
-  long long div[3];
-  for (int d = 0; d < 3; ++d) {
-    const float a = std::floor(lo[d] * inv_leaf), b = std::floor(hi[d] * inv_leaf);
-    if (!(std::fabs(a) < 1073741824.f) || !(std::fabs(b) < 1073741824.f)) {
-      h->last_error = "sicp_bootstrap: the voxel grid of leaf size " + std::to_string(p.leaf_size) + " has coordinates beyond int32";
-      return SICP_ERR_INVALID_ARGUMENT;
-    }
-    min_b[d] = (int)a;
-    div[d] = (long long)b - (long long)a + 1;
-  }
-  if (div[0] * div[1] > (long long)INT32_MAX || div[0] * div[1] * div[2] > (long long)INT32_MAX) {
-    h->last_error = "sicp_bootstrap: leaf size " + std::to_string(p.leaf_size) + " is too small for the cloud: the voxel grid (" +
-                    std::to_string(div[0]) + " x " + std::to_string(div[1]) + " x " + std::to_string(div[2]) + ") overflows int32";
-    return SICP_ERR_INVALID_ARGUMENT;
-  }
-  HIPCHECK(s.key.reserve(n)); HIPCHECK(s.key2.reserve(n));
-  HIPCHECK(launch_boot_voxel_keys(n, s.x.p, s.y.p, s.z.p, p.box_max, inv_leaf, min_b, (int)div[0], (int)(div[0] * div[1]), s.key.p, st));
-  size_t sort_bytes = 0, scan_bytes = 0;
-  HIPCHECK(boot_sort_keys(nullptr, sort_bytes, s.key.p, s.key2.p, n, st));
-  HIPCHECK(boot_scan_int(nullptr, scan_bytes, s.flag.p, s.pos.p, (int)n_kept, st));
-  SICPCHECK(temp_reserve(h, s, std::max(sort_bytes, scan_bytes)));
-  HIPCHECK(boot_sort_keys(s.temp.p, sort_bytes, s.key.p, s.key2.p, n, st));
-  HIPCHECK(s.flag.reserve(n_kept)); HIPCHECK(s.pos.reserve(n_kept)); HIPCHECK(s.heads.reserve(n_kept)); HIPCHECK(s.nout.reserve(1));
-  HIPCHECK(launch_boot_voxel_compact((int)n_kept, s.key2.p, s.flag.p, s.pos.p, s.heads.p, s.nout.p, s.temp.p, scan_bytes, st));
-  int n_kp = 0;
-  HIPCHECK(hipMemcpyAsync(&n_kp, s.nout.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipStreamSynchronize(st));
-  out.n = n_kp;
-  const size_t m = (size_t)std::max(n_kp, 1);
-  HIPCHECK(out.kx.reserve(m)); HIPCHECK(out.ky.reserve(m)); HIPCHECK(out.kz.reserve(m));
-  HIPCHECK(launch_boot_centroids(n_kp, (int)n_kept, s.heads.p, s.key2.p, s.x.p, s.y.p, s.z.p, out.kx.p, out.ky.p, out.kz.p, st));
-  out.hx.resize(n_kp); out.hy.resize(n_kp); out.hz.resize(n_kp);
-  HIPCHECK(hipMemcpyAsync(out.hx.data(), out.kx.p, sizeof(float) * n_kp, hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipMemcpyAsync(out.hy.data(), out.ky.p, sizeof(float) * n_kp, hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipMemcpyAsync(out.hz.data(), out.kz.p, sizeof(float) * n_kp, hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipStreamSynchronize(st));
-  return SICP_OK;
-}
-
-// radius-r neighbourhoods of the keypoints among themselves, CSR sorted by (d^2, index): count, scan, fill, segmented sort
-int radius_lists(sicp_context* h, const BootCloud& k, double r, BootScratch& s, DevBuf<long long>& off, DevBuf<int>& idx,
-                 DevBuf<float>& d2, long long* total_out, int* max_out) {
-  const int m = k.n;
-  const hipStream_t st = h->stream;
-  const float r2 = (float)(r * r);
-  const float inv_cell = 1.0f / ((float)r * 1.001f);  // cells a little larger than r: every neighbour is in an adjacent cell
-  HIPCHECK(s.key.reserve(m)); HIPCHECK(s.key2.reserve(m)); HIPCHECK(s.val.reserve(m)); HIPCHECK(s.val2.reserve(m));
-  HIPCHECK(s.cnt.reserve((size_t)m + 1)); HIPCHECK(off.reserve((size_t)m + 1));
-  HIPCHECK(launch_boot_cell_keys(m, k.kx.p, k.ky.p, k.kz.p, inv_cell, s.key.p, s.val.p, st));
-  size_t bytes = 0, scan_bytes = 0;
-  HIPCHECK(boot_sort_pairs(nullptr, bytes, s.key.p, s.key2.p, s.val.p, s.val2.p, m, st));
-  HIPCHECK(boot_scan_ll(nullptr, scan_bytes, s.cnt.p, off.p, m + 1, st));
-  SICPCHECK(temp_reserve(h, s, std::max(bytes, scan_bytes)));
-  HIPCHECK(boot_sort_pairs(s.temp.p, bytes, s.key.p, s.key2.p, s.val.p, s.val2.p, m, st));
-  HIPCHECK(hipMemsetAsync(s.cnt.p + m, 0, sizeof(long long), st));
-  HIPCHECK(launch_boot_radius(0, m, k.kx.p, k.ky.p, k.kz.p, inv_cell, s.key2.p, s.val2.p, r2, s.cnt.p, nullptr, nullptr, st));
-  HIPCHECK(boot_scan_ll(s.temp.p, scan_bytes, s.cnt.p, off.p, m + 1, st));
-  std::vector<long long> cnt(m);
-  long long total = 0;
-  HIPCHECK(hipMemcpyAsync(cnt.data(), s.cnt.p, sizeof(long long) * m, hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipMemcpyAsync(&total, off.p + m, sizeof(long long), hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipStreamSynchronize(st));
-  if (total > (long long)INT32_MAX) {
-    h->last_error = "sicp_bootstrap: the radius neighbourhoods hold more than 2^31 entries";
-    return SICP_ERR_INVALID_ARGUMENT;
-  }
-  long long mx = 0;
-  for (long long v : cnt) mx = std::max(mx, v);
-  HIPCHECK(s.list.reserve((size_t)total + 1)); HIPCHECK(s.list2.reserve((size_t)total + 1));
-  HIPCHECK(idx.reserve((size_t)total + 1)); HIPCHECK(d2.reserve((size_t)total + 1));
-  HIPCHECK(launch_boot_radius(1, m, k.kx.p, k.ky.p, k.kz.p, inv_cell, s.key2.p, s.val2.p, r2, nullptr, off.p, s.list.p, st));
-  bytes = 0;
-  HIPCHECK(boot_segmented_sort(nullptr, bytes, s.list.p, s.list2.p, total, m, off.p, st));
-  SICPCHECK(temp_reserve(h, s, bytes));
-  HIPCHECK(boot_segmented_sort(s.temp.p, bytes, s.list.p, s.list2.p, total, m, off.p, st));
-  HIPCHECK(launch_boot_split(total, s.list2.p, idx.p, d2.p, st));
-  *total_out = total;
-  *max_out = (int)mx;
-  return SICP_OK;
-}
-
-// normals (normal radius) and FPFH (feature radius) of a keypoint cloud
-int keypoint_features(sicp_context* h, const sicp_bootstrap_params& p, BootScratch& s, BootCloud& k) {
-  const int m = k.n;
-  if (m <= 0) return SICP_OK;
-  const hipStream_t st = h->stream;
-  HIPCHECK(k.n3.reserve((size_t)m * 3)); HIPCHECK(k.fpfh.reserve((size_t)m * 33)); HIPCHECK(s.spfh.reserve((size_t)m * 33));
-  SICPCHECK(radius_lists(h, k, p.feature_radius, s, k.off, k.idx, k.d2, &k.n_nbrs, &k.max_nbrs));
-  if (p.normal_radius == p.feature_radius) {
-    HIPCHECK(launch_boot_normals(m, k.kx.p, k.ky.p, k.kz.p, k.off.p, k.idx.p, k.n3.p, st));
-  } else {
-    long long nt = 0;
-    int nm = 0;
-    SICPCHECK(radius_lists(h, k, p.normal_radius, s, s.noff, s.nidx, s.nd2, &nt, &nm));
-    k.max_nbrs = std::max(k.max_nbrs, nm);
-    HIPCHECK(launch_boot_normals(m, k.kx.p, k.ky.p, k.kz.p, s.noff.p, s.nidx.p, k.n3.p, st));
-  }
-  HIPCHECK(launch_boot_fpfh(m, k.kx.p, k.ky.p, k.kz.p, k.n3.p, k.off.p, k.idx.p, k.d2.p, s.spfh.p, k.fpfh.p, st));
   return SICP_OK;
 }
 
@@ -271,103 +227,544 @@ void rigid_from_pairs(int n, const double* s, const double* t, double q[4], doub
   }
 }
 
-// the truncated error of n hypotheses (rows 0..2 of their 4x4 matrices): one K = 1 search of every source keypoint per
-// hypothesis on a box tree of the target keypoints, collected into job launches, then one reduction per batch
-int score_hypotheses(sicp_context* h, const sicp_bootstrap_params& p, const BootCloud& S, const BootCloud& T, int n,
-                     const double* M12, double* err) {
+// box filter + voxel grid of every cloud: keypoints = centroids of the occupied voxels in ascending voxel index.  Three
+// synchronisations for all clouds: the bounds, the keypoint counts, the keypoints' host copies.
+int voxel_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vector<CloudWork*>& W) {
   const hipStream_t st = h->stream;
-  BootParamsScope scope(h);
-  std::shared_ptr<Cloud> qc = acquire_cloud(h->device), tc = acquire_cloud(h->device);
-  const StridedCloud qs = {(const char*)S.hx.data(), (const char*)S.hy.data(), (const char*)S.hz.data(), nullptr, 4, 4};
-  const StridedCloud ts = {(const char*)T.hx.data(), (const char*)T.hy.data(), (const char*)T.hz.data(), nullptr, 4, 4};
-  SICPCHECK(stage_cloud(h, *qc, S.n, qs));
-  qc->is_set = true; qc->layout = -1;
-  SICPCHECK(prepare_cloud(h, *qc));
-  SICPCHECK(stage_cloud(h, *tc, T.n, ts));
-  tc->is_set = true; tc->layout = -1;
-  SICPCHECK(prepare_cloud(h, *tc));
-  SICPCHECK(cloud_wait(h, *qc));
-  SICPCHECK(cloud_wait(h, *tc));
-  const int nq = qc->n;
-  const int batch = (int)std::max<long long>(1, std::min<long long>(n, (32ll << 20) / std::max(nq, 1)));
-  DevBuf<int> oi;
-  DevBuf<float> od;
-  DevBuf<double> derr;
-  HIPCHECK(oi.reserve((size_t)batch * nq)); HIPCHECK(od.reserve((size_t)batch * nq)); HIPCHECK(derr.reserve((size_t)n));
-  const float inf = std::numeric_limits<float>::infinity();
-  const double t = (double)(float)p.max_corr_distance;
-  for (int b0 = 0; b0 < n; b0 += batch) {
-    const int cnt = std::min(batch, n - b0);
-    JobCollector jc;
-    {
-      CollectScope cs(h, &jc);
-      for (int i = 0; i < cnt; ++i)
-        SICPCHECK(run_nn(h, 1, *qc, 0, nq, M12 + 12 * (size_t)(b0 + i), *tc, 0, false, inf, oi.p + (size_t)i * nq,
-                         od.p + (size_t)i * nq, 0, st));
-    }
-    HIPCHECK(sicp::launch_bvh_knn_packet_jobs(jc.knn_K[0], jc.knn[0].data(), (int)jc.knn[0].size(), st));
-    HIPCHECK(launch_boot_error(cnt, nq, od.p, t, derr.p + b0, st));
+  for (CloudWork* w : W) {
+    const Cloud& c = *w->c;
+    const int n = c.n;
+    w->k.n = 0;
+    w->n_kept = 0;
+    if (n <= 0) continue;
+    if (c.hx.size() < (size_t)n) { w->fail(SICP_ERR_NOT_READY, "a cloud has no host copy"); continue; }
+    BootScratch& s = w->s;
+    HIPCHECK(s.x.reserve(n)); HIPCHECK(s.y.reserve(n)); HIPCHECK(s.z.reserve(n));
+    HIPCHECK(hipMemcpyAsync(s.x.p, c.hx.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(s.y.p, c.hy.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(s.z.p, c.hz.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
+    const int nb = boot_bounds_blocks(n);
+    HIPCHECK(s.blk.reserve((size_t)nb * 8));
+    HIPCHECK(launch_boot_bounds(n, s.x.p, s.y.p, s.z.p, p.box_max, s.blk.p, st));
+    w->blk.assign((size_t)nb * 8, 0.f);
+    HIPCHECK(hipMemcpyAsync(w->blk.data(), s.blk.p, sizeof(float) * w->blk.size(), hipMemcpyDeviceToHost, st));
   }
-  HIPCHECK(hipMemcpyAsync(err, derr.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipStreamSynchronize(st));
+  const float inv_leaf = 1.0f / (float)p.leaf_size;
+  for (CloudWork* w : W) {
+    if (!w->live() || w->c->n <= 0) continue;
+    const int n = w->c->n;
+    const int nb = boot_bounds_blocks(n);
+    const float inf = std::numeric_limits<float>::infinity();
+    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+    long long n_kept = 0;
+    for (int b = 0; b < nb; ++b) {
+      for (int d = 0; d < 3; ++d) { lo[d] = std::min(lo[d], w->blk[b * 8 + d]); hi[d] = std::max(hi[d], w->blk[b * 8 + 3 + d]); }
+      n_kept += (long long)w->blk[b * 8 + 6];
+    }
+    if (n_kept == 0) continue;
+    // PCL VoxelGrid::applyFilter: min_b / max_b = floor(min_p / max_p * (1 / leaf)) in f32
+    int min_b[3];
+    long long div[3];
+    bool beyond = false;
+    for (int d = 0; d < 3; ++d) {
+      const float a = std::floor(lo[d] * inv_leaf), b = std::floor(hi[d] * inv_leaf);
+      if (!(std::fabs(a) < 1073741824.f) || !(std::fabs(b) < 1073741824.f)) { beyond = true; break; }
+      min_b[d] = (int)a;
+      div[d] = (long long)b - (long long)a + 1;
+    }
+    if (beyond) {
+      w->fail(SICP_ERR_INVALID_ARGUMENT, "the voxel grid of leaf size " + std::to_string(p.leaf_size) + " has coordinates beyond int32");
+      continue;
+    }
+    if (div[0] * div[1] > (long long)INT32_MAX || div[0] * div[1] * div[2] > (long long)INT32_MAX) {
+      w->fail(SICP_ERR_INVALID_ARGUMENT, "leaf size " + std::to_string(p.leaf_size) + " is too small for the cloud: the voxel grid (" +
+                                             std::to_string(div[0]) + " x " + std::to_string(div[1]) + " x " + std::to_string(div[2]) +
+                                             ") overflows int32");
+      continue;
+    }
+    w->n_kept = n_kept;
+    BootScratch& s = w->s;
+    HIPCHECK(s.key.reserve(n)); HIPCHECK(s.key2.reserve(n));
+    HIPCHECK(launch_boot_voxel_keys(n, s.x.p, s.y.p, s.z.p, p.box_max, inv_leaf, min_b, (int)div[0], (int)(div[0] * div[1]), s.key.p, st));
+    size_t sort_bytes = 0, scan_bytes = 0;
+    HIPCHECK(boot_sort_keys(nullptr, sort_bytes, s.key.p, s.key2.p, n, st));
+    HIPCHECK(boot_scan_int(nullptr, scan_bytes, s.flag.p, s.pos.p, (int)n_kept, st));
+    SICPCHECK(temp_reserve(h, s, std::max(sort_bytes, scan_bytes)));
+    HIPCHECK(boot_sort_keys(s.temp.p, sort_bytes, s.key.p, s.key2.p, n, st));
+    HIPCHECK(s.flag.reserve(n_kept)); HIPCHECK(s.pos.reserve(n_kept)); HIPCHECK(s.heads.reserve(n_kept)); HIPCHECK(s.nout.reserve(1));
+    HIPCHECK(launch_boot_voxel_compact((int)n_kept, s.key2.p, s.flag.p, s.pos.p, s.heads.p, s.nout.p, s.temp.p, scan_bytes, st));
+    w->n_kp = 0;
+    HIPCHECK(hipMemcpyAsync(&w->n_kp, s.nout.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHECK(hipStreamSynchronize(st));
+  for (CloudWork* w : W) {
+    if (!w->live() || w->n_kept == 0) continue;
+    BootScratch& s = w->s;
+    BootCloud& out = w->k;
+    const int n_kp = w->n_kp;
+    out.n = n_kp;
+    const size_t m = (size_t)std::max(n_kp, 1);
+    HIPCHECK(out.kx.reserve(m)); HIPCHECK(out.ky.reserve(m)); HIPCHECK(out.kz.reserve(m));
+    HIPCHECK(launch_boot_centroids(n_kp, (int)w->n_kept, s.heads.p, s.key2.p, s.x.p, s.y.p, s.z.p, out.kx.p, out.ky.p, out.kz.p, st));
+    out.hx.resize(n_kp); out.hy.resize(n_kp); out.hz.resize(n_kp);
+    HIPCHECK(hipMemcpyAsync(out.hx.data(), out.kx.p, sizeof(float) * n_kp, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(out.hy.data(), out.ky.p, sizeof(float) * n_kp, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(out.hz.data(), out.kz.p, sizeof(float) * n_kp, hipMemcpyDeviceToHost, st));
+  }
   HIPCHECK(hipStreamSynchronize(st));
   return SICP_OK;
 }
 
-// keypoints + features of both clouds and the feature k-NN of every source keypoint
-struct BootState {
-  BootCloud k[2];
-  std::vector<int> knn;  // [n_source][k]
-  int k_eff = 0;         // k clamped to the target keypoints with a feature
-  std::vector<int> src_valid;
-  int tgt_valid = 0;
-};
+// radius-r neighbourhoods of every cloud's keypoints among themselves, CSR sorted by (d^2, index): count (one job launch),
+// scan, fill (one job launch), segmented sort.  One synchronisation (the list totals) for all clouds.  normal = 0: the
+// feature radius' lists (k.off / idx / d2), 1: the normal radius' own (s.noff / nidx / nd2)
+int radius_stage(sicp_context* h, double r, int normal, const std::vector<CloudWork*>& W) {
+  const hipStream_t st = h->stream;
+  const float r2 = (float)(r * r);
+  const float inv_cell = 1.0f / ((float)r * 1.001f);  // cells a little larger than r: every neighbour is in an adjacent cell
+  std::vector<CloudWork*> L;
+  for (CloudWork* w : W)
+    if (w->live() && w->k.n > 0) L.push_back(w);
+  auto lists = [&](CloudWork* w, DevBuf<long long>*& off, DevBuf<int>*& idx, DevBuf<float>*& d2) {
+    if (normal) { off = &w->s.noff; idx = &w->s.nidx; d2 = &w->s.nd2; }
+    else { off = &w->k.off; idx = &w->k.idx; d2 = &w->k.d2; }
+  };
+  auto job_of = [&](CloudWork* w) {
+    BootCloudJob j;
+    std::memset(&j, 0, sizeof j);
+    j.m = w->k.n;
+    j.x = w->k.kx.p; j.y = w->k.ky.p; j.z = w->k.kz.p;
+    j.inv_cell = inv_cell; j.r2 = r2;
+    j.skey = w->s.key2.p; j.sval = w->s.val2.p;
+    return j;
+  };
+  JobTable<BootCloudJob> count;
+  for (CloudWork* w : L) {
+    const int m = w->k.n;
+    BootScratch& s = w->s;
+    DevBuf<long long>* off; DevBuf<int>* idx; DevBuf<float>* d2;
+    lists(w, off, idx, d2);
+    HIPCHECK(s.key.reserve(m)); HIPCHECK(s.key2.reserve(m)); HIPCHECK(s.val.reserve(m)); HIPCHECK(s.val2.reserve(m));
+    HIPCHECK(s.cnt.reserve((size_t)m + 1)); HIPCHECK(off->reserve((size_t)m + 1));
+    HIPCHECK(launch_boot_cell_keys(m, w->k.kx.p, w->k.ky.p, w->k.kz.p, inv_cell, s.key.p, s.val.p, st));
+    size_t bytes = 0;
+    w->scan_bytes = 0;
+    HIPCHECK(boot_sort_pairs(nullptr, bytes, s.key.p, s.key2.p, s.val.p, s.val2.p, m, st));
+    HIPCHECK(boot_scan_ll(nullptr, w->scan_bytes, s.cnt.p, off->p, m + 1, st));
+    SICPCHECK(temp_reserve(h, s, std::max(bytes, w->scan_bytes)));
+    HIPCHECK(boot_sort_pairs(s.temp.p, bytes, s.key.p, s.key2.p, s.val.p, s.val2.p, m, st));
+    HIPCHECK(hipMemsetAsync(s.cnt.p + m, 0, sizeof(long long), st));
+    BootCloudJob j = job_of(w);
+    j.count = s.cnt.p;
+    count.add(j, (m + 255) / 256);
+  }
+  HIPCHECK(count.upload(st));
+  HIPCHECK(launch_boot_radius_jobs(0, count.d_jobs(), count.d_end(), count.nj(), count.blocks, st));
+  for (CloudWork* w : L) {
+    const int m = w->k.n;
+    BootScratch& s = w->s;
+    DevBuf<long long>* off; DevBuf<int>* idx; DevBuf<float>* d2;
+    lists(w, off, idx, d2);
+    HIPCHECK(boot_scan_ll(s.temp.p, w->scan_bytes, s.cnt.p, off->p, m + 1, st));
+    w->cnt.assign(m, 0);
+    w->total = 0;
+    HIPCHECK(hipMemcpyAsync(w->cnt.data(), s.cnt.p, sizeof(long long) * m, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(&w->total, off->p + m, sizeof(long long), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHECK(hipStreamSynchronize(st));
+  JobTable<BootCloudJob> fill;
+  std::vector<CloudWork*> F;
+  for (CloudWork* w : L) {
+    if (w->total > (long long)INT32_MAX) { w->fail(SICP_ERR_INVALID_ARGUMENT, "the radius neighbourhoods hold more than 2^31 entries"); continue; }
+    long long mx = 0;
+    for (long long v : w->cnt) mx = std::max(mx, v);
+    if (normal) w->k.max_nbrs = std::max(w->k.max_nbrs, (int)mx);
+    else { w->k.n_nbrs = w->total; w->k.max_nbrs = (int)mx; }
+    BootScratch& s = w->s;
+    DevBuf<long long>* off; DevBuf<int>* idx; DevBuf<float>* d2;
+    lists(w, off, idx, d2);
+    HIPCHECK(s.list.reserve((size_t)w->total + 1)); HIPCHECK(s.list2.reserve((size_t)w->total + 1));
+    HIPCHECK(idx->reserve((size_t)w->total + 1)); HIPCHECK(d2->reserve((size_t)w->total + 1));
+    BootCloudJob j = job_of(w);
+    j.loff = off->p; j.list = s.list.p;
+    fill.add(j, (w->k.n + 255) / 256);
+    F.push_back(w);
+  }
+  HIPCHECK(fill.upload(st));
+  HIPCHECK(launch_boot_radius_jobs(1, fill.d_jobs(), fill.d_end(), fill.nj(), fill.blocks, st));
+  for (CloudWork* w : F) {
+    BootScratch& s = w->s;
+    DevBuf<long long>* off; DevBuf<int>* idx; DevBuf<float>* d2;
+    lists(w, off, idx, d2);
+    size_t bytes = 0;
+    HIPCHECK(boot_segmented_sort(nullptr, bytes, s.list.p, s.list2.p, w->total, w->k.n, off->p, st));
+    SICPCHECK(temp_reserve(h, s, bytes));
+    HIPCHECK(boot_segmented_sort(s.temp.p, bytes, s.list.p, s.list2.p, w->total, w->k.n, off->p, st));
+    HIPCHECK(launch_boot_split(w->total, s.list2.p, idx->p, d2->p, st));
+  }
+  // (the tables' host copies live until here: the stream is synchronised by the caller's next stage before they go)
+  HIPCHECK(hipStreamSynchronize(st));
+  return SICP_OK;
+}
+
+// normals (normal radius) and FPFH (feature radius) of every cloud's keypoints: one job launch each; then which
+// keypoints have a feature (one synchronisation)
+int feature_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vector<CloudWork*>& W) {
+  const hipStream_t st = h->stream;
+  SICPCHECK(radius_stage(h, p.feature_radius, 0, W));
+  const bool own_normal_lists = p.normal_radius != p.feature_radius;
+  if (own_normal_lists) SICPCHECK(radius_stage(h, p.normal_radius, 1, W));
+  JobTable<BootCloudJob> nrm, pts;
+  for (CloudWork* w : W) {
+    if (!w->live() || w->k.n <= 0) continue;
+    BootCloud& k = w->k;
+    const int m = k.n;
+    HIPCHECK(k.n3.reserve((size_t)m * 3)); HIPCHECK(k.fpfh.reserve((size_t)m * 33)); HIPCHECK(w->s.spfh.reserve((size_t)m * 33));
+    BootCloudJob j;
+    std::memset(&j, 0, sizeof j);
+    j.m = m;
+    j.x = k.kx.p; j.y = k.ky.p; j.z = k.kz.p;
+    j.noff = own_normal_lists ? w->s.noff.p : k.off.p;
+    j.nidx = own_normal_lists ? w->s.nidx.p : k.idx.p;
+    j.off = k.off.p; j.idx = k.idx.p; j.d2 = k.d2.p;
+    j.n3 = k.n3.p; j.spfh = w->s.spfh.p; j.fpfh = k.fpfh.p;
+    nrm.add(j, (m + 255) / 256);
+    pts.add(j, m);
+  }
+  HIPCHECK(nrm.upload(st));
+  HIPCHECK(pts.upload(st));
+  HIPCHECK(launch_boot_normal_jobs(nrm.d_jobs(), nrm.d_end(), nrm.nj(), nrm.blocks, st));
+  HIPCHECK(launch_boot_fpfh_jobs(pts.d_jobs(), pts.d_end(), pts.nj(), pts.blocks, st));
+  for (CloudWork* w : W) {
+    if (!w->live()) continue;
+    w->n3.assign((size_t)w->k.n * 3, 0.0);
+    if (w->k.n > 0) HIPCHECK(hipMemcpyAsync(w->n3.data(), w->k.n3.p, sizeof(double) * w->n3.size(), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHECK(hipStreamSynchronize(st));
+  for (CloudWork* w : W) {
+    if (!w->live()) continue;
+    w->valid.resize(w->k.n);
+    for (int i = 0; i < w->k.n; ++i) w->valid[i] = !std::isnan(w->n3[3 * (size_t)i]);
+  }
+  return SICP_OK;
+}
+
+// the feature k-NN of every source keypoint of every pair: one job launch, one read-back
+int knn_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vector<PairWork*>& P) {
+  const hipStream_t st = h->stream;
+  const int k = p.k_correspondences;
+  JobTable<BootPairJob> tab;
+  size_t total = 0;
+  std::vector<PairWork*> L;
+  for (PairWork* q : P) {
+    const int ns = q->S->k.n, nt = q->T->k.n;
+    q->knn.assign((size_t)ns * k, -1);
+    if (ns > 0 && nt > 0) {
+      q->knn_at = total;
+      total += (size_t)ns * k;
+      L.push_back(q);
+    }
+  }
+  DevBuf<int> dk;
+  HIPCHECK(dk.reserve(std::max<size_t>(total, 1)));
+  for (PairWork* q : L) {
+    BootPairJob j;
+    std::memset(&j, 0, sizeof j);
+    j.n = q->S->k.n; j.nt = q->T->k.n;
+    j.sf = q->S->k.fpfh.p; j.tf = q->T->k.fpfh.p;
+    j.out = dk.p + q->knn_at;
+    tab.add(j, (j.n + 255) / 256);
+  }
+  HIPCHECK(tab.upload(st));
+  HIPCHECK(launch_boot_feature_knn_jobs(tab.d_jobs(), tab.d_end(), tab.nj(), tab.blocks, k, st));
+  for (PairWork* q : L) HIPCHECK(hipMemcpyAsync(q->knn.data(), dk.p + q->knn_at, sizeof(int) * q->knn.size(), hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipStreamSynchronize(st));
+  for (PairWork* q : P) {
+    q->src_valid.clear();
+    for (int i = 0; i < q->S->k.n; ++i)
+      if (q->S->valid[i]) q->src_valid.push_back(i);
+    q->tgt_valid = 0;
+    for (char v : q->T->valid) q->tgt_valid += v;
+    q->k_eff = std::min(k, q->tgt_valid);
+  }
+  return SICP_OK;
+}
+
+// SampleConsensusInitialAlignment::computeTransformation of one pair on the host: per iteration selectSamples, then one
+// random feature neighbour per sample (findSimilarFeatures), then the rigid transform of the pairs.  Depends on the
+// pair and the seed only.
+void draw_hypotheses(const sicp_bootstrap_params& p, PairWork& q) {
+  const int iters = p.max_iterations, k = p.k_correspondences, nr = p.nr_samples;
+  q.n_hyp = iters;
+  q.M.assign((size_t)iters * 12, 0.0);
+  q.Q.assign((size_t)iters * 4, 0.0);
+  BootRng rng{p.seed};
+  const int nv = (int)q.src_valid.size();
+  const BootCloud &S = q.S->k, &T = q.T->k;
+  std::vector<int> smp(nr);
+  double sp[3 * kBootMaxSamples], tp[3 * kBootMaxSamples];
+  for (int it = 0; it < iters; ++it) {
+    int got = 0, fails = 0;
+    float min_d = (float)p.min_sample_distance;
+    const int max_fails = 3 * nv;
+    while (got < nr) {
+      const int si = q.src_valid[rng.index(nv)];
+      bool ok = true;
+      for (int j = 0; j < got; ++j) {
+        const int sj = smp[j];
+        const float dx = S.hx[si] - S.hx[sj], dy = S.hy[si] - S.hy[sj], dz = S.hz[si] - S.hz[sj];
+        const float d = std::sqrt((dx * dx + dy * dy) + dz * dz);
+        if (si == sj || d < min_d) { ok = false; break; }
+      }
+      if (ok) { smp[got++] = si; fails = 0; } else ++fails;
+      if (fails >= max_fails) { min_d *= 0.5f; fails = 0; }
+    }
+    for (int j = 0; j < nr; ++j) {
+      const int tj = q.knn[(size_t)smp[j] * k + rng.index(q.k_eff)];
+      sp[3 * j] = S.hx[smp[j]]; sp[3 * j + 1] = S.hy[smp[j]]; sp[3 * j + 2] = S.hz[smp[j]];
+      tp[3 * j] = T.hx[tj]; tp[3 * j + 1] = T.hy[tj]; tp[3 * j + 2] = T.hz[tj];
+    }
+    rigid_from_pairs(nr, sp, tp, &q.Q[(size_t)it * 4], &q.M[(size_t)it * 12]);
+  }
+}
+
+// the pairs' hypotheses on up to kGenThreads host threads (each pair is drawn by one thread: the result does not depend on
+// how many there are)
+void draw_all(const sicp_bootstrap_params& p, const std::vector<PairWork*>& P) {
+  const int nt = std::min<int>(kGenThreads, (int)P.size());
+  if (nt <= 1) {
+    for (PairWork* q : P) draw_hypotheses(p, *q);
+    return;
+  }
+  std::vector<std::thread> th;
+  for (int t = 0; t < nt; ++t)
+    th.emplace_back([&, t] {
+      for (size_t i = t; i < P.size(); i += nt) draw_hypotheses(p, *P[i]);
+    });
+  for (std::thread& x : th) x.join();
+}
+
+// the keypoints of a cloud as an engine cloud (flat layout, box tree): the scoring's query set and search tree
+int keypoint_tree(sicp_context* h, CloudWork& w) {
+  if (w.tree) return SICP_OK;
+  w.tree = acquire_cloud(h->device);
+  const BootCloud& k = w.k;
+  const StridedCloud ks = {(const char*)k.hx.data(), (const char*)k.hy.data(), (const char*)k.hz.data(), nullptr, 4, 4};
+  SICPCHECK(stage_cloud(h, *w.tree, k.n, ks));
+  w.tree->is_set = true; w.tree->layout = -1;
+  return prepare_cloud(h, *w.tree);
+}
+
+// the truncated error of every pair's hypotheses (rows 0..2 of their 4x4 matrices): one K = 1 search of every source
+// keypoint per hypothesis on a box tree of the target keypoints.  The hypotheses of all pairs are cut into chunks of at most
+// kScoreOutputs search outputs; a chunk's searches are collected into the packet kernel's job launches, then one
+// error launch reduces the whole chunk.  One read-back at the end.
+int score_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vector<PairWork*>& P) {
+  const hipStream_t st = h->stream;
+  BootParamsScope scope(h);
+  for (PairWork* q : P) { SICPCHECK(keypoint_tree(h, *q->S)); SICPCHECK(keypoint_tree(h, *q->T)); }
+  for (PairWork* q : P) { SICPCHECK(cloud_wait(h, *q->S->tree)); SICPCHECK(cloud_wait(h, *q->T->tree)); }
+  size_t n_err = 0;
+  long long outputs = 0, max_nq = 1;
+  for (PairWork* q : P) {
+    q->err_at = n_err;
+    n_err += (size_t)q->n_hyp;
+    const long long nq = q->S->tree->n;
+    outputs += nq * q->n_hyp;
+    max_nq = std::max(max_nq, nq);
+  }
+  if (n_err == 0) return SICP_OK;
+  const long long cap = std::max(max_nq, std::min(outputs, kScoreOutputs));
+  DevBuf<int> oi;
+  DevBuf<float> od;
+  DevBuf<double> derr;
+  HIPCHECK(oi.reserve((size_t)cap)); HIPCHECK(od.reserve((size_t)cap)); HIPCHECK(derr.reserve(n_err));
+  const float inf = std::numeric_limits<float>::infinity();
+  const double t = (double)(float)p.max_corr_distance;
+  std::vector<std::unique_ptr<JobTable<BootPairJob>>> tables;  // (alive until the read-back's synchronisation)
+  JobCollector jc;
+  std::unique_ptr<JobTable<BootPairJob>> tab(new JobTable<BootPairJob>);
+  long long used = 0;
+  auto flush = [&]() -> int {
+    if (jc.knn[0].empty()) return SICP_OK;
+    HIPCHECK(sicp::launch_bvh_knn_packet_jobs(jc.knn_K[0], jc.knn[0].data(), (int)jc.knn[0].size(), st));
+    HIPCHECK(tab->upload(st));
+    HIPCHECK(launch_boot_error_jobs(tab->d_jobs(), tab->d_end(), tab->nj(), tab->blocks, t, st));
+    tables.push_back(std::move(tab));
+    tab.reset(new JobTable<BootPairJob>);
+    jc.knn[0].clear();
+    used = 0;
+    return SICP_OK;
+  };
+  for (PairWork* q : P) {
+    const Cloud &qc = *q->S->tree, &tc = *q->T->tree;
+    const int nq = qc.n;
+    for (int i0 = 0; i0 < q->n_hyp;) {
+      if (used > 0 && used + nq > cap) SICPCHECK(flush());
+      // this pair's hypotheses that fit into the chunk: one error job
+      const int cnt = (int)std::min<long long>(q->n_hyp - i0, std::max<long long>(1, (cap - used) / std::max(nq, 1)));
+      BootPairJob j;
+      std::memset(&j, 0, sizeof j);
+      j.n = cnt; j.nt = nq;
+      j.d2 = od.p + used;
+      j.err = derr.p + q->err_at + i0;
+      {
+        CollectScope cs(h, &jc);
+        for (int i = 0; i < cnt; ++i)
+          SICPCHECK(run_nn(h, 1, qc, 0, nq, q->M.data() + 12 * (size_t)(i0 + i), tc, 0, false, inf, oi.p + used + (size_t)i * nq,
+                           od.p + used + (size_t)i * nq, 0, st));
+      }
+      tab->add(j, cnt);
+      used += (long long)cnt * nq;
+      i0 += cnt;
+    }
+  }
+  SICPCHECK(flush());
+  std::vector<double> err(n_err);
+  HIPCHECK(hipMemcpyAsync(err.data(), derr.p, sizeof(double) * n_err, hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipStreamSynchronize(st));
+  for (PairWork* q : P) q->err.assign(err.begin() + q->err_at, err.begin() + q->err_at + q->n_hyp);
+  return SICP_OK;
+}
 
 int check_clouds(sicp_context* h) {
   if (!h->cl[0] || !h->cl[1] || !h->cloud(SICP_SOURCE).is_set || !h->cloud(SICP_TARGET).is_set) return SICP_ERR_NOT_READY;
   return SICP_OK;
 }
 
-int valid_flags(sicp_context* h, const BootCloud& k, std::vector<char>& ok) {
-  std::vector<double> n3((size_t)k.n * 3);
-  if (k.n > 0) HIPCHECK(hipMemcpyAsync(n3.data(), k.n3.p, sizeof(double) * n3.size(), hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  ok.resize(k.n);
-  for (int i = 0; i < k.n; ++i) ok[i] = !std::isnan(n3[3 * (size_t)i]);
+// keypoints + features of every cloud, then the feature k-NN of every pair whose clouds have them
+int prepare(sicp_context* h, const sicp_bootstrap_params& p, const std::vector<CloudWork*>& W, const std::vector<PairWork*>& P,
+            double* t_kp, double* t_feat, double* t_knn) {
+  const double t0 = now_ms();
+  SICPCHECK(voxel_stage(h, p, W));
+  const double t1 = now_ms();
+  SICPCHECK(feature_stage(h, p, W));
+  const double t2 = now_ms();
+  std::vector<PairWork*> L;
+  for (PairWork* q : P) {
+    if (q->status != SICP_OK) continue;
+    for (CloudWork* w : {q->S, q->T})
+      if (!w->live() && q->status == SICP_OK) { q->status = w->status; q->msg = w->msg; }
+    if (q->status == SICP_OK) L.push_back(q);
+  }
+  SICPCHECK(knn_stage(h, p, L));
+  const double t3 = now_ms();
+  if (t_kp) *t_kp += t1 - t0;
+  if (t_feat) *t_feat += t2 - t1;
+  if (t_knn) *t_knn += t3 - t2;
   return SICP_OK;
 }
 
-int prepare(sicp_context* h, const sicp_bootstrap_params& p, BootState& B, double* t_kp, double* t_feat, double* t_knn) {
-  BootScratch s;
-  double t0 = now_ms();
-  for (int w = 0; w < 2; ++w) SICPCHECK(voxel_keypoints(h, h->cloud(w), p, s, B.k[w]));
-  double t1 = now_ms();
-  for (int w = 0; w < 2; ++w) SICPCHECK(keypoint_features(h, p, s, B.k[w]));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  double t2 = now_ms();
-  std::vector<char> sv, tv;
-  SICPCHECK(valid_flags(h, B.k[0], sv));
-  SICPCHECK(valid_flags(h, B.k[1], tv));
-  B.src_valid.clear();
-  for (int i = 0; i < B.k[0].n; ++i)
-    if (sv[i]) B.src_valid.push_back(i);
-  B.tgt_valid = 0;
-  for (char v : tv) B.tgt_valid += v;
-  const int k = p.k_correspondences;
-  B.k_eff = std::min(k, B.tgt_valid);
-  const int ns = B.k[0].n;
-  B.knn.assign((size_t)ns * k, -1);
-  if (ns > 0 && B.k[1].n > 0) {
-    DevBuf<int> dk;
-    HIPCHECK(dk.reserve((size_t)ns * k));
-    HIPCHECK(launch_boot_feature_knn(ns, B.k[0].fpfh.p, B.k[1].n, B.k[1].fpfh.p, k, dk.p, h->stream));
-    HIPCHECK(hipMemcpyAsync(B.knn.data(), dk.p, sizeof(int) * B.knn.size(), hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
+// the whole bootstrap of n pairs (hs[i]'s source onto its target) on h's stream; status[i] per pair, messages prefixed
+// with `who` (and the pair's index when `indexed`).  Returns SICP_OK or the code of a failure of the call itself (HIP,
+// memory), which is then every unfinished pair's status too.
+int run_batch(sicp_context* h, sicp_handle* hs, int n, const sicp_bootstrap_params& p, double* out_qt, int32_t* status,
+              sicp_bootstrap_info* infos, const char* who, bool indexed) {
+  const double t_begin = now_ms();
+  std::vector<PairWork> pairs(n);
+  for (int i = 0; i < n; ++i) {
+    pairs[i].index = i;
+    if (check_clouds(hs[i]) != SICP_OK) { pairs[i].status = SICP_ERR_NOT_READY; pairs[i].msg = "the handle has no source or no target cloud"; }
   }
-  double t3 = now_ms();
-  if (t_kp) *t_kp = t1 - t0;
-  if (t_feat) *t_feat = t2 - t1;
-  if (t_knn) *t_knn = t3 - t2;
-  return SICP_OK;
+  double t_kp = 0, t_feat = 0, t_match = 0, t_score = 0;
+  std::map<const Cloud*, std::unique_ptr<CloudWork>> cache;  // this group's clouds (and the previous group's it shares)
+  int rc = SICP_OK;
+  int i0 = 0;
+  while (i0 < n && rc == SICP_OK) {
+    // the next group: up to kGroupPairs pairs whose clouds not yet prepared hold up to kGroupPoints points (at least one pair)
+    std::vector<PairWork*> G;
+    std::set<const Cloud*> need;
+    long long pts = 0;
+    int i1 = i0;
+    for (; i1 < n && (int)G.size() < kGroupPairs; ++i1) {
+      PairWork& q = pairs[i1];
+      if (q.status != SICP_OK) continue;
+      const Cloud *a = hs[i1]->cl[0].get(), *b = hs[i1]->cl[1].get();
+      long long add = 0;
+      for (const Cloud* c : {a, b})
+        if (!need.count(c) && !cache.count(c) && !(c == b && a == b)) add += c->n;  // (a == b: counted once)
+      if (!G.empty() && pts + add > kGroupPoints) break;
+      pts += add;
+      need.insert(a); need.insert(b);
+      G.push_back(&q);
+    }
+    i0 = i1;
+    for (auto it = cache.begin(); it != cache.end();) it = need.count(it->first) ? std::next(it) : cache.erase(it);
+    std::vector<CloudWork*> W;
+    for (PairWork* q : G) {
+      const Cloud* cs[2] = {hs[q->index]->cl[0].get(), hs[q->index]->cl[1].get()};
+      for (int w = 0; w < 2; ++w) {
+        std::unique_ptr<CloudWork>& slot = cache[cs[w]];
+        if (!slot) { slot.reset(new CloudWork); slot->c = cs[w]; W.push_back(slot.get()); }
+        (w == 0 ? q->S : q->T) = slot.get();
+      }
+    }
+    rc = prepare(h, p, W, G, &t_kp, &t_feat, &t_match);
+    if (rc != SICP_OK) break;
+    const double tm0 = now_ms();
+    std::vector<PairWork*> L;
+    for (PairWork* q : G) {
+      if (q->status != SICP_OK) continue;
+      if ((int)q->src_valid.size() < p.nr_samples || q->tgt_valid < 1) {
+        q->status = SICP_ERR_TOO_FEW_POINTS;
+        q->msg = std::to_string(q->src_valid.size()) + " source / " + std::to_string(q->tgt_valid) + " target keypoints with features";
+        continue;
+      }
+      L.push_back(q);
+    }
+    draw_all(p, L);
+    const double tm1 = now_ms();
+    t_match += tm1 - tm0;
+    rc = score_stage(h, p, L);
+    t_score += now_ms() - tm1;
+    if (rc != SICP_OK) break;
+    for (PairWork* q : L) {
+      int best = 0;
+      for (int it = 1; it < q->n_hyp; ++it)
+        if (q->err[it] < q->err[best]) best = it;
+      const double* Q = &q->Q[(size_t)best * 4];
+      double* o = out_qt + 7 * (size_t)q->index;
+      o[0] = Q[1]; o[1] = Q[2]; o[2] = Q[3]; o[3] = Q[0];
+      o[4] = q->M[(size_t)best * 12 + 3]; o[5] = q->M[(size_t)best * 12 + 7]; o[6] = q->M[(size_t)best * 12 + 11];
+      if (infos) {
+        sicp_bootstrap_info& info = infos[q->index];
+        info.n_source_keypoints = q->S->k.n;
+        info.n_target_keypoints = q->T->k.n;
+        info.max_neighbours = std::max(q->S->k.max_nbrs, q->T->k.max_nbrs);
+        info.best_iteration = best;
+        info.best_error = q->err[best];
+      }
+      q->err.clear(); q->M.clear(); q->Q.clear(); q->knn.clear();
+      q->done = true;
+    }
+  }
+  const std::string why = rc != SICP_OK ? h->last_error : std::string();
+  int first = -1;
+  for (int i = 0; i < n; ++i) {
+    PairWork& q = pairs[i];
+    if (q.status == SICP_OK && !q.done) { q.status = rc != SICP_OK ? rc : SICP_ERR_INTERNAL; q.msg = rc != SICP_OK ? why : "not run"; }
+    if (status) status[i] = q.status;
+    if (q.status != SICP_OK) {
+      const std::string m = std::string(who) + ": " + (indexed ? "pair " + std::to_string(i) + ": " : std::string()) + q.msg;
+      hs[i]->last_error = m;
+      if (first < 0) { first = i; h->last_error = m; }
+    }
+  }
+  if (infos) {
+    const double t_total = now_ms() - t_begin;
+    for (int i = 0; i < n; ++i) {
+      if (pairs[i].status != SICP_OK) continue;
+      sicp_bootstrap_info& info = infos[i];
+      info.t_keypoints_ms = t_kp;
+      info.t_features_ms = t_feat;
+      info.t_match_ms = t_match;
+      info.t_score_ms = t_score;
+      info.t_total_ms = t_total;
+    }
+  }
+  if (rc != SICP_OK) return rc;
+  return first < 0 ? SICP_OK : pairs[first].status;
 }
 
 }  // namespace
@@ -401,74 +798,35 @@ void bootstrap_default_params(sicp_bootstrap_params* p) {
 int bootstrap_run(sicp_context* h, const sicp_bootstrap_params* pp, double* out_qt, sicp_bootstrap_info* info) {
   if (!pp || !out_qt) return SICP_ERR_INVALID_ARGUMENT;
   const sicp_bootstrap_params p = *pp;
-  SICPCHECK(check_params(h, p));
+  SICPCHECK(check_params(h, p, "sicp_bootstrap"));
   SICPCHECK(set_device(h));
   SICPCHECK(check_clouds(h));
-  const double t_begin = now_ms();
-  BootState B;
-  double t_kp = 0, t_feat = 0, t_knn = 0;
-  SICPCHECK(prepare(h, p, B, &t_kp, &t_feat, &t_knn));
-  const int ns = B.k[0].n, nr = p.nr_samples;
-  if ((int)B.src_valid.size() < nr || B.tgt_valid < 1) {
-    h->last_error = "sicp_bootstrap: " + std::to_string(B.src_valid.size()) + " source / " + std::to_string(B.tgt_valid) +
-                    " target keypoints with features";
-    return SICP_ERR_TOO_FEW_POINTS;
-  }
-  // SampleConsensusInitialAlignment::computeTransformation: per iteration selectSamples, then one random feature
-  // neighbour per sample (findSimilarFeatures), then the rigid transform of the pairs
-  const double tm0 = now_ms();
-  const int iters = p.max_iterations, k = p.k_correspondences;
-  std::vector<double> M((size_t)iters * 12), Q((size_t)iters * 4);
-  BootRng rng{p.seed};
-  const int nv = (int)B.src_valid.size();
-  const BootCloud &S = B.k[0], &T = B.k[1];
-  std::vector<int> smp(nr);
-  double sp[3 * kBootMaxSamples], tp[3 * kBootMaxSamples];
-  for (int it = 0; it < iters; ++it) {
-    int got = 0, fails = 0;
-    float min_d = (float)p.min_sample_distance;
-    const int max_fails = 3 * nv;
-    while (got < nr) {
-      const int si = B.src_valid[rng.index(nv)];
-      bool ok = true;
-      for (int j = 0; j < got; ++j) {
-        const int sj = smp[j];
-        const float dx = S.hx[si] - S.hx[sj], dy = S.hy[si] - S.hy[sj], dz = S.hz[si] - S.hz[sj];
-        const float d = std::sqrt((dx * dx + dy * dy) + dz * dz);
-        if (si == sj || d < min_d) { ok = false; break; }
-      }
-      if (ok) { smp[got++] = si; fails = 0; } else ++fails;
-      if (fails >= max_fails) { min_d *= 0.5f; fails = 0; }
-    }
-    for (int j = 0; j < nr; ++j) {
-      const int tj = B.knn[(size_t)smp[j] * k + rng.index(B.k_eff)];
-      sp[3 * j] = S.hx[smp[j]]; sp[3 * j + 1] = S.hy[smp[j]]; sp[3 * j + 2] = S.hz[smp[j]];
-      tp[3 * j] = T.hx[tj]; tp[3 * j + 1] = T.hy[tj]; tp[3 * j + 2] = T.hz[tj];
-    }
-    rigid_from_pairs(nr, sp, tp, &Q[(size_t)it * 4], &M[(size_t)it * 12]);
-  }
-  const double tm1 = now_ms();
-  std::vector<double> err(iters);
-  SICPCHECK(score_hypotheses(h, p, S, T, iters, M.data(), err.data()));
-  int best = 0;
-  for (int it = 1; it < iters; ++it)
-    if (err[it] < err[best]) best = it;
-  const double* q = &Q[(size_t)best * 4];
-  out_qt[0] = q[1]; out_qt[1] = q[2]; out_qt[2] = q[3]; out_qt[3] = q[0];
-  out_qt[4] = M[(size_t)best * 12 + 3]; out_qt[5] = M[(size_t)best * 12 + 7]; out_qt[6] = M[(size_t)best * 12 + 11];
-  if (info) {
-    info->n_source_keypoints = ns;
-    info->n_target_keypoints = T.n;
-    info->max_neighbours = std::max(S.max_nbrs, T.max_nbrs);
-    info->best_iteration = best;
-    info->best_error = err[best];
-    info->t_keypoints_ms = t_kp;
-    info->t_features_ms = t_feat;
-    info->t_match_ms = t_knn + (tm1 - tm0);
-    info->t_score_ms = now_ms() - tm1;
-    info->t_total_ms = now_ms() - t_begin;
-  }
-  return SICP_OK;
+  // a batch of one: the same stages and kernels as any batch
+  int32_t st = SICP_OK;
+  sicp_handle hs[1] = {h};
+  const int rc = run_batch(h, hs, 1, p, out_qt, &st, info, "sicp_bootstrap", false);
+  return rc != SICP_OK ? rc : st;
+}
+
+int bootstrap_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* pp, double* out_qt, int32_t* status,
+                    sicp_bootstrap_info* infos) {
+  if (!hs || n < 1) return SICP_ERR_INVALID_ARGUMENT;
+  sicp_context* h = hs[0];
+  auto refuse = [&](const std::string& why) {
+    if (h) h->last_error = "sicp_bootstrap_batch: " + why;
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  for (int i = 0; i < n; ++i)
+    if (!hs[i]) return refuse("handle " + std::to_string(i) + " is NULL");
+  if (!pp) return refuse("params is NULL");
+  if (!out_qt) return refuse("out_qt is NULL");
+  for (int i = 1; i < n; ++i)
+    if (hs[i]->device != h->device)
+      return refuse("handle " + std::to_string(i) + " is on device " + std::to_string(hs[i]->device) + ", handle 0 on " + std::to_string(h->device));
+  const sicp_bootstrap_params p = *pp;
+  SICPCHECK(check_params(h, p, "sicp_bootstrap_batch"));
+  SICPCHECK(set_device(h));
+  return run_batch(h, hs, n, p, out_qt, status, infos, "sicp_bootstrap_batch", true);
 }
 
 int bootstrap_keypoints(sicp_context* h, int which, const sicp_bootstrap_params* pp, int32_t capacity, int64_t nbr_capacity,
@@ -476,14 +834,19 @@ int bootstrap_keypoints(sicp_context* h, int which, const sicp_bootstrap_params*
                         int64_t* nbr_offsets, int32_t* nbr_idx) {
   if (!pp || (which != SICP_SOURCE && which != SICP_TARGET)) return SICP_ERR_INVALID_ARGUMENT;
   const sicp_bootstrap_params p = *pp;
-  SICPCHECK(check_params(h, p));
+  SICPCHECK(check_params(h, p, "sicp_bootstrap"));
   SICPCHECK(set_device(h));
   SICPCHECK(check_clouds(h));
-  BootScratch s;
-  BootCloud k;
-  SICPCHECK(voxel_keypoints(h, h->cloud(which), p, s, k));
-  SICPCHECK(keypoint_features(h, p, s, k));
-  HIPCHECK(hipStreamSynchronize(h->stream));
+  CloudWork w;
+  w.c = &h->cloud(which);
+  const std::vector<CloudWork*> W = {&w};
+  SICPCHECK(voxel_stage(h, p, W));
+  SICPCHECK(feature_stage(h, p, W));
+  if (!w.live()) {
+    h->last_error = "sicp_bootstrap: " + w.msg;
+    return w.status;
+  }
+  const BootCloud& k = w.k;
   if (n_keypoints) *n_keypoints = k.n;
   if (n_nbrs) *n_nbrs = k.n_nbrs;
   const int m = k.n;
@@ -496,7 +859,7 @@ int bootstrap_keypoints(sicp_context* h, int which, const sicp_bootstrap_params*
   const hipStream_t st = h->stream;
   if (xyz3)
     for (int i = 0; i < m; ++i) { xyz3[3 * i] = k.hx[i]; xyz3[3 * i + 1] = k.hy[i]; xyz3[3 * i + 2] = k.hz[i]; }
-  if (normal3) HIPCHECK(hipMemcpyAsync(normal3, k.n3.p, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, st));
+  if (normal3) std::memcpy(normal3, w.n3.data(), sizeof(double) * 3 * m);
   if (fpfh33) HIPCHECK(hipMemcpyAsync(fpfh33, k.fpfh.p, sizeof(float) * 33 * m, hipMemcpyDeviceToHost, st));
   if (nbr_offsets) HIPCHECK(hipMemcpyAsync(nbr_offsets, k.off.p, sizeof(long long) * (m + 1), hipMemcpyDeviceToHost, st));
   if (nbr_idx && k.n_nbrs > 0) HIPCHECK(hipMemcpyAsync(nbr_idx, k.idx.p, sizeof(int) * k.n_nbrs, hipMemcpyDeviceToHost, st));
@@ -508,21 +871,30 @@ int bootstrap_score(sicp_context* h, const sicp_bootstrap_params* pp, int32_t n,
                     double* M12, double* err, int32_t knn_capacity, int32_t* feat_knn) {
   if (!pp || n < 0 || (n > 0 && (!src_idx || !tgt_idx || !err))) return SICP_ERR_INVALID_ARGUMENT;
   const sicp_bootstrap_params p = *pp;
-  SICPCHECK(check_params(h, p));
+  SICPCHECK(check_params(h, p, "sicp_bootstrap"));
   SICPCHECK(set_device(h));
   SICPCHECK(check_clouds(h));
-  BootState B;
-  SICPCHECK(prepare(h, p, B, nullptr, nullptr, nullptr));
-  const BootCloud &S = B.k[0], &T = B.k[1];
+  CloudWork cw[2];
+  cw[0].c = &h->cloud(SICP_SOURCE);
+  cw[1].c = &h->cloud(SICP_TARGET);
+  PairWork q;
+  q.S = &cw[0]; q.T = &cw[1];
+  SICPCHECK(prepare(h, p, {&cw[0], &cw[1]}, {&q}, nullptr, nullptr, nullptr));
+  if (q.status != SICP_OK) {
+    h->last_error = "sicp_bootstrap: " + q.msg;
+    return q.status;
+  }
+  const BootCloud &S = cw[0].k, &T = cw[1].k;
   if (feat_knn) {
     if ((long long)knn_capacity < (long long)S.n * p.k_correspondences) return SICP_ERR_INVALID_ARGUMENT;
-    std::memcpy(feat_knn, B.knn.data(), sizeof(int) * B.knn.size());
+    std::memcpy(feat_knn, q.knn.data(), sizeof(int) * q.knn.size());
   }
   if (n == 0) return SICP_OK;
   if (S.n < 1 || T.n < 1) return SICP_ERR_TOO_FEW_POINTS;
   const int nr = p.nr_samples;
-  std::vector<double> M((size_t)n * 12);
-  double sp[3 * kBootMaxSamples], tp[3 * kBootMaxSamples], q[4];
+  q.n_hyp = n;
+  q.M.assign((size_t)n * 12, 0.0);
+  double sp[3 * kBootMaxSamples], tp[3 * kBootMaxSamples], qq[4];
   for (int i = 0; i < n; ++i) {
     for (int j = 0; j < nr; ++j) {
       const int a = src_idx[(size_t)i * nr + j], b = tgt_idx[(size_t)i * nr + j];
@@ -533,10 +905,11 @@ int bootstrap_score(sicp_context* h, const sicp_bootstrap_params* pp, int32_t n,
       sp[3 * j] = S.hx[a]; sp[3 * j + 1] = S.hy[a]; sp[3 * j + 2] = S.hz[a];
       tp[3 * j] = T.hx[b]; tp[3 * j + 1] = T.hy[b]; tp[3 * j + 2] = T.hz[b];
     }
-    rigid_from_pairs(nr, sp, tp, q, &M[(size_t)i * 12]);
+    rigid_from_pairs(nr, sp, tp, qq, &q.M[(size_t)i * 12]);
   }
-  SICPCHECK(score_hypotheses(h, p, S, T, n, M.data(), err));
-  if (M12) std::memcpy(M12, M.data(), sizeof(double) * M.size());
+  SICPCHECK(score_stage(h, p, {&q}));
+  std::memcpy(err, q.err.data(), sizeof(double) * n);
+  if (M12) std::memcpy(M12, q.M.data(), sizeof(double) * q.M.size());
   return SICP_OK;
 }
 

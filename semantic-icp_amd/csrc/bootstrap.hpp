@@ -20,6 +20,9 @@ struct BootRng {
 
 void bootstrap_default_params(sicp_bootstrap_params* p);
 int bootstrap_run(sicp_context* h, const sicp_bootstrap_params* p, double* out_qt, sicp_bootstrap_info* info);
+// sicp_bootstrap_batch: checks its arguments, then runs every pair (status[i] per pair)
+int bootstrap_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* p, double* out_qt, int32_t* status,
+                    sicp_bootstrap_info* infos);
 int bootstrap_keypoints(sicp_context* h, int which, const sicp_bootstrap_params* p, int32_t capacity, int64_t nbr_capacity,
                         int32_t* n_keypoints, int64_t* n_nbrs, float* xyz3, double* normal3, float* fpfh33,
                         int64_t* nbr_offsets, int32_t* nbr_idx);

@@ -22,6 +22,20 @@ __device__ __forceinline__ bool boot_kept(float x, float y, float z, double box_
   return (double)x < box_max && (double)y < box_max && (double)z < box_max;  // signed, bootstrap.h:24-28
 }
 
+// ---- job forms: one launch over every cloud (or pair) of a batch -------------------------------------------------------
+// Job j owns the blocks [blk_end[j - 1], blk_end[j]) of the launch (blk_end: inclusive prefix of the per-job block counts,
+// built on the host); the block's job is found by bisection, *local = its place among the job's blocks.  A block never
+// straddles two jobs, so a job's items see exactly the lone launch's block shapes.
+__device__ __forceinline__ int boot_job_of(const int* blk_end, int nj, int b, int* local) {
+  int lo = 0, hi = nj - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (blk_end[mid] > b) hi = mid; else lo = mid + 1;
+  }
+  *local = b - (lo > 0 ? blk_end[lo - 1] : 0);
+  return lo;
+}
+
 // ---- voxel grid ----------------------------------------------------------------------------------------------------
 // per workgroup: min / max of the kept points and their count -> blk[b * 8 + (lo0 lo1 lo2 hi0 hi1 hi2 count)]
 __global__ __launch_bounds__(256) void boot_bounds_kernel(int n, const float* x, const float* y, const float* z,
@@ -125,14 +139,18 @@ __device__ __forceinline__ int boot_lower_bound(const u64* a, int n, u64 v) {
 
 // d^2 = (dx dx + dy dy) + dz dz in f32; a neighbour when d^2 < r^2.  FILL = 0: count, 1: write (d^2 bits << 32 | index)
 template <int FILL>
-__global__ __launch_bounds__(256) void boot_radius_kernel(int m, const float* x, const float* y, const float* z, float inv_cell,
-                                                          const u64* skey, const int* sval, float r2, long long* count,
-                                                          const long long* off, u64* list) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+__global__ __launch_bounds__(256) void boot_radius_kernel(const BootCloudJob* jobs, const int* blk_end, int nj) {
+  int lb;
+  const BootCloudJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &lb)];
+  const int i = lb * 256 + threadIdx.x, m = J.m;
   if (i >= m) return;
+  const float *x = J.x, *y = J.y, *z = J.z;
+  const float inv_cell = J.inv_cell, r2 = J.r2;
+  const u64* skey = J.skey;
+  const int* sval = J.sval;
   const float px = x[i], py = y[i], pz = z[i];
   const int c0 = boot_cell(px, inv_cell), c1 = boot_cell(py, inv_cell), c2 = boot_cell(pz, inv_cell);
-  long long w = FILL ? off[i] : 0;
+  long long w = FILL ? J.loff[i] : 0;
   for (int a = -1; a <= 1; ++a)
     for (int b = -1; b <= 1; ++b) {
       // the three cells (c0 + a, c1 + b, c2 - 1 .. c2 + 1) are adjacent keys: one range
@@ -143,12 +161,12 @@ __global__ __launch_bounds__(256) void boot_radius_kernel(int m, const float* x,
         const float ddx = x[q] - px, ddy = y[q] - py, ddz = z[q] - pz;
         const float d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
         if (d2 < r2) {
-          if (FILL) list[w] = ((u64)__float_as_uint(d2) << 32) | (unsigned)q;
+          if (FILL) J.list[w] = ((u64)__float_as_uint(d2) << 32) | (unsigned)q;
           ++w;
         }
       }
     }
-  if (!FILL) count[i] = w;
+  if (!FILL) J.count[i] = w;
 }
 
 __global__ __launch_bounds__(256) void boot_split_kernel(long long total, const u64* list, int* idx, float* d2) {
@@ -160,10 +178,16 @@ __global__ __launch_bounds__(256) void boot_split_kernel(long long total, const 
 }
 
 // ---- normals: f64 covariance of the neighbourhood, smallest-eigenvalue eigenvector, flipped towards (0, 0, 0) -------
-__global__ __launch_bounds__(256) void boot_normal_kernel(int m, const float* x, const float* y, const float* z, const long long* off,
-                                                          const int* idx, double* n3) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= m) return;
+// (the lists of the normal radius: noff / nidx)
+__global__ __launch_bounds__(256) void boot_normal_kernel(const BootCloudJob* jobs, const int* blk_end, int nj) {
+  int lb;
+  const BootCloudJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &lb)];
+  const int i = lb * 256 + threadIdx.x;
+  if (i >= J.m) return;
+  const float *x = J.x, *y = J.y, *z = J.z;
+  const long long* off = J.noff;
+  const int* idx = J.nidx;
+  double* n3 = J.n3;
   const long long b = off[i], e = off[i + 1];
   const double nan = __builtin_nan("");
   if (e - b < 3) { n3[3 * i] = n3[3 * i + 1] = n3[3 * i + 2] = nan; return; }
@@ -232,10 +256,17 @@ __device__ __forceinline__ int boot_bin(double v) {
 }
 
 // one wave per point: SPFH counts in LDS (integer atomics: order-free), each pair adds 100 / (|neighbourhood| - 1)
-__global__ __launch_bounds__(64) void boot_spfh_kernel(int m, const float* x, const float* y, const float* z, const double* n3,
-                                                       const long long* off, const int* idx, double* spfh) {
+// (block = point: blk_end is the prefix of the keypoint counts)
+__global__ __launch_bounds__(64) void boot_spfh_kernel(const BootCloudJob* jobs, const int* blk_end, int nj) {
   __shared__ int h[33];
-  const int p = blockIdx.x, t = threadIdx.x;
+  int p;
+  const BootCloudJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &p)];
+  const int t = threadIdx.x;
+  const float *x = J.x, *y = J.y, *z = J.z;
+  const double* n3 = J.n3;
+  const long long* off = J.off;
+  const int* idx = J.idx;
+  double* spfh = J.spfh;
   if (t < 33) h[t] = 0;
   __syncthreads();
   const double n1x = n3[3 * p], n1y = n3[3 * p + 1], n1z = n3[3 * p + 2];
@@ -261,10 +292,17 @@ __global__ __launch_bounds__(64) void boot_spfh_kernel(int m, const float* x, co
 
 // one wave per point, lane = bin: sum SPFH(q) / d^2 over the neighbours with d^2 > 0 in list order (f64), then each
 // third scaled to a sum of 100 (its 11 bins summed in bin order)
-__global__ __launch_bounds__(64) void boot_fpfh_kernel(int m, const double* n3, const long long* off, const int* idx, const float* d2,
-                                                       const double* spfh, float* fpfh) {
+__global__ __launch_bounds__(64) void boot_fpfh_kernel(const BootCloudJob* jobs, const int* blk_end, int nj) {
   __shared__ double acc[33];
-  const int p = blockIdx.x, t = threadIdx.x;
+  int p;
+  const BootCloudJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &p)];
+  const int t = threadIdx.x;
+  const double* n3 = J.n3;
+  const long long* off = J.off;
+  const int* idx = J.idx;
+  const float* d2 = J.d2;
+  const double* spfh = J.spfh;
+  float* fpfh = J.fpfh;
   if (isnan(n3[3 * p])) {
     if (t < 33) fpfh[(size_t)p * 33 + t] = __builtin_nanf("");
     return;
@@ -290,10 +328,16 @@ __global__ __launch_bounds__(64) void boot_fpfh_kernel(int m, const double* n3, 
 
 // ---- feature k-NN: f32 L2 over bins 0..32 in order, ties to the lower index; target features tiled through LDS --------
 constexpr int kKnnTile = 64;
-__global__ __launch_bounds__(256) void boot_feature_knn_kernel(int ns, const float* sf, int nt, const float* tf, int k, int* out) {
+// (job = pair: n source features sf, nt target features tf -> out[n][k])
+__global__ __launch_bounds__(256) void boot_feature_knn_kernel(const BootPairJob* jobs, const int* blk_end, int nj, int k) {
   __shared__ float tile[kKnnTile][33];
   __shared__ int ok[kKnnTile];
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  int lb;
+  const BootPairJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &lb)];
+  const int ns = J.n, nt = J.nt;
+  const float *sf = J.sf, *tf = J.tf;
+  int* out = J.out;
+  const int i = lb * 256 + threadIdx.x;
   float qf[33];
   bool qvalid = false;
   if (i < ns) {
@@ -339,10 +383,14 @@ __global__ __launch_bounds__(256) void boot_feature_knn_kernel(int ns, const flo
 }
 
 // ---- truncated error of every hypothesis: one workgroup each, fixed-shape f64 sum of (e <= t ? e / t : 1) ------------
-__global__ __launch_bounds__(256) void boot_error_kernel(int nq, const float* d2, double t, double* err) {
+// (job = the hypotheses of one pair in a chunk, block = hypothesis: n hypotheses of nt squared distances each, d2 -> err)
+__global__ __launch_bounds__(256) void boot_error_kernel(const BootPairJob* jobs, const int* blk_end, int nj, double t) {
   __shared__ double s[256];
-  const int h = blockIdx.x, l = threadIdx.x;
-  const float* d = d2 + (size_t)h * nq;
+  int h;
+  const BootPairJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &h)];
+  const int l = threadIdx.x, nq = J.nt;
+  double* err = J.err;
+  const float* d = J.d2 + (size_t)h * nq;
   double a = 0.0;
   for (int q = l; q < nq; q += 256) {
     const double e = (double)d[q];
@@ -424,14 +472,10 @@ hipError_t launch_boot_cell_keys(int m, const float* x, const float* y, const fl
   return hipGetLastError();
 }
 
-hipError_t launch_boot_radius(int fill, int m, const float* x, const float* y, const float* z, float inv_cell,
-                              const unsigned long long* skey, const int* sval, float r2, long long* count, const long long* off,
-                              unsigned long long* list, hipStream_t st) {
-  if (m <= 0) return hipSuccess;
-  if (fill)
-    hipLaunchKernelGGL(boot_radius_kernel<1>, boot_grid(m), dim3(256), 0, st, m, x, y, z, inv_cell, skey, sval, r2, count, off, list);
-  else
-    hipLaunchKernelGGL(boot_radius_kernel<0>, boot_grid(m), dim3(256), 0, st, m, x, y, z, inv_cell, skey, sval, r2, count, off, list);
+hipError_t launch_boot_radius_jobs(int fill, const BootCloudJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st) {
+  if (nj <= 0 || blocks <= 0) return hipSuccess;
+  if (fill) hipLaunchKernelGGL(boot_radius_kernel<1>, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj);
+  else hipLaunchKernelGGL(boot_radius_kernel<0>, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj);
   return hipGetLastError();
 }
 
@@ -441,31 +485,29 @@ hipError_t launch_boot_split(long long total, const unsigned long long* list, in
   return hipGetLastError();
 }
 
-hipError_t launch_boot_normals(int m, const float* x, const float* y, const float* z, const long long* off, const int* idx,
-                               double* n3, hipStream_t st) {
-  if (m <= 0) return hipSuccess;
-  hipLaunchKernelGGL(boot_normal_kernel, boot_grid(m), dim3(256), 0, st, m, x, y, z, off, idx, n3);
+hipError_t launch_boot_normal_jobs(const BootCloudJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st) {
+  if (nj <= 0 || blocks <= 0) return hipSuccess;
+  hipLaunchKernelGGL(boot_normal_kernel, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj);
   return hipGetLastError();
 }
 
-hipError_t launch_boot_fpfh(int m, const float* x, const float* y, const float* z, const double* n3, const long long* off,
-                            const int* idx, const float* d2, double* spfh, float* fpfh, hipStream_t st) {
-  if (m <= 0) return hipSuccess;
-  hipLaunchKernelGGL(boot_spfh_kernel, dim3(m), dim3(64), 0, st, m, x, y, z, n3, off, idx, spfh);
-  hipLaunchKernelGGL(boot_fpfh_kernel, dim3(m), dim3(64), 0, st, m, n3, off, idx, d2, spfh, fpfh);
+hipError_t launch_boot_fpfh_jobs(const BootCloudJob* jobs, const int* pt_end, int nj, int points, hipStream_t st) {
+  if (nj <= 0 || points <= 0) return hipSuccess;
+  hipLaunchKernelGGL(boot_spfh_kernel, dim3(points), dim3(64), 0, st, jobs, pt_end, nj);
+  hipLaunchKernelGGL(boot_fpfh_kernel, dim3(points), dim3(64), 0, st, jobs, pt_end, nj);
   return hipGetLastError();
 }
 
-hipError_t launch_boot_feature_knn(int ns, const float* sf, int nt, const float* tf, int k, int* out, hipStream_t st) {
-  if (ns <= 0) return hipSuccess;
+hipError_t launch_boot_feature_knn_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, hipStream_t st) {
+  if (nj <= 0 || blocks <= 0) return hipSuccess;
   if (k < 1 || k > kBootMaxK) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(boot_feature_knn_kernel, boot_grid(ns), dim3(256), 0, st, ns, sf, nt, tf, k, out);
+  hipLaunchKernelGGL(boot_feature_knn_kernel, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj, k);
   return hipGetLastError();
 }
 
-hipError_t launch_boot_error(int n_hyp, int nq, const float* d2, double t, double* err, hipStream_t st) {
-  if (n_hyp <= 0) return hipSuccess;
-  hipLaunchKernelGGL(boot_error_kernel, dim3(n_hyp), dim3(256), 0, st, nq, d2, t, err);
+hipError_t launch_boot_error_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, hipStream_t st) {
+  if (nj <= 0 || hypotheses <= 0) return hipSuccess;
+  hipLaunchKernelGGL(boot_error_kernel, dim3(hypotheses), dim3(256), 0, st, jobs, hyp_end, nj, t);
   return hipGetLastError();
 }
 

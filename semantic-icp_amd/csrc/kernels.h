@@ -369,23 +369,51 @@ hipError_t launch_boot_voxel_compact(int n_kept, const unsigned long long* key, 
                                      void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t launch_boot_centroids(int n_kp, int n_kept, const int* heads, const unsigned long long* key, const float* x,
                                  const float* y, const float* z, float* kx, float* ky, float* kz, hipStream_t st);
-// radius neighbourhoods on a uniform grid: cell keys + point ids (to be sorted by key), then count (fill = 0) or write the
-// unsorted lists of (d^2 bits << 32 | index) at off[i] (fill = 1); split: sorted lists -> index / d^2 arrays
+// Job forms (one launch over every cloud or pair of a bootstrap batch): the jobs live in device memory, and job j owns the
+// blocks [blk_end[j - 1], blk_end[j]) of the launch -- blk_end is the inclusive prefix of the per-job block counts, in the
+// unit of the launch (256 items for radius / normals / k-NN, one keypoint for SPFH / FPFH, one hypothesis for the error).
+// Per item every kernel runs what the lone launch ran, in the same order: a batch gives every job the bits of a batch of one.
+struct BootCloudJob {
+  int m, pad_;                  // keypoints
+  const float *x, *y, *z;       // keypoints (device)
+  // radius lists under construction: the cell grid, its sorted keys / point ids, and the counts (fill 0) or lists (fill 1)
+  float inv_cell, r2;
+  const unsigned long long* skey;
+  const int* sval;
+  long long* count;
+  const long long* loff;
+  unsigned long long* list;
+  // the finished lists: normal radius (noff / nidx: normals) and feature radius (off / idx / d2: SPFH, FPFH)
+  const long long* noff;
+  const int* nidx;
+  const long long* off;
+  const int* idx;
+  const float* d2;
+  double* n3;    // [m][3]
+  double* spfh;  // [m][33] scratch
+  float* fpfh;   // [m][33]
+};
+struct BootPairJob {
+  int n;   // feature k-NN: source keypoints;  error: hypotheses of the pair in this launch
+  int nt;  // feature k-NN: target keypoints;  error: squared distances per hypothesis (source keypoints)
+  const float *sf, *tf;  // k-NN: features [n][33], [nt][33]
+  int* out;              // k-NN: [n][k]
+  const float* d2;       // error: [n][nt]
+  double* err;           // error: [n]
+};
+// radius neighbourhoods on a uniform grid: cell keys + point ids (to be sorted by key), then count (fill = 0: count[i]) or
+// write the unsorted lists of (d^2 bits << 32 | index) at loff[i] (fill = 1); split: sorted lists -> index / d^2 arrays
 hipError_t launch_boot_cell_keys(int m, const float* x, const float* y, const float* z, float inv_cell, unsigned long long* key,
                                  int* val, hipStream_t st);
-hipError_t launch_boot_radius(int fill, int m, const float* x, const float* y, const float* z, float inv_cell,
-                              const unsigned long long* skey, const int* sval, float r2, long long* count, const long long* off,
-                              unsigned long long* list, hipStream_t st);
+hipError_t launch_boot_radius_jobs(int fill, const BootCloudJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st);
 hipError_t launch_boot_split(long long total, const unsigned long long* list, int* idx, float* d2, hipStream_t st);
-hipError_t launch_boot_normals(int m, const float* x, const float* y, const float* z, const long long* off, const int* idx,
-                               double* n3, hipStream_t st);
-// SPFH (spfh: m * 33 doubles of scratch) and FPFH (fpfh: m * 33 floats)
-hipError_t launch_boot_fpfh(int m, const float* x, const float* y, const float* z, const double* n3, const long long* off,
-                            const int* idx, const float* d2, double* spfh, float* fpfh, hipStream_t st);
-// out[ns][k]: the k nearest target features of every source feature (-1: none / no feature)
-hipError_t launch_boot_feature_knn(int ns, const float* sf, int nt, const float* tf, int k, int* out, hipStream_t st);
-// err[h] = sum over the nq squared distances d2[h][.] of (e <= t ? e / t : 1)
-hipError_t launch_boot_error(int n_hyp, int nq, const float* d2, double t, double* err, hipStream_t st);
+hipError_t launch_boot_normal_jobs(const BootCloudJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st);
+// SPFH (into spfh) then FPFH; pt_end: prefix of the keypoint counts, points = all keypoints of the launch
+hipError_t launch_boot_fpfh_jobs(const BootCloudJob* jobs, const int* pt_end, int nj, int points, hipStream_t st);
+// out[n][k]: the k nearest target features of every source feature (-1: none / no feature)
+hipError_t launch_boot_feature_knn_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, hipStream_t st);
+// err[h] = sum over the nt squared distances d2[h][.] of (e <= t ? e / t : 1); hyp_end: prefix of the hypothesis counts
+hipError_t launch_boot_error_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, hipStream_t st);
 
 }  // namespace sicp
 #endif

@@ -920,6 +920,13 @@ int sicp_bootstrap(sicp_handle h, const sicp_bootstrap_params* p, double out_qt[
   });
 }
 
+int sicp_bootstrap_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* p, double* out_qt, int32_t* status,
+                         sicp_bootstrap_info* infos) {
+  return abi_guard((hs && n > 0) ? hs[0] : nullptr, [&]() -> int {
+    return bootstrap_batch(hs, n, p, out_qt, status, infos);
+  });
+}
+
 int sicp_bootstrap_keypoints(sicp_handle h, int which, const sicp_bootstrap_params* p, int32_t capacity, int64_t nbr_capacity,
                              int32_t* n_keypoints, int64_t* n_nbrs, float* xyz3, double* normal3, float* fpfh33,
                              int64_t* nbr_offsets, int32_t* nbr_idx) {

@@ -120,6 +120,24 @@ class EmIterativeClosestPoint {
     }
   }
 
+  // Engine extension (no reference counterpart): the reference's Bootstrap (exec/bootstrap.h, default parameters) of
+  // several objects' pairs -- clouds already set -- in one call (sicp_bootstrap_batch): the coarse pose source -> target of
+  // each, from no initial guess, for align()'s initTransform.  Per pair the pose sicp_bootstrap gives.
+  static std::vector<Sophus::SE3d> bootstrapBatch(const std::vector<EmIterativeClosestPoint*>& objs) {
+    const size_t n = objs.size();
+    std::vector<Sophus::SE3d> out(n);
+    if (n == 0) return out;
+    std::vector<sicp_handle> hs(n);
+    for (size_t p = 0; p < n; ++p) hs[p] = objs[p]->engine_.get();
+    sicp_bootstrap_params bp;
+    detail::check(sicp_default_bootstrap_params(&bp), hs[0], "sicp_default_bootstrap_params");
+    std::vector<double> qt(7 * n);
+    const int rc = sicp_bootstrap_batch(hs.data(), (int32_t)n, &bp, qt.data(), nullptr, nullptr);
+    if (rc != SICP_OK) throw std::runtime_error(std::string("sicp_bootstrap_batch: ") + sicp_strerror(rc) + " -- " + sicp_last_error(hs[0]));
+    for (size_t p = 0; p < n; ++p) out[p] = detail::to_se3(&qt[7 * p]);
+    return out;
+  }
+
  protected:
   void configure(sicp_handle h) {
     sicp_params p;

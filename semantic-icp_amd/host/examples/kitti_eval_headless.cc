@@ -16,6 +16,9 @@
 // <in flight> registrations sharing the GPU while this thread reads the next files -- no closed batches, no
 // pair waiting for the slowest pair of its batch.  Same rows again (the time column is the run's wall time
 // per pair).
+// -B: bootstrap every pair before it is registered, as the reference's commented lines do (exec/kitti_eval.cc:175-181):
+// the coarse poses of sicp_bootstrap_batch over each batch of -b (a batch of one without -b) go to <prefix>initkitti.csv
+// (the file :109-115 opens) and are the initial pose of both EM-ICP and SE3-GICP.  Batch path only (not with -S / -G).
 // -G <n>: the sequence sharded over the GPUs of the node (BASELINE config 5; exec/kitti_eval.cc:124-249 is the loop that
 // shards): the pair list is cut into n contiguous runs, each an open stream per method with its own host thread on device
 // g % (devices visible), no exchange between them; the rows are merged in pair order.  Same rows again.  -S sets the
@@ -102,8 +105,11 @@ int main(int argc, char** argv) {
   const char *dir = arg(argc, argv, "-s"), *gt = arg(argc, argv, "-t"), *cmf = arg(argc, argv, "-m"), *prefix = arg(argc, argv, "-o");
   const char* barg = arg(argc, argv, "-b");
   const size_t batch = barg ? (size_t)std::max(1, std::atoi(barg)) : 1;
-  bool share = false;
-  for (int i = 1; i < argc; ++i) share = share || std::string(argv[i]) == "-r";
+  bool share = false, boot = false;
+  for (int i = 1; i < argc; ++i) {
+    share = share || std::string(argv[i]) == "-r";
+    boot = boot || std::string(argv[i]) == "-B";
+  }
   if (!dir) { std::cout << "Need source directory (-s)\n"; return -1; }
   if (!gt) { std::cout << "Need ground truth file (-t)\n"; return -1; }
   if (!cmf) { std::cout << "Need ground confusion matrix file (-m)\n"; return -1; }
@@ -117,6 +123,13 @@ int main(int argc, char** argv) {
   typedef semanticicp::GICP<pcl::PointXYZ> Gicp;
   const char* sarg = arg(argc, argv, "-S");
   const char* garg = arg(argc, argv, "-G");
+  if ((sarg || garg) && boot) { std::cout << "-B runs on the batch path: not with -S / -G\n"; return -1; }
+  std::unique_ptr<std::ofstream> foutBoot;
+  std::unique_ptr<KittiMetrics> bootstrapMetrics;
+  if (boot) {
+    foutBoot.reset(new std::ofstream(pre + "initkitti.csv"));
+    bootstrapMetrics.reset(new KittiMetrics(gtFile, foutBoot.get()));
+  }
   if (sarg || garg) {
     try {
       const int in_flight = std::max(1, sarg ? std::atoi(sarg) : 64);
@@ -216,12 +229,23 @@ int main(int argc, char** argv) {
         finalGi[b].reset(new pcl::PointCloud<pcl::PointXYZ>);
         prev_slot = b;
       }
+      if (boot) {  // :175-181 with the Bootstrap lines enabled
+        const auto b0 = std::chrono::steady_clock::now();
+        inits = Em::bootstrapBatch(eo);
+        const double secsBoot = std::chrono::duration<double>(std::chrono::steady_clock::now() - b0).count() / double(cnt);
+        for (size_t b = 0; b < cnt; ++b) {
+          const size_t indxTarget = starts[g0 + b], indxSource = indxTarget + 3;
+          const double e0 = bootstrapMetrics->evaluate(inits[b], indxTarget, indxSource, secsBoot, 0);
+          std::printf("pair %zu<-%zu  Init MSE %.3e\n", indxTarget, indxSource, e0);
+        }
+      }
       auto begin = std::chrono::steady_clock::now();
       if (batch == 1) eo[0]->align(finalEm[0], inits[0]);
       else Em::alignBatch(eo, finalEm, inits);
       const double secsEm = std::chrono::duration<double>(std::chrono::steady_clock::now() - begin).count() / double(cnt);
       begin = std::chrono::steady_clock::now();
-      if (batch == 1) go[0]->align(finalGi[0]);
+      if (batch == 1 && boot) go[0]->align(finalGi[0], inits[0]);
+      else if (batch == 1) go[0]->align(finalGi[0]);
       else Gicp::alignBatch(go, finalGi, inits);
       const double secsGi = std::chrono::duration<double>(std::chrono::steady_clock::now() - begin).count() / double(cnt);
       for (size_t b = 0; b < cnt; ++b) {
