@@ -30,16 +30,25 @@ def pose_matrix(rot_deg: float, axis, trans) -> np.ndarray:
 
 
 def _noisy_labels(rng, labels, cm, frac):
-    """Re-draw `frac` of the labels from the confusion-matrix row of the true class."""
+    """Re-draw `frac` of the labels from the confusion-matrix row of the true class (without it).
+    The draws are those of `1 + rng.choice(C, p=row)` once per flipped label, in label order: one
+    uniform each, looked up in the row's normalised cumulative sum -- done here for all at once."""
     labels = labels.copy()
     n = labels.shape[0]
-    flip = rng.random(n) < frac
+    flip = np.nonzero(rng.random(n) < frac)[0]
     C = cm.shape[0]
-    for i in np.nonzero(flip)[0]:
-        row = cm[labels[i] - 1].copy()
-        row[labels[i] - 1] = 0
+    cls = labels[flip].astype(np.int64) - 1
+    if flip.size and (cls.min() < 0 or cls.max() >= C):
+        raise ValueError("labels must lie in 1..C")
+    u = rng.random(flip.size)
+    for c in range(C):
+        row = cm[c].copy()
+        row[c] = 0
         row /= row.sum()
-        labels[i] = 1 + rng.choice(C, p=row)
+        cdf = row.cumsum()
+        cdf /= cdf[-1]
+        m = cls == c
+        labels[flip[m]] = 1 + cdf.searchsorted(u[m], side="right")
     return labels
 
 
@@ -105,12 +114,36 @@ def _street(rng):
     return boxes, poles
 
 
+_AZ_MARGIN = 1e-6   # rad: far wider than the rounding of any hit test near the edge of an object
+
+
 def _raycast(origin, dirs, boxes, poles):
     """Nearest hit of each ray against ground z=0 (label 1), walls y=+-9 (label 2),
-    axis-aligned boxes and vertical cylinders.  Returns (t, label)."""
+    axis-aligned boxes and vertical cylinders.  Returns (t, label).
+
+    A ray can only hit a box or a pole if its azimuth lies within the azimuths the object's
+    footprint spans from the origin, so each object is tested against those rays alone (found
+    by a binary search in the rays sorted by azimuth; all rays when the origin is inside the
+    footprint).  Every ray gets the same arithmetic as when all are tested, object after object."""
     n = dirs.shape[0]
     tbest = np.full(n, np.inf)
     lab = np.zeros(n, dtype=np.uint32)
+    dx, dy, dz = (np.ascontiguousarray(dirs[:, k]) for k in range(3))
+    order = np.argsort(np.arctan2(dy, dx), kind="stable")
+    az_sorted = np.arctan2(dy, dx)[order]
+    everyone = np.arange(n)
+
+    def rays_towards(center, lo, hi):
+        """rays whose azimuth lies in [center + lo, center + hi] widened by _AZ_MARGIN (modulo 2 pi)"""
+        a, width = center + lo - _AZ_MARGIN, hi - lo + 2 * _AZ_MARGIN
+        if width >= 2 * np.pi:
+            return everyone
+        a = (a + np.pi) % (2 * np.pi) - np.pi
+        i0 = np.searchsorted(az_sorted, a, side="left")
+        if a + width <= np.pi:
+            return order[i0:np.searchsorted(az_sorted, a + width, side="right")]
+        return np.concatenate([order[:np.searchsorted(az_sorted, a + width - 2 * np.pi, side="right")], order[i0:]])
+
     with np.errstate(divide="ignore", invalid="ignore"):
         t = (0.0 - origin[2]) / dirs[:, 2]
         ok = (t > 0.5) & np.isfinite(t)
@@ -121,23 +154,35 @@ def _raycast(origin, dirs, boxes, poles):
             ok = (t > 0.5) & np.isfinite(t) & (z >= 0) & (z <= 12)
             upd = ok & (t < tbest); tbest[upd] = t[upd]; lab[upd] = 2
         inv = 1.0 / dirs
+        ix, iy, iz = (np.ascontiguousarray(inv[:, k]) for k in range(3))
         for lo, hi, bl in boxes:
-            t0 = (lo - origin) * inv
-            t1 = (hi - origin) * inv
-            tn = np.minimum(t0, t1).max(axis=1)
-            tf = np.maximum(t0, t1).min(axis=1)
+            lo_o, hi_o = lo - origin, hi - origin
+            if lo_o[0] <= 0 <= hi_o[0] and lo_o[1] <= 0 <= hi_o[1]:
+                sel = everyone
+            else:
+                c = np.arctan2(0.5 * (lo_o[1] + hi_o[1]), 0.5 * (lo_o[0] + hi_o[0]))
+                corners = [(np.arctan2(y, x) - c + np.pi) % (2 * np.pi) - np.pi for x in (lo_o[0], hi_o[0]) for y in (lo_o[1], hi_o[1])]
+                sel = rays_towards(c, min(corners), max(corners))
+            t0x, t1x = lo_o[0] * ix[sel], hi_o[0] * ix[sel]
+            t0y, t1y = lo_o[1] * iy[sel], hi_o[1] * iy[sel]
+            t0z, t1z = lo_o[2] * iz[sel], hi_o[2] * iz[sel]
+            tn = np.maximum(np.maximum(np.minimum(t0x, t1x), np.minimum(t0y, t1y)), np.minimum(t0z, t1z))
+            tf = np.minimum(np.minimum(np.maximum(t0x, t1x), np.maximum(t0y, t1y)), np.maximum(t0z, t1z))
             ok = (tn <= tf) & (tn > 0.5)
-            upd = ok & (tn < tbest); tbest[upd] = tn[upd]; lab[upd] = bl
+            upd = ok & (tn < tbest[sel]); tbest[sel[upd]] = tn[upd]; lab[sel[upd]] = bl
         for cx, cy, r, h, pl in poles:
             ox, oy = origin[0] - cx, origin[1] - cy
-            a = dirs[:, 0] ** 2 + dirs[:, 1] ** 2
-            b = 2 * (ox * dirs[:, 0] + oy * dirs[:, 1])
+            dist = np.hypot(ox, oy)
+            sel = everyone if dist <= r * (1 + 1e-6) else rays_towards(np.arctan2(-oy, -ox), -np.arcsin(r / dist), np.arcsin(r / dist))
+            sx, sy = dx[sel], dy[sel]
+            a = sx ** 2 + sy ** 2
+            b = 2 * (ox * sx + oy * sy)
             c = ox * ox + oy * oy - r * r
             disc = b * b - 4 * a * c
             t = (-b - np.sqrt(np.where(disc > 0, disc, np.nan))) / (2 * a)
-            z = origin[2] + t * dirs[:, 2]
+            z = origin[2] + t * dz[sel]
             ok = np.isfinite(t) & (t > 0.5) & (z >= 0) & (z <= h)
-            upd = ok & (t < tbest); tbest[upd] = t[upd]; lab[upd] = pl
+            upd = ok & (t < tbest[sel]); tbest[sel[upd]] = t[upd]; lab[sel[upd]] = pl
     return tbest, lab
 
 

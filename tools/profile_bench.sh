@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage (GPU box): tools/profile_bench.sh <prefix>
-# rocprofv3 --kernel-trace --stats of the default bench command with the CPU leg off and SICP_NO_GRAPH=1 (rocprofv3 of
+# rocprofv3 --kernel-trace --stats of `bench.py --full` with the CPU leg off and SICP_NO_GRAPH=1 (rocprofv3 of
 # ROCm 7.2 dies with a segmentation fault on hipGraphLaunch -- tools/r04/two_thread_dispatch.hip reproduces it without this
 # library; with the ticks as plain launches the whole bench, stream legs included, profiles), the per-kernel statistics csv,
 # and a summary of the accumulate launches that separates the roofline legs of bench.py -- the LAST 60 launches
@@ -13,7 +13,7 @@ pre=$1
 export SICP_NO_GRAPH=1
 for attempt in 1 2; do
   rm -rf /tmp/pb_prof
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb_prof -- python3 bench.py --no-cpu-baseline --no-dropin \
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb_prof -- python3 bench.py --full --no-cpu-baseline --no-dropin \
     > gpurun_out/${pre}_bench_under_rocprof.json 2> /tmp/pb_prof.err
   [ -n "$(find /tmp/pb_prof -name '*kernel_trace.csv' 2>/dev/null | head -1)" ] && break
   echo "attempt $attempt: no kernel trace (rocprofv3 crashed?)"

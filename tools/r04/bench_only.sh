@@ -1,7 +1,7 @@
 #!/bin/bash
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/r04_final; mkdir -p $O
-SECONDS=0; timeout 900 python3 bench.py > $O/bench_final.json 2> $O/bench_final.err; echo "bench exit $? after $SECONDS s"
+SECONDS=0; timeout 900 python3 bench.py --full > $O/bench_final.json 2> $O/bench_final.err; echo "bench exit $? after $SECONDS s"
 python3 - <<'PY'
 import json
 d = json.loads([l for l in open("gpurun_out/r04_final/bench_final.json") if l.startswith("{")][-1])

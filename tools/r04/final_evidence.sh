@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/r04_final; mkdir -p $O
 timeout 1800 python -m pytest tests -m gpu -x -q > $O/gpu_tests_final.txt 2>&1; tail -4 $O/gpu_tests_final.txt
-timeout 900 python3 bench.py > $O/bench_final.json 2> $O/bench_final.err; echo "bench exit $?"
+timeout 900 python3 bench.py --full > $O/bench_final.json 2> $O/bench_final.err; echo "bench exit $?"
 python3 - <<'PY'
 import json
 d = json.loads([l for l in open("gpurun_out/r04_final/bench_final.json") if l.startswith("{")][-1])

@@ -6,7 +6,7 @@ O=gpurun_out/r06_final; mkdir -p $O
 bash tools/probe_ref_deps.sh $O/probe_ref_deps_gpubox.txt
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 timeout 2700 python -m pytest tests -m gpu -x -q > $O/gpu_tests_final.txt 2>&1; tail -4 $O/gpu_tests_final.txt
-timeout 900 python3 bench.py > $O/bench_final.json 2> $O/bench_final.err; echo "bench exit $?"
+timeout 900 python3 bench.py --full > $O/bench_final.json 2> $O/bench_final.err; echo "bench exit $?"
 python3 - <<'PY'
 import json
 d = json.loads([l for l in open("gpurun_out/r06_final/bench_final.json") if l.startswith("{")][-1])
