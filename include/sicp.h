@@ -394,6 +394,46 @@ int sicp_bootstrap(sicp_handle h, const sicp_bootstrap_params* p, double out_qt[
  * changes. */
 int sicp_bootstrap_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* p, double* out_qt, int32_t* status,
                          sicp_bootstrap_info* infos);
+/* ---- how well a registration's pose is determined ------------------------------
+ * The 6x6 covariance of the pose at qt (Censi's estimate with the solver's Gauss-Newton matrix), in the tangent space of
+ * the right perturbation T * exp(delta), delta = [upsilon; omega] (units m^2, m rad, rad^2).  The slots are those
+ * sicp_correspondences(qt) finds (gate, EM weights, SEMANTIC label segments and min_class_pts included); with them, the
+ * weights, both clouds' covariances and R held fixed, per slot i with gradient share g_i = rho'(r^2) r J:
+ *   B_i^p = d g_i / d p_i,  B_i^q = d g_i / d q_i   (6x3; kappa = rho' + 2 s rho'' in closed form)
+ *   G_j = sum of B^p over source point j's slots,  G_k = sum of B^q over every slot whose target is point k
+ *   S_src = sum_j G_j G_j^T,  S_tgt = sum_k G_k G_k^T,  H = the Gauss-Newton sums of sicp_accumulate at qt
+ *   covariance    = H^-1 (sigma_source^2 S_src + sigma_target^2 S_tgt) H^-1   (isotropic point noise sigma^2 I)
+ *   covariance_gn = H^-1                                                     (what ceres::Covariance gives for the pose)
+ * For the left form (perturbation exp(delta) * T) use Ad_T Sigma Ad_T^T.  Not modelled: how the point covariances depend
+ * on neighbouring points, changes in the data association, the exact Hessian. */
+typedef struct sicp_pose_covariance_result {
+  double hessian[21];        /* = sicp_accumulate out28[0:21] at qt after sicp_correspondences(qt): same order, same bits */
+  double gradient[6];        /* = out28[21:27] */
+  double cost;               /* = out28[27] */
+  double cross_source[21];   /* S_src, upper triangle in hessian's order */
+  double cross_target[21];   /* S_tgt, likewise */
+  double covariance[36];     /* row-major; NaN unless positive_definite */
+  double covariance_gn[36];  /* H^-1, row-major; NaN unless positive_definite */
+  int64_t active;            /* slots that passed the gate */
+  int32_t positive_definite; /* the Cholesky factorisation of H succeeded */
+  int32_t reserved_;
+} sicp_pose_covariance_result;
+/* The handle's correspondences end up as after sicp_correspondences(qt).  H that is not positive definite (zero active
+ * slots included) gives positive_definite = 0, NaN covariances and SICP_OK.  Refused with SICP_ERR_INVALID_ARGUMENT and
+ * nothing written: a NULL handle, qt or out; a sigma that is negative or not finite; a cloud that holds caller covariances
+ * of general form (sicp_set_covariances; the reason in sicp_last_error).  Missing clouds or confusion matrix:
+ * SICP_ERR_NOT_READY, as sicp_align.  Bit-reproducible: no float atomics anywhere in the sums. */
+int sicp_pose_covariance(sicp_handle h, const double qt[7], double sigma_source, double sigma_target,
+                         sicp_pose_covariance_result* out);
+/* sicp_pose_covariance for n pairs: pair i = handle hs[i] at qt[7 i .. 7 i + 7), out[i].  The pairs run one after another
+ * through the lone path (one device scratch for all of them), so every row is bit-identical to its lone call.  status[n]
+ * (nullable) gets each pair's own code; a failing pair does not stop the others and its row is not written; the call
+ * returns SICP_OK when every pair succeeded, else the first failing pair's code.  Refused before any work, with
+ * SICP_ERR_INVALID_ARGUMENT and nothing written: n < 1, a NULL array or handle, a bad sigma, handles on different devices.
+ * Not yet available for streams (no submit flag): evaluate it on the pair's handle after align(). */
+int sicp_pose_covariance_batch(sicp_handle* hs, int32_t n, const double* qt, double sigma_source, double sigma_target,
+                               sicp_pose_covariance_result* out, int32_t* status);
+
 /* test / bench hook: the keypoints of cloud `which` with their normals, FPFH features and feature-radius
  * neighbour lists (CSR: nbr_offsets[n + 1], nbr_idx sorted by (d^2, index)).  Counts are always written; an output
  * array is written when it is non-NULL and its capacity (points / neighbour entries) suffices, otherwise the call

@@ -144,6 +144,45 @@ class SicpBootstrapInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class SicpPoseCovarianceResult(C.Structure):
+    """sicp_pose_covariance_result (include/sicp.h)"""
+    _fields_ = [
+        ("hessian", C.c_double * 21),
+        ("gradient", C.c_double * 6),
+        ("cost", C.c_double),
+        ("cross_source", C.c_double * 21),
+        ("cross_target", C.c_double * 21),
+        ("covariance", C.c_double * 36),
+        ("covariance_gn", C.c_double * 36),
+        ("active", C.c_int64),
+        ("positive_definite", C.c_int32),
+        ("reserved_", C.c_int32),
+    ]
+
+    def as_dict(self):
+        """6x6 arrays (hessian, cross_source, cross_target: the symmetric matrices of the upper triangles; covariance,
+        covariance_gn as stored), plus the raw 21-entry triangles, gradient, cost, active and positive_definite"""
+        def sym(u):
+            M = np.empty((6, 6))
+            M[np.triu_indices(6)] = np.asarray(u)
+            M.T[np.triu_indices(6)] = np.asarray(u)
+            return M
+        return {
+            "covariance": np.array(self.covariance).reshape(6, 6),
+            "covariance_gn": np.array(self.covariance_gn).reshape(6, 6),
+            "hessian": sym(self.hessian),
+            "cross_source": sym(self.cross_source),
+            "cross_target": sym(self.cross_target),
+            "hessian21": np.array(self.hessian),
+            "cross_source21": np.array(self.cross_source),
+            "cross_target21": np.array(self.cross_target),
+            "gradient": np.array(self.gradient),
+            "cost": float(self.cost),
+            "active": int(self.active),
+            "positive_definite": bool(self.positive_definite),
+        }
+
+
 class SicpError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -236,6 +275,9 @@ def lib():
                                      C.POINTER(SicpBootstrapInfo)],
             "sicp_bootstrap_keypoints": [C.c_void_p, C.c_int, C.POINTER(SicpBootstrapParams), C.c_int32, C.c_int64, _ip,
                                          C.POINTER(C.c_int64), _fp, _dp, _fp, C.POINTER(C.c_int64), _ip],
+            "sicp_pose_covariance": [C.c_void_p, _dp, C.c_double, C.c_double, C.POINTER(SicpPoseCovarianceResult)],
+            "sicp_pose_covariance_batch": [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_double, C.c_double,
+                                           C.POINTER(SicpPoseCovarianceResult), _ip],
             "sicp_bootstrap_score": [C.c_void_p, C.POINTER(SicpBootstrapParams), C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, _ip],
         }.items():
             fn = getattr(_lib, name)
@@ -493,6 +535,14 @@ class Engine:
         self._check(lib().sicp_accumulate(self._h, _ptr(qt, _dp), _ptr(out, _dp)), "sicp_accumulate")
         return out
 
+    def pose_covariance(self, qt, sigma_source: float = 1.0, sigma_target: float = 1.0):
+        """sicp_pose_covariance: the 6x6 covariance of the pose qt (tangent space of T * exp(delta), [upsilon; omega]) for
+        isotropic point noise sigma^2 I on each cloud.  Returns SicpPoseCovarianceResult.as_dict()."""
+        qt = np.ascontiguousarray(qt, dtype=np.float64)
+        r = SicpPoseCovarianceResult()
+        self._check(lib().sicp_pose_covariance(self._h, _ptr(qt, _dp), sigma_source, sigma_target, C.byref(r)), "sicp_pose_covariance")
+        return r.as_dict()
+
     def solve(self, init_qt):
         init = np.ascontiguousarray(init_qt, dtype=np.float64)
         out = np.empty(7)
@@ -559,6 +609,22 @@ def bootstrap_batch(engines, params: SicpBootstrapParams | None = None):
         else:
             res.append((int(status[i]), None, {"error": lib().sicp_last_error(engines[i]._h).decode()}))
     return res
+
+
+def pose_covariance_batch(engines, qts, sigma_source: float = 1.0, sigma_target: float = 1.0):
+    """sicp_pose_covariance_batch: Engine.pose_covariance for every engine at its row of qts.  Returns [(status, dict or
+    None)] in the order of `engines`; per pair identical to the lone call.  Raises SicpError only when the whole call is
+    refused."""
+    n = len(engines)
+    qts = np.ascontiguousarray(qts, dtype=np.float64).reshape(n, 7) if n else np.zeros((1, 7))
+    out = (SicpPoseCovarianceResult * max(n, 1))()
+    unset = -(2 ** 31)
+    status = np.full(max(n, 1), unset, dtype=np.int32)
+    rc = lib().sicp_pose_covariance_batch(_handles(engines) if n else None, n, _ptr(qts, _dp), sigma_source, sigma_target, out,
+                                          _ptr(status, _ip))
+    if rc != OK and (n == 0 or status[0] == unset):
+        raise SicpError(rc, "sicp_pose_covariance_batch", lib().sicp_last_error(engines[0]._h).decode() if n else "")
+    return [(OK, out[i].as_dict()) if status[i] == OK else (int(status[i]), None) for i in range(n)]
 
 
 def accumulate_batch(engines, qts, repeat: int = 1):

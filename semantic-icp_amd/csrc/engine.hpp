@@ -569,6 +569,8 @@ int count_active(sicp_context* h);
 bool weights_from_histograms(const sicp_params& P, int K);
 int run_weights(sicp_context* h, const double* qt);
 int run_correspondences(sicp_context* h, const double* qt, int K, bool weights);
+// sicp_correspondences without the read-back: clouds, features (and EM projections), then run_correspondences(qt, knn)
+int search_at(sicp_context* h, const double* qt);
 void fill_acc(sicp_context* h, sicp::AccArgs& a);
 constexpr int kMaxActivePairs = 256;  // pairs one launch evaluates (12 bytes of LDS each in the accumulate kernel)
 int eval28(sicp_context* h, const double* qt, double* out28);
@@ -716,6 +718,10 @@ int labels_search(sicp_context* h, const double* qt);
 // ... and the label kernel behind it on `st`, device order -> h->tmpl
 int labels_launch(sicp_context* h, const double* qt, hipStream_t st);
 int align_batch(sicp_handle* hs, int32_t n, const double* init_qt, double* out_qt, int32_t* outer_iters, sicp_stats* stats);
+// sicp_pose_covariance / _batch (pose_cov.cpp): argument checks, then the search, the accumulate sweep and the sums
+int pose_covariance(sicp_context* h, const double* qt, double sigma_source, double sigma_target, sicp_pose_covariance_result* out);
+int pose_covariance_batch(sicp_handle* hs, int32_t n, const double* qt, double sigma_source, double sigma_target,
+                          sicp_pose_covariance_result* out, int32_t* status);
 
 }  // namespace host
 }  // namespace sicp

@@ -348,6 +348,40 @@ hipError_t launch_se3_ops(int op, int n, const double* in, double* out, hipStrea
 hipError_t launch_transform_float(int n, const float* x, const float* y, const float* z, const Mat4f& M,
                                   float* ox, float* oy, float* oz, hipStream_t st);
 
+// ---- the pose covariance's sums (pose_cov_kernels.hip; driver: pose_cov.cpp) ----
+// Per active slot i, B_i^p and B_i^q = d g_i / d p and d g_i / d q (6x3 each, g_i the slot's share of the gradient); per source
+// point G_j = sum of its slots' B^p, per target point G_k = sum of B^q over the slots that hit it; S = sum G G^T (21 sums each).
+// No float atomics: source points are a lane's own slots, target points are summed through the slots sorted by (target, slot).
+constexpr int kPoseCovTile = 8;  // sorted slots per lane of the target-side pass (the split unit of long target lists)
+struct PoseCovArgs {
+  int n_s, K;
+  const int* idx;           // [n_s][K] device target indices, -1 = gated out
+  const double* w;          // nullable: weight 1
+  const PointRec *srec, *trec;
+  Pose pose;
+  double one_m_eps, cauchy_a;
+  int use_sqloss, pad_;
+  double* bq;               // out: [n_s * K][18] B^q of every active slot, row-major 6x3
+  unsigned long long* key;  // out: [n_s * K] target << 32 | slot, ~0 for a gated-out slot
+  double* part_src;         // out: [21][pose_cov_blocks(n_s)]
+  long long* part_active;   // out: [pose_cov_blocks(n_s)]
+};
+struct PoseCovTgtArgs {
+  int total;                      // slots (n_s * K)
+  const unsigned long long* key;  // sorted ascending
+  const double* bq;
+  double* piece;     // [tiles][2][18] partial target sums of lists that cross a tile edge
+  int* flag;         // [tiles]
+  double* part_tgt;  // [21][2 * pose_cov_blocks(tiles)]
+};
+SICP_HD inline int pose_cov_blocks(int items) { return items > 0 ? (items + 255) / 256 : 0; }
+SICP_HD inline int pose_cov_tiles(int total) { return (total + kPoseCovTile - 1) / kPoseCovTile; }
+hipError_t launch_pose_cov_src(const PoseCovArgs& a, hipStream_t st);
+hipError_t launch_pose_cov_tgt(const PoseCovTgtArgs& a, hipStream_t st);
+// out42 = [S_src 21 | S_tgt 21], *active = active slots: fixed-order sums of the partial columns
+hipError_t launch_pose_cov_finalize(const double* part_src, const long long* part_active, int src_cols, const double* part_tgt,
+                                    int tgt_cols, double* out42, long long* active, hipStream_t st);
+
 // ---- initial alignment without a pose prior (bootstrap_kernels.hip; driver: bootstrap.cpp) ----
 // The sort / scan wrappers follow rocPRIM's convention: temp == nullptr asks for the bytes.
 constexpr int kBootMaxK = 16;  // feature neighbours per source keypoint (k_correspondences)

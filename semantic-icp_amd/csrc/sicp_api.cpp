@@ -776,18 +776,9 @@ int sicp_correspondences(sicp_handle h, const double qt[7], int32_t* idx, float*
     if (!h || !qt) return SICP_ERR_INVALID_ARGUMENT;
     SICPCHECK(set_device(h));
     SICPCHECK(check_ready(h, false));
+    SICPCHECK(search_at(h, qt));
     const sicp_params& P = h->params;
-    const bool em = P.mode == SICP_MODE_EM;
     Cloud &S = h->cloud(0), &T = h->cloud(1);
-    SICPCHECK(prepare_cloud(h, S));
-    SICPCHECK(prepare_cloud(h, T));
-    if (!features_current(h, S, em)) SICPCHECK(compute_features(h, S, em));
-    if (!features_current(h, T, em)) SICPCHECK(compute_features(h, T, em));
-    if (em && !weights_from_histograms(P, P.knn)) {  // as align_begin: the projections belong to the feature phase
-      SICPCHECK(ensure_proj(h, S));
-      SICPCHECK(ensure_proj(h, T));
-    }
-    SICPCHECK(run_correspondences(h, qt, P.knn, true));
     const int n = S.n, K = P.knn;
     const size_t slots = (size_t)n * K;
     std::vector<int> hi(slots);
@@ -826,6 +817,20 @@ int sicp_accumulate(sicp_handle h, const double qt[7], double out28[28]) {
     if (!h->corr_valid) return SICP_ERR_NOT_READY;
     SICPCHECK(set_device(h));
     return eval28(h, qt, out28);
+  });
+}
+
+int sicp_pose_covariance(sicp_handle h, const double qt[7], double sigma_source, double sigma_target,
+                         sicp_pose_covariance_result* out) {
+  return abi_guard(h, [&]() -> int {
+    return pose_covariance(h, qt, sigma_source, sigma_target, out);
+  });
+}
+
+int sicp_pose_covariance_batch(sicp_handle* hs, int32_t n, const double* qt, double sigma_source, double sigma_target,
+                               sicp_pose_covariance_result* out, int32_t* status) {
+  return abi_guard((hs && n > 0) ? hs[0] : nullptr, [&]() -> int {
+    return pose_covariance_batch(hs, n, qt, sigma_source, sigma_target, out, status);
   });
 }
 

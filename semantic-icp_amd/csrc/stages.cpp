@@ -337,6 +337,21 @@ int run_correspondences(sicp_context* h, const double* qt, int K, bool weights) 
   return SICP_OK;
 }
 
+int search_at(sicp_context* h, const double* qt) {
+  const sicp_params& P = h->params;
+  const bool em = P.mode == SICP_MODE_EM;
+  Cloud &S = h->cloud(0), &T = h->cloud(1);
+  SICPCHECK(prepare_cloud(h, S));
+  SICPCHECK(prepare_cloud(h, T));
+  if (!features_current(h, S, em)) SICPCHECK(compute_features(h, S, em));
+  if (!features_current(h, T, em)) SICPCHECK(compute_features(h, T, em));
+  if (em && !weights_from_histograms(P, P.knn)) {  // as align_begin: the projections belong to the feature phase
+    SICPCHECK(ensure_proj(h, S));
+    SICPCHECK(ensure_proj(h, T));
+  }
+  return run_correspondences(h, qt, P.knn, true);
+}
+
 // SICP_WEIGHTS_FROM_HIST (developer switch; K = 4 and at most 16 classes): the weight kernel reads the 16-byte label
 // histograms themselves and forms the projections it needs (feature_kernels.hip: em_weight_hist4_body; same bits), no
 // projection array is computed for align().  Built and measured in round 4 (profiles/r04/weights_from_histograms.json): the
