@@ -328,7 +328,8 @@ __global__ __launch_bounds__(64) void boot_fpfh_kernel(const BootCloudJob* jobs,
 
 // ---- feature k-NN: f32 L2 over bins 0..32 in order, ties to the lower index; target features tiled through LDS --------
 constexpr int kKnnTile = 64;
-// (job = pair: n source features sf, nt target features tf -> out[n][k])
+// (job = pair: n source features sf, nt target features tf -> out[n][k]).  A feature row is NaN in all 33 bins or in none
+// (boot_fpfh_kernel), so the source's test of every bin and the target's of bin 0 are one rule: "has a feature".
 __global__ __launch_bounds__(256) void boot_feature_knn_kernel(const BootPairJob* jobs, const int* blk_end, int nj, int k) {
   __shared__ float tile[kKnnTile][33];
   __shared__ int ok[kKnnTile];
@@ -368,11 +369,16 @@ __global__ __launch_bounds__(256) void boot_feature_knn_kernel(const BootPairJob
 #pragma unroll
       for (int b = 0; b < 33; ++b) { const float df = qf[b] - tile[r][b]; d = d + df * df; }
       if (!(d < bd[kBootMaxK - 1])) continue;  // (a later index never displaces an equal distance)
+      // insert behind every entry at most as far, then move the rest down one place each.  (The rest moves whatever it
+      // compares to: a displaced entry tested with `<` again would jump over an entry at its own distance, and two
+      // target rows with the same distance would swap whenever a nearer row arrived after them.)
       float cd = d;
       int ci = t0 + r;
+      bool moving = false;
 #pragma unroll
       for (int s = 0; s < kBootMaxK; ++s) {
-        if (cd < bd[s]) { const float td = bd[s]; const int ti = bi[s]; bd[s] = cd; bi[s] = ci; cd = td; ci = ti; }
+        moving = moving || cd < bd[s];
+        if (moving) { const float td = bd[s]; const int ti = bi[s]; bd[s] = cd; bi[s] = ci; cd = td; ci = ti; }
       }
     }
   }

@@ -158,6 +158,11 @@ def fpfh(kp, nrm, off, idx, d2):
 
 
 def features(kp, normal_radius=3.0, feature_radius=3.0):
+    """lists of the feature radius, normals from the normal radius' lists (their own when the radii differ), FPFH"""
+    if len(kp) == 0:
+        z = np.zeros(0)
+        return dict(off=np.zeros(1, np.int64), idx=z.astype(np.int32), d2=z.astype(np.float32), normals=np.zeros((0, 3)),
+                    gap=z, fpfh=np.zeros((0, 33), np.float32))
     off, idx, d2 = radius_lists(kp, feature_radius)
     if normal_radius == feature_radius:
         n, gap = normals(kp, off, idx)
@@ -197,6 +202,15 @@ def umeyama(src, tgt):
     return np.hstack([R, (ct - R @ cs)[:, None]])
 
 
+def fit_rank_ratio(src, tgt):
+    """second over first singular value of the pairs' cross-covariance.  The rotation of the rigid fit is unique only when
+    this matrix has rank 2 or more: at 0 (either side collinear -- one target keypoint drawn for two of three samples is
+    enough) every rotation about the common line is an optimum, and the result belongs to the solver."""
+    s, t = np.asarray(src, np.float64), np.asarray(tgt, np.float64)
+    sv = np.linalg.svd((s - s.mean(axis=0)).T @ (t - t.mean(axis=0)), compute_uv=False)
+    return float(sv[1] / sv[0]) if sv[0] > 0 else 0.0
+
+
 def transform_f32(M, p):
     """f64 products and sums ((m0 x + m1 y) + m2 z) + m3, rounded to f32"""
     P = p.astype(np.float64)
@@ -212,9 +226,14 @@ def truncated_error(M, src_kp, tgt_tree, tgt_kp, t):
     return float(np.sum(np.where(e <= t, e / t, 1.0)))
 
 
-def sac_ia(src_kp, src_f, tgt_kp, tgt_f, knn=None, **kw):
-    """SampleConsensusInitialAlignment: (best iteration, its error, all errors, all matrices)"""
+def sac_ia(src_kp, src_f, tgt_kp, tgt_f, knn=None, stats=None, **kw):
+    """SampleConsensusInitialAlignment: (best iteration, its error, all errors, all matrices).  `stats` (a dict) receives
+    what the run went through: "halvings" (times min_sample_distance was halved), "k_eff", "draws" (sample draws),
+    "samples" ([(source indices, target indices)] per iteration) and "ambiguous": the iterations whose pairs do not fix a
+    rotation (fit_rank_ratio below 1e-6), where any two solvers may return different optima."""
     P = dict(DEFAULTS, **kw)
+    halvings = draws = 0
+    samples, ambiguous = [], []
     k, nr = P["k_correspondences"], P["nr_samples"]
     if knn is None:
         knn = feature_knn(src_f, tgt_f, k)
@@ -228,6 +247,7 @@ def sac_ia(src_kp, src_f, tgt_kp, tgt_f, knn=None, **kw):
         smp, fails, min_d = [], 0, np.float32(P["min_sample_distance"])
         while len(smp) < nr:
             si = int(valid[rng.index(nv)])
+            draws += 1
             ok = True
             for sj in smp:
                 d = src_kp[si] - src_kp[sj]
@@ -243,10 +263,16 @@ def sac_ia(src_kp, src_f, tgt_kp, tgt_f, knn=None, **kw):
             if fails >= 3 * nv:
                 min_d = np.float32(min_d * np.float32(0.5))
                 fails = 0
+                halvings += 1
         tj = [int(knn[s, rng.index(k_eff)]) for s in smp]
         M = umeyama(src_kp[smp], tgt_kp[tj])
+        samples.append((list(smp), tj))
+        if fit_rank_ratio(src_kp[smp], tgt_kp[tj]) < 1e-6:
+            ambiguous.append(len(Ms))
         Ms.append(M)
         errs.append(truncated_error(M, src_kp, tree, tgt_kp, P["max_corr_distance"]))
+    if stats is not None:
+        stats.update(halvings=halvings, k_eff=k_eff, draws=draws, samples=samples, ambiguous=ambiguous)
     errs = np.array(errs)
     best = int(np.argmin(errs))
     return best, float(errs[best]), errs, np.array(Ms)
