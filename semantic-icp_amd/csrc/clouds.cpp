@@ -86,7 +86,7 @@ int stage_cloud(sicp_context* h, Cloud& c, int32_t n, const StridedCloud& in) {
   c.bb_valid = true;
   c.is_set = true;
   c.layout = -1;
-  c.feat_valid = false;
+  c.feat_valid = false; c.rec_dense_n = 0;
   c.cov_general = false;
   c.proj_valid = false;
   return SICP_OK;
@@ -221,7 +221,7 @@ int prepare_cloud(sicp_context* h, Cloud& c) {
   HIPCHECK(hipEventRecord(c.ready_ev, h->stream));
   c.pending = true;
   c.layout = want;
-  c.feat_valid = false;
+  c.feat_valid = false; c.rec_dense_n = 0;
   c.cov_general = false;
   h->corr_valid = false;
   h->hint_ok = false;
@@ -256,7 +256,7 @@ int set_cloud_common(sicp_handle h, int which, int32_t n, const StridedCloud& in
   SICPCHECK(stage_cloud(h, c, n, in));
   c.is_set = true;
   c.layout = -1;
-  c.feat_valid = false;
+  c.feat_valid = false; c.rec_dense_n = 0;
   c.cov_general = false;
   h->corr_valid = false;
   h->hint_ok = false;

@@ -275,8 +275,8 @@ struct Cloud {
   DevBuf<int> d_seg_begin, d_seg_end;
   HostBuf<int> h_seg_begin, h_seg_end;
   DevBuf<sicp::PointRec> rec;  // position + normal of every point (what the weight / accumulate kernels gather)
-  DevBuf<char> rec_dense;      // the same as three dense arrays (what the accumulate kernel streams for the source points)
-  int rec_dense_n = 0;         // the cloud size they were written for (0: not written)
+  DevBuf<char> rec_dense;      // the same as three dense arrays (what the accumulate kernel streams for the source points and gathers for the targets)
+  int rec_dense_n = 0;         // the cloud size they were written for (0: not written); set with rec, cleared wherever feat_valid is cleared
   // Caller-supplied covariances that are NOT of the form I - (1-eps) n n^T (sicp_set_covariances): the six entries xx xy xz yy
   // yz zz of every point's symmetric matrix, device order.  A handle with such a cloud evaluates through
   // accumulate_general_kernel (the literal gicp_cost_function.h:27-73 with full 3x3 matrices), one pair at a time.

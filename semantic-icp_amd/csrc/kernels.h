@@ -159,8 +159,13 @@ struct CovArgs {
 
 // The records again, dense: [n] x 16 B (nx ny) | [n] x 16 B (nz x y) | [n] x 4 B (z).  What the accumulate kernel STREAMS
 // -- the source points of a pass, in order -- is read from here: 36 bytes per point from HBM instead of the 48 of a
-// record (the 48-byte record is what a gather wants: one point, one place).
+// record.  Its GATHERS of target records come from here too: neighbouring source points hit neighbouring targets, and 4 (16)
+// consecutive targets share a 64-byte line of a 16-byte (4-byte) array where a 48-byte record shares its lines with at most
+// one neighbour ("dense gathers").  Every writer of `rec` writes this copy beside it.
 SICP_HD inline size_t dense_rec_bytes(int n) { return (size_t)(n > 0 ? n : 1) * 36; }
+// The accumulate kernel's GATHERS of target records come from the dense arrays too (AccArgs::trec_dense), addressed as an
+// array's base plus a 32-bit byte offset 16 j: clouds beyond this size keep the record path.
+constexpr int kDenseGatherMaxPoints = 1 << 27;
 
 // rows of the label histograms (uint8 neighbour counts) are padded to 16 bytes: one aligned dwordx4 load fetches the row of up
 // to 16 classes (the EM weight kernel gathers a target's 16-byte row instead of its 96-byte projection row)
@@ -199,6 +204,8 @@ struct AccArgs {
   const double* w;  // nullable (weight 1)
   const PointRec *srec, *trec;
   const char* srec_dense;  // nullable: the source records as dense arrays (dense_rec_*), pitch n_s
+  const char* trec_dense;  // nullable: the target records as dense arrays, pitch n_t: the staged kernel gathers from them
+  int n_t, pad_;           // (null: from the 48-byte records)
   Pose pose;            // used when lm == nullptr
   const LmState* lm;    // device-resident solve: evaluate at lm->pose, skip when it has finished
   LmState* lm_step;     // batched solve: the state lm_step_batch_kernel advances (== lm)

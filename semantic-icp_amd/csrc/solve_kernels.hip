@@ -215,7 +215,8 @@ struct LoadCtx {
   const SICP_GLOBAL PointRec* srec;
   const SICP_GLOBAL PointRec* trec;
   const SICP_GLOBAL char* sdense;    // nullable: the source records as dense arrays (kernels.h: dense_rec_*), pitch n_s
-  int n_s, total;
+  const SICP_GLOBAL char* tdense;    // nullable: the target records as dense arrays, pitch n_t (the gathers then come from them)
+  int n_s, n_t, total;
 };
 struct MathCtx {
   Pose P;
@@ -374,6 +375,20 @@ __device__ __forceinline__ void lds_dma_rec(const SICP_GLOBAL PointRec* r, SICP_
   __builtin_amdgcn_global_load_lds((const SICP_GLOBAL void*)(p + 32), (SICP_LDS void*)(slot + 2048), 4, 0, 0);
 }
 
+// The same three pieces of target j from the dense arrays (kernels.h: dense_rec_*): 4 consecutive targets share a 64-byte
+// line per 16-byte piece and 16 share one for the 4-byte piece, where a 48-byte record shares its lines with at most one
+// neighbour -- and neighbouring source points hit neighbouring targets ("dense gathers").  b0 / b1 / b2 are the
+// three arrays' bases (uniform: SGPR pairs) and the lane's part is a 32-bit byte offset, the instruction's own address form:
+// two shifts per record, no 64-bit vector arithmetic.  The host hands the arrays over only for clouds whose offsets fit
+// (kDenseGatherMaxPoints).
+__device__ __forceinline__ void lds_dma_rec_dense(const SICP_GLOBAL char* b0, const SICP_GLOBAL char* b1, const SICP_GLOBAL char* b2, int j,
+                                                  SICP_LDS char* slot) {
+  const unsigned o16 = (unsigned)j << 4, o4 = (unsigned)j << 2;
+  __builtin_amdgcn_global_load_lds((const SICP_GLOBAL void*)(b0 + o16), (SICP_LDS void*)slot, 16, 0, 0);
+  __builtin_amdgcn_global_load_lds((const SICP_GLOBAL void*)(b1 + o16), (SICP_LDS void*)(slot + 1024), 16, 0, 0);
+  __builtin_amdgcn_global_load_lds((const SICP_GLOBAL void*)(b2 + o4), (SICP_LDS void*)(slot + 2048), 4, 0, 0);
+}
+
 __device__ __forceinline__ void lds_read_rec(const SICP_LDS char* slot, int lane, float& x, float& y, float& z, double& nx, double& ny, double& nz) {
   const v2d a = *(const SICP_LDS v2d*)(slot + 16 * lane);
   const v4f b = *(const SICP_LDS v4f*)(slot + 1024 + 16 * lane);
@@ -500,13 +515,32 @@ __device__ __forceinline__ void accumulate_segment(const LoadCtx& L, const MathC
     __builtin_amdgcn_s_barrier();
     parked = 0;
   };
+  // (uniform for the segment: the choice below is a scalar branch around instructions that write no register, so nothing
+  //  merges behind it and the stage stays free of waits)
+  const SICP_GLOBAL char* const td0 = L.tdense;
+  const SICP_GLOBAL char* const td1 = td0 + 16 * (size_t)L.n_t;
+  const SICP_GLOBAL char* const td2 = td0 + 32 * (size_t)L.n_t;
+  const int dense_gather = uniform_i32(td0 != nullptr);
   auto issue_targets = [&](const int (&j)[SG]) {
-#pragma unroll
 #if defined(SICP_DEBUG_NOGATHER)  // developer aid: every gather reads target 0 (results are wrong)
-    for (int c = 0; c < SG; ++c) lds_dma_rec(L.trec + (max(j[c], 0) & 0), stage + c * STAGE_SLOT_BYTES);
+#define SICP_GATHER_INDEX(jc) (max(jc, 0) & 0)
 #else
-    for (int c = 0; c < SG; ++c) lds_dma_rec(L.trec + max(j[c], 0), stage + c * STAGE_SLOT_BYTES);
+#define SICP_GATHER_INDEX(jc) max(jc, 0)
 #endif
+    // (the flag passes through an empty asm statement: a test the compiler can hoist out of the step loop comes back as a
+    //  lane mask that it re-materialises through a VGPR -- two vector instructions per step for a scalar branch)
+    int dense = dense_gather;
+    asm volatile("" : "+s"(dense));
+    if (dense) {
+#pragma unroll
+      for (int c = 0; c < SG; ++c) lds_dma_rec_dense(td0, td1, td2, SICP_GATHER_INDEX(j[c]), stage + c * STAGE_SLOT_BYTES);
+      asm volatile("; dense gathers issued");  // (distinct tails: merged, the two forms' last loads share one 64-bit address)
+    } else {
+#pragma unroll
+      for (int c = 0; c < SG; ++c) lds_dma_rec(L.trec + SICP_GATHER_INDEX(j[c]), stage + c * STAGE_SLOT_BYTES);
+      asm volatile("; record gathers issued");
+    }
+#undef SICP_GATHER_INDEX
   };
   // fill: indices of the first two groups, then targets / weights / source of the first
   load_idx_raw<K>(L, g, R0.j);
@@ -760,7 +794,9 @@ __global__ __launch_bounds__(BS, SICP_ACC_OCC) void accumulate_staged_kernel(Bat
     L.srec = (const SICP_GLOBAL PointRec*)uniform_ptr(a.srec);
     L.trec = (const SICP_GLOBAL PointRec*)uniform_ptr(a.trec);
     L.sdense = (const SICP_GLOBAL char*)uniform_ptr(a.srec_dense);
+    L.tdense = (const SICP_GLOBAL char*)uniform_ptr(a.trec_dense);
     L.n_s = uniform_i32(a.n_s);
+    L.n_t = uniform_i32(a.n_t);
     L.total = uniform_i32(a.n_s * a.K);
     const AccGeometry geo = acc_geometry(L.total, SG);
     const int n_chunks = uniform_i32(geo.n_chunks), steps = uniform_i32(geo.steps);
@@ -886,7 +922,9 @@ __global__ __launch_bounds__(BS, 1) void solve_one_kernel(const SoloArgs A) {
   L.srec = (const SICP_GLOBAL PointRec*)uniform_ptr(a.srec);
   L.trec = (const SICP_GLOBAL PointRec*)uniform_ptr(a.trec);
   L.sdense = nullptr;  // (a worker loads its chunk once)
+  L.tdense = nullptr;
   L.n_s = uniform_i32(a.n_s);
+  L.n_t = 0;
   L.total = uniform_i32(a.n_s * a.K);
   const AccGeometry geo = acc_geometry(L.total, SG);
   const int n_chunks = uniform_i32(geo.n_chunks), chunk_groups = uniform_i32(geo.chunk_groups);

@@ -208,7 +208,7 @@ int compute_features(sicp_context* h, Cloud& c, bool with_hist, hipStream_t stre
   a.rec = c.rec.p;
   a.hist = with_hist ? c.hist.p : nullptr;
   // the records also as dense arrays (without them the accumulate kernel streams the 48-byte records: 814 instead of
-  // 800 us per 256-pair launch, 2.18 instead of 2.22 G corr/s)
+  // 800 us per 256-pair launch, 2.18 instead of 2.22 G corr/s -- and gathers them: 796 instead of 780 us)
   a.rec_dense = nullptr; a.rec_dense_n = 0;
   c.rec_dense_n = 0;
   if (n > 0) {
@@ -406,6 +406,10 @@ void fill_acc(sicp_context* h, sicp::AccArgs& a) {
   a.w = h->corr_weighted ? h->w.p : nullptr;
   a.srec = S.rec.p; a.trec = T.rec.p;
   a.srec_dense = (S.rec_dense_n == S.n && S.n > 0 && S.n == h->corr_n) ? S.rec_dense.p : nullptr;
+  // the gathers come from the target's dense arrays whenever they are current: rec_dense_n is set where rec is written (cov_kernel,
+  // set_normals_kernel) and cleared wherever feat_valid is (a cloud that is re-set, re-laid out or recycled by the pool)
+  a.trec_dense = (T.feat_valid && T.rec_dense_n == T.n && T.n > 0 && T.n <= sicp::kDenseGatherMaxPoints) ? T.rec_dense.p : nullptr;
+  a.n_t = T.n; a.pad_ = 0;
   a.lm = nullptr;
   a.lm_step = nullptr;
   a.one_m_eps = 1.0 - P.epsilon;
