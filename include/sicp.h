@@ -307,8 +307,15 @@ int sicp_stream_submit(sicp_stream s, int64_t source_id, int64_t target_id, cons
  *       the stream is destroyed -- a caller may take them long after the poll that returned the registration.
  *   SICP_SUBMIT_FRESH_FEATURES the normals / label histograms of BOTH clouds are recomputed for this registration,
  *       like every align() of the reference does (em_icp.hpp:28-29, gicp.hpp:33-34), instead of being kept with the
- *       cloud (a stream's default: what setSourceCloud(cloud, kdtree, covs) exists for).  Same values either way. */
-enum { SICP_SUBMIT_FUSED_LABELS = 1, SICP_SUBMIT_FRESH_FEATURES = 2 };
+ *       cloud (a stream's default: what setSourceCloud(cloud, kdtree, covs) exists for).  Same values either way.
+ *   SICP_SUBMIT_POSE_COVARIANCE (any mode; may be combined with the other two) the sums of sicp_pose_covariance at the
+ *       final pose are computed when the registration retires -- one more search at that pose, one accumulate sweep and
+ *       the covariance kernels, shared by all flagged registrations that retire in the same turn and queued beside the
+ *       running ones -- and kept (about 0.6 KB) until sicp_stream_take_pose_covariance(ticket) fetches them.  The
+ *       registration's result is only handed out by sicp_stream_poll when they are there; its pose, outer_iters and
+ *       counters are those of the same registration without the flag.
+ * The value 8, not 4: bit 4 has always been refused as an unknown flag and stays refused, as do bits 16 and above. */
+enum { SICP_SUBMIT_FUSED_LABELS = 1, SICP_SUBMIT_FRESH_FEATURES = 2, SICP_SUBMIT_POSE_COVARIANCE = 8 };
 int sicp_stream_submit_ex(sicp_stream s, int64_t source_id, int64_t target_id, const double init_qt[7],
                           uint32_t flags, int64_t* ticket);
 int sicp_stream_take_labels(sicp_stream s, int64_t ticket, int32_t n, uint32_t* out_labels);
@@ -425,14 +432,26 @@ typedef struct sicp_pose_covariance_result {
  * SICP_ERR_NOT_READY, as sicp_align.  Bit-reproducible: no float atomics anywhere in the sums. */
 int sicp_pose_covariance(sicp_handle h, const double qt[7], double sigma_source, double sigma_target,
                          sicp_pose_covariance_result* out);
-/* sicp_pose_covariance for n pairs: pair i = handle hs[i] at qt[7 i .. 7 i + 7), out[i].  The pairs run one after another
- * through the lone path (one device scratch for all of them), so every row is bit-identical to its lone call.  status[n]
+/* sicp_pose_covariance for n pairs: pair i = handle hs[i] at qt[7 i .. 7 i + 7), out[i].  The pairs run in groups that
+ * share every launch -- one job flush for the searches, the batched accumulate kernel, the covariance kernels over a job
+ * table with one sort, one read-back and one wait per group; a group holds a handle once (a handle may repeat in the
+ * call) and is bounded by its scratch -- and a pair keeps the summation order of its lone call, so every row is
+ * bit-identical to it.  Handles may be in different modes.  status[n]
  * (nullable) gets each pair's own code; a failing pair does not stop the others and its row is not written; the call
  * returns SICP_OK when every pair succeeded, else the first failing pair's code.  Refused before any work, with
  * SICP_ERR_INVALID_ARGUMENT and nothing written: n < 1, a NULL array or handle, a bad sigma, handles on different devices.
- * Not yet available for streams (no submit flag): evaluate it on the pair's handle after align(). */
+ * Streams: SICP_SUBMIT_POSE_COVARIANCE and sicp_stream_take_pose_covariance. */
 int sicp_pose_covariance_batch(sicp_handle* hs, int32_t n, const double* qt, double sigma_source, double sigma_target,
                                sicp_pose_covariance_result* out, int32_t* status);
+/* The pose covariance of a registration submitted with SICP_SUBMIT_POSE_COVARIANCE, once sicp_stream_poll has handed the
+ * registration out: *out is what sicp_pose_covariance(h, final pose, sigma_source, sigma_target) gives on a handle that
+ * holds the two clouds, bit for bit (the stream keeps the sums; the 6x6 algebra runs here, with these sigmas -- which is
+ * why they are no submit arguments).  H that is not positive definite: positive_definite = 0, NaN matrices, SICP_OK.  A
+ * successful call takes the entry: it works once per ticket.  SICP_ERR_NOT_READY: the ticket was not flagged, is not
+ * finished, or has been taken.  SICP_ERR_INVALID_ARGUMENT, nothing written and the entry kept (a later correct call
+ * succeeds): a NULL stream or out, a sigma that is negative or not finite. */
+int sicp_stream_take_pose_covariance(sicp_stream s, int64_t ticket, double sigma_source, double sigma_target,
+                                     sicp_pose_covariance_result* out);
 
 /* test / bench hook: the keypoints of cloud `which` with their normals, FPFH features and feature-radius
  * neighbour lists (CSR: nbr_offsets[n + 1], nbr_idx sorted by (d^2, index)).  Counts are always written; an output

@@ -401,6 +401,7 @@ struct sicp_context {
   DevBuf<double> tmp9;  // sicp_covariances: the 3x3 matrices in the caller's order on their way out
   DevBuf<uint32_t> tmpl;
   HostBuf<uint32_t> h_labels;  // pinned: fused labels of a stream slot on their way back
+  HostBuf<unsigned char> pc_stage;  // pinned: arguments and results of the pose-covariance sweeps this handle leads (pose_cov.cpp)
   // lock-step batch (sicp_align_batch), owned by the batch's first handle: one BatchArgs and one LM
   // state per pair, pinned mirrors, and the captured [accumulate_batch, lm_step_batch] x lm_batch graph
   TickSet ts[2];  // two sets: the halves of a batch alternate, one's tick runs while the host turns the other around
@@ -434,6 +435,17 @@ struct sicp_context {
 // batch.  Clouds are uploaded by the submitting thread on the stream's own upload stream; a worker thread owns
 // `cap` handles (slots) and runs the tick loop: admit queued registrations into free slots, one turn, retire.
 struct StreamCloudRef;
+namespace sicp {
+namespace host {
+// the raw sums of a pose covariance: what remains to be done with them is host algebra with the caller's sigmas
+struct PoseCovSums {
+  double out28[28];  // hessian 21 | gradient 6 | cost
+  double sums[42];   // S_src 21 | S_tgt 21
+  long long active;
+};
+struct PoseCovStream;  // pose_cov.cpp: a stream's covariance scratch and pinned stages
+}  // namespace host
+}  // namespace sicp
 struct sicp_stream_ctx {
   int device = 0, cap = 0;
   sicp_params params;
@@ -456,6 +468,7 @@ struct sicp_stream_ctx {
   std::deque<Submission> queue;
   std::deque<sicp_stream_result> done;
   std::unordered_map<long long, std::vector<uint32_t>> labels;  // ticket -> getFusedLabels of a SICP_SUBMIT_FUSED_LABELS registration, until taken
+  std::unordered_map<long long, PoseCovSums> cov_sums;  // ticket -> sums of a SICP_SUBMIT_POSE_COVARIANCE registration, until taken
   std::unordered_map<long long, std::shared_ptr<Cloud>> clouds;
   long long next_cloud = 1, next_ticket = 1;
   long long submitted = 0, completed = 0, busy_evals = 0, slot_evals = 0;
@@ -472,6 +485,8 @@ struct sicp_stream_ctx {
   std::vector<double> slot_t0;
   std::vector<unsigned> slot_flags;
   std::vector<hipEvent_t> slot_ev;  // SICP_SUBMIT_FUSED_LABELS: recorded behind the label kernel + read-back of the slot
+  PoseCovStream* cov = nullptr;     // SICP_SUBMIT_POSE_COVARIANCE: reserved with the first flagged registration, released with the stream
+  std::vector<int> slot_cov_stage, slot_cov_row;  // the stage of the slot's covariance pass and its row there
   std::thread worker;
 };
 
@@ -635,8 +650,9 @@ int run_tick(sicp_context* h, hipStream_t M, sicp_handle* hs, int n, const std::
 // loop -- only for the end of the current tick.
 // PAIR_FIRST: the pair's start-up pipeline (features, first search, weights) is queued on the start-up stream; it joins
 // the ticks when the event of its chunk has completed
-// PAIR_LABELS (streams only): converged; its getFusedLabels pass is queued and the slot waits for the labels
-enum { PAIR_FREE = -1, PAIR_NEED_SEARCH = 0, PAIR_JOINING, PAIR_SOLVING, PAIR_DONE, PAIR_FIRST, PAIR_LABELS };
+// PAIR_PASS (streams only): converged; the passes its flags ask for at the final pose (getFusedLabels, the pose covariance's
+// sums) are queued and the slot waits for their read-back
+enum { PAIR_FREE = -1, PAIR_NEED_SEARCH = 0, PAIR_JOINING, PAIR_SOLVING, PAIR_DONE, PAIR_FIRST, PAIR_PASS };
 
 // pairs [lo, hi) that advance together: one tick stream, one argument set
 struct TickGroup {
@@ -722,6 +738,16 @@ int align_batch(sicp_handle* hs, int32_t n, const double* init_qt, double* out_q
 int pose_covariance(sicp_context* h, const double* qt, double sigma_source, double sigma_target, sicp_pose_covariance_result* out);
 int pose_covariance_batch(sicp_handle* hs, int32_t n, const double* qt, double sigma_source, double sigma_target,
                           sicp_pose_covariance_result* out, int32_t* status);
+// A stream's covariance pass: the sweep of the slots whose searches at their final poses are queued on `side`, with the
+// read-back and one event per sweep behind it (slot_cov_stage / slot_cov_row say where a slot's sums arrive) ...
+int stream_cov_pass(sicp_stream_ctx* S, const std::vector<int>& slots, const std::vector<const double*>& qts, hipStream_t side);
+hipEvent_t stream_cov_event(sicp_stream_ctx* S, int slot);
+// ... the slot's sums once that event has completed (once per slot and pass), and the end of the stream's scratch (idle:
+// the side stream has been waited for)
+void stream_cov_take(sicp_stream_ctx* S, int slot, PoseCovSums* out);
+void stream_cov_destroy(sicp_stream_ctx* S, bool idle);
+// the caller's result from the sums: SICP_ERR_INVALID_ARGUMENT (nothing written) for a NULL out or a sigma that is negative or not finite
+int pose_covariance_from_sums(const PoseCovSums& u, double sigma_source, double sigma_target, sicp_pose_covariance_result* out);
 
 }  // namespace host
 }  // namespace sicp

@@ -369,25 +369,40 @@ struct PoseCovArgs {
   double one_m_eps, cauchy_a;
   int use_sqloss, pad_;
   double* bq;               // out: [n_s * K][18] B^q of every active slot, row-major 6x3
-  unsigned long long* key;  // out: [n_s * K] target << 32 | slot, ~0 for a gated-out slot
+  unsigned long long* key;  // out: [n_s * K] job | target | slot (PoseCovJob), target = n_t for a gated-out slot
   double* part_src;         // out: [21][pose_cov_blocks(n_s)]
   long long* part_active;   // out: [pose_cov_blocks(n_s)]
 };
-struct PoseCovTgtArgs {
-  int total;                      // slots (n_s * K)
-  const unsigned long long* key;  // sorted ascending
-  const double* bq;
-  double* piece;     // [tiles][2][18] partial target sums of lists that cross a tile edge
-  int* flag;         // [tiles]
-  double* part_tgt;  // [21][2 * pose_cov_blocks(tiles)]
-};
 SICP_HD inline int pose_cov_blocks(int items) { return items > 0 ? (items + 255) / 256 : 0; }
 SICP_HD inline int pose_cov_tiles(int total) { return (total + kPoseCovTile - 1) / kPoseCovTile; }
-hipError_t launch_pose_cov_src(const PoseCovArgs& a, hipStream_t st);
-hipError_t launch_pose_cov_tgt(const PoseCovTgtArgs& a, hipStream_t st);
-// out42 = [S_src 21 | S_tgt 21], *active = active slots: fixed-order sums of the partial columns
-hipError_t launch_pose_cov_finalize(const double* part_src, const long long* part_active, int src_cols, const double* part_tgt,
-                                    int tgt_cols, double* out42, long long* active, hipStream_t st);
+// Job form: one launch of each kernel over every pair of a group (a lone call is a group of one).  The jobs live in device
+// memory; job j owns the workgroups [blk_end[j - 1], blk_end[j]) of a launch (inclusive prefix of the per-job counts, as in
+// the bootstrap's job launches): pose_cov_blocks(n_s) of the source kernel, pose_cov_blocks(tiles) of the tile and the
+// owner kernel, 43 of the finalize.  A job keeps the column layout and the summation order of a launch of its own -- column
+// = workgroup within the job, the butterfly per wave, the four waves in order, the columns in order -- so its sums have
+// the same bits whatever else the launch holds.
+// The keys of all jobs are sorted at once: key = job << (tgt_bits + slot_bits) | target << slot_bits | slot, target = n_t for a
+// gated-out slot (last within its job), the three widths those of the group's largest job.  Job j's keys occupy
+// [off_j, off_j + n_s K) of the key array before and after the sort, so a tile never spans two jobs.
+struct PoseCovJob {
+  PoseCovArgs a;                   // a.key: the job's range of the group's key array
+  const unsigned long long* skey;  // the same range of the sorted keys
+  double* piece;                   // [tiles][2][18] partial target sums of lists that cross a tile edge
+  int* flag;                       // [tiles]
+  double* part_tgt;                // [21][2 * pose_cov_blocks(tiles)]
+  double* out42;                   // [S_src 21 | S_tgt 21]
+  long long* active;               // active slots
+  unsigned long long job_key;      // job << (tgt_bits + slot_bits)
+  int n_t, slot_bits, tgt_bits, pad_;
+};
+hipError_t launch_pose_cov_src_jobs(const PoseCovJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st);
+// ascending radix sort of bits [0, end_bit) (rocPRIM's convention: temp == nullptr asks for the bytes)
+hipError_t pose_cov_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long n, int end_bit,
+                              hipStream_t st);
+hipError_t launch_pose_cov_tile_jobs(const PoseCovJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st);
+hipError_t launch_pose_cov_owner_jobs(const PoseCovJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st);
+// fixed-order sums of the partial columns -> out42, active of every job
+hipError_t launch_pose_cov_finalize_jobs(const PoseCovJob* jobs, int nj, hipStream_t st);
 
 // ---- initial alignment without a pose prior (bootstrap_kernels.hip; driver: bootstrap.cpp) ----
 // The sort / scan wrappers follow rocPRIM's convention: temp == nullptr asks for the bytes.

@@ -6,20 +6,25 @@
 // summed per POINT: G_j = sum of B^p over source point j's slots, G_k = sum of B^q over the slots that hit target k, and
 // S = sum G G^T over each cloud (include/sicp.h gives the formulas).
 //
-//   pose_cov_src_kernel     one lane per source point: its K slots (contiguous) -> G_j in registers, G_j G_j^T into a
+//   pose_cov_src_jobs       one lane per source point: its K slots (contiguous) -> G_j in registers, G_j G_j^T into a
 //                           fixed-order column of partials; every active slot's B^q stored once (144 bytes) with its sort
-//                           key target << 32 | slot
-//   (rocPRIM radix sort of the keys: every target's slots become one run, in slot order)
-//   pose_cov_tile_kernel    one lane per tile of kPoseCovTile sorted slots: a run that lies inside the tile is summed and
+//                           key job | target | slot
+//   (ONE rocPRIM radix sort of the keys of all jobs, over the bits in use: every target's slots become one run, in slot
+//   order, inside the job's own range of the array)
+//   pose_cov_tile_jobs      one lane per tile of kPoseCovTile sorted slots: a run that lies inside the tile is summed and
 //                           squared at once; a run that crosses a tile edge leaves its part as a piece
-//   pose_cov_owner_kernel   one lane per tile whose last run starts a crossing list: adds the following tiles' pieces in
+//   pose_cov_owner_jobs     one lane per tile whose last run starts a crossing list: adds the following tiles' pieces in
 //                           tile order, then squares
-//   pose_cov_finalize_kernel the columns in a fixed order, one workgroup per output
-// Every sum has one fixed order that depends on the pair alone: no float atomics, so a pair gives the same bits alone,
-// in a batch and run after run.  A long target list costs its owner lane one 144-byte read per tile it spans instead of one
+//   pose_cov_finalize_jobs  the columns in a fixed order, one workgroup per output
+// Every kernel is launched once for a whole group of pairs (kernels.h: PoseCovJob; a lone call is a group of one).  A job
+// owns whole workgroups, and inside them everything is indexed from the job's own origin: its columns, tiles, pieces and
+// flags are those of a launch of its own.  Every sum therefore has one fixed order that depends on the pair alone -- the
+// butterfly per wave, the four waves in order, the job's columns in order -- and there are no float atomics: a pair gives
+// the same bits alone, in any group and run after run.  A long target list costs its owner lane one 144-byte read per tile it spans instead of one
 // per slot (the split rule of store-and-sum reductions with skewed destination counts).  Nothing here is GEMM shaped.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <rocprim/device/device_radix_sort.hpp>
 
 #define SICP_HD __host__ __device__
 #include "kernels.h"
@@ -120,7 +125,8 @@ __device__ __forceinline__ void add_outer(const double (&G)[18], double (&acc)[2
 }
 
 // 21 sums of a 256-lane workgroup into column `col` of part[21][cols]: a fixed butterfly per wave, the four waves in order
-__device__ __forceinline__ void block_sum21(double (&acc)[21], double* part, int cols, int col) {
+template <class PartPtr>
+__device__ __forceinline__ void block_sum21(double (&acc)[21], PartPtr part, int cols, int col) {
   __shared__ double s_w[4][21];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -134,18 +140,54 @@ __device__ __forceinline__ void block_sum21(double (&acc)[21], double* part, int
   if (threadIdx.x < 21) part[(size_t)threadIdx.x * cols + col] = (s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + (s_w[2][threadIdx.x] + s_w[3][threadIdx.x]);
 }
 
-__global__ __launch_bounds__(256) void pose_cov_src_kernel(PoseCovArgs a) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const int cols = gridDim.x;
+// A pointer read from a job record is a generic pointer to the compiler (flat loads and stores: 41 instead of 29 us for the
+// tile kernel of a 100K-point pair); the records only ever hold device memory, and saying so gives global ones.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SICP_GLOBAL __attribute__((address_space(1)))
+#else
+#define SICP_GLOBAL  // (the host pass only parses the kernels)
+#endif
+template <class T>
+__device__ __forceinline__ SICP_GLOBAL T* dev(T* p) {
+  return (SICP_GLOBAL T*)p;
+}
+
+// the job of workgroup b (blk_end: inclusive prefix of the per-job workgroup counts), *local = its place among the job's
+// workgroups.  Wave-uniform: the bisection and the job's fields stay in scalar registers.
+__device__ __forceinline__ int job_of(const int* __restrict__ blk_end, int nj, int b, int* local) {
+  int lo = 0, hi = nj - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (blk_end[mid] > b) hi = mid; else lo = mid + 1;
+  }
+  *local = b - (lo > 0 ? blk_end[lo - 1] : 0);
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void pose_cov_src_jobs_kernel(const PoseCovJob* __restrict__ jobs, const int* __restrict__ blk_end, int nj) {
+  int lb;
+  const PoseCovJob& J = jobs[job_of(blk_end, nj, blockIdx.x, &lb)];
+  const PoseCovArgs& a = J.a;
+  const int n_s = a.n_s, K = a.K;
+  const int i = lb * 256 + threadIdx.x;
+  const int cols = pose_cov_blocks(n_s);
   double acc[21];
 #pragma unroll
   for (int e = 0; e < 21; ++e) acc[e] = 0.0;
   int active = 0;
-  if (i < a.n_s) {
-    const Pose& P = a.pose;
+  if (i < n_s) {
+    const Pose P = a.pose;
     const double* R = P.R;
     const double k = a.one_m_eps, gw = 2.0 / k - 1.0, loss_b = a.cauchy_a * a.cauchy_a;
-    const PointRec sr = a.srec[i];
+    const bool sqloss = a.use_sqloss != 0;
+    const auto idx = dev(a.idx);
+    const auto wgt = dev(a.w);
+    const auto trec = dev(a.trec);
+    const auto keys = dev(a.key);
+    const auto bq = dev(a.bq);
+    const unsigned long long job_key = J.job_key, gated = job_key | ((unsigned long long)(unsigned)J.n_t << J.slot_bits);
+    const int slot_bits = J.slot_bits;
+    const PointRec sr = dev(a.srec)[i];
     const V3 p{(double)sr.x, (double)sr.y, (double)sr.z}, ns{sr.nx, sr.ny, sr.nz};
     const V3 m{R[0] * ns.x + R[1] * ns.y + R[2] * ns.z, R[3] * ns.x + R[4] * ns.y + R[5] * ns.z, R[6] * ns.x + R[7] * ns.y + R[8] * ns.z};
     const V3 qs{R[0] * p.x + R[1] * p.y + R[2] * p.z + P.t[0], R[3] * p.x + R[4] * p.y + R[5] * p.z + P.t[1],
@@ -153,22 +195,22 @@ __global__ __launch_bounds__(256) void pose_cov_src_kernel(PoseCovArgs a) {
     double G[18];
 #pragma unroll
     for (int e = 0; e < 18; ++e) G[e] = 0.0;
-    for (int c = 0; c < a.K; ++c) {
-      const int s = i * a.K + c;
-      const int j = a.idx[s];
+    for (int c = 0; c < K; ++c) {
+      const int s = i * K + c;
+      const int j = idx[s];
       if (j < 0) {
-        a.key[s] = ~0ull;
+        keys[s] = gated | (unsigned)s;
         continue;
       }
       ++active;
-      a.key[s] = ((unsigned long long)(unsigned)j << 32) | (unsigned)s;
-      const PointRec tr = a.trec[j];
+      keys[s] = job_key | ((unsigned long long)(unsigned)j << slot_bits) | (unsigned)s;
+      const PointRec tr = trec[j];
       const V3 q{(double)tr.x, (double)tr.y, (double)tr.z}, nt{tr.nx, tr.ny, tr.nz};
       double Bp[18], Bq[18];
-      slot_derivatives(P, k, gw, a.use_sqloss != 0, loss_b, a.w ? a.w[s] : 1.0, p, ns, m, qs, q, nt, Bp, Bq);
+      slot_derivatives(P, k, gw, sqloss, loss_b, wgt ? wgt[s] : 1.0, p, ns, m, qs, q, nt, Bp, Bq);
 #pragma unroll
       for (int e = 0; e < 18; ++e) G[e] += Bp[e];
-      double2* o = (double2*)(a.bq + (size_t)s * 18);
+      SICP_GLOBAL double2* o = (SICP_GLOBAL double2*)(bq + (size_t)s * 18);
 #pragma unroll
       for (int e = 0; e < 9; ++e) o[e] = make_double2(Bq[2 * e], Bq[2 * e + 1]);
     }
@@ -179,27 +221,38 @@ __global__ __launch_bounds__(256) void pose_cov_src_kernel(PoseCovArgs a) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
   if ((threadIdx.x & 63) == 0) s_act[threadIdx.x >> 6] = v;
-  block_sum21(acc, a.part_src, cols, blockIdx.x);  // (its barrier also orders s_act)
-  if (threadIdx.x == 0) a.part_active[blockIdx.x] = (long long)s_act[0] + s_act[1] + s_act[2] + s_act[3];
+  block_sum21(acc, dev(a.part_src), cols, lb);  // (its barrier also orders s_act)
+  if (threadIdx.x == 0) dev(a.part_active)[lb] = (long long)s_act[0] + s_act[1] + s_act[2] + s_act[3];
 }
-
-// target of a sorted key; -1 for a gated-out slot (those sort last)
-__device__ __forceinline__ long long key_target(unsigned long long key) { return key == ~0ull ? -1 : (long long)(key >> 32); }
 
 // flag bits of a tile: its first run continues the previous tile's list (piece 0), its last run starts a list that goes on
 // into the next tile (piece 1: the tile owns that list), its only run comes from the previous tile AND goes on (pass-through)
 constexpr int kFirstContinues = 1, kOwnsLast = 2, kPassThrough = 4;
 
-__global__ __launch_bounds__(256) void pose_cov_tile_kernel(PoseCovTgtArgs a) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const int tiles = pose_cov_tiles(a.total), cols = 2 * gridDim.x;
+__global__ __launch_bounds__(256) void pose_cov_tile_jobs_kernel(const PoseCovJob* __restrict__ jobs, const int* __restrict__ blk_end, int nj) {
+  int lb;
+  const PoseCovJob& J = jobs[job_of(blk_end, nj, blockIdx.x, &lb)];
+  const int total = J.a.n_s * J.a.K;
+  const int t = lb * 256 + threadIdx.x;
+  const int tiles = pose_cov_tiles(total), cols = 2 * pose_cov_blocks(tiles);
   double acc[21];
 #pragma unroll
   for (int e = 0; e < 21; ++e) acc[e] = 0.0;
   if (t < tiles) {
-    const int b = t * kPoseCovTile, e = min(b + kPoseCovTile, a.total);
-    const long long prev = b > 0 ? key_target(a.key[b - 1]) : -2;
-    const long long next = e < a.total ? key_target(a.key[e]) : -2;
+    const auto skey = dev(J.skey);
+    const auto bq = dev(J.a.bq);
+    const auto piece = dev(J.piece);
+    const int slot_bits = J.slot_bits;
+    const unsigned long long slot_mask = (1ull << slot_bits) - 1ull, tgt_mask = (1ull << J.tgt_bits) - 1ull;
+    const long long n_t = J.n_t;
+    // target of a sorted key; -1 for a gated-out slot (those sort last within the job)
+    auto key_target = [&](unsigned long long key) {
+      const long long tg = (long long)((key >> slot_bits) & tgt_mask);
+      return tg == n_t ? -1ll : tg;
+    };
+    const int b = t * kPoseCovTile, e = min(b + kPoseCovTile, total);
+    const long long prev = b > 0 ? key_target(skey[b - 1]) : -2;
+    const long long next = e < total ? key_target(skey[e]) : -2;
     int flag = 0;
     double sum[18];
 #pragma unroll
@@ -211,7 +264,7 @@ __global__ __launch_bounds__(256) void pose_cov_tile_kernel(PoseCovTgtArgs a) {
       if (!cin && !cout) {
         add_outer(sum, acc);
       } else {
-        double2* o = (double2*)(a.piece + ((size_t)t * 2 + (cin ? 0 : 1)) * 18);
+        SICP_GLOBAL double2* o = (SICP_GLOBAL double2*)(piece + ((size_t)t * 2 + (cin ? 0 : 1)) * 18);
 #pragma unroll
         for (int x = 0; x < 9; ++x) o[x] = make_double2(sum[2 * x], sum[2 * x + 1]);
         flag |= cin ? (kFirstContinues | (cout ? kPassThrough : 0)) : kOwnsLast;
@@ -219,7 +272,7 @@ __global__ __launch_bounds__(256) void pose_cov_tile_kernel(PoseCovTgtArgs a) {
     };
     int pos = b;
     for (; pos < e; ++pos) {
-      const unsigned long long key = a.key[pos];
+      const unsigned long long key = skey[pos];
       const long long tg = key_target(key);
       if (tg < 0) break;
       if (tg != cur) {
@@ -229,7 +282,7 @@ __global__ __launch_bounds__(256) void pose_cov_tile_kernel(PoseCovTgtArgs a) {
 #pragma unroll
         for (int x = 0; x < 18; ++x) sum[x] = 0.0;
       }
-      const double2* r = (const double2*)(a.bq + (size_t)(unsigned)(key & 0xffffffffu) * 18);
+      const SICP_GLOBAL double2* r = (const SICP_GLOBAL double2*)(bq + (size_t)(key & slot_mask) * 18);
 #pragma unroll
       for (int x = 0; x < 9; ++x) {
         const double2 v = r[x];
@@ -238,87 +291,98 @@ __global__ __launch_bounds__(256) void pose_cov_tile_kernel(PoseCovTgtArgs a) {
       }
     }
     if (cur >= 0) finish(pos);
-    a.flag[t] = flag;
+    dev(J.flag)[t] = flag;
   }
-  block_sum21(acc, a.part_tgt, cols, blockIdx.x);
+  block_sum21(acc, dev(J.part_tgt), cols, lb);
 }
 
-__global__ __launch_bounds__(256) void pose_cov_owner_kernel(PoseCovTgtArgs a) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const int tiles = pose_cov_tiles(a.total), cols = 2 * gridDim.x;
+__global__ __launch_bounds__(256) void pose_cov_owner_jobs_kernel(const PoseCovJob* __restrict__ jobs, const int* __restrict__ blk_end, int nj) {
+  int lb;
+  const PoseCovJob& J = jobs[job_of(blk_end, nj, blockIdx.x, &lb)];
+  const int t = lb * 256 + threadIdx.x;
+  const int tiles = pose_cov_tiles(J.a.n_s * J.a.K), tb = pose_cov_blocks(tiles), cols = 2 * tb;
   double acc[21];
 #pragma unroll
   for (int e = 0; e < 21; ++e) acc[e] = 0.0;
-  if (t < tiles && (a.flag[t] & kOwnsLast)) {
+  const auto flags = dev(J.flag);
+  if (t < tiles && (flags[t] & kOwnsLast)) {
+    const auto pieces = dev(J.piece);
     double sum[18];
-    const double* p = a.piece + ((size_t)t * 2 + 1) * 18;
+    const auto p = pieces + ((size_t)t * 2 + 1) * 18;
 #pragma unroll
     for (int x = 0; x < 18; ++x) sum[x] = p[x];
     for (int u = t + 1; u < tiles; ++u) {
-      const int f = a.flag[u];
+      const int f = flags[u];
       if (!(f & kFirstContinues)) break;  // (cannot happen: the owner's list goes on into tile t + 1)
-      const double* q = a.piece + (size_t)u * 2 * 18;
+      const auto q = pieces + (size_t)u * 2 * 18;
 #pragma unroll
       for (int x = 0; x < 18; ++x) sum[x] += q[x];
       if (!(f & kPassThrough)) break;
     }
     add_outer(sum, acc);
   }
-  block_sum21(acc, a.part_tgt, cols, gridDim.x + blockIdx.x);
+  block_sum21(acc, dev(J.part_tgt), cols, tb + lb);
 }
 
-// one workgroup per output: rows 0..20 S_src, 21..41 S_tgt, 42 the active count.  Every lane sums the columns c = lane,
-// lane + 256, ... in order, then the fixed butterfly and the four waves in order (a lane walking a whole row alone took
-// 150 us at 100K points: one dependent load per column).
-__global__ __launch_bounds__(256) void pose_cov_finalize_kernel(const double* __restrict__ part_src, const long long* __restrict__ part_active,
-                                                                int src_cols, const double* __restrict__ part_tgt, int tgt_cols,
-                                                                double* __restrict__ out42, long long* __restrict__ active) {
+// 43 workgroups per job, one per output: rows 0..20 S_src, 21..41 S_tgt, 42 the active count.  Every lane sums the job's
+// columns c = lane, lane + 256, ... in order, then the fixed butterfly and the four waves in order (a lane walking a whole
+// row alone took 150 us at 100K points: one dependent load per column).
+__global__ __launch_bounds__(256) void pose_cov_finalize_jobs_kernel(const PoseCovJob* __restrict__ jobs) {
   __shared__ double s_w[4];
   __shared__ long long s_a[4];
-  const int e = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const PoseCovJob& J = jobs[blockIdx.x / 43];
+  const int e = blockIdx.x % 43, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int src_cols = pose_cov_blocks(J.a.n_s), tgt_cols = 2 * pose_cov_blocks(pose_cov_tiles(J.a.n_s * J.a.K));
   if (e < 42) {
     const int cols = e < 21 ? src_cols : tgt_cols;
-    const double* row = e < 21 ? part_src + (size_t)e * src_cols : part_tgt + (size_t)(e - 21) * tgt_cols;
+    const SICP_GLOBAL double* row = e < 21 ? dev(J.a.part_src) + (size_t)e * src_cols : dev(J.part_tgt) + (size_t)(e - 21) * tgt_cols;
     double v = 0.0;
     for (int c = threadIdx.x; c < cols; c += 256) v += row[c];
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     if (lane == 0) s_w[wave] = v;
     __syncthreads();
-    if (threadIdx.x == 0) out42[e] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+    if (threadIdx.x == 0) dev(J.out42)[e] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
   } else {
+    const auto part_active = dev(J.a.part_active);
     long long v = 0;
     for (int c = threadIdx.x; c < src_cols; c += 256) v += part_active[c];
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     if (lane == 0) s_a[wave] = v;
     __syncthreads();
-    if (threadIdx.x == 0) *active = (s_a[0] + s_a[1]) + (s_a[2] + s_a[3]);
+    if (threadIdx.x == 0) *dev(J.active) = (s_a[0] + s_a[1]) + (s_a[2] + s_a[3]);
   }
 }
 
 }  // namespace
 
-hipError_t launch_pose_cov_src(const PoseCovArgs& a, hipStream_t st) {
-  const int blocks = pose_cov_blocks(a.n_s);
-  if (blocks == 0) return hipSuccess;
-  hipLaunchKernelGGL(pose_cov_src_kernel, dim3(blocks), dim3(256), 0, st, a);
+hipError_t launch_pose_cov_src_jobs(const PoseCovJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st) {
+  if (nj <= 0 || blocks <= 0) return hipSuccess;
+  hipLaunchKernelGGL(pose_cov_src_jobs_kernel, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj);
   return hipGetLastError();
 }
 
-hipError_t launch_pose_cov_tgt(const PoseCovTgtArgs& a, hipStream_t st) {
-  const int blocks = pose_cov_blocks(pose_cov_tiles(a.total));
-  if (blocks == 0) return hipSuccess;
-  hipLaunchKernelGGL(pose_cov_tile_kernel, dim3(blocks), dim3(256), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(pose_cov_owner_kernel, dim3(blocks), dim3(256), 0, st, a);
+hipError_t pose_cov_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long n, int end_bit,
+                              hipStream_t st) {
+  return rocprim::radix_sort_keys(temp, bytes, in, out, (size_t)(n > 0 ? n : 1), 0u, (unsigned)end_bit, st);
+}
+
+hipError_t launch_pose_cov_tile_jobs(const PoseCovJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st) {
+  if (nj <= 0 || blocks <= 0) return hipSuccess;
+  hipLaunchKernelGGL(pose_cov_tile_jobs_kernel, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj);
   return hipGetLastError();
 }
 
-hipError_t launch_pose_cov_finalize(const double* part_src, const long long* part_active, int src_cols, const double* part_tgt,
-                                    int tgt_cols, double* out42, long long* active, hipStream_t st) {
-  hipLaunchKernelGGL(pose_cov_finalize_kernel, dim3(43), dim3(256), 0, st, part_src, part_active, src_cols, part_tgt, tgt_cols, out42, active);
+hipError_t launch_pose_cov_owner_jobs(const PoseCovJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st) {
+  if (nj <= 0 || blocks <= 0) return hipSuccess;
+  hipLaunchKernelGGL(pose_cov_owner_jobs_kernel, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj);
+  return hipGetLastError();
+}
+
+hipError_t launch_pose_cov_finalize_jobs(const PoseCovJob* jobs, int nj, hipStream_t st) {
+  if (nj <= 0) return hipSuccess;
+  hipLaunchKernelGGL(pose_cov_finalize_jobs_kernel, dim3(43 * nj), dim3(256), 0, st, jobs);
   return hipGetLastError();
 }
 

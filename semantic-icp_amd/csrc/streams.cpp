@@ -74,6 +74,8 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
   };
   std::vector<std::pair<const Cloud*, const Cloud*>> slot_clouds((size_t)S->cap, {nullptr, nullptr});
   std::vector<sicp_stream_result> out;
+  std::vector<int> pass_lab, pass_cov, pass_later;  // slots whose passes at the final pose are queued in this turn
+  std::vector<const double*> pass_qt;
   std::vector<std::array<double, 11>> dbg_log;
   double dbg_admit_ms = 0, dbg_flush_ms = 0, dbg_turn_ms = 0;
   for (;;) {
@@ -213,29 +215,54 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
       if (rc != SICP_OK) { stream_fail(S, rc, L->last_error); return; }
     }
     dbg_turn_ms += now_ms() - t_turn0;
-    // ---- fused labels of the pairs that have just converged (SICP_SUBMIT_FUSED_LABELS): the K = 4 searches of all of
-    //      them in one job launch on the side stream, then per pair the label kernel, the read-back into the slot's
-    //      pinned buffer and an event; the slot stays taken (PAIR_LABELS) until that event has completed
+    // ---- the passes of the pairs that have just converged, at their final poses, on the side stream beside the ticks:
+    //      fused labels (SICP_SUBMIT_FUSED_LABELS): the K = 4 searches of all of them in one job launch, then per pair the
+    //      label kernel, the read-back into the slot's pinned buffer and an event;
+    //      pose covariance (SICP_SUBMIT_POSE_COVARIANCE): search_at of all of them in the same job flush -- in one of its own
+    //      behind the label kernels for a pair that carries both flags (both searches write the slot's correspondence
+    //      buffers) or when the two list lengths differ -- then ONE sweep for all of them (pose_cov.cpp), its read-back
+    //      and an event.
+    //      The slot stays taken (PAIR_PASS) until its events have completed.  A turn without a flagged pair queues nothing.
     {
-      bool any = false;
+      pass_lab.clear(); pass_cov.clear(); pass_later.clear(); pass_qt.clear();
       for (int p = 0; p < S->cap; ++p) {
-        if (run.phase[p] != PAIR_DONE || !(S->slot_flags[p] & SICP_SUBMIT_FUSED_LABELS)) continue;
-        sicp_context* h = S->slots[p];
-        jc.slice = 0;
-        const sicp_stats keep = h->st;  // (the registration's own counters: the label pass is not part of its align())
-        const int rc = labels_search(h, run.o[p].cur);
-        h->st = keep;
-        if (rc != SICP_OK) { stream_fail(S, rc, h->last_error); return; }
-        run.phase[p] = PAIR_LABELS;
-        S->slot_flags[p] |= 0x80000000u;  // queued in this turn
-        any = true;
+        if (run.phase[p] != PAIR_DONE) continue;
+        if (S->slot_flags[p] & SICP_SUBMIT_FUSED_LABELS) pass_lab.push_back(p);
+        if (S->slot_flags[p] & SICP_SUBMIT_POSE_COVARIANCE) pass_cov.push_back(p);
       }
-      if (any) {
+      if (!pass_lab.empty() || !pass_cov.empty()) {
+        // (the registration's own counters stay as they are: the passes are not part of its align())
+        auto cov_search = [&](int p) {
+          sicp_context* h = S->slots[p];
+          jc.slice = 0;
+          const sicp_stats keep = h->st;
+          const int rc = search_at(h, run.o[p].cur);
+          h->st = keep;
+          return rc;
+        };
+        const bool one_length = pass_lab.empty() || sicp::nn_list_len(S->params.knn) == sicp::nn_list_len(4);
+        for (int p : pass_lab) {
+          sicp_context* h = S->slots[p];
+          jc.slice = 0;
+          const sicp_stats keep = h->st;
+          const int rc = labels_search(h, run.o[p].cur);
+          h->st = keep;
+          if (rc != SICP_OK) { stream_fail(S, rc, h->last_error); return; }
+          run.phase[p] = PAIR_PASS;
+        }
+        for (int p : pass_cov) {
+          if (one_length && !(S->slot_flags[p] & SICP_SUBMIT_FUSED_LABELS)) {
+            const int rc = cov_search(p);
+            if (rc != SICP_OK) { stream_fail(S, rc, S->slots[p]->last_error); return; }
+          } else {
+            pass_later.push_back(p);
+          }
+          run.phase[p] = PAIR_PASS;
+          pass_qt.push_back(run.o[p].cur);
+        }
         int rc = flush_jobs(L, jc, run.side);
         if (rc != SICP_OK) { stream_fail(S, rc, L->last_error); return; }
-        for (int p = 0; p < S->cap; ++p) {
-          if (!(S->slot_flags[p] & 0x80000000u)) continue;
-          S->slot_flags[p] &= ~0x80000000u;
+        for (int p : pass_lab) {
           sicp_context* h = S->slots[p];
           const int n = h->cloud(0).n;
           rc = labels_launch(h, run.o[p].cur, run.side);
@@ -246,27 +273,48 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
           if (rc == SICP_OK && e == hipSuccess) e = hipEventRecord(S->slot_ev[p], run.side);
           if (rc != SICP_OK || e != hipSuccess) { stream_fail(S, rc != SICP_OK ? rc : SICP_ERR_HIP, rc != SICP_OK ? h->last_error : std::string("fused labels: ") + hipGetErrorString(e)); return; }
         }
+        if (!pass_later.empty()) {
+          for (int p : pass_later) {
+            rc = cov_search(p);
+            if (rc != SICP_OK) { stream_fail(S, rc, S->slots[p]->last_error); return; }
+          }
+          rc = flush_jobs(L, jc, run.side);
+          if (rc != SICP_OK) { stream_fail(S, rc, L->last_error); return; }
+        }
+        if (!pass_cov.empty()) {
+          rc = stream_cov_pass(S, pass_cov, pass_qt, run.side);
+          if (rc != SICP_OK) { stream_fail(S, rc, L->last_error); return; }
+        }
       }
     }
     // ---- retire
     long long busy = 0, slots_sat = 0;
-    int labels_waiting = -1;
+    hipEvent_t pass_waiting = nullptr;
     for (int p = 0; p < S->cap; ++p) {
-      if (run.phase[p] == PAIR_LABELS) {
-        const hipError_t q = hipEventQuery(S->slot_ev[p]);
-        if (q == hipErrorNotReady) { if (labels_waiting < 0) labels_waiting = p; continue; }
-        if (q != hipSuccess) { stream_fail(S, SICP_ERR_HIP, std::string("fused labels: ") + hipGetErrorString(q)); return; }
-        // device order -> the caller's order (a point that never went to the device has no correspondences: label 0)
+      if (run.phase[p] == PAIR_PASS) {
+        // (one stream carries both passes, the covariance sweep last: its event covers the labels of the same slot)
+        const bool with_cov = (S->slot_flags[p] & SICP_SUBMIT_POSE_COVARIANCE) != 0, with_labels = (S->slot_flags[p] & SICP_SUBMIT_FUSED_LABELS) != 0;
+        const hipEvent_t ev = with_cov ? stream_cov_event(S, p) : S->slot_ev[p];
+        const hipError_t q = hipEventQuery(ev);
+        if (q == hipErrorNotReady) { if (!pass_waiting) pass_waiting = ev; continue; }
+        if (q != hipSuccess) { stream_fail(S, SICP_ERR_HIP, std::string(with_cov ? "pose covariance: " : "fused labels: ") + hipGetErrorString(q)); return; }
         sicp_context* h = S->slots[p];
-        const Cloud& C0 = h->cloud(0);
-        std::vector<uint32_t> lab((size_t)C0.n_caller, 0u);
-        for (int d = 0; d < C0.n; ++d) lab[(size_t)C0.caller_index(d)] = h->h_labels[d];
+        std::vector<uint32_t> lab;
+        if (with_labels) {
+          // device order -> the caller's order (a point that never went to the device has no correspondences: label 0)
+          const Cloud& C0 = h->cloud(0);
+          lab.assign((size_t)C0.n_caller, 0u);
+          for (int d = 0; d < C0.n; ++d) lab[(size_t)C0.caller_index(d)] = h->h_labels[d];
+        }
+        PoseCovSums sums;
+        if (with_cov) stream_cov_take(S, p, &sums);
         {
           std::lock_guard<std::mutex> lock(S->m);
-          S->labels[S->slot_ticket[p]] = std::move(lab);  // kept until sicp_stream_take_labels(ticket) (or the stream's end)
+          if (with_labels) S->labels[S->slot_ticket[p]] = std::move(lab);  // kept until sicp_stream_take_labels(ticket) (or the stream's end)
+          if (with_cov) S->cov_sums[S->slot_ticket[p]] = sums;  // kept until sicp_stream_take_pose_covariance(ticket) (or the stream's end)
         }
         run.phase[p] = PAIR_DONE;
-        S->slot_flags[p] &= ~(unsigned)SICP_SUBMIT_FUSED_LABELS;
+        S->slot_flags[p] &= ~(unsigned)(SICP_SUBMIT_FUSED_LABELS | SICP_SUBMIT_POSE_COVARIANCE);
       }
       if (run.phase[p] != PAIR_DONE) continue;
       sicp_context* h = S->slots[p];
@@ -292,8 +340,8 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
         dbg_log.push_back({now_ms(), (double)(S->completed + (long long)out.size()), (double)run.dbg_ticks, run.dbg_wait_ms,
                            run.dbg_ticks ? (double)run.dbg_act / run.dbg_ticks : 0.0, (double)run.solo, dbg_admit_ms, dbg_flush_ms, dbg_turn_ms, run.dbg_search_ms, run.dbg_launch_ms});
     }
-    // nothing left to advance but label read-backs: wait for the first instead of spinning through empty turns
-    if (out.empty() && labels_waiting >= 0 && run.live(G) == 0 && !G.pending) (void)hipEventSynchronize(S->slot_ev[labels_waiting]);
+    // nothing left to advance but the passes' read-backs: wait for the first instead of spinning through empty turns
+    if (out.empty() && pass_waiting && run.live(G) == 0 && !G.pending) (void)hipEventSynchronize(pass_waiting);
     if (!out.empty()) {
       std::lock_guard<std::mutex> lock(S->m);
       for (const sicp_stream_result& r : out) S->done.push_back(r);
@@ -390,6 +438,8 @@ int sicp_stream_create(int device_id, const sicp_params* params, int32_t max_in_
     S->slot_t0.assign(S->cap, 0.0);
     S->slot_flags.assign(S->cap, 0u);
     S->slot_ev.assign(S->cap, nullptr);
+    S->slot_cov_stage.assign(S->cap, -1);
+    S->slot_cov_row.assign(S->cap, 0);
     S->worker = std::thread(stream_worker, S.get());
     *out = S.release();
     return SICP_OK;
@@ -421,6 +471,7 @@ int sicp_stream_destroy(sicp_stream S) {
     }
     for (hipEvent_t e : S->slot_ev)
       if (e) (void)hipEventDestroy(e);
+    stream_cov_destroy(S, true);  // (the side stream has been waited for)
     S->clouds.clear();
     S->queue.clear();
     if (S->uploader) sicp_destroy(S->uploader);
@@ -533,10 +584,25 @@ int sicp_stream_take_labels(sicp_stream S, int64_t ticket, int32_t n, uint32_t* 
   });
 }
 
+int sicp_stream_take_pose_covariance(sicp_stream S, int64_t ticket, double sigma_source, double sigma_target, sicp_pose_covariance_result* out) {
+  return abi_guard(S, [&]() -> int {
+    if (!S || !out) return SICP_ERR_INVALID_ARGUMENT;
+    // (a refused call writes nothing and keeps the entry: a later correct take succeeds)
+    if (!(std::isfinite(sigma_source) && sigma_source >= 0.0 && std::isfinite(sigma_target) && sigma_target >= 0.0)) return SICP_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lock(S->m);
+    auto it = S->cov_sums.find(ticket);
+    if (it == S->cov_sums.end()) return SICP_ERR_NOT_READY;  // not submitted with SICP_SUBMIT_POSE_COVARIANCE, not finished yet, or taken already
+    const int rc = pose_covariance_from_sums(it->second, sigma_source, sigma_target, out);
+    if (rc != SICP_OK) return rc;
+    S->cov_sums.erase(it);
+    return SICP_OK;
+  });
+}
+
 int sicp_stream_submit_ex(sicp_stream S, int64_t source_id, int64_t target_id, const double init_qt[7], uint32_t flags, int64_t* ticket) {
   return abi_guard(S, [&]() -> int {
     if (!S || !init_qt) return SICP_ERR_INVALID_ARGUMENT;
-    if (flags & ~(uint32_t)(SICP_SUBMIT_FUSED_LABELS | SICP_SUBMIT_FRESH_FEATURES)) return SICP_ERR_INVALID_ARGUMENT;
+    if (flags & ~(uint32_t)(SICP_SUBMIT_FUSED_LABELS | SICP_SUBMIT_FRESH_FEATURES | SICP_SUBMIT_POSE_COVARIANCE)) return SICP_ERR_INVALID_ARGUMENT;
     if ((flags & SICP_SUBMIT_FUSED_LABELS) && S->params.mode != SICP_MODE_EM) return SICP_ERR_INVALID_ARGUMENT;  // getFusedLabels is EmIterativeClosestPoint's
     std::unique_lock<std::mutex> lock(S->m);
     if (S->error != SICP_OK) return S->error;
