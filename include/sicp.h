@@ -453,6 +453,50 @@ int sicp_pose_covariance_batch(sicp_handle* hs, int32_t n, const double* qt, dou
 int sicp_stream_take_pose_covariance(sicp_stream s, int64_t ticket, double sigma_source, double sigma_target,
                                      sicp_pose_covariance_result* out);
 
+/* ---- how well the clouds fit at a pose -----------------------------------------
+ * The question after align(): overlap, inlier RMSE and label agreement of the handle's source onto its target at qt -- what
+ * PCL calls getFitnessScore, Open3D evaluate_registration, and the reference ROCMetrics::evaluate (exec/roc_metrics.h:21-41:
+ * the nearest target of every transformed source point, kept when d^2 < 25, and the two labels).  The queries are the finite
+ * source points transformed exactly as sicp_correspondences transforms them; the candidates are the WHOLE target cloud; per
+ * query the result is the one nearest neighbour under the search's own order (float32 d^2, ties to the lower caller index).
+ * The same in every mode: params.knn, gate_sq, min_class_pts and the mode's label segments play no part (on a
+ * SICP_MODE_SEMANTIC handle, whose target holds one search tree per label, the trees' winners are merged by (d^2, caller
+ * index): the result does not depend on the layout). */
+typedef struct sicp_evaluate_result {
+  int64_t n_source;      /* queries = finite source points the handle holds */
+  int64_t inliers;       /* queries whose nearest target has d2 < (float)max_dist_sq, strict (roc_metrics.h:34; the gate's own rule) */
+  int64_t label_agree;   /* inliers with equal labels; 0 when either cloud was set without labels */
+  int64_t label_outside; /* inliers left out of the table because a label is outside 1..C; 0 when no table was asked for */
+  double  sum_d2;        /* sum of the inliers' float32 d2, accumulated in double in a fixed order */
+  double  fitness;       /* inliers / n_source; 0 when n_source = 0 */
+  double  inlier_rmse;   /* sqrt(sum_d2 / inliers); NaN when inliers = 0 */
+  double  reserved_;
+} sicp_evaluate_result;
+/* confusion (nullable, num_classes^2 counts, row-major): confusion[(ls - 1) * C + (lt - 1)] = inliers with source label ls and
+ * target label lt, the tabulated output of ROCMetrics::evaluate; num_classes is read only with it.  nn_idx / nn_d2 (nullable,
+ * n_points of the source each, caller order): the nearest target's caller index and d^2; a query without an inlier gets -1
+ * and keeps its d^2, a non-finite source point (sicp_cloud_size) gets -1 and NaN.
+ * Needs both clouds and nothing else: no confusion matrix, no features (no self-search, no covariances -- clouds with caller
+ * covariances of any form are fine).  Nothing on the handle changes: its correspondences, statistics and solver state are
+ * those from before the call (the searches write to scratch of their own).  SICP_ERR_NOT_READY: a cloud is missing (or, on a
+ * SICP_MODE_SEMANTIC handle, has no labels to lay its trees out by); SICP_ERR_TOO_FEW_POINTS: the target holds no finite
+ * point; n_source = 0: SICP_OK, zeros and a NaN inlier_rmse.  Refused with SICP_ERR_INVALID_ARGUMENT before any device call,
+ * nothing written: a NULL handle, qt or out; max_dist_sq NaN or <= 0 (+inf is allowed: every query is an inlier); confusion
+ * with num_classes outside 1..255 or with a cloud that has no labels.  Bit-reproducible: integer counts, and sum_d2 from
+ * partial sums over fixed chunks of 256 queries added in index order -- no float atomics. */
+int sicp_evaluate(sicp_handle h, const double qt[7], double max_dist_sq, int32_t num_classes, int64_t* confusion,
+                  int32_t* nn_idx, float* nn_d2, sicp_evaluate_result* out);
+/* sicp_evaluate for n pairs: pair i = handle hs[i] at qt[7 i .. 7 i + 7), out[i], confusion + i C^2 (nullable; no per-point
+ * outputs).  The pairs run in groups that share every launch -- one job flush for all searches, one evaluation launch, one
+ * read-back and one wait per group; a group holds a handle once (a handle may repeat in the call) and is bounded by its
+ * scratch -- and every row, tables included, is bit-identical to the pair's lone call.  Handles may be in different modes and
+ * may share clouds.  status[n] (nullable) gets each pair's own code; a failing pair does not stop the others and its row and
+ * table are not written; the call returns SICP_OK when every pair succeeded, else the first failing pair's code.  Refused
+ * before any work, with SICP_ERR_INVALID_ARGUMENT and nothing written: n < 1, a NULL array or handle, a bad max_dist_sq, a
+ * table with num_classes outside 1..255, handles on different devices. */
+int sicp_evaluate_batch(sicp_handle* hs, int32_t n, const double* qt, double max_dist_sq, int32_t num_classes,
+                        int64_t* confusion, sicp_evaluate_result* out, int32_t* status);
+
 /* test / bench hook: the keypoints of cloud `which` with their normals, FPFH features and feature-radius
  * neighbour lists (CSR: nbr_offsets[n + 1], nbr_idx sorted by (d^2, index)).  Counts are always written; an output
  * array is written when it is non-NULL and its capacity (points / neighbour entries) suffices, otherwise the call

@@ -183,6 +183,23 @@ class SicpPoseCovarianceResult(C.Structure):
         }
 
 
+class SicpEvaluateResult(C.Structure):
+    """sicp_evaluate_result (include/sicp.h)"""
+    _fields_ = [
+        ("n_source", C.c_int64),
+        ("inliers", C.c_int64),
+        ("label_agree", C.c_int64),
+        ("label_outside", C.c_int64),
+        ("sum_d2", C.c_double),
+        ("fitness", C.c_double),
+        ("inlier_rmse", C.c_double),
+        ("reserved_", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
+
+
 class SicpError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -279,6 +296,9 @@ def lib():
             "sicp_pose_covariance": [C.c_void_p, _dp, C.c_double, C.c_double, C.POINTER(SicpPoseCovarianceResult)],
             "sicp_pose_covariance_batch": [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_double, C.c_double,
                                            C.POINTER(SicpPoseCovarianceResult), _ip],
+            "sicp_evaluate": [C.c_void_p, _dp, C.c_double, C.c_int32, C.POINTER(C.c_int64), _ip, _fp, C.POINTER(SicpEvaluateResult)],
+            "sicp_evaluate_batch": [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_double, C.c_int32, C.POINTER(C.c_int64),
+                                    C.POINTER(SicpEvaluateResult), _ip],
             "sicp_bootstrap_score": [C.c_void_p, C.POINTER(SicpBootstrapParams), C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, _ip],
         }.items():
             fn = getattr(_lib, name)
@@ -544,6 +564,29 @@ class Engine:
         self._check(lib().sicp_pose_covariance(self._h, _ptr(qt, _dp), sigma_source, sigma_target, C.byref(r)), "sicp_pose_covariance")
         return r.as_dict()
 
+    def evaluate(self, qt, max_dist_sq: float, num_classes: int | None = None, per_point: bool = False):
+        """sicp_evaluate: how well the source fits the target at qt -- every finite source point's nearest target in the whole
+        target cloud, an inlier when its float32 d^2 < max_dist_sq.  Returns SicpEvaluateResult.as_dict(), with `confusion`
+        ([C, C] int64, inliers by source and target label) when num_classes is given and `nn_idx` / `nn_d2` (caller order; -1 where
+        there is no inlier, -1 / NaN for a non-finite source point) when per_point is set.  Nothing on the engine changes."""
+        qt = np.ascontiguousarray(qt, dtype=np.float64)
+        r = SicpEvaluateResult()
+        C_ = 0 if num_classes is None else int(num_classes)
+        conf = None if num_classes is None else np.zeros((max(C_, 0), max(C_, 0)), dtype=np.int64)
+        if conf is not None and conf.size == 0:
+            conf = np.zeros((1, 1), dtype=np.int64)  # (a pointer to hand over: the library refuses the class count)
+        n = self.n[SOURCE]
+        idx = np.empty(n, dtype=np.int32) if per_point else None
+        d2 = np.empty(n, dtype=np.float32) if per_point else None
+        self._check(lib().sicp_evaluate(self._h, _ptr(qt, _dp), max_dist_sq, C_, _ptr(conf, C.POINTER(C.c_int64)), _ptr(idx, _ip),
+                                        _ptr(d2, _fp), C.byref(r)), "sicp_evaluate")
+        out = r.as_dict()
+        if conf is not None:
+            out["confusion"] = conf
+        if per_point:
+            out["nn_idx"], out["nn_d2"] = idx, d2
+        return out
+
     def solve(self, init_qt):
         init = np.ascontiguousarray(init_qt, dtype=np.float64)
         out = np.empty(7)
@@ -626,6 +669,33 @@ def pose_covariance_batch(engines, qts, sigma_source: float = 1.0, sigma_target:
     if rc != OK and (n == 0 or status[0] == unset):
         raise SicpError(rc, "sicp_pose_covariance_batch", lib().sicp_last_error(engines[0]._h).decode() if n else "")
     return [(OK, out[i].as_dict()) if status[i] == OK else (int(status[i]), None) for i in range(n)]
+
+
+def evaluate_batch(engines, qts, max_dist_sq: float, num_classes: int | None = None):
+    """sicp_evaluate_batch: Engine.evaluate (without per-point outputs) for every engine at its row of qts.  Returns [(status,
+    dict or None)] in the order of `engines`; per pair identical to the lone call, `confusion` included when num_classes is
+    given.  Raises SicpError only when the whole call is refused."""
+    n = len(engines)
+    qts = np.ascontiguousarray(qts, dtype=np.float64).reshape(n, 7) if n else np.zeros((1, 7))
+    out = (SicpEvaluateResult * max(n, 1))()
+    unset = -(2 ** 31)
+    status = np.full(max(n, 1), unset, dtype=np.int32)
+    C_ = 0 if num_classes is None else int(num_classes)
+    conf = None if num_classes is None else np.zeros((max(n, 1), max(C_, 1), max(C_, 1)), dtype=np.int64)
+    rc = lib().sicp_evaluate_batch(_handles(engines) if n else None, n, _ptr(qts, _dp), max_dist_sq, C_, _ptr(conf, C.POINTER(C.c_int64)),
+                                   out, _ptr(status, _ip))
+    if rc != OK and (n == 0 or status[0] == unset):
+        raise SicpError(rc, "sicp_evaluate_batch", lib().sicp_last_error(engines[0]._h).decode() if n else "")
+    res = []
+    for i in range(n):
+        if status[i] != OK:
+            res.append((int(status[i]), None))
+            continue
+        d = out[i].as_dict()
+        if conf is not None:
+            d["confusion"] = conf[i].copy()
+        res.append((OK, d))
+    return res
 
 
 def accumulate_batch(engines, qts, repeat: int = 1):

@@ -6,6 +6,8 @@
 //   stages.cpp    stage drivers of one align(): searches, covariances, projections, weights, one evaluation
 //   solve.cpp     inner solve: ticks, the persistent launch, continuous batching (BatchRun), sicp_align_batch
 //   streams.cpp   registration streams (worker thread + sicp_stream_*)
+//   pose_cov.cpp  sicp_pose_covariance: the sweep over a group of pairs, the 6x6 algebra
+//   evaluate.cpp  sicp_evaluate: overlap, inlier RMSE and label agreement at a pose
 //   sicp_api.cpp  the remaining C-ABI entry points
 // Every extern "C" entry runs inside abi_guard (abi_barrier.hpp): no exception crosses the boundary.
 #ifndef SICP_ENGINE_HPP_
@@ -402,6 +404,11 @@ struct sicp_context {
   DevBuf<uint32_t> tmpl;
   HostBuf<uint32_t> h_labels;  // pinned: fused labels of a stream slot on their way back
   HostBuf<unsigned char> pc_stage;  // pinned: arguments and results of the pose-covariance sweeps this handle leads (pose_cov.cpp)
+  // sicp_evaluate (evaluate.cpp): the K = 1 searches of the pair, [target segments][source points] -- scratch of its own, so that
+  // idx / d2 above (the correspondences) stay what they were -- and the pinned stage of the sweeps this handle leads
+  DevBuf<int> ev_idx;
+  DevBuf<float> ev_d2;
+  HostBuf<unsigned char> ev_stage;
   // lock-step batch (sicp_align_batch), owned by the batch's first handle: one BatchArgs and one LM
   // state per pair, pinned mirrors, and the captured [accumulate_batch, lm_step_batch] x lm_batch graph
   TickSet ts[2];  // two sets: the halves of a batch alternate, one's tick runs while the host turns the other around
@@ -748,6 +755,11 @@ void stream_cov_take(sicp_stream_ctx* S, int slot, PoseCovSums* out);
 void stream_cov_destroy(sicp_stream_ctx* S, bool idle);
 // the caller's result from the sums: SICP_ERR_INVALID_ARGUMENT (nothing written) for a NULL out or a sigma that is negative or not finite
 int pose_covariance_from_sums(const PoseCovSums& u, double sigma_source, double sigma_target, sicp_pose_covariance_result* out);
+// sicp_evaluate / _batch (evaluate.cpp): argument checks, the K = 1 searches per target segment, the evaluation sweep
+int evaluate(sicp_context* h, const double* qt, double max_dist_sq, int32_t num_classes, int64_t* confusion, int32_t* nn_idx,
+             float* nn_d2, sicp_evaluate_result* out);
+int evaluate_batch(sicp_handle* hs, int32_t n, const double* qt, double max_dist_sq, int32_t num_classes, int64_t* confusion,
+                   sicp_evaluate_result* out, int32_t* status);
 
 }  // namespace host
 }  // namespace sicp

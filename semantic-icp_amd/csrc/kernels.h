@@ -404,6 +404,39 @@ hipError_t launch_pose_cov_owner_jobs(const PoseCovJob* jobs, const int* blk_end
 // fixed-order sums of the partial columns -> out42, active of every job
 hipError_t launch_pose_cov_finalize_jobs(const PoseCovJob* jobs, int nj, hipStream_t st);
 
+// ---- how well the clouds fit at a pose (evaluate_kernels.hip; driver: evaluate.cpp) ----
+// sicp_evaluate: per source point the nearest target of the whole target cloud (K = 1 searches, one per target segment, their
+// winners merged by (d^2, caller index)), the gate, and over the inliers: counts, the sum of d^2, the label confusion table.
+// Job form, as the pose covariance's: one launch over every pair of a group, job j owns the workgroups [blk_end[j - 1],
+// blk_end[j]) and indexes everything from its own origin, so a pair has the bits of its lone call in any group.
+constexpr int kEvalChunk = 256;         // queries per partial sum: fixed, whatever the launch looks like
+constexpr int kEvalChunksPerBlock = 8;  // consecutive chunks one workgroup walks (what its LDS table collects before it is flushed)
+constexpr int kEvalLdsClasses = 64;     // confusion tables up to 64 x 64 are privatised in LDS (16 KB of 32-bit counts)
+struct EvalOut {
+  long long inliers, label_agree, label_outside;
+  double sum_d2;
+};
+struct EvalJob {
+  int n_s, n_seg;          // queries (device order of the source); target segments whose winners are merged
+  const int* idx;          // [n_seg][n_s] device target indices, -1 = gated out (the search's own strict float compare)
+  const float* d2;         // [n_seg][n_s] float32 d^2 of every segment's winner, gated out or not
+  const uint32_t *slabel, *tlabel;  // device order; both null when either cloud has no labels
+  const int *sperm, *tperm;         // device index -> caller index (among the finite points)
+  float gate_sq;
+  int C;                   // classes of the table (0: none)
+  unsigned long long* conf;  // nullable: [C][C], zeroed before the launch
+  int* nn_idx;             // nullable: [n_s] by source caller index: the winner's caller index, -1 when it is no inlier
+  float* nn_d2;            // nullable: [n_s] likewise, the winner's d^2 whatever the gate says
+  double* part_sum;        // [eval_chunks(n_s)] sum of the inliers' d^2 per chunk
+  int* part_cnt;           // [eval_chunks(n_s)][4] inliers, equal labels, labels outside 1..C, unused
+  EvalOut* out;
+};
+SICP_HD inline int eval_chunks(int n_s) { return n_s > 0 ? (n_s + kEvalChunk - 1) / kEvalChunk : 0; }
+SICP_HD inline int eval_blocks(int n_s) { return (eval_chunks(n_s) + kEvalChunksPerBlock - 1) / kEvalChunksPerBlock; }
+hipError_t launch_evaluate_jobs(const EvalJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st);
+// the chunk partials of every job in index order, by one wave per job -> out
+hipError_t launch_evaluate_finalize_jobs(const EvalJob* jobs, int nj, hipStream_t st);
+
 // ---- initial alignment without a pose prior (bootstrap_kernels.hip; driver: bootstrap.cpp) ----
 // The sort / scan wrappers follow rocPRIM's convention: temp == nullptr asks for the bytes.
 constexpr int kBootMaxK = 16;  // feature neighbours per source keypoint (k_correspondences)

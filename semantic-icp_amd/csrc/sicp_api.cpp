@@ -834,6 +834,20 @@ int sicp_pose_covariance_batch(sicp_handle* hs, int32_t n, const double* qt, dou
   });
 }
 
+int sicp_evaluate(sicp_handle h, const double qt[7], double max_dist_sq, int32_t num_classes, int64_t* confusion, int32_t* nn_idx,
+                  float* nn_d2, sicp_evaluate_result* out) {
+  return abi_guard(h, [&]() -> int {
+    return evaluate(h, qt, max_dist_sq, num_classes, confusion, nn_idx, nn_d2, out);
+  });
+}
+
+int sicp_evaluate_batch(sicp_handle* hs, int32_t n, const double* qt, double max_dist_sq, int32_t num_classes, int64_t* confusion,
+                        sicp_evaluate_result* out, int32_t* status) {
+  return abi_guard((hs && n > 0) ? hs[0] : nullptr, [&]() -> int {
+    return evaluate_batch(hs, n, qt, max_dist_sq, num_classes, confusion, out, status);
+  });
+}
+
 int sicp_solve(sicp_handle h, const double init_qt[7], double out_qt[7], int32_t* lm_iters, int32_t* evals,
                double* final_cost) {
   return abi_guard(h, [&]() -> int {
