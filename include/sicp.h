@@ -497,6 +497,62 @@ int sicp_evaluate(sicp_handle h, const double qt[7], double max_dist_sq, int32_t
 int sicp_evaluate_batch(sicp_handle* hs, int32_t n, const double* qt, double max_dist_sq, int32_t num_classes,
                         int64_t* confusion, sicp_evaluate_result* out, int32_t* status);
 
+/* ---- registered scans into one cloud --------------------------------------------
+ * The step after align() in scan-to-local-map odometry: several clouds, each at its pose, cropped about the vehicle and
+ * reduced on a voxel grid to the next target, without leaving the device.  Part i is slot part_which[i] of handle parts[i];
+ * handles may be in any mode (and modes may be mixed), may repeat and may share clouds; dst may be one of the parts (the
+ * rolling map: map = merge(map, scan)).
+ *  1. The points are the finite points each cloud holds (sicp_cloud_size's n_indexed) in caller order, the parts in the order
+ *     given; a point's global index is its position in that concatenation.  The result does not depend on a cloud's device
+ *     layout (a SICP_MODE_SEMANTIC handle groups it by label).
+ *  2. Transform, exactly as sicp_correspondences transforms sources: the matrix of qt as the engine forms it (no
+ *     normalisation), ((m0 x + m1 y) + m2 z) + m3 in double without contraction, one rounding to float.  qt = NULL: identities,
+ *     through the same arithmetic.
+ *  3. Crop, when crop_range > 0: c = (float)crop_center, d = p - c in float, d2 = (dx dx + dy dy) + dz dz in float (each
+ *     operation rounded), kept when (double)d2 <= crop_range * crop_range.  With the identity, centre 0 and leaf_size 0 this is
+ *     the reference drivers' filterRange(cloud, range) (exec/filter_range.h), value for value.
+ *  4. Voxel grid, when leaf_size > 0: v = floor(p * (1.0f / (float)leaf_size)) per axis in float -- an absolute grid anchored
+ *     at the origin, so a merge is stable from call to call; the voxel membership is that of sicp_bootstrap's grid.  One
+ *     output point per occupied voxel in ascending (vz, vy, vx): the double sum of the voxel's points in ascending global index,
+ *     divided by their number, rounded once to float; count[j] = that number; label[j] = the most frequent label of the voxel,
+ *     ties to the smallest label value (labels are arbitrary uint32).  |v| >= 2^20 on any axis: SICP_ERR_INVALID_ARGUMENT (the
+ *     text names the leaf size).
+ *  5. leaf_size = 0: the result is the kept points themselves in global index order, their own labels, count = 1.
+ *  6. Labels: every part's cloud has them -> the result has them; none has -> it has none (label untouched, has_label = 0); a
+ *     mixture is refused. */
+typedef struct sicp_merge_params {
+  double leaf_size;       /* voxel edge; 0 = no voxel grid.  default 0.2 */
+  double crop_center[3];  /* default 0 0 0 */
+  double crop_range;      /* 0 = no crop (default); +inf allowed (keeps everything finite) */
+} sicp_merge_params;
+typedef struct sicp_merge_info {
+  int64_t n_in;              /* finite points of all parts (a cloud used twice counts twice) */
+  int64_t n_kept;            /* after the crop */
+  int32_t n_out;             /* points of the result */
+  int32_t max_voxel_points;  /* 1 when leaf_size = 0 and n_out > 0; 0 when n_out = 0 */
+  int32_t has_label, reserved_;
+  double t_total_ms;         /* host wall clock */
+} sicp_merge_info;
+int sicp_default_merge_params(sicp_merge_params* p);
+/* Outputs: info (nullable) is written on success and on the capacity refusal; an output array (each nullable, capacity
+ * elements) is written when it is non-NULL and capacity >= n_out; a non-NULL array with a smaller capacity gives
+ * SICP_ERR_INVALID_ARGUMENT and nothing else happens (call once without arrays, or size them by the sum of n_indexed).
+ * dst (nullable): slot dst_which of dst becomes the result exactly as if the caller had passed the output arrays to
+ * sicp_set_cloud -- everything downstream, sicp_align included, is bit-identical to that; the whole result is computed before
+ * the slot lets go of its old cloud, and other handles sharing the old cloud keep it (sicp_share_cloud's rule).  n_out = 0
+ * with a dst: SICP_ERR_TOO_FEW_POINTS, dst unchanged.
+ * Refused before any work, with SICP_ERR_INVALID_ARGUMENT and nothing written: n_parts < 1; a NULL array or handle; a `which`
+ * outside SICP_SOURCE / SICP_TARGET; handles (dst included) on different devices; leaf_size negative or not finite;
+ * crop_range negative or NaN; a centre or pose that is not finite; labelled and unlabelled parts together; more than 2^31 - 1
+ * points in all.  SICP_ERR_NOT_READY: a part's slot holds no cloud (or, on a SICP_MODE_SEMANTIC handle, a cloud that was never
+ * uploaded because it has no labels).  No part's cloud, correspondences, features or statistics change, unless it is dst's
+ * slot; parts already on the device are not uploaded again.  Bit-reproducible: a stable sort and fixed-order sums, no float
+ * atomics.  Streams: merge on handles and pass the arrays to sicp_stream_add_cloud. */
+int sicp_merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_parts, const double* qt /* n_parts*7, NULL = identities */,
+                      const sicp_merge_params* p, sicp_handle dst /* nullable */, int dst_which,
+                      int32_t capacity, float* x, float* y, float* z, uint32_t* label, uint32_t* count /* all nullable */,
+                      sicp_merge_info* info /* nullable */);
+
 /* test / bench hook: the keypoints of cloud `which` with their normals, FPFH features and feature-radius
  * neighbour lists (CSR: nbr_offsets[n + 1], nbr_idx sorted by (d^2, index)).  Counts are always written; an output
  * array is written when it is non-NULL and its capacity (points / neighbour entries) suffices, otherwise the call

@@ -200,6 +200,31 @@ class SicpEvaluateResult(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
 
 
+class SicpMergeParams(C.Structure):
+    """sicp_merge_params (include/sicp.h)"""
+    _fields_ = [
+        ("leaf_size", C.c_double),
+        ("crop_center", C.c_double * 3),
+        ("crop_range", C.c_double),
+    ]
+
+
+class SicpMergeInfo(C.Structure):
+    """sicp_merge_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_in", C.c_int64),
+        ("n_kept", C.c_int64),
+        ("n_out", C.c_int32),
+        ("max_voxel_points", C.c_int32),
+        ("has_label", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
+
+
 class SicpError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -300,6 +325,9 @@ def lib():
             "sicp_evaluate_batch": [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_double, C.c_int32, C.POINTER(C.c_int64),
                                     C.POINTER(SicpEvaluateResult), _ip],
             "sicp_bootstrap_score": [C.c_void_p, C.POINTER(SicpBootstrapParams), C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, _ip],
+            "sicp_default_merge_params": [C.POINTER(SicpMergeParams)],
+            "sicp_merge_clouds": [C.POINTER(C.c_void_p), _ip, C.c_int32, _dp, C.POINTER(SicpMergeParams), C.c_void_p, C.c_int, C.c_int32,
+                                  _fp, _fp, _fp, _up, _up, C.POINTER(SicpMergeInfo)],
         }.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
@@ -354,6 +382,19 @@ def default_bootstrap_params(**overrides) -> SicpBootstrapParams:
         if not hasattr(p, k):
             raise AttributeError(k)
         setattr(p, k, v)
+    return p
+
+
+def default_merge_params(**overrides) -> SicpMergeParams:
+    """sicp_default_merge_params (leaf 0.2, centre 0, no crop), with any field overridden by keyword (crop_center: 3 values)"""
+    p = SicpMergeParams()
+    st = lib().sicp_default_merge_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_merge_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, (C.c_double * 3)(*v) if k == "crop_center" else v)
     return p
 
 
@@ -696,6 +737,40 @@ def evaluate_batch(engines, qts, max_dist_sq: float, num_classes: int | None = N
             d["confusion"] = conf[i].copy()
         res.append((OK, d))
     return res
+
+
+def merge_clouds(parts, qts=None, params: SicpMergeParams | None = None, dst=None, want_points: bool = True):
+    """sicp_merge_clouds: the clouds in `parts` -- a list of (Engine, which) -- each at its row of qts (None: identities),
+    cropped and reduced on the voxel grid of `params` to one cloud; with dst = (Engine, which) that slot becomes the result as
+    if it had been handed to set_cloud.  Returns {"xyz": [n_out, 3] float32, "labels": uint32 or None, "count": uint32,
+    "info": SicpMergeInfo.as_dict()}; with want_points=False no arrays are asked for and xyz / labels / count are None.  The
+    buffers are sized by the sum of the parts' finite points."""
+    n = len(parts)
+    p = params if params is not None else default_merge_params()
+    hs = _handles([e for e, _ in parts]) if n else None
+    which = np.array([w for _, w in parts] if n else [0], dtype=np.int32)
+    q = None if qts is None else np.ascontiguousarray(qts, dtype=np.float64).reshape(max(n, 1), 7)
+    cap = 0
+    x = y = z = lab = cnt = None
+    if want_points and n:
+        cap = sum(e.cloud_size(w)[1] for e, w in parts)
+        x, y, z = (np.empty(max(cap, 1), dtype=np.float32) for _ in range(3))
+        lab, cnt = (np.empty(max(cap, 1), dtype=np.uint32) for _ in range(2))
+    info = SicpMergeInfo()
+    rc = lib().sicp_merge_clouds(hs, _ptr(which, _ip), n, _ptr(q, _dp), C.byref(p), None if dst is None else dst[0]._h,
+                                 0 if dst is None else dst[1], cap, _ptr(x, _fp), _ptr(y, _fp), _ptr(z, _fp), _ptr(lab, _up),
+                                 _ptr(cnt, _up), C.byref(info))
+    if rc != OK:
+        raise SicpError(rc, "sicp_merge_clouds", lib().sicp_last_error(parts[0][0]._h).decode() if n else "")
+    if dst is not None:
+        dst[0].n[dst[1]] = info.n_out
+    m = info.n_out
+    return {
+        "xyz": None if x is None else np.stack([x[:m], y[:m], z[:m]], axis=1),
+        "labels": lab[:m].copy() if (lab is not None and info.has_label) else None,
+        "count": None if cnt is None else cnt[:m].copy(),
+        "info": info.as_dict(),
+    }
 
 
 def accumulate_batch(engines, qts, repeat: int = 1):

@@ -8,6 +8,7 @@
 //   streams.cpp   registration streams (worker thread + sicp_stream_*)
 //   pose_cov.cpp  sicp_pose_covariance: the sweep over a group of pairs, the 6x6 algebra
 //   evaluate.cpp  sicp_evaluate: overlap, inlier RMSE and label agreement at a pose
+//   merge.cpp     sicp_merge_clouds: posed clouds into one voxel-grid cloud
 //   sicp_api.cpp  the remaining C-ABI entry points
 // Every extern "C" entry runs inside abi_guard (abi_barrier.hpp): no exception crosses the boundary.
 #ifndef SICP_ENGINE_HPP_
@@ -264,7 +265,8 @@ struct Cloud {
   DevBuf<float4> pts4, box_lo, box_hi;
   DevBuf<unsigned long long> leaf_code;
   DevBuf<int> inv;  // caller index -> device index
-  // build scratch: the cloud as the caller gave it, sort buffers
+  // build scratch: the cloud as the caller gave it (the finite points in caller order: they stay valid while layout >= 0, in
+  // either layout -- what sicp_merge_clouds reads), sort buffers
   DevBuf<float> rx, ry, rz;
   DevBuf<uint32_t> rl;
   DevBuf<int> ids, d_perm, vals_in, vals_out;
@@ -409,6 +411,10 @@ struct sicp_context {
   DevBuf<int> ev_idx;
   DevBuf<float> ev_d2;
   HostBuf<unsigned char> ev_stage;
+  // sicp_merge_clouds (merge.cpp), on the handle that leads a call: the pinned part table + counts, and the pinned result
+  // (x | y | z | label | count) on its way to the caller and into dst
+  HostBuf<unsigned char> mg_stage;
+  HostBuf<uint32_t> mg_out;
   // lock-step batch (sicp_align_batch), owned by the batch's first handle: one BatchArgs and one LM
   // state per pair, pinned mirrors, and the captured [accumulate_batch, lm_step_batch] x lm_batch graph
   TickSet ts[2];  // two sets: the halves of a batch alternate, one's tick runs while the host turns the other around
@@ -760,6 +766,12 @@ int evaluate(sicp_context* h, const double* qt, double max_dist_sq, int32_t num_
              float* nn_d2, sicp_evaluate_result* out);
 int evaluate_batch(sicp_handle* hs, int32_t n, const double* qt, double max_dist_sq, int32_t num_classes, int64_t* confusion,
                    sicp_evaluate_result* out, int32_t* status);
+// sicp_merge_clouds (merge.cpp): argument checks, the key / sort / reduce kernels on the parts' device copies, the result's
+// read-back and its way into dst (set_cloud_common)
+void merge_default_params(sicp_merge_params* p);
+int merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_parts, const double* qt, const sicp_merge_params* p,
+                 sicp_context* dst, int dst_which, int32_t capacity, float* x, float* y, float* z, uint32_t* label, uint32_t* count,
+                 sicp_merge_info* info);
 
 }  // namespace host
 }  // namespace sicp

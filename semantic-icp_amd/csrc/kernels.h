@@ -437,6 +437,59 @@ hipError_t launch_evaluate_jobs(const EvalJob* jobs, const int* blk_end, int nj,
 // the chunk partials of every job in index order, by one wave per job -> out
 hipError_t launch_evaluate_finalize_jobs(const EvalJob* jobs, int nj, hipStream_t st);
 
+// ---- posed clouds into one voxel-grid cloud (merge_kernels.hip; driver: merge.cpp) ----
+// sicp_merge_clouds: every finite point of every part, transformed as the search transforms its queries, cropped, keyed by
+// its voxel of an absolute grid, sorted (stable: the global indices ascend inside a voxel), and reduced per voxel in that
+// order.  All parts go through ONE key launch: part j owns the workgroups [blk_end[j - 1], blk_end[j]) (blk_end: inclusive
+// prefix of the parts' workgroup counts), so a workgroup never straddles two parts.
+constexpr int kMergeBias = 1 << 20;  // |voxel coordinate| < 2^20: three biased 21-bit fields, z highest, bit 63 clear
+struct MergePart {
+  const float *x, *y, *z;  // the part's finite points in caller order (Cloud::rx ...)
+  const uint32_t* label;   // nullable
+  double M[12];            // rows 0..2 of the pose's 4x4 matrix
+  int n, off;              // points; global index of the first
+};
+struct MergeKeyArgs {
+  const MergePart* parts;
+  const int* blk_end;
+  int n_parts;
+  int voxel, crop;         // leaf_size > 0; crop_range > 0
+  float inv_leaf;          // 1.0f / (float)leaf_size
+  float cx, cy, cz;        // (float)crop_center
+  double range_sq;         // crop_range * crop_range
+  float *tx, *ty, *tz;     // [n_in] transformed points by global index
+  uint32_t* tlabel;        // [n_in], nullable
+  unsigned long long* key; // [n_in] voxel key (0 without a grid), ~0 for a cropped point
+  int* val;                // [n_in] global index
+  int* res;                // kMergeRes words, zeroed before the launch
+};
+enum { kMergeKept = 0, kMergeOut = 1, kMergeRange = 2, kMergeMaxCount = 3, kMergeRes = 4 };
+struct MergeReduceArgs {
+  int n;                          // n_in
+  int voxel, labels;
+  const unsigned long long* skey; // sorted keys
+  const int* sval;                // their global indices
+  int *flag, *pos, *heads;        // [n] first-of-voxel flags, their exclusive scan, first sorted position of every voxel
+  const float *tx, *ty, *tz;
+  const uint32_t* tlabel;
+  float *gx, *gy, *gz;            // [n] the transformed points in sorted order
+  unsigned long long* lkey;       // [n] voxel rank << 32 | label in sorted order (~0 past the kept points)
+  const unsigned long long* lsorted;  // lkey sorted (lkey itself without a grid: every voxel is one point)
+  float *ox, *oy, *oz;            // [n] the result
+  uint32_t *olabel, *ocount;
+  int* res;
+};
+hipError_t launch_merge_keys(const MergeKeyArgs& a, int blocks, hipStream_t st);
+// rocPRIM's convention: temp == nullptr asks for the bytes.  Keys: bits [begin_bit, 64).
+hipError_t merge_sort_pairs(void* temp, size_t& bytes, const unsigned long long* kin, unsigned long long* kout, const int* vin,
+                            int* vout, int n, int begin_bit, hipStream_t st);
+hipError_t merge_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, int n, hipStream_t st);
+hipError_t merge_scan(void* temp, size_t& bytes, const int* in, int* out, int n, hipStream_t st);
+hipError_t launch_merge_heads(const MergeReduceArgs& a, hipStream_t st);    // flag
+hipError_t launch_merge_gather(const MergeReduceArgs& a, hipStream_t st);   // heads, res[kept, out], gx gy gz, lkey
+hipError_t launch_merge_centroids(const MergeReduceArgs& a, hipStream_t st);  // ox oy oz, ocount, res[max count]
+hipError_t launch_merge_labels(const MergeReduceArgs& a, hipStream_t st);   // olabel
+
 // ---- initial alignment without a pose prior (bootstrap_kernels.hip; driver: bootstrap.cpp) ----
 // The sort / scan wrappers follow rocPRIM's convention: temp == nullptr asks for the bytes.
 constexpr int kBootMaxK = 16;  // feature neighbours per source keypoint (k_correspondences)

@@ -848,6 +848,22 @@ int sicp_evaluate_batch(sicp_handle* hs, int32_t n, const double* qt, double max
   });
 }
 
+int sicp_default_merge_params(sicp_merge_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    merge_default_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_parts, const double* qt, const sicp_merge_params* p,
+                      sicp_handle dst, int dst_which, int32_t capacity, float* x, float* y, float* z, uint32_t* label,
+                      uint32_t* count, sicp_merge_info* info) {
+  return abi_guard((parts && n_parts > 0) ? parts[0] : nullptr, [&]() -> int {
+    return merge_clouds(parts, part_which, n_parts, qt, p, dst, dst_which, capacity, x, y, z, label, count, info);
+  });
+}
+
 int sicp_solve(sicp_handle h, const double init_qt[7], double out_qt[7], int32_t* lm_iters, int32_t* evals,
                double* final_cost) {
   return abi_guard(h, [&]() -> int {
