@@ -361,7 +361,7 @@ int sicp_fused_labels(sicp_handle h, const double qt[7], uint32_t* out_labels);
  * The reference's Bootstrap (exec/bootstrap.h): box filter -> VoxelGrid -> NormalEstimation -> FPFHEstimation on the
  * keypoints of both clouds -> SampleConsensusInitialAlignment.  Registers the handle's current source onto its current
  * target from no initial guess; the result is a coarse pose for sicp_align's init_qt.  Works in every mode, ignores
- * labels, uses the finite points the handle holds.  Orders, precisions and the deviations from PCL: INTEGRATION.md. */
+ * labels (sicp_bootstrap_semantic below uses them), uses the finite points the handle holds.  Orders, precisions and the deviations from PCL: INTEGRATION.md. */
 typedef struct sicp_bootstrap_params {
   double box_max;              /* keep a point when x < box_max && y < box_max && z < box_max: 35 (bootstrap.h:24-28) */
   double leaf_size;            /* VoxelGrid leaf: 0.4 (bootstrap.h:29-33)                                              */
@@ -401,6 +401,40 @@ int sicp_bootstrap(sicp_handle h, const sicp_bootstrap_params* p, double out_qt[
  * changes. */
 int sicp_bootstrap_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* p, double* out_qt, int32_t* status,
                          sicp_bootstrap_info* infos);
+/* ---- label-aware initial alignment ------------------------------------------------
+ * sicp_bootstrap with the clouds' labels (an extension: the reference has no such stage).  Labels are any uint32 values,
+ * compared for equality only; the mode, num_classes and the confusion matrix play no part.  Both clouds must carry labels.
+ *   filter   a point is kept when it is finite, passes the box filter and its label is not in `ignore` (moving classes:
+ *            cars, people); the voxel grid is sicp_bootstrap's over the kept points.
+ *   labels   a keypoint gets the most frequent label of its voxel's kept points, ties to the smallest label (the rule of
+ *            sicp_merge_clouds).
+ *   match    match_same_label: a source keypoint's feature neighbours are the k_correspondences nearest among the target
+ *            keypoints with a feature AND its label (fewer: the row ends in -1); a source keypoint can be sampled when it
+ *            has a feature and at least one such neighbour, and its target is drawn among the neighbours it has.
+ *   score    score_same_label: a source keypoint whose nearest target keypoint lies within max_corr_distance but carries
+ *            another label scores 1, as an outlier does.
+ * With both flags 0 and n_ignore 0, and with both flags 1 on clouds of a single label, the result is sicp_bootstrap's bit
+ * for bit.  Orders and precisions: INTEGRATION.md ("Bootstrap"). */
+#define SICP_BOOTSTRAP_MAX_IGNORE 64
+typedef struct sicp_bootstrap_label_params {
+  int32_t match_same_label;  /* 1 (default): a source keypoint's feature neighbours are drawn only from target keypoints of its label */
+  int32_t score_same_label;  /* 1 (default): a source keypoint whose nearest target keypoint has another label scores 1 (an outlier) */
+  int32_t n_ignore;          /* 0 (default) .. SICP_BOOTSTRAP_MAX_IGNORE */
+  int32_t reserved_;
+  uint32_t ignore[SICP_BOOTSTRAP_MAX_IGNORE]; /* points with one of these labels are dropped with the box filter, in both clouds */
+} sicp_bootstrap_label_params;
+int sicp_default_bootstrap_label_params(sicp_bootstrap_label_params* lp);
+/* As sicp_bootstrap (statuses, info, nothing on the handle changes).  SICP_ERR_TOO_FEW_POINTS when fewer than nr_samples
+ * source keypoints can be sampled or the target has no keypoint with a feature.  Refused with SICP_ERR_INVALID_ARGUMENT,
+ * nothing written and the reason in sicp_last_error: a NULL lp, n_ignore outside 0..64, a flag that is neither 0 nor 1,
+ * a cloud without labels. */
+int sicp_bootstrap_semantic(sicp_handle h, const sicp_bootstrap_params* p, const sicp_bootstrap_label_params* lp,
+                            double out_qt[7], sicp_bootstrap_info* info);
+/* As sicp_bootstrap_batch, with the same p and lp for every pair; per pair bit-identical to sicp_bootstrap_semantic.  A
+ * pair with a cloud without labels fails alone (SICP_ERR_INVALID_ARGUMENT in its status); a NULL or bad lp refuses the call. */
+int sicp_bootstrap_semantic_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* p,
+                                  const sicp_bootstrap_label_params* lp, double* out_qt, int32_t* status,
+                                  sicp_bootstrap_info* infos);
 /* ---- how well a registration's pose is determined ------------------------------
  * The 6x6 covariance of the pose at qt (Censi's estimate with the solver's Gauss-Newton matrix), in the tangent space of
  * the right perturbation T * exp(delta), delta = [upsilon; omega] (units m^2, m rad, rad^2).  The slots are those
@@ -566,6 +600,16 @@ int sicp_bootstrap_keypoints(sicp_handle h, int which, const sicp_bootstrap_para
  * keypoint, target keypoint indices, -1 where there are fewer or the keypoint has no feature. */
 int sicp_bootstrap_score(sicp_handle h, const sicp_bootstrap_params* p, int32_t n, const int32_t* src_idx,
                          const int32_t* tgt_idx, double* M12, double* err, int32_t knn_capacity, int32_t* feat_knn);
+/* test / bench hooks of sicp_bootstrap_semantic.  keypoints: the keypoints of cloud `which` under p and lp and their
+ * voted labels (xyz3 n*3, label n; the count is always written, an array when it is non-NULL and capacity suffices).
+ * score: sicp_bootstrap_score under lp -- feat_knn holds the label-restricted rows when match_same_label is set, err the
+ * label-aware errors when score_same_label is. */
+int sicp_bootstrap_semantic_keypoints(sicp_handle h, int which, const sicp_bootstrap_params* p,
+                                      const sicp_bootstrap_label_params* lp, int32_t capacity, int32_t* n_keypoints,
+                                      float* xyz3, uint32_t* label);
+int sicp_bootstrap_semantic_score(sicp_handle h, const sicp_bootstrap_params* p, const sicp_bootstrap_label_params* lp,
+                                  int32_t n, const int32_t* src_idx, const int32_t* tgt_idx, double* M12, double* err,
+                                  int32_t knn_capacity, int32_t* feat_knn);
 
 /* ---- test / bench hooks: the individual stages -------------------------------- */
 /* ComputeCovariances (em_icp.hpp:270-343 = gicp.hpp:177-239 =

@@ -126,6 +126,19 @@ class SicpBootstrapParams(C.Structure):
     ]
 
 
+BOOTSTRAP_MAX_IGNORE = 64
+
+
+class SicpBootstrapLabelParams(C.Structure):
+    _fields_ = [
+        ("match_same_label", C.c_int32),
+        ("score_same_label", C.c_int32),
+        ("n_ignore", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("ignore", C.c_uint32 * BOOTSTRAP_MAX_IGNORE),
+    ]
+
+
 class SicpBootstrapInfo(C.Structure):
     _fields_ = [
         ("n_source_keypoints", C.c_int32),
@@ -325,6 +338,15 @@ def lib():
             "sicp_evaluate_batch": [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_double, C.c_int32, C.POINTER(C.c_int64),
                                     C.POINTER(SicpEvaluateResult), _ip],
             "sicp_bootstrap_score": [C.c_void_p, C.POINTER(SicpBootstrapParams), C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, _ip],
+            "sicp_default_bootstrap_label_params": [C.POINTER(SicpBootstrapLabelParams)],
+            "sicp_bootstrap_semantic": [C.c_void_p, C.POINTER(SicpBootstrapParams), C.POINTER(SicpBootstrapLabelParams), _dp,
+                                        C.POINTER(SicpBootstrapInfo)],
+            "sicp_bootstrap_semantic_batch": [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(SicpBootstrapParams),
+                                              C.POINTER(SicpBootstrapLabelParams), _dp, _ip, C.POINTER(SicpBootstrapInfo)],
+            "sicp_bootstrap_semantic_keypoints": [C.c_void_p, C.c_int, C.POINTER(SicpBootstrapParams),
+                                                  C.POINTER(SicpBootstrapLabelParams), C.c_int32, _ip, _fp, _up],
+            "sicp_bootstrap_semantic_score": [C.c_void_p, C.POINTER(SicpBootstrapParams), C.POINTER(SicpBootstrapLabelParams),
+                                              C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, _ip],
             "sicp_default_merge_params": [C.POINTER(SicpMergeParams)],
             "sicp_merge_clouds": [C.POINTER(C.c_void_p), _ip, C.c_int32, _dp, C.POINTER(SicpMergeParams), C.c_void_p, C.c_int, C.c_int32,
                                   _fp, _fp, _fp, _up, _up, C.POINTER(SicpMergeInfo)],
@@ -383,6 +405,26 @@ def default_bootstrap_params(**overrides) -> SicpBootstrapParams:
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def default_bootstrap_label_params(ignore=(), **overrides) -> SicpBootstrapLabelParams:
+    """sicp_default_bootstrap_label_params (both flags 1, nothing ignored), with `ignore` as the list of labels to drop and
+    any field overridden by keyword"""
+    lp = SicpBootstrapLabelParams()
+    st = lib().sicp_default_bootstrap_label_params(C.byref(lp))
+    if st != OK:
+        raise SicpError(st, "sicp_default_bootstrap_label_params")
+    ignore = [int(v) for v in ignore]
+    if len(ignore) > BOOTSTRAP_MAX_IGNORE:
+        raise ValueError(f"at most {BOOTSTRAP_MAX_IGNORE} labels can be ignored")
+    lp.n_ignore = len(ignore)
+    for i, v in enumerate(ignore):
+        lp.ignore[i] = v
+    for k, v in overrides.items():
+        if not hasattr(lp, k):
+            raise AttributeError(k)
+        setattr(lp, k, v)
+    return lp
 
 
 def default_merge_params(**overrides) -> SicpMergeParams:
@@ -566,6 +608,48 @@ class Engine:
                                                _ptr(knn, _ip)), "sicp_bootstrap_score")
         return M, err, knn
 
+    # ---- label-aware initial alignment (sicp_bootstrap_semantic) --------------------------
+    def bootstrap_semantic(self, params: SicpBootstrapParams | None = None, label_params: SicpBootstrapLabelParams | None = None):
+        """Engine.bootstrap with the clouds' labels: ignored labels are filtered out, feature neighbours and inliers must
+        carry the source keypoint's label (label_params; default: both on, nothing ignored).  (qt[7], info dict)"""
+        p = params if params is not None else default_bootstrap_params()
+        lp = label_params if label_params is not None else default_bootstrap_label_params()
+        qt = np.empty(7)
+        info = SicpBootstrapInfo()
+        self._check(lib().sicp_bootstrap_semantic(self._h, C.byref(p), C.byref(lp), _ptr(qt, _dp), C.byref(info)), "sicp_bootstrap_semantic")
+        return qt, info.as_dict()
+
+    def bootstrap_semantic_keypoints(self, which: int, params: SicpBootstrapParams | None = None,
+                                     label_params: SicpBootstrapLabelParams | None = None):
+        """keypoints of one cloud under the label params: xyz (n,3) f32 and their voted labels (n,) uint32"""
+        p = params if params is not None else default_bootstrap_params()
+        lp = label_params if label_params is not None else default_bootstrap_label_params()
+        n = C.c_int32(0)
+        self._check(lib().sicp_bootstrap_semantic_keypoints(self._h, which, C.byref(p), C.byref(lp), 0, C.byref(n), None, None),
+                    "sicp_bootstrap_semantic_keypoints")
+        xyz = np.empty((n.value, 3), dtype=np.float32)
+        lab = np.empty(n.value, dtype=np.uint32)
+        self._check(lib().sicp_bootstrap_semantic_keypoints(self._h, which, C.byref(p), C.byref(lp), n.value, C.byref(n), _ptr(xyz, _fp),
+                                                            _ptr(lab, _up)), "sicp_bootstrap_semantic_keypoints")
+        return xyz, lab
+
+    def bootstrap_semantic_score(self, src_idx, tgt_idx, params: SicpBootstrapParams | None = None,
+                                 label_params: SicpBootstrapLabelParams | None = None, n_source_keypoints: int | None = None):
+        """Engine.bootstrap_score under the label params: M (n,3,4), label-aware errors (n,), and -- when n_source_keypoints is
+        given -- every source keypoint's (label-restricted) feature neighbours (n_source_keypoints, k)"""
+        p = params if params is not None else default_bootstrap_params()
+        lp = label_params if label_params is not None else default_bootstrap_label_params()
+        a = np.ascontiguousarray(src_idx, dtype=np.int32).reshape(-1, p.nr_samples)
+        b = np.ascontiguousarray(tgt_idx, dtype=np.int32).reshape(-1, p.nr_samples)
+        n = a.shape[0]
+        M = np.empty((n, 3, 4))
+        err = np.empty(n)
+        knn = None if n_source_keypoints is None else np.empty((n_source_keypoints, p.k_correspondences), dtype=np.int32)
+        cap = 0 if knn is None else knn.size
+        self._check(lib().sicp_bootstrap_semantic_score(self._h, C.byref(p), C.byref(lp), n, _ptr(a, _ip), _ptr(b, _ip), _ptr(M, _dp),
+                                                        _ptr(err, _dp), cap, _ptr(knn, _ip)), "sicp_bootstrap_semantic_score")
+        return M, err, knn
+
     # ---- stage hooks -----------------------------------------------------------------
     def covariances(self, which: int, want_hist: bool = False, want_nn: bool = False):
         n = self.n[which]
@@ -687,6 +771,29 @@ def bootstrap_batch(engines, params: SicpBootstrapParams | None = None):
     rc = lib().sicp_bootstrap_batch(_handles(engines) if n else None, n, C.byref(p), _ptr(out, _dp), _ptr(status, _ip), infos)
     if rc != OK and (n == 0 or status[0] == unset):
         raise SicpError(rc, "sicp_bootstrap_batch", lib().sicp_last_error(engines[0]._h).decode() if n else "")
+    res = []
+    for i in range(n):
+        if status[i] == OK:
+            res.append((OK, out[i].copy(), infos[i].as_dict()))
+        else:
+            res.append((int(status[i]), None, {"error": lib().sicp_last_error(engines[i]._h).decode()}))
+    return res
+
+
+def bootstrap_semantic_batch(engines, params: SicpBootstrapParams | None = None, label_params: SicpBootstrapLabelParams | None = None):
+    """sicp_bootstrap_semantic_batch: Engine.bootstrap_semantic for every engine's pair in one call (the same params for
+    all).  Returns [(status, qt, info)] as bootstrap_batch does; per pair identical to the lone call."""
+    n = len(engines)
+    p = params if params is not None else default_bootstrap_params()
+    lp = label_params if label_params is not None else default_bootstrap_label_params()
+    out = np.empty((max(n, 1), 7))
+    unset = -(2 ** 31)
+    status = np.full(max(n, 1), unset, dtype=np.int32)
+    infos = (SicpBootstrapInfo * max(n, 1))()
+    rc = lib().sicp_bootstrap_semantic_batch(_handles(engines) if n else None, n, C.byref(p), C.byref(lp), _ptr(out, _dp),
+                                             _ptr(status, _ip), infos)
+    if rc != OK and (n == 0 or status[0] == unset):
+        raise SicpError(rc, "sicp_bootstrap_semantic_batch", lib().sicp_last_error(engines[0]._h).decode() if n else "")
     res = []
     for i in range(n):
         if status[i] == OK:

@@ -9,6 +9,10 @@
 // once -- the hot kernels as one job launch (kernels.h: BootCloudJob / BootPairJob), the rocPRIM sorts and scans queued
 // cloud after cloud -- with one host synchronisation per stage for the whole group.  A cloud shared by several pairs
 // (sicp_share_cloud) gets its keypoints and features once per call.
+//
+// The label forms (sicp_bootstrap_semantic*) run the same stages with a sicp_bootstrap_label_params (`lp`, NULL in the
+// label-blind calls): the ignore list joins the box filter, every keypoint gets its voxel's label vote, and the two flags
+// choose the label forms of the feature k-NN and of the error kernel.
 #include <map>
 #include <set>
 #include <thread>
@@ -35,6 +39,9 @@ struct BootCloud {
   int n = 0;
   std::vector<float> hx, hy, hz;  // host copy of the keypoints (sampling distances, the search tree's staging)
   DevBuf<float> kx, ky, kz;
+  // the keypoints' labels (the label forms only)
+  std::vector<uint32_t> hl;
+  DevBuf<uint32_t> kl;
   // neighbourhoods of the feature radius (CSR); those of the normal radius when the two radii differ live in nrm_*
   long long n_nbrs = 0;
   int max_nbrs = 0;
@@ -48,6 +55,7 @@ struct BootCloud {
 // every scratch buffer of one cloud (arena blocks: recycled between calls)
 struct BootScratch {
   DevBuf<float> x, y, z, blk;
+  DevBuf<uint32_t> lab;  // the points' labels (the label forms only)
   DevBuf<u64> key, key2;
   DevBuf<int> flag, pos, heads, nout, val, val2;
   DevBuf<long long> cnt;
@@ -90,7 +98,8 @@ struct PairWork {
   std::string msg;
   std::vector<int> knn;  // [n_source][k]
   int k_eff = 0;         // k clamped to the target keypoints with a feature
-  std::vector<int> src_valid;
+  std::vector<int> row_k;  // match_same_label: the entries >= 0 of every row of knn (empty otherwise: k_eff for every row)
+  std::vector<int> src_valid;  // the source keypoints that can be sampled
   int tgt_valid = 0;
   int n_hyp = 0;
   std::vector<double> M, Q, err;  // [n_hyp][12], [n_hyp][4], [n_hyp]
@@ -148,6 +157,26 @@ int check_params(sicp_context* h, const sicp_bootstrap_params& p, const char* wh
   if (p.nr_samples < 3 || p.nr_samples > kBootMaxSamples) return bad("nr_samples must be in 3..8");
   if (p.k_correspondences < 1 || p.k_correspondences > kBootMaxK) return bad("k_correspondences must be in 1..16");
   return SICP_OK;
+}
+
+int check_label_params(sicp_context* h, const sicp_bootstrap_label_params& lp, const char* who) {
+  auto bad = [&](const char* what) {
+    h->last_error = std::string(who) + ": " + what;
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (lp.match_same_label != 0 && lp.match_same_label != 1) return bad("match_same_label must be 0 or 1");
+  if (lp.score_same_label != 0 && lp.score_same_label != 1) return bad("score_same_label must be 0 or 1");
+  if (lp.n_ignore < 0 || lp.n_ignore > SICP_BOOTSTRAP_MAX_IGNORE) return bad("n_ignore must be in 0..64");
+  return SICP_OK;
+}
+
+sicp::BootIgnore ignore_of(const sicp_bootstrap_label_params& lp) {
+  static_assert(sicp::kBootMaxIgnore == SICP_BOOTSTRAP_MAX_IGNORE, "the kernel argument holds the whole ignore list");
+  sicp::BootIgnore ig;
+  std::memset(&ig, 0, sizeof ig);
+  ig.n = lp.n_ignore;
+  for (int k = 0; k < lp.n_ignore; ++k) ig.v[k] = lp.ignore[k];
+  return ig;
 }
 
 // the engine's searches run on flat clouds with the box tree whatever the handle's mode / engine knobs: they are restored after
@@ -229,8 +258,11 @@ void rigid_from_pairs(int n, const double* s, const double* t, double q[4], doub
 
 // box filter + voxel grid of every cloud: keypoints = centroids of the occupied voxels in ascending voxel index.  Three
 // synchronisations for all clouds: the bounds, the keypoint counts, the keypoints' host copies.
-int voxel_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vector<CloudWork*>& W) {
+int voxel_stage(sicp_context* h, const sicp_bootstrap_params& p, const sicp_bootstrap_label_params* lp,
+                const std::vector<CloudWork*>& W) {
   const hipStream_t st = h->stream;
+  const bool ignoring = lp && lp->n_ignore > 0;
+  const sicp::BootIgnore ig = lp ? ignore_of(*lp) : sicp::BootIgnore();
   for (CloudWork* w : W) {
     const Cloud& c = *w->c;
     const int n = c.n;
@@ -238,14 +270,20 @@ int voxel_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vect
     w->n_kept = 0;
     if (n <= 0) continue;
     if (c.hx.size() < (size_t)n) { w->fail(SICP_ERR_NOT_READY, "a cloud has no host copy"); continue; }
+    if (lp && (!c.has_label || c.hl.size() < (size_t)n)) { w->fail(SICP_ERR_INVALID_ARGUMENT, "a cloud has no labels"); continue; }
     BootScratch& s = w->s;
+    if (lp) {
+      HIPCHECK(s.lab.reserve(n));
+      HIPCHECK(hipMemcpyAsync(s.lab.p, c.hl.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
+    }
     HIPCHECK(s.x.reserve(n)); HIPCHECK(s.y.reserve(n)); HIPCHECK(s.z.reserve(n));
     HIPCHECK(hipMemcpyAsync(s.x.p, c.hx.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(s.y.p, c.hy.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(s.z.p, c.hz.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
     const int nb = boot_bounds_blocks(n);
     HIPCHECK(s.blk.reserve((size_t)nb * 8));
-    HIPCHECK(launch_boot_bounds(n, s.x.p, s.y.p, s.z.p, p.box_max, s.blk.p, st));
+    if (ignoring) HIPCHECK(launch_boot_bounds_ignore(n, s.x.p, s.y.p, s.z.p, s.lab.p, ig, p.box_max, s.blk.p, st));
+    else HIPCHECK(launch_boot_bounds(n, s.x.p, s.y.p, s.z.p, p.box_max, s.blk.p, st));
     w->blk.assign((size_t)nb * 8, 0.f);
     HIPCHECK(hipMemcpyAsync(w->blk.data(), s.blk.p, sizeof(float) * w->blk.size(), hipMemcpyDeviceToHost, st));
   }
@@ -286,7 +324,11 @@ int voxel_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vect
     w->n_kept = n_kept;
     BootScratch& s = w->s;
     HIPCHECK(s.key.reserve(n)); HIPCHECK(s.key2.reserve(n));
-    HIPCHECK(launch_boot_voxel_keys(n, s.x.p, s.y.p, s.z.p, p.box_max, inv_leaf, min_b, (int)div[0], (int)(div[0] * div[1]), s.key.p, st));
+    if (ignoring)
+      HIPCHECK(launch_boot_voxel_keys_ignore(n, s.x.p, s.y.p, s.z.p, s.lab.p, ig, p.box_max, inv_leaf, min_b, (int)div[0],
+                                             (int)(div[0] * div[1]), s.key.p, st));
+    else
+      HIPCHECK(launch_boot_voxel_keys(n, s.x.p, s.y.p, s.z.p, p.box_max, inv_leaf, min_b, (int)div[0], (int)(div[0] * div[1]), s.key.p, st));
     size_t sort_bytes = 0, scan_bytes = 0;
     HIPCHECK(boot_sort_keys(nullptr, sort_bytes, s.key.p, s.key2.p, n, st));
     HIPCHECK(boot_scan_int(nullptr, scan_bytes, s.flag.p, s.pos.p, (int)n_kept, st));
@@ -311,6 +353,12 @@ int voxel_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vect
     HIPCHECK(hipMemcpyAsync(out.hx.data(), out.kx.p, sizeof(float) * n_kp, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(out.hy.data(), out.ky.p, sizeof(float) * n_kp, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(out.hz.data(), out.kz.p, sizeof(float) * n_kp, hipMemcpyDeviceToHost, st));
+    if (lp) {
+      HIPCHECK(out.kl.reserve(m));
+      HIPCHECK(launch_boot_label_vote(n_kp, (int)w->n_kept, s.heads.p, s.key2.p, s.lab.p, out.kl.p, st));
+      out.hl.resize(n_kp);
+      HIPCHECK(hipMemcpyAsync(out.hl.data(), out.kl.p, sizeof(uint32_t) * n_kp, hipMemcpyDeviceToHost, st));
+    }
   }
   HIPCHECK(hipStreamSynchronize(st));
   return SICP_OK;
@@ -451,9 +499,11 @@ int feature_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::ve
 }
 
 // the feature k-NN of every source keypoint of every pair: one job launch, one read-back
-int knn_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vector<PairWork*>& P) {
+int knn_stage(sicp_context* h, const sicp_bootstrap_params& p, const sicp_bootstrap_label_params* lp,
+              const std::vector<PairWork*>& P) {
   const hipStream_t st = h->stream;
   const int k = p.k_correspondences;
+  const bool same_label = lp && lp->match_same_label;
   JobTable<BootPairJob> tab;
   size_t total = 0;
   std::vector<PairWork*> L;
@@ -474,16 +524,30 @@ int knn_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vector
     j.n = q->S->k.n; j.nt = q->T->k.n;
     j.sf = q->S->k.fpfh.p; j.tf = q->T->k.fpfh.p;
     j.out = dk.p + q->knn_at;
+    if (same_label) { j.sl = q->S->k.kl.p; j.tl = q->T->k.kl.p; }
     tab.add(j, (j.n + 255) / 256);
   }
   HIPCHECK(tab.upload(st));
-  HIPCHECK(launch_boot_feature_knn_jobs(tab.d_jobs(), tab.d_end(), tab.nj(), tab.blocks, k, st));
+  if (same_label) HIPCHECK(launch_boot_feature_knn_label_jobs(tab.d_jobs(), tab.d_end(), tab.nj(), tab.blocks, k, st));
+  else HIPCHECK(launch_boot_feature_knn_jobs(tab.d_jobs(), tab.d_end(), tab.nj(), tab.blocks, k, st));
   for (PairWork* q : L) HIPCHECK(hipMemcpyAsync(q->knn.data(), dk.p + q->knn_at, sizeof(int) * q->knn.size(), hipMemcpyDeviceToHost, st));
   HIPCHECK(hipStreamSynchronize(st));
   for (PairWork* q : P) {
     q->src_valid.clear();
-    for (int i = 0; i < q->S->k.n; ++i)
-      if (q->S->valid[i]) q->src_valid.push_back(i);
+    q->row_k.clear();
+    if (same_label) {
+      // a row holds its label's neighbours first and -1 behind them; a keypoint without any cannot be sampled
+      q->row_k.assign(q->S->k.n, 0);
+      for (int i = 0; i < q->S->k.n; ++i) {
+        int c = 0;
+        while (c < k && q->knn[(size_t)i * k + c] >= 0) ++c;
+        q->row_k[i] = c;
+        if (q->S->valid[i] && c >= 1) q->src_valid.push_back(i);
+      }
+    } else {
+      for (int i = 0; i < q->S->k.n; ++i)
+        if (q->S->valid[i]) q->src_valid.push_back(i);
+    }
     q->tgt_valid = 0;
     for (char v : q->T->valid) q->tgt_valid += v;
     q->k_eff = std::min(k, q->tgt_valid);
@@ -521,7 +585,7 @@ void draw_hypotheses(const sicp_bootstrap_params& p, PairWork& q) {
       if (fails >= max_fails) { min_d *= 0.5f; fails = 0; }
     }
     for (int j = 0; j < nr; ++j) {
-      const int tj = q.knn[(size_t)smp[j] * k + rng.index(q.k_eff)];
+      const int tj = q.knn[(size_t)smp[j] * k + rng.index(q.row_k.empty() ? q.k_eff : q.row_k[smp[j]])];
       sp[3 * j] = S.hx[smp[j]]; sp[3 * j + 1] = S.hy[smp[j]]; sp[3 * j + 2] = S.hz[smp[j]];
       tp[3 * j] = T.hx[tj]; tp[3 * j + 1] = T.hy[tj]; tp[3 * j + 2] = T.hz[tj];
     }
@@ -546,11 +610,13 @@ void draw_all(const sicp_bootstrap_params& p, const std::vector<PairWork*>& P) {
 }
 
 // the keypoints of a cloud as an engine cloud (flat layout, box tree): the scoring's query set and search tree
-int keypoint_tree(sicp_context* h, CloudWork& w) {
+// (labels: with the keypoints' labels, which the tree build carries into its device order beside the coordinates)
+int keypoint_tree(sicp_context* h, CloudWork& w, bool labels) {
   if (w.tree) return SICP_OK;
   w.tree = acquire_cloud(h->device);
   const BootCloud& k = w.k;
-  const StridedCloud ks = {(const char*)k.hx.data(), (const char*)k.hy.data(), (const char*)k.hz.data(), nullptr, 4, 4};
+  const StridedCloud ks = {(const char*)k.hx.data(), (const char*)k.hy.data(), (const char*)k.hz.data(),
+                           labels ? (const char*)k.hl.data() : nullptr, 4, 4};
   SICPCHECK(stage_cloud(h, *w.tree, k.n, ks));
   w.tree->is_set = true; w.tree->layout = -1;
   return prepare_cloud(h, *w.tree);
@@ -560,10 +626,12 @@ int keypoint_tree(sicp_context* h, CloudWork& w) {
 // keypoint per hypothesis on a box tree of the target keypoints.  The hypotheses of all pairs are cut into chunks of at most
 // kScoreOutputs search outputs; a chunk's searches are collected into the packet kernel's job launches, then one
 // error launch reduces the whole chunk.  One read-back at the end.
-int score_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vector<PairWork*>& P) {
+int score_stage(sicp_context* h, const sicp_bootstrap_params& p, const sicp_bootstrap_label_params* lp,
+                const std::vector<PairWork*>& P) {
   const hipStream_t st = h->stream;
+  const bool same_label = lp && lp->score_same_label;
   BootParamsScope scope(h);
-  for (PairWork* q : P) { SICPCHECK(keypoint_tree(h, *q->S)); SICPCHECK(keypoint_tree(h, *q->T)); }
+  for (PairWork* q : P) { SICPCHECK(keypoint_tree(h, *q->S, same_label)); SICPCHECK(keypoint_tree(h, *q->T, same_label)); }
   for (PairWork* q : P) { SICPCHECK(cloud_wait(h, *q->S->tree)); SICPCHECK(cloud_wait(h, *q->T->tree)); }
   size_t n_err = 0;
   long long outputs = 0, max_nq = 1;
@@ -590,7 +658,8 @@ int score_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vect
     if (jc.knn[0].empty()) return SICP_OK;
     HIPCHECK(sicp::launch_bvh_knn_packet_jobs(jc.knn_K[0], jc.knn[0].data(), (int)jc.knn[0].size(), st));
     HIPCHECK(tab->upload(st));
-    HIPCHECK(launch_boot_error_jobs(tab->d_jobs(), tab->d_end(), tab->nj(), tab->blocks, t, st));
+    if (same_label) HIPCHECK(launch_boot_error_label_jobs(tab->d_jobs(), tab->d_end(), tab->nj(), tab->blocks, t, st));
+    else HIPCHECK(launch_boot_error_jobs(tab->d_jobs(), tab->d_end(), tab->nj(), tab->blocks, t, st));
     tables.push_back(std::move(tab));
     tab.reset(new JobTable<BootPairJob>);
     jc.knn[0].clear();
@@ -609,6 +678,8 @@ int score_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::vect
       j.n = cnt; j.nt = nq;
       j.d2 = od.p + used;
       j.err = derr.p + q->err_at + i0;
+      // (the search writes row r for the source tree's device point r, and the target tree's device index of its neighbour)
+      if (same_label) { j.nbr = oi.p + used; j.sl = qc.label.p; j.tl = tc.label.p; }
       {
         CollectScope cs(h, &jc);
         for (int i = 0; i < cnt; ++i)
@@ -634,10 +705,10 @@ int check_clouds(sicp_context* h) {
 }
 
 // keypoints + features of every cloud, then the feature k-NN of every pair whose clouds have them
-int prepare(sicp_context* h, const sicp_bootstrap_params& p, const std::vector<CloudWork*>& W, const std::vector<PairWork*>& P,
-            double* t_kp, double* t_feat, double* t_knn) {
+int prepare(sicp_context* h, const sicp_bootstrap_params& p, const sicp_bootstrap_label_params* lp,
+            const std::vector<CloudWork*>& W, const std::vector<PairWork*>& P, double* t_kp, double* t_feat, double* t_knn) {
   const double t0 = now_ms();
-  SICPCHECK(voxel_stage(h, p, W));
+  SICPCHECK(voxel_stage(h, p, lp, W));
   const double t1 = now_ms();
   SICPCHECK(feature_stage(h, p, W));
   const double t2 = now_ms();
@@ -648,7 +719,7 @@ int prepare(sicp_context* h, const sicp_bootstrap_params& p, const std::vector<C
       if (!w->live() && q->status == SICP_OK) { q->status = w->status; q->msg = w->msg; }
     if (q->status == SICP_OK) L.push_back(q);
   }
-  SICPCHECK(knn_stage(h, p, L));
+  SICPCHECK(knn_stage(h, p, lp, L));
   const double t3 = now_ms();
   if (t_kp) *t_kp += t1 - t0;
   if (t_feat) *t_feat += t2 - t1;
@@ -659,13 +730,17 @@ int prepare(sicp_context* h, const sicp_bootstrap_params& p, const std::vector<C
 // the whole bootstrap of n pairs (hs[i]'s source onto its target) on h's stream; status[i] per pair, messages prefixed
 // with `who` (and the pair's index when `indexed`).  Returns SICP_OK or the code of a failure of the call itself (HIP,
 // memory), which is then every unfinished pair's status too.
-int run_batch(sicp_context* h, sicp_handle* hs, int n, const sicp_bootstrap_params& p, double* out_qt, int32_t* status,
-              sicp_bootstrap_info* infos, const char* who, bool indexed) {
+int run_batch(sicp_context* h, sicp_handle* hs, int n, const sicp_bootstrap_params& p, const sicp_bootstrap_label_params* lp,
+              double* out_qt, int32_t* status, sicp_bootstrap_info* infos, const char* who, bool indexed) {
   const double t_begin = now_ms();
   std::vector<PairWork> pairs(n);
   for (int i = 0; i < n; ++i) {
     pairs[i].index = i;
     if (check_clouds(hs[i]) != SICP_OK) { pairs[i].status = SICP_ERR_NOT_READY; pairs[i].msg = "the handle has no source or no target cloud"; }
+    else if (lp && (!hs[i]->cloud(SICP_SOURCE).has_label || !hs[i]->cloud(SICP_TARGET).has_label)) {
+      pairs[i].status = SICP_ERR_INVALID_ARGUMENT;
+      pairs[i].msg = std::string(hs[i]->cloud(SICP_SOURCE).has_label ? "the target" : "the source") + " cloud has no labels";
+    }
   }
   double t_kp = 0, t_feat = 0, t_match = 0, t_score = 0;
   std::map<const Cloud*, std::unique_ptr<CloudWork>> cache;  // this group's clouds (and the previous group's it shares)
@@ -700,7 +775,7 @@ int run_batch(sicp_context* h, sicp_handle* hs, int n, const sicp_bootstrap_para
         (w == 0 ? q->S : q->T) = slot.get();
       }
     }
-    rc = prepare(h, p, W, G, &t_kp, &t_feat, &t_match);
+    rc = prepare(h, p, lp, W, G, &t_kp, &t_feat, &t_match);
     if (rc != SICP_OK) break;
     const double tm0 = now_ms();
     std::vector<PairWork*> L;
@@ -716,7 +791,7 @@ int run_batch(sicp_context* h, sicp_handle* hs, int n, const sicp_bootstrap_para
     draw_all(p, L);
     const double tm1 = now_ms();
     t_match += tm1 - tm0;
-    rc = score_stage(h, p, L);
+    rc = score_stage(h, p, lp, L);
     t_score += now_ms() - tm1;
     if (rc != SICP_OK) break;
     for (PairWork* q : L) {
@@ -735,7 +810,7 @@ int run_batch(sicp_context* h, sicp_handle* hs, int n, const sicp_bootstrap_para
         info.best_iteration = best;
         info.best_error = q->err[best];
       }
-      q->err.clear(); q->M.clear(); q->Q.clear(); q->knn.clear();
+      q->err.clear(); q->M.clear(); q->Q.clear(); q->knn.clear(); q->row_k.clear();
       q->done = true;
     }
   }
@@ -795,38 +870,145 @@ void bootstrap_default_params(sicp_bootstrap_params* p) {
   p->seed = 1;
 }
 
-int bootstrap_run(sicp_context* h, const sicp_bootstrap_params* pp, double* out_qt, sicp_bootstrap_info* info) {
+namespace {
+
+// sicp_bootstrap / sicp_bootstrap_semantic (lp: NULL in the former, checked by the caller in the latter)
+int run_one(sicp_context* h, const sicp_bootstrap_params* pp, const sicp_bootstrap_label_params* lp, double* out_qt,
+            sicp_bootstrap_info* info, const char* who) {
   if (!pp || !out_qt) return SICP_ERR_INVALID_ARGUMENT;
   const sicp_bootstrap_params p = *pp;
-  SICPCHECK(check_params(h, p, "sicp_bootstrap"));
+  SICPCHECK(check_params(h, p, who));
+  if (lp) SICPCHECK(check_label_params(h, *lp, who));
   SICPCHECK(set_device(h));
   SICPCHECK(check_clouds(h));
   // a batch of one: the same stages and kernels as any batch
   int32_t st = SICP_OK;
   sicp_handle hs[1] = {h};
-  const int rc = run_batch(h, hs, 1, p, out_qt, &st, info, "sicp_bootstrap", false);
+  const int rc = run_batch(h, hs, 1, p, lp, out_qt, &st, info, who, false);
   return rc != SICP_OK ? rc : st;
 }
 
-int bootstrap_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* pp, double* out_qt, int32_t* status,
-                    sicp_bootstrap_info* infos) {
+int run_many(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* pp, const sicp_bootstrap_label_params* lp, bool semantic,
+             double* out_qt, int32_t* status, sicp_bootstrap_info* infos, const char* who) {
   if (!hs || n < 1) return SICP_ERR_INVALID_ARGUMENT;
   sicp_context* h = hs[0];
   auto refuse = [&](const std::string& why) {
-    if (h) h->last_error = "sicp_bootstrap_batch: " + why;
+    if (h) h->last_error = std::string(who) + ": " + why;
     return SICP_ERR_INVALID_ARGUMENT;
   };
   for (int i = 0; i < n; ++i)
     if (!hs[i]) return refuse("handle " + std::to_string(i) + " is NULL");
   if (!pp) return refuse("params is NULL");
+  if (semantic && !lp) return refuse("label params is NULL");
   if (!out_qt) return refuse("out_qt is NULL");
   for (int i = 1; i < n; ++i)
     if (hs[i]->device != h->device)
       return refuse("handle " + std::to_string(i) + " is on device " + std::to_string(hs[i]->device) + ", handle 0 on " + std::to_string(h->device));
   const sicp_bootstrap_params p = *pp;
-  SICPCHECK(check_params(h, p, "sicp_bootstrap_batch"));
+  SICPCHECK(check_params(h, p, who));
+  sicp_bootstrap_label_params l;
+  if (lp) { l = *lp; SICPCHECK(check_label_params(h, l, who)); }
   SICPCHECK(set_device(h));
-  return run_batch(h, hs, n, p, out_qt, status, infos, "sicp_bootstrap_batch", true);
+  return run_batch(h, hs, n, p, lp ? &l : nullptr, out_qt, status, infos, who, true);
+}
+
+// a semantic entry point's label params: NULL is refused with its message
+int need_label_params(sicp_context* h, const sicp_bootstrap_label_params* lp, const char* who) {
+  if (lp) return SICP_OK;
+  h->last_error = std::string(who) + ": label params is NULL";
+  return SICP_ERR_INVALID_ARGUMENT;
+}
+
+// a hook's clouds carry labels when it runs a label form
+int need_labels(sicp_context* h, const sicp_bootstrap_label_params* lp, int first, int last, const char* who) {
+  if (!lp) return SICP_OK;
+  for (int w = first; w <= last; ++w)
+    if (!h->cloud(w).has_label) {
+      h->last_error = std::string(who) + ": the " + (w == SICP_SOURCE ? "source" : "target") + " cloud has no labels";
+      return SICP_ERR_INVALID_ARGUMENT;
+    }
+  return SICP_OK;
+}
+
+// sicp_bootstrap_score / sicp_bootstrap_semantic_score
+int score_hook(sicp_context* h, const sicp_bootstrap_params* pp, const sicp_bootstrap_label_params* lpp, int32_t n,
+               const int32_t* src_idx, const int32_t* tgt_idx, double* M12, double* err, int32_t knn_capacity, int32_t* feat_knn,
+               const char* who) {
+  if (!pp || n < 0 || (n > 0 && (!src_idx || !tgt_idx || !err))) return SICP_ERR_INVALID_ARGUMENT;
+  const sicp_bootstrap_params p = *pp;
+  SICPCHECK(check_params(h, p, who));
+  sicp_bootstrap_label_params l;
+  if (lpp) { l = *lpp; SICPCHECK(check_label_params(h, l, who)); }
+  const sicp_bootstrap_label_params* lp = lpp ? &l : nullptr;
+  SICPCHECK(set_device(h));
+  SICPCHECK(check_clouds(h));
+  SICPCHECK(need_labels(h, lp, SICP_SOURCE, SICP_TARGET, who));
+  CloudWork cw[2];
+  cw[0].c = &h->cloud(SICP_SOURCE);
+  cw[1].c = &h->cloud(SICP_TARGET);
+  PairWork q;
+  q.S = &cw[0]; q.T = &cw[1];
+  SICPCHECK(prepare(h, p, lp, {&cw[0], &cw[1]}, {&q}, nullptr, nullptr, nullptr));
+  if (q.status != SICP_OK) {
+    h->last_error = std::string(who) + ": " + q.msg;
+    return q.status;
+  }
+  const BootCloud &S = cw[0].k, &T = cw[1].k;
+  if (feat_knn) {
+    if ((long long)knn_capacity < (long long)S.n * p.k_correspondences) return SICP_ERR_INVALID_ARGUMENT;
+    std::memcpy(feat_knn, q.knn.data(), sizeof(int) * q.knn.size());
+  }
+  if (n == 0) return SICP_OK;
+  if (S.n < 1 || T.n < 1) return SICP_ERR_TOO_FEW_POINTS;
+  const int nr = p.nr_samples;
+  q.n_hyp = n;
+  q.M.assign((size_t)n * 12, 0.0);
+  double sp[3 * kBootMaxSamples], tp[3 * kBootMaxSamples], qq[4];
+  for (int i = 0; i < n; ++i) {
+    for (int j = 0; j < nr; ++j) {
+      const int a = src_idx[(size_t)i * nr + j], b = tgt_idx[(size_t)i * nr + j];
+      if (a < 0 || a >= S.n || b < 0 || b >= T.n) {
+        h->last_error = std::string(who) + "_score: sample " + std::to_string(i) + " names a keypoint that does not exist";
+        return SICP_ERR_INVALID_ARGUMENT;
+      }
+      sp[3 * j] = S.hx[a]; sp[3 * j + 1] = S.hy[a]; sp[3 * j + 2] = S.hz[a];
+      tp[3 * j] = T.hx[b]; tp[3 * j + 1] = T.hy[b]; tp[3 * j + 2] = T.hz[b];
+    }
+    rigid_from_pairs(nr, sp, tp, qq, &q.M[(size_t)i * 12]);
+  }
+  SICPCHECK(score_stage(h, p, lp, {&q}));
+  std::memcpy(err, q.err.data(), sizeof(double) * n);
+  if (M12) std::memcpy(M12, q.M.data(), sizeof(double) * q.M.size());
+  return SICP_OK;
+}
+
+}  // namespace
+
+void bootstrap_default_label_params(sicp_bootstrap_label_params* lp) {
+  std::memset(lp, 0, sizeof *lp);
+  lp->match_same_label = 1;
+  lp->score_same_label = 1;
+}
+
+int bootstrap_run(sicp_context* h, const sicp_bootstrap_params* pp, double* out_qt, sicp_bootstrap_info* info) {
+  return run_one(h, pp, nullptr, out_qt, info, "sicp_bootstrap");
+}
+
+int bootstrap_semantic_run(sicp_context* h, const sicp_bootstrap_params* pp, const sicp_bootstrap_label_params* lpp, double* out_qt,
+                           sicp_bootstrap_info* info) {
+  SICPCHECK(need_label_params(h, lpp, "sicp_bootstrap_semantic"));
+  const sicp_bootstrap_label_params lp = *lpp;
+  return run_one(h, pp, &lp, out_qt, info, "sicp_bootstrap_semantic");
+}
+
+int bootstrap_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* pp, double* out_qt, int32_t* status,
+                    sicp_bootstrap_info* infos) {
+  return run_many(hs, n, pp, nullptr, false, out_qt, status, infos, "sicp_bootstrap_batch");
+}
+
+int bootstrap_semantic_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* pp, const sicp_bootstrap_label_params* lp,
+                             double* out_qt, int32_t* status, sicp_bootstrap_info* infos) {
+  return run_many(hs, n, pp, lp, true, out_qt, status, infos, "sicp_bootstrap_semantic_batch");
 }
 
 int bootstrap_keypoints(sicp_context* h, int which, const sicp_bootstrap_params* pp, int32_t capacity, int64_t nbr_capacity,
@@ -840,7 +1022,7 @@ int bootstrap_keypoints(sicp_context* h, int which, const sicp_bootstrap_params*
   CloudWork w;
   w.c = &h->cloud(which);
   const std::vector<CloudWork*> W = {&w};
-  SICPCHECK(voxel_stage(h, p, W));
+  SICPCHECK(voxel_stage(h, p, nullptr, W));
   SICPCHECK(feature_stage(h, p, W));
   if (!w.live()) {
     h->last_error = "sicp_bootstrap: " + w.msg;
@@ -867,50 +1049,45 @@ int bootstrap_keypoints(sicp_context* h, int which, const sicp_bootstrap_params*
   return SICP_OK;
 }
 
-int bootstrap_score(sicp_context* h, const sicp_bootstrap_params* pp, int32_t n, const int32_t* src_idx, const int32_t* tgt_idx,
-                    double* M12, double* err, int32_t knn_capacity, int32_t* feat_knn) {
-  if (!pp || n < 0 || (n > 0 && (!src_idx || !tgt_idx || !err))) return SICP_ERR_INVALID_ARGUMENT;
+// the keypoints of the label forms and their labels: the voxel stage alone
+int bootstrap_semantic_keypoints(sicp_context* h, int which, const sicp_bootstrap_params* pp, const sicp_bootstrap_label_params* lpp,
+                                 int32_t capacity, int32_t* n_keypoints, float* xyz3, uint32_t* label) {
+  const char* who = "sicp_bootstrap_semantic_keypoints";
+  if (!pp || (which != SICP_SOURCE && which != SICP_TARGET)) return SICP_ERR_INVALID_ARGUMENT;
+  SICPCHECK(need_label_params(h, lpp, who));
   const sicp_bootstrap_params p = *pp;
-  SICPCHECK(check_params(h, p, "sicp_bootstrap"));
+  const sicp_bootstrap_label_params lp = *lpp;
+  SICPCHECK(check_params(h, p, who));
+  SICPCHECK(check_label_params(h, lp, who));
   SICPCHECK(set_device(h));
   SICPCHECK(check_clouds(h));
-  CloudWork cw[2];
-  cw[0].c = &h->cloud(SICP_SOURCE);
-  cw[1].c = &h->cloud(SICP_TARGET);
-  PairWork q;
-  q.S = &cw[0]; q.T = &cw[1];
-  SICPCHECK(prepare(h, p, {&cw[0], &cw[1]}, {&q}, nullptr, nullptr, nullptr));
-  if (q.status != SICP_OK) {
-    h->last_error = "sicp_bootstrap: " + q.msg;
-    return q.status;
+  SICPCHECK(need_labels(h, &lp, which, which, who));
+  CloudWork w;
+  w.c = &h->cloud(which);
+  SICPCHECK(voxel_stage(h, p, &lp, {&w}));
+  if (!w.live()) {
+    h->last_error = std::string(who) + ": " + w.msg;
+    return w.status;
   }
-  const BootCloud &S = cw[0].k, &T = cw[1].k;
-  if (feat_knn) {
-    if ((long long)knn_capacity < (long long)S.n * p.k_correspondences) return SICP_ERR_INVALID_ARGUMENT;
-    std::memcpy(feat_knn, q.knn.data(), sizeof(int) * q.knn.size());
-  }
-  if (n == 0) return SICP_OK;
-  if (S.n < 1 || T.n < 1) return SICP_ERR_TOO_FEW_POINTS;
-  const int nr = p.nr_samples;
-  q.n_hyp = n;
-  q.M.assign((size_t)n * 12, 0.0);
-  double sp[3 * kBootMaxSamples], tp[3 * kBootMaxSamples], qq[4];
-  for (int i = 0; i < n; ++i) {
-    for (int j = 0; j < nr; ++j) {
-      const int a = src_idx[(size_t)i * nr + j], b = tgt_idx[(size_t)i * nr + j];
-      if (a < 0 || a >= S.n || b < 0 || b >= T.n) {
-        h->last_error = "sicp_bootstrap_score: sample " + std::to_string(i) + " names a keypoint that does not exist";
-        return SICP_ERR_INVALID_ARGUMENT;
-      }
-      sp[3 * j] = S.hx[a]; sp[3 * j + 1] = S.hy[a]; sp[3 * j + 2] = S.hz[a];
-      tp[3 * j] = T.hx[b]; tp[3 * j + 1] = T.hy[b]; tp[3 * j + 2] = T.hz[b];
-    }
-    rigid_from_pairs(nr, sp, tp, qq, &q.M[(size_t)i * 12]);
-  }
-  SICPCHECK(score_stage(h, p, {&q}));
-  std::memcpy(err, q.err.data(), sizeof(double) * n);
-  if (M12) std::memcpy(M12, q.M.data(), sizeof(double) * q.M.size());
+  const BootCloud& k = w.k;
+  if (n_keypoints) *n_keypoints = k.n;
+  if ((xyz3 || label) && capacity < k.n) return SICP_ERR_INVALID_ARGUMENT;
+  if (xyz3)
+    for (int i = 0; i < k.n; ++i) { xyz3[3 * i] = k.hx[i]; xyz3[3 * i + 1] = k.hy[i]; xyz3[3 * i + 2] = k.hz[i]; }
+  if (label && k.n > 0) std::memcpy(label, k.hl.data(), sizeof(uint32_t) * k.n);
   return SICP_OK;
+}
+
+int bootstrap_score(sicp_context* h, const sicp_bootstrap_params* pp, int32_t n, const int32_t* src_idx, const int32_t* tgt_idx,
+                    double* M12, double* err, int32_t knn_capacity, int32_t* feat_knn) {
+  return score_hook(h, pp, nullptr, n, src_idx, tgt_idx, M12, err, knn_capacity, feat_knn, "sicp_bootstrap");
+}
+
+int bootstrap_semantic_score(sicp_context* h, const sicp_bootstrap_params* pp, const sicp_bootstrap_label_params* lp, int32_t n,
+                             const int32_t* src_idx, const int32_t* tgt_idx, double* M12, double* err, int32_t knn_capacity,
+                             int32_t* feat_knn) {
+  SICPCHECK(need_label_params(h, lp, "sicp_bootstrap_semantic_score"));
+  return score_hook(h, pp, lp, n, src_idx, tgt_idx, M12, err, knn_capacity, feat_knn, "sicp_bootstrap_semantic");
 }
 
 }  // namespace host

@@ -29,6 +29,18 @@ int bootstrap_keypoints(sicp_context* h, int which, const sicp_bootstrap_params*
 int bootstrap_score(sicp_context* h, const sicp_bootstrap_params* p, int32_t n, const int32_t* src_idx, const int32_t* tgt_idx,
                     double* M12, double* err, int32_t knn_capacity, int32_t* feat_knn);
 
+// the label forms (sicp_bootstrap_semantic*): the same stages with the label rules of lp ("Bootstrap")
+void bootstrap_default_label_params(sicp_bootstrap_label_params* lp);
+int bootstrap_semantic_run(sicp_context* h, const sicp_bootstrap_params* p, const sicp_bootstrap_label_params* lp, double* out_qt,
+                           sicp_bootstrap_info* info);
+int bootstrap_semantic_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* p, const sicp_bootstrap_label_params* lp,
+                             double* out_qt, int32_t* status, sicp_bootstrap_info* infos);
+int bootstrap_semantic_keypoints(sicp_context* h, int which, const sicp_bootstrap_params* p, const sicp_bootstrap_label_params* lp,
+                                 int32_t capacity, int32_t* n_keypoints, float* xyz3, uint32_t* label);
+int bootstrap_semantic_score(sicp_context* h, const sicp_bootstrap_params* p, const sicp_bootstrap_label_params* lp, int32_t n,
+                             const int32_t* src_idx, const int32_t* tgt_idx, double* M12, double* err, int32_t knn_capacity,
+                             int32_t* feat_knn);
+
 }  // namespace host
 }  // namespace sicp
 #endif

@@ -38,15 +38,25 @@ __device__ __forceinline__ int boot_job_of(const int* blk_end, int nj, int b, in
 
 // ---- voxel grid ----------------------------------------------------------------------------------------------------
 // per workgroup: min / max of the kept points and their count -> blk[b * 8 + (lo0 lo1 lo2 hi0 hi1 hi2 count)]
-__global__ __launch_bounds__(256) void boot_bounds_kernel(int n, const float* x, const float* y, const float* z,
-                                                          double box_max, float* blk) {
+// (LAB: a point whose label is in the ignore list is not kept either)
+__device__ __forceinline__ bool boot_ignored(const BootIgnore& ig, unsigned l) {
+  bool hit = false;
+  for (int k = 0; k < ig.n; ++k) hit = hit || ig.v[k] == l;
+  return hit;
+}
+
+template <bool LAB>
+__device__ __forceinline__ void boot_bounds_body(int n, const float* x, const float* y, const float* z, const unsigned* label,
+                                                 const BootIgnore* ig, double box_max, float* blk) {
   __shared__ float s[7][256];
   const int t = threadIdx.x, i = blockIdx.x * 256 + t;
   const float inf = __builtin_inff();
   float v[7] = {inf, inf, inf, -inf, -inf, -inf, 0.f};
   if (i < n) {
     const float px = x[i], py = y[i], pz = z[i];
-    if (boot_kept(px, py, pz, box_max)) { v[0] = v[3] = px; v[1] = v[4] = py; v[2] = v[5] = pz; v[6] = 1.f; }
+    bool kept = boot_kept(px, py, pz, box_max);
+    if (LAB) kept = kept && !boot_ignored(*ig, label[i]);
+    if (kept) { v[0] = v[3] = px; v[1] = v[4] = py; v[2] = v[5] = pz; v[6] = 1.f; }
   }
   for (int k = 0; k < 7; ++k) s[k][t] = v[k];
   __syncthreads();
@@ -60,17 +70,28 @@ __global__ __launch_bounds__(256) void boot_bounds_kernel(int n, const float* x,
   }
   if (t < 7) blk[blockIdx.x * 8 + t] = s[t][0];
 }
+__global__ __launch_bounds__(256) void boot_bounds_kernel(int n, const float* x, const float* y, const float* z,
+                                                          double box_max, float* blk) {
+  boot_bounds_body<false>(n, x, y, z, nullptr, nullptr, box_max, blk);
+}
+__global__ __launch_bounds__(256) void boot_bounds_ignore_kernel(int n, const float* x, const float* y, const float* z,
+                                                                 const unsigned* label, BootIgnore ig, double box_max, float* blk) {
+  boot_bounds_body<true>(n, x, y, z, label, &ig, box_max, blk);
+}
 
 // key = voxel index << 32 | point index (kept points), ~0 otherwise: sorted, points of one voxel are adjacent and in
 // ascending index order
-__global__ __launch_bounds__(256) void boot_voxel_key_kernel(int n, const float* x, const float* y, const float* z,
-                                                             double box_max, float inv_leaf, int mb0, int mb1, int mb2,
-                                                             int dx, int dxy, u64* key) {
+template <bool LAB>
+__device__ __forceinline__ void boot_voxel_key_body(int n, const float* x, const float* y, const float* z, const unsigned* label,
+                                                    const BootIgnore* ig, double box_max, float inv_leaf, int mb0, int mb1, int mb2,
+                                                    int dx, int dxy, u64* key) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float px = x[i], py = y[i], pz = z[i];
   u64 k = ~0ull;
-  if (boot_kept(px, py, pz, box_max)) {
+  bool kept = boot_kept(px, py, pz, box_max);
+  if (LAB) kept = kept && !boot_ignored(*ig, label[i]);
+  if (kept) {
     const int i0 = (int)floorf(px * inv_leaf) - mb0;
     const int i1 = (int)floorf(py * inv_leaf) - mb1;
     const int i2 = (int)floorf(pz * inv_leaf) - mb2;
@@ -78,6 +99,17 @@ __global__ __launch_bounds__(256) void boot_voxel_key_kernel(int n, const float*
     k = ((u64)idx << 32) | (unsigned)i;
   }
   key[i] = k;
+}
+__global__ __launch_bounds__(256) void boot_voxel_key_kernel(int n, const float* x, const float* y, const float* z,
+                                                             double box_max, float inv_leaf, int mb0, int mb1, int mb2,
+                                                             int dx, int dxy, u64* key) {
+  boot_voxel_key_body<false>(n, x, y, z, nullptr, nullptr, box_max, inv_leaf, mb0, mb1, mb2, dx, dxy, key);
+}
+__global__ __launch_bounds__(256) void boot_voxel_key_ignore_kernel(int n, const float* x, const float* y, const float* z,
+                                                                    const unsigned* label, BootIgnore ig, double box_max,
+                                                                    float inv_leaf, int mb0, int mb1, int mb2, int dx, int dxy,
+                                                                    u64* key) {
+  boot_voxel_key_body<true>(n, x, y, z, label, &ig, box_max, inv_leaf, mb0, mb1, mb2, dx, dxy, key);
 }
 
 __global__ __launch_bounds__(256) void boot_heads_kernel(int n_kept, const u64* key, int* flag) {
@@ -107,6 +139,41 @@ __global__ __launch_bounds__(256) void boot_centroid_kernel(int n_kp, int n_kept
   }
   const double c = (double)(e - b);
   kx[k] = (float)(sx / c); ky[k] = (float)(sy / c); kz[k] = (float)(sz / c);
+}
+
+// one wave per voxel: the most frequent label of its points, ties to the smallest label (the rule of sicp_merge_clouds).
+// Integer counts only.  The wave walks the voxel's distinct labels in ascending order: every pass counts the points with
+// the current label and finds the smallest label above it (lanes stride over the voxel's range of the sorted keys, then a
+// butterfly over the wave), so a voxel of c points with d distinct labels costs (d + 1) * ceil(c / 64) loads per lane --
+// two points or several hundred alike -- and `>` keeps the smallest label among equal counts.
+__global__ __launch_bounds__(256) void boot_label_vote_kernel(int n_kp, int n_kept, const int* heads, const u64* key,
+                                                              const unsigned* label, unsigned* klabel) {
+  const int k = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (k >= n_kp) return;  // (a whole wave)
+  const int b = heads[k], e = k + 1 < n_kp ? heads[k + 1] : n_kept;
+  bool started = false;  // false: the first pass only looks for the smallest label
+  unsigned cur = 0, best = 0;
+  int best_cnt = 0;
+  for (;;) {
+    int cnt = 0;
+    unsigned nxt = 0xffffffffu;
+    bool more = false;
+    for (int j = b + lane; j < e; j += 64) {
+      const unsigned l = label[(unsigned)(key[j] & 0xffffffffull)];
+      if (started && l == cur) ++cnt;
+      else if (!started || l > cur) { more = true; nxt = l < nxt ? l : nxt; }
+    }
+    for (int w = 32; w > 0; w >>= 1) {
+      cnt += __shfl_xor(cnt, w, 64);
+      const unsigned o = __shfl_xor(nxt, w, 64);
+      nxt = o < nxt ? o : nxt;
+    }
+    if (started && cnt > best_cnt) { best_cnt = cnt; best = cur; }
+    if (__ballot(more) == 0ull) break;
+    cur = nxt;
+    started = true;
+  }
+  if (lane == 0) klabel[k] = best;
 }
 
 // ---- radius neighbourhoods: a uniform grid of cells a little larger than the radius ---------------------------------
@@ -330,9 +397,13 @@ __global__ __launch_bounds__(64) void boot_fpfh_kernel(const BootCloudJob* jobs,
 constexpr int kKnnTile = 64;
 // (job = pair: n source features sf, nt target features tf -> out[n][k]).  A feature row is NaN in all 33 bins or in none
 // (boot_fpfh_kernel), so the source's test of every bin and the target's of bin 0 are one rule: "has a feature".
+// LAB: the label form -- the tile carries the target keypoints' labels beside ok[], and a row of another label than the
+// source keypoint's is passed over like a row without a feature.
+template <bool LAB>
 __global__ __launch_bounds__(256) void boot_feature_knn_kernel(const BootPairJob* jobs, const int* blk_end, int nj, int k) {
   __shared__ float tile[kKnnTile][33];
   __shared__ int ok[kKnnTile];
+  __shared__ unsigned tlab[LAB ? kKnnTile : 1];
   int lb;
   const BootPairJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &lb)];
   const int ns = J.n, nt = J.nt;
@@ -341,6 +412,8 @@ __global__ __launch_bounds__(256) void boot_feature_knn_kernel(const BootPairJob
   const int i = lb * 256 + threadIdx.x;
   float qf[33];
   bool qvalid = false;
+  unsigned ql = 0;
+  if (LAB && i < ns) ql = J.sl[i];
   if (i < ns) {
     qvalid = true;
 #pragma unroll
@@ -360,11 +433,13 @@ __global__ __launch_bounds__(256) void boot_feature_knn_kernel(const BootPairJob
       tile[r][c] = t0 + r < nt ? tf[(size_t)(t0 + r) * 33 + c] : 0.f;
     }
     if (threadIdx.x < kKnnTile) ok[threadIdx.x] = t0 + (int)threadIdx.x < nt && !isnan(tf[(size_t)(t0 + threadIdx.x) * 33]);
+    if (LAB && threadIdx.x < kKnnTile) tlab[threadIdx.x] = t0 + (int)threadIdx.x < nt ? J.tl[t0 + threadIdx.x] : 0u;
     __syncthreads();
     const int cnt = nt - t0 < kKnnTile ? nt - t0 : kKnnTile;
     if (!qvalid) continue;
     for (int r = 0; r < cnt; ++r) {
       if (!ok[r]) continue;
+      if (LAB && tlab[r] != ql) continue;
       float d = 0.f;
 #pragma unroll
       for (int b = 0; b < 33; ++b) { const float df = qf[b] - tile[r][b]; d = d + df * df; }
@@ -390,6 +465,10 @@ __global__ __launch_bounds__(256) void boot_feature_knn_kernel(const BootPairJob
 
 // ---- truncated error of every hypothesis: one workgroup each, fixed-shape f64 sum of (e <= t ? e / t : 1) ------------
 // (job = the hypotheses of one pair in a chunk, block = hypothesis: n hypotheses of nt squared distances each, d2 -> err)
+// LAB: the label form -- a distance within t counts as e / t only when the neighbour the search found (nbr: its index in the
+// target tree's device order, as the search writes it; rows in the source tree's device order) has the source keypoint's
+// label, and as 1 otherwise.
+template <bool LAB>
 __global__ __launch_bounds__(256) void boot_error_kernel(const BootPairJob* jobs, const int* blk_end, int nj, double t) {
   __shared__ double s[256];
   int h;
@@ -400,7 +479,12 @@ __global__ __launch_bounds__(256) void boot_error_kernel(const BootPairJob* jobs
   double a = 0.0;
   for (int q = l; q < nq; q += 256) {
     const double e = (double)d[q];
-    a += e <= t ? e / t : 1.0;
+    bool in = e <= t;
+    if (LAB && in) {
+      const int j = J.nbr[(size_t)h * nq + q];
+      in = j >= 0 && J.tl[j] == J.sl[q];
+    }
+    a += in ? e / t : 1.0;
   }
   s[l] = a;
   __syncthreads();
@@ -428,6 +512,31 @@ hipError_t launch_boot_voxel_keys(int n, const float* x, const float* y, const f
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(boot_voxel_key_kernel, boot_grid(n), dim3(256), 0, st, n, x, y, z, box_max, inv_leaf, min_b[0], min_b[1],
                      min_b[2], dx, dxy, key);
+  return hipGetLastError();
+}
+
+hipError_t launch_boot_bounds_ignore(int n, const float* x, const float* y, const float* z, const unsigned* label, const BootIgnore& ig,
+                                     double box_max, float* blk, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (ig.n < 0 || ig.n > kBootMaxIgnore) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(boot_bounds_ignore_kernel, boot_grid(n), dim3(256), 0, st, n, x, y, z, label, ig, box_max, blk);
+  return hipGetLastError();
+}
+
+hipError_t launch_boot_voxel_keys_ignore(int n, const float* x, const float* y, const float* z, const unsigned* label,
+                                         const BootIgnore& ig, double box_max, float inv_leaf, const int* min_b, int dx, int dxy,
+                                         unsigned long long* key, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (ig.n < 0 || ig.n > kBootMaxIgnore) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(boot_voxel_key_ignore_kernel, boot_grid(n), dim3(256), 0, st, n, x, y, z, label, ig, box_max, inv_leaf,
+                     min_b[0], min_b[1], min_b[2], dx, dxy, key);
+  return hipGetLastError();
+}
+
+hipError_t launch_boot_label_vote(int n_kp, int n_kept, const int* heads, const unsigned long long* key, const unsigned* label,
+                                  unsigned* klabel, hipStream_t st) {
+  if (n_kp <= 0) return hipSuccess;
+  hipLaunchKernelGGL(boot_label_vote_kernel, boot_grid(n_kp, 4), dim3(256), 0, st, n_kp, n_kept, heads, key, label, klabel);
   return hipGetLastError();
 }
 
@@ -507,13 +616,26 @@ hipError_t launch_boot_fpfh_jobs(const BootCloudJob* jobs, const int* pt_end, in
 hipError_t launch_boot_feature_knn_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, hipStream_t st) {
   if (nj <= 0 || blocks <= 0) return hipSuccess;
   if (k < 1 || k > kBootMaxK) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(boot_feature_knn_kernel, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj, k);
+  hipLaunchKernelGGL(boot_feature_knn_kernel<false>, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj, k);
+  return hipGetLastError();
+}
+
+hipError_t launch_boot_feature_knn_label_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, hipStream_t st) {
+  if (nj <= 0 || blocks <= 0) return hipSuccess;
+  if (k < 1 || k > kBootMaxK) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(boot_feature_knn_kernel<true>, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj, k);
   return hipGetLastError();
 }
 
 hipError_t launch_boot_error_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, hipStream_t st) {
   if (nj <= 0 || hypotheses <= 0) return hipSuccess;
-  hipLaunchKernelGGL(boot_error_kernel, dim3(hypotheses), dim3(256), 0, st, jobs, hyp_end, nj, t);
+  hipLaunchKernelGGL(boot_error_kernel<false>, dim3(hypotheses), dim3(256), 0, st, jobs, hyp_end, nj, t);
+  return hipGetLastError();
+}
+
+hipError_t launch_boot_error_label_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, hipStream_t st) {
+  if (nj <= 0 || hypotheses <= 0) return hipSuccess;
+  hipLaunchKernelGGL(boot_error_kernel<true>, dim3(hypotheses), dim3(256), 0, st, jobs, hyp_end, nj, t);
   return hipGetLastError();
 }
 

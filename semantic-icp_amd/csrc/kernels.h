@@ -499,6 +499,20 @@ hipError_t launch_boot_bounds(int n, const float* x, const float* y, const float
 // key[i] = voxel index << 32 | i for a kept point, ~0 otherwise
 hipError_t launch_boot_voxel_keys(int n, const float* x, const float* y, const float* z, double box_max, float inv_leaf,
                                   const int* min_b, int dx, int dxy, unsigned long long* key, hipStream_t st);
+// the label forms (sicp_bootstrap_semantic): a point whose label is in the ignore list is dropped with the box filter
+constexpr int kBootMaxIgnore = 64;
+struct BootIgnore {  // a kernel argument: n <= kBootMaxIgnore labels
+  int n;
+  unsigned v[kBootMaxIgnore];
+};
+hipError_t launch_boot_bounds_ignore(int n, const float* x, const float* y, const float* z, const unsigned* label, const BootIgnore& ig,
+                                     double box_max, float* blk, hipStream_t st);
+hipError_t launch_boot_voxel_keys_ignore(int n, const float* x, const float* y, const float* z, const unsigned* label,
+                                         const BootIgnore& ig, double box_max, float inv_leaf, const int* min_b, int dx, int dxy,
+                                         unsigned long long* key, hipStream_t st);
+// klabel[k] = the most frequent label among voxel k's points (its range of the sorted keys), ties to the smallest label
+hipError_t launch_boot_label_vote(int n_kp, int n_kept, const int* heads, const unsigned long long* key, const unsigned* label,
+                                  unsigned* klabel, hipStream_t st);
 hipError_t boot_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, int n, hipStream_t st);
 hipError_t boot_sort_pairs(void* temp, size_t& bytes, const unsigned long long* kin, unsigned long long* kout, const int* vin,
                            int* vout, int n, hipStream_t st);
@@ -542,6 +556,10 @@ struct BootPairJob {
   int* out;              // k-NN: [n][k]
   const float* d2;       // error: [n][nt]
   double* err;           // error: [n]
+  // the label forms only (keypoint labels):
+  const unsigned *sl, *tl;  // k-NN: of the source / target keypoints, keypoint order;  error: in the order of the search's
+                            // rows (sl: the source tree's device order) and of its neighbour indices (tl: the target tree's)
+  const int* nbr;           // error: [n][nt] the search's neighbour index of every squared distance (-1: none)
 };
 // radius neighbourhoods on a uniform grid: cell keys + point ids (to be sorted by key), then count (fill = 0: count[i]) or
 // write the unsorted lists of (d^2 bits << 32 | index) at loff[i] (fill = 1); split: sorted lists -> index / d^2 arrays
@@ -554,8 +572,12 @@ hipError_t launch_boot_normal_jobs(const BootCloudJob* jobs, const int* blk_end,
 hipError_t launch_boot_fpfh_jobs(const BootCloudJob* jobs, const int* pt_end, int nj, int points, hipStream_t st);
 // out[n][k]: the k nearest target features of every source feature (-1: none / no feature)
 hipError_t launch_boot_feature_knn_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, hipStream_t st);
+// the same among the target keypoints with the source keypoint's label (sl / tl)
+hipError_t launch_boot_feature_knn_label_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, hipStream_t st);
 // err[h] = sum over the nt squared distances d2[h][.] of (e <= t ? e / t : 1); hyp_end: prefix of the hypothesis counts
 hipError_t launch_boot_error_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, hipStream_t st);
+// the same, where a distance counts as e / t only when the neighbour found has the source keypoint's label (sl / tl / nbr)
+hipError_t launch_boot_error_label_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, hipStream_t st);
 
 }  // namespace sicp
 #endif

@@ -979,4 +979,45 @@ int sicp_bootstrap_score(sicp_handle h, const sicp_bootstrap_params* p, int32_t 
   });
 }
 
+// ---- the label forms of the initial alignment (bootstrap.cpp) -------------------------------------------------------
+int sicp_default_bootstrap_label_params(sicp_bootstrap_label_params* lp) {
+  return abi_guard([&]() -> int {
+    if (!lp) return SICP_ERR_INVALID_ARGUMENT;
+    bootstrap_default_label_params(lp);
+    return SICP_OK;
+  });
+}
+
+int sicp_bootstrap_semantic(sicp_handle h, const sicp_bootstrap_params* p, const sicp_bootstrap_label_params* lp, double out_qt[7],
+                            sicp_bootstrap_info* info) {
+  return abi_guard(h, [&]() -> int {
+    if (!h) return SICP_ERR_INVALID_ARGUMENT;
+    return bootstrap_semantic_run(h, p, lp, out_qt, info);
+  });
+}
+
+int sicp_bootstrap_semantic_batch(sicp_handle* hs, int32_t n, const sicp_bootstrap_params* p, const sicp_bootstrap_label_params* lp,
+                                  double* out_qt, int32_t* status, sicp_bootstrap_info* infos) {
+  return abi_guard((hs && n > 0) ? hs[0] : nullptr, [&]() -> int {
+    return bootstrap_semantic_batch(hs, n, p, lp, out_qt, status, infos);
+  });
+}
+
+int sicp_bootstrap_semantic_keypoints(sicp_handle h, int which, const sicp_bootstrap_params* p, const sicp_bootstrap_label_params* lp,
+                                      int32_t capacity, int32_t* n_keypoints, float* xyz3, uint32_t* label) {
+  return abi_guard(h, [&]() -> int {
+    if (!h) return SICP_ERR_INVALID_ARGUMENT;
+    return bootstrap_semantic_keypoints(h, which, p, lp, capacity, n_keypoints, xyz3, label);
+  });
+}
+
+int sicp_bootstrap_semantic_score(sicp_handle h, const sicp_bootstrap_params* p, const sicp_bootstrap_label_params* lp, int32_t n,
+                                  const int32_t* src_idx, const int32_t* tgt_idx, double* M12, double* err, int32_t knn_capacity,
+                                  int32_t* feat_knn) {
+  return abi_guard(h, [&]() -> int {
+    if (!h) return SICP_ERR_INVALID_ARGUMENT;
+    return bootstrap_semantic_score(h, p, lp, n, src_idx, tgt_idx, M12, err, knn_capacity, feat_knn);
+  });
+}
+
 }  // extern "C"
