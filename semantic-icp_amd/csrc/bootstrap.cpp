@@ -106,35 +106,21 @@ struct PairWork {
   size_t knn_at = 0, err_at = 0;  // places in the stage buffers
 };
 
-// one launch's job table: the jobs and the inclusive prefix of their block counts, uploaded as one block of device memory.
-// The host copy stays alive with the table (a table lives until its stage synchronises).
+// one launch's job table with its two copies: the device block, and the host bytes (pageable) that stay alive with the
+// table -- a table lives until its stage synchronises.  (Callers skip empty clouds and pairs themselves: a job added with
+// zero blocks would be kept in the table.)
 template <class J>
-struct JobTable {
-  std::vector<J> jobs;
-  std::vector<int> end;
-  int blocks = 0;
+struct BootTable : sicp::JobTable<J> {
   std::vector<unsigned char> host;
   DevBuf<unsigned char> dev;
-  size_t end_at = 0;
-  void add(const J& j, long long nblocks) {
-    if (nblocks <= 0) return;
-    jobs.push_back(j);
-    blocks += (int)nblocks;
-    end.push_back(blocks);
-  }
-  int nj() const { return (int)jobs.size(); }
   hipError_t upload(hipStream_t st) {
-    if (jobs.empty()) return hipSuccess;
-    end_at = (sizeof(J) * jobs.size() + 255) & ~(size_t)255;
-    host.assign(end_at + sizeof(int) * end.size(), 0);
-    std::memcpy(host.data(), jobs.data(), sizeof(J) * jobs.size());
-    std::memcpy(host.data() + end_at, end.data(), sizeof(int) * end.size());
+    if (this->nj() == 0) return hipSuccess;
+    host.resize(this->bytes());
     hipError_t e = dev.reserve(host.size());
     if (e != hipSuccess) return e;
+    this->pack(host.data(), dev.p);
     return hipMemcpyAsync(dev.p, host.data(), host.size(), hipMemcpyHostToDevice, st);
   }
-  const J* d_jobs() const { return reinterpret_cast<const J*>(dev.p); }
-  const int* d_end() const { return reinterpret_cast<const int*>(dev.p + end_at); }
 };
 
 int temp_reserve(sicp_context* h, BootScratch& s, size_t bytes) {
@@ -262,7 +248,8 @@ int voxel_stage(sicp_context* h, const sicp_bootstrap_params& p, const sicp_boot
                 const std::vector<CloudWork*>& W) {
   const hipStream_t st = h->stream;
   const bool ignoring = lp && lp->n_ignore > 0;
-  const sicp::BootIgnore ig = lp ? ignore_of(*lp) : sicp::BootIgnore();
+  const sicp::BootIgnore ig_list = lp ? ignore_of(*lp) : sicp::BootIgnore();
+  const sicp::BootIgnore* ig = ignoring ? &ig_list : nullptr;  // (without a list: the label-blind kernels)
   for (CloudWork* w : W) {
     const Cloud& c = *w->c;
     const int n = c.n;
@@ -282,8 +269,7 @@ int voxel_stage(sicp_context* h, const sicp_bootstrap_params& p, const sicp_boot
     HIPCHECK(hipMemcpyAsync(s.z.p, c.hz.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
     const int nb = boot_bounds_blocks(n);
     HIPCHECK(s.blk.reserve((size_t)nb * 8));
-    if (ignoring) HIPCHECK(launch_boot_bounds_ignore(n, s.x.p, s.y.p, s.z.p, s.lab.p, ig, p.box_max, s.blk.p, st));
-    else HIPCHECK(launch_boot_bounds(n, s.x.p, s.y.p, s.z.p, p.box_max, s.blk.p, st));
+    HIPCHECK(launch_boot_bounds(n, s.x.p, s.y.p, s.z.p, s.lab.p, ig, p.box_max, s.blk.p, st));
     w->blk.assign((size_t)nb * 8, 0.f);
     HIPCHECK(hipMemcpyAsync(w->blk.data(), s.blk.p, sizeof(float) * w->blk.size(), hipMemcpyDeviceToHost, st));
   }
@@ -324,16 +310,13 @@ int voxel_stage(sicp_context* h, const sicp_bootstrap_params& p, const sicp_boot
     w->n_kept = n_kept;
     BootScratch& s = w->s;
     HIPCHECK(s.key.reserve(n)); HIPCHECK(s.key2.reserve(n));
-    if (ignoring)
-      HIPCHECK(launch_boot_voxel_keys_ignore(n, s.x.p, s.y.p, s.z.p, s.lab.p, ig, p.box_max, inv_leaf, min_b, (int)div[0],
-                                             (int)(div[0] * div[1]), s.key.p, st));
-    else
-      HIPCHECK(launch_boot_voxel_keys(n, s.x.p, s.y.p, s.z.p, p.box_max, inv_leaf, min_b, (int)div[0], (int)(div[0] * div[1]), s.key.p, st));
+    HIPCHECK(launch_boot_voxel_keys(n, s.x.p, s.y.p, s.z.p, s.lab.p, ig, p.box_max, inv_leaf, min_b, (int)div[0], (int)(div[0] * div[1]),
+                                    s.key.p, st));
     size_t sort_bytes = 0, scan_bytes = 0;
-    HIPCHECK(boot_sort_keys(nullptr, sort_bytes, s.key.p, s.key2.p, n, st));
-    HIPCHECK(boot_scan_int(nullptr, scan_bytes, s.flag.p, s.pos.p, (int)n_kept, st));
+    HIPCHECK(prim_sort_keys(nullptr, sort_bytes, s.key.p, s.key2.p, n, 0, 64, st));
+    HIPCHECK(prim_scan_int(nullptr, scan_bytes, s.flag.p, s.pos.p, n_kept, st));
     SICPCHECK(temp_reserve(h, s, std::max(sort_bytes, scan_bytes)));
-    HIPCHECK(boot_sort_keys(s.temp.p, sort_bytes, s.key.p, s.key2.p, n, st));
+    HIPCHECK(prim_sort_keys(s.temp.p, sort_bytes, s.key.p, s.key2.p, n, 0, 64, st));
     HIPCHECK(s.flag.reserve(n_kept)); HIPCHECK(s.pos.reserve(n_kept)); HIPCHECK(s.heads.reserve(n_kept)); HIPCHECK(s.nout.reserve(1));
     HIPCHECK(launch_boot_voxel_compact((int)n_kept, s.key2.p, s.flag.p, s.pos.p, s.heads.p, s.nout.p, s.temp.p, scan_bytes, st));
     w->n_kp = 0;
@@ -387,7 +370,7 @@ int radius_stage(sicp_context* h, double r, int normal, const std::vector<CloudW
     j.skey = w->s.key2.p; j.sval = w->s.val2.p;
     return j;
   };
-  JobTable<BootCloudJob> count;
+  BootTable<BootCloudJob> count;
   for (CloudWork* w : L) {
     const int m = w->k.n;
     BootScratch& s = w->s;
@@ -398,10 +381,10 @@ int radius_stage(sicp_context* h, double r, int normal, const std::vector<CloudW
     HIPCHECK(launch_boot_cell_keys(m, w->k.kx.p, w->k.ky.p, w->k.kz.p, inv_cell, s.key.p, s.val.p, st));
     size_t bytes = 0;
     w->scan_bytes = 0;
-    HIPCHECK(boot_sort_pairs(nullptr, bytes, s.key.p, s.key2.p, s.val.p, s.val2.p, m, st));
-    HIPCHECK(boot_scan_ll(nullptr, w->scan_bytes, s.cnt.p, off->p, m + 1, st));
+    HIPCHECK(prim_sort_pairs(nullptr, bytes, s.key.p, s.key2.p, s.val.p, s.val2.p, m, 0, 63, st));
+    HIPCHECK(prim_scan_ll(nullptr, w->scan_bytes, s.cnt.p, off->p, m + 1, st));
     SICPCHECK(temp_reserve(h, s, std::max(bytes, w->scan_bytes)));
-    HIPCHECK(boot_sort_pairs(s.temp.p, bytes, s.key.p, s.key2.p, s.val.p, s.val2.p, m, st));
+    HIPCHECK(prim_sort_pairs(s.temp.p, bytes, s.key.p, s.key2.p, s.val.p, s.val2.p, m, 0, 63, st));
     HIPCHECK(hipMemsetAsync(s.cnt.p + m, 0, sizeof(long long), st));
     BootCloudJob j = job_of(w);
     j.count = s.cnt.p;
@@ -414,14 +397,14 @@ int radius_stage(sicp_context* h, double r, int normal, const std::vector<CloudW
     BootScratch& s = w->s;
     DevBuf<long long>* off; DevBuf<int>* idx; DevBuf<float>* d2;
     lists(w, off, idx, d2);
-    HIPCHECK(boot_scan_ll(s.temp.p, w->scan_bytes, s.cnt.p, off->p, m + 1, st));
+    HIPCHECK(prim_scan_ll(s.temp.p, w->scan_bytes, s.cnt.p, off->p, m + 1, st));
     w->cnt.assign(m, 0);
     w->total = 0;
     HIPCHECK(hipMemcpyAsync(w->cnt.data(), s.cnt.p, sizeof(long long) * m, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(&w->total, off->p + m, sizeof(long long), hipMemcpyDeviceToHost, st));
   }
   HIPCHECK(hipStreamSynchronize(st));
-  JobTable<BootCloudJob> fill;
+  BootTable<BootCloudJob> fill;
   std::vector<CloudWork*> F;
   for (CloudWork* w : L) {
     if (w->total > (long long)INT32_MAX) { w->fail(SICP_ERR_INVALID_ARGUMENT, "the radius neighbourhoods hold more than 2^31 entries"); continue; }
@@ -446,9 +429,9 @@ int radius_stage(sicp_context* h, double r, int normal, const std::vector<CloudW
     DevBuf<long long>* off; DevBuf<int>* idx; DevBuf<float>* d2;
     lists(w, off, idx, d2);
     size_t bytes = 0;
-    HIPCHECK(boot_segmented_sort(nullptr, bytes, s.list.p, s.list2.p, w->total, w->k.n, off->p, st));
+    HIPCHECK(prim_segmented_sort_keys(nullptr, bytes, s.list.p, s.list2.p, w->total, w->k.n, off->p, st));
     SICPCHECK(temp_reserve(h, s, bytes));
-    HIPCHECK(boot_segmented_sort(s.temp.p, bytes, s.list.p, s.list2.p, w->total, w->k.n, off->p, st));
+    HIPCHECK(prim_segmented_sort_keys(s.temp.p, bytes, s.list.p, s.list2.p, w->total, w->k.n, off->p, st));
     HIPCHECK(launch_boot_split(w->total, s.list2.p, idx->p, d2->p, st));
   }
   // (the tables' host copies live until here: the stream is synchronised by the caller's next stage before they go)
@@ -463,7 +446,7 @@ int feature_stage(sicp_context* h, const sicp_bootstrap_params& p, const std::ve
   SICPCHECK(radius_stage(h, p.feature_radius, 0, W));
   const bool own_normal_lists = p.normal_radius != p.feature_radius;
   if (own_normal_lists) SICPCHECK(radius_stage(h, p.normal_radius, 1, W));
-  JobTable<BootCloudJob> nrm, pts;
+  BootTable<BootCloudJob> nrm, pts;
   for (CloudWork* w : W) {
     if (!w->live() || w->k.n <= 0) continue;
     BootCloud& k = w->k;
@@ -504,7 +487,7 @@ int knn_stage(sicp_context* h, const sicp_bootstrap_params& p, const sicp_bootst
   const hipStream_t st = h->stream;
   const int k = p.k_correspondences;
   const bool same_label = lp && lp->match_same_label;
-  JobTable<BootPairJob> tab;
+  BootTable<BootPairJob> tab;
   size_t total = 0;
   std::vector<PairWork*> L;
   for (PairWork* q : P) {
@@ -528,8 +511,7 @@ int knn_stage(sicp_context* h, const sicp_bootstrap_params& p, const sicp_bootst
     tab.add(j, (j.n + 255) / 256);
   }
   HIPCHECK(tab.upload(st));
-  if (same_label) HIPCHECK(launch_boot_feature_knn_label_jobs(tab.d_jobs(), tab.d_end(), tab.nj(), tab.blocks, k, st));
-  else HIPCHECK(launch_boot_feature_knn_jobs(tab.d_jobs(), tab.d_end(), tab.nj(), tab.blocks, k, st));
+  HIPCHECK(launch_boot_feature_knn_jobs(tab.d_jobs(), tab.d_end(), tab.nj(), tab.blocks, k, same_label, st));
   for (PairWork* q : L) HIPCHECK(hipMemcpyAsync(q->knn.data(), dk.p + q->knn_at, sizeof(int) * q->knn.size(), hipMemcpyDeviceToHost, st));
   HIPCHECK(hipStreamSynchronize(st));
   for (PairWork* q : P) {
@@ -650,18 +632,17 @@ int score_stage(sicp_context* h, const sicp_bootstrap_params& p, const sicp_boot
   HIPCHECK(oi.reserve((size_t)cap)); HIPCHECK(od.reserve((size_t)cap)); HIPCHECK(derr.reserve(n_err));
   const float inf = std::numeric_limits<float>::infinity();
   const double t = (double)(float)p.max_corr_distance;
-  std::vector<std::unique_ptr<JobTable<BootPairJob>>> tables;  // (alive until the read-back's synchronisation)
+  std::vector<std::unique_ptr<BootTable<BootPairJob>>> tables;  // (alive until the read-back's synchronisation)
   JobCollector jc;
-  std::unique_ptr<JobTable<BootPairJob>> tab(new JobTable<BootPairJob>);
+  std::unique_ptr<BootTable<BootPairJob>> tab(new BootTable<BootPairJob>);
   long long used = 0;
   auto flush = [&]() -> int {
     if (jc.knn[0].empty()) return SICP_OK;
     HIPCHECK(sicp::launch_bvh_knn_packet_jobs(jc.knn_K[0], jc.knn[0].data(), (int)jc.knn[0].size(), st));
     HIPCHECK(tab->upload(st));
-    if (same_label) HIPCHECK(launch_boot_error_label_jobs(tab->d_jobs(), tab->d_end(), tab->nj(), tab->blocks, t, st));
-    else HIPCHECK(launch_boot_error_jobs(tab->d_jobs(), tab->d_end(), tab->nj(), tab->blocks, t, st));
+    HIPCHECK(launch_boot_error_jobs(tab->d_jobs(), tab->d_end(), tab->nj(), tab->blocks, t, same_label, st));
     tables.push_back(std::move(tab));
-    tab.reset(new JobTable<BootPairJob>);
+    tab.reset(new BootTable<BootPairJob>);
     jc.knn[0].clear();
     used = 0;
     return SICP_OK;

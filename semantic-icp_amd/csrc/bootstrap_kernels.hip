@@ -4,11 +4,9 @@
 // atomics: every sum runs in a fixed order, so every output is run-to-run bit-reproducible.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
-
+#define SICP_HD __host__ __device__
 #include "device_geometry.hpp"
+#include "job_table.hpp"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -22,19 +20,7 @@ __device__ __forceinline__ bool boot_kept(float x, float y, float z, double box_
   return (double)x < box_max && (double)y < box_max && (double)z < box_max;  // signed, bootstrap.h:24-28
 }
 
-// ---- job forms: one launch over every cloud (or pair) of a batch -------------------------------------------------------
-// Job j owns the blocks [blk_end[j - 1], blk_end[j]) of the launch (blk_end: inclusive prefix of the per-job block counts,
-// built on the host); the block's job is found by bisection, *local = its place among the job's blocks.  A block never
-// straddles two jobs, so a job's items see exactly the lone launch's block shapes.
-__device__ __forceinline__ int boot_job_of(const int* blk_end, int nj, int b, int* local) {
-  int lo = 0, hi = nj - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (blk_end[mid] > b) hi = mid; else lo = mid + 1;
-  }
-  *local = b - (lo > 0 ? blk_end[lo - 1] : 0);
-  return lo;
-}
+// (the job forms -- one launch over every cloud or pair of a batch -- find a block's job with job_of: job_table.hpp)
 
 // ---- voxel grid ----------------------------------------------------------------------------------------------------
 // per workgroup: min / max of the kept points and their count -> blk[b * 8 + (lo0 lo1 lo2 hi0 hi1 hi2 count)]
@@ -208,7 +194,7 @@ __device__ __forceinline__ int boot_lower_bound(const u64* a, int n, u64 v) {
 template <int FILL>
 __global__ __launch_bounds__(256) void boot_radius_kernel(const BootCloudJob* jobs, const int* blk_end, int nj) {
   int lb;
-  const BootCloudJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &lb)];
+  const BootCloudJob& J = jobs[job_of(blk_end, nj, blockIdx.x, &lb)];
   const int i = lb * 256 + threadIdx.x, m = J.m;
   if (i >= m) return;
   const float *x = J.x, *y = J.y, *z = J.z;
@@ -248,7 +234,7 @@ __global__ __launch_bounds__(256) void boot_split_kernel(long long total, const 
 // (the lists of the normal radius: noff / nidx)
 __global__ __launch_bounds__(256) void boot_normal_kernel(const BootCloudJob* jobs, const int* blk_end, int nj) {
   int lb;
-  const BootCloudJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &lb)];
+  const BootCloudJob& J = jobs[job_of(blk_end, nj, blockIdx.x, &lb)];
   const int i = lb * 256 + threadIdx.x;
   if (i >= J.m) return;
   const float *x = J.x, *y = J.y, *z = J.z;
@@ -327,7 +313,7 @@ __device__ __forceinline__ int boot_bin(double v) {
 __global__ __launch_bounds__(64) void boot_spfh_kernel(const BootCloudJob* jobs, const int* blk_end, int nj) {
   __shared__ int h[33];
   int p;
-  const BootCloudJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &p)];
+  const BootCloudJob& J = jobs[job_of(blk_end, nj, blockIdx.x, &p)];
   const int t = threadIdx.x;
   const float *x = J.x, *y = J.y, *z = J.z;
   const double* n3 = J.n3;
@@ -362,7 +348,7 @@ __global__ __launch_bounds__(64) void boot_spfh_kernel(const BootCloudJob* jobs,
 __global__ __launch_bounds__(64) void boot_fpfh_kernel(const BootCloudJob* jobs, const int* blk_end, int nj) {
   __shared__ double acc[33];
   int p;
-  const BootCloudJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &p)];
+  const BootCloudJob& J = jobs[job_of(blk_end, nj, blockIdx.x, &p)];
   const int t = threadIdx.x;
   const double* n3 = J.n3;
   const long long* off = J.off;
@@ -405,7 +391,7 @@ __global__ __launch_bounds__(256) void boot_feature_knn_kernel(const BootPairJob
   __shared__ int ok[kKnnTile];
   __shared__ unsigned tlab[LAB ? kKnnTile : 1];
   int lb;
-  const BootPairJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &lb)];
+  const BootPairJob& J = jobs[job_of(blk_end, nj, blockIdx.x, &lb)];
   const int ns = J.n, nt = J.nt;
   const float *sf = J.sf, *tf = J.tf;
   int* out = J.out;
@@ -472,7 +458,7 @@ template <bool LAB>
 __global__ __launch_bounds__(256) void boot_error_kernel(const BootPairJob* jobs, const int* blk_end, int nj, double t) {
   __shared__ double s[256];
   int h;
-  const BootPairJob& J = jobs[boot_job_of(blk_end, nj, blockIdx.x, &h)];
+  const BootPairJob& J = jobs[job_of(blk_end, nj, blockIdx.x, &h)];
   const int l = threadIdx.x, nq = J.nt;
   double* err = J.err;
   const float* d = J.d2 + (size_t)h * nq;
@@ -501,35 +487,27 @@ inline dim3 boot_grid(long long n, int block = 256) { return dim3((unsigned)((n 
 
 int boot_bounds_blocks(int n) { return (n + 255) / 256; }
 
-hipError_t launch_boot_bounds(int n, const float* x, const float* y, const float* z, double box_max, float* blk, hipStream_t st) {
+// (ig == nullptr: the label-blind kernels, as launched before the label forms existed)
+hipError_t launch_boot_bounds(int n, const float* x, const float* y, const float* z, const unsigned* label, const BootIgnore* ig,
+                              double box_max, float* blk, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(boot_bounds_kernel, boot_grid(n), dim3(256), 0, st, n, x, y, z, box_max, blk);
+  if (ig && (ig->n < 0 || ig->n > kBootMaxIgnore)) return hipErrorInvalidValue;
+  if (ig) hipLaunchKernelGGL(boot_bounds_ignore_kernel, boot_grid(n), dim3(256), 0, st, n, x, y, z, label, *ig, box_max, blk);
+  else hipLaunchKernelGGL(boot_bounds_kernel, boot_grid(n), dim3(256), 0, st, n, x, y, z, box_max, blk);
   return hipGetLastError();
 }
 
-hipError_t launch_boot_voxel_keys(int n, const float* x, const float* y, const float* z, double box_max, float inv_leaf,
-                                  const int* min_b, int dx, int dxy, unsigned long long* key, hipStream_t st) {
+hipError_t launch_boot_voxel_keys(int n, const float* x, const float* y, const float* z, const unsigned* label, const BootIgnore* ig,
+                                  double box_max, float inv_leaf, const int* min_b, int dx, int dxy, unsigned long long* key,
+                                  hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(boot_voxel_key_kernel, boot_grid(n), dim3(256), 0, st, n, x, y, z, box_max, inv_leaf, min_b[0], min_b[1],
-                     min_b[2], dx, dxy, key);
-  return hipGetLastError();
-}
-
-hipError_t launch_boot_bounds_ignore(int n, const float* x, const float* y, const float* z, const unsigned* label, const BootIgnore& ig,
-                                     double box_max, float* blk, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  if (ig.n < 0 || ig.n > kBootMaxIgnore) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(boot_bounds_ignore_kernel, boot_grid(n), dim3(256), 0, st, n, x, y, z, label, ig, box_max, blk);
-  return hipGetLastError();
-}
-
-hipError_t launch_boot_voxel_keys_ignore(int n, const float* x, const float* y, const float* z, const unsigned* label,
-                                         const BootIgnore& ig, double box_max, float inv_leaf, const int* min_b, int dx, int dxy,
-                                         unsigned long long* key, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  if (ig.n < 0 || ig.n > kBootMaxIgnore) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(boot_voxel_key_ignore_kernel, boot_grid(n), dim3(256), 0, st, n, x, y, z, label, ig, box_max, inv_leaf,
-                     min_b[0], min_b[1], min_b[2], dx, dxy, key);
+  if (ig && (ig->n < 0 || ig->n > kBootMaxIgnore)) return hipErrorInvalidValue;
+  if (ig)
+    hipLaunchKernelGGL(boot_voxel_key_ignore_kernel, boot_grid(n), dim3(256), 0, st, n, x, y, z, label, *ig, box_max, inv_leaf,
+                       min_b[0], min_b[1], min_b[2], dx, dxy, key);
+  else
+    hipLaunchKernelGGL(boot_voxel_key_kernel, boot_grid(n), dim3(256), 0, st, n, x, y, z, box_max, inv_leaf, min_b[0], min_b[1],
+                       min_b[2], dx, dxy, key);
   return hipGetLastError();
 }
 
@@ -540,34 +518,11 @@ hipError_t launch_boot_label_vote(int n_kp, int n_kept, const int* heads, const 
   return hipGetLastError();
 }
 
-hipError_t boot_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, int n, hipStream_t st) {
-  return rocprim::radix_sort_keys(temp, bytes, in, out, (size_t)(n > 0 ? n : 1), 0, 64, st);
-}
-
-hipError_t boot_sort_pairs(void* temp, size_t& bytes, const unsigned long long* kin, unsigned long long* kout, const int* vin,
-                           int* vout, int n, hipStream_t st) {
-  return rocprim::radix_sort_pairs(temp, bytes, kin, kout, vin, vout, (size_t)(n > 0 ? n : 1), 0, 63, st);
-}
-
-hipError_t boot_scan_int(void* temp, size_t& bytes, const int* in, int* out, int n, hipStream_t st) {
-  return rocprim::exclusive_scan(temp, bytes, in, out, 0, (size_t)(n > 0 ? n : 1), rocprim::plus<int>(), st);
-}
-
-hipError_t boot_scan_ll(void* temp, size_t& bytes, const long long* in, long long* out, int n, hipStream_t st) {
-  return rocprim::exclusive_scan(temp, bytes, in, out, 0ll, (size_t)(n > 0 ? n : 1), rocprim::plus<long long>(), st);
-}
-
-hipError_t boot_segmented_sort(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long total,
-                               int segments, const long long* off, hipStream_t st) {
-  return rocprim::segmented_radix_sort_keys(temp, bytes, in, out, (unsigned)(total > 0 ? total : 1), (unsigned)segments, off,
-                                            off + 1, 0, 64, st);
-}
-
 hipError_t launch_boot_voxel_compact(int n_kept, const unsigned long long* key, int* flag, int* pos, int* heads, int* n_out,
                                      void* temp, size_t temp_bytes, hipStream_t st) {
   if (n_kept <= 0) return hipSuccess;
   hipLaunchKernelGGL(boot_heads_kernel, boot_grid(n_kept), dim3(256), 0, st, n_kept, key, flag);
-  hipError_t e = boot_scan_int(temp, temp_bytes, flag, pos, n_kept, st);
+  hipError_t e = prim_scan_int(temp, temp_bytes, flag, pos, n_kept, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(boot_compact_kernel, boot_grid(n_kept), dim3(256), 0, st, n_kept, flag, pos, heads, n_out);
   return hipGetLastError();
@@ -613,29 +568,20 @@ hipError_t launch_boot_fpfh_jobs(const BootCloudJob* jobs, const int* pt_end, in
   return hipGetLastError();
 }
 
-hipError_t launch_boot_feature_knn_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, hipStream_t st) {
+hipError_t launch_boot_feature_knn_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, bool same_label,
+                                        hipStream_t st) {
   if (nj <= 0 || blocks <= 0) return hipSuccess;
   if (k < 1 || k > kBootMaxK) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(boot_feature_knn_kernel<false>, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj, k);
+  if (same_label) hipLaunchKernelGGL(boot_feature_knn_kernel<true>, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj, k);
+  else hipLaunchKernelGGL(boot_feature_knn_kernel<false>, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj, k);
   return hipGetLastError();
 }
 
-hipError_t launch_boot_feature_knn_label_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, hipStream_t st) {
-  if (nj <= 0 || blocks <= 0) return hipSuccess;
-  if (k < 1 || k > kBootMaxK) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(boot_feature_knn_kernel<true>, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj, k);
-  return hipGetLastError();
-}
-
-hipError_t launch_boot_error_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, hipStream_t st) {
+hipError_t launch_boot_error_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, bool same_label,
+                                  hipStream_t st) {
   if (nj <= 0 || hypotheses <= 0) return hipSuccess;
-  hipLaunchKernelGGL(boot_error_kernel<false>, dim3(hypotheses), dim3(256), 0, st, jobs, hyp_end, nj, t);
-  return hipGetLastError();
-}
-
-hipError_t launch_boot_error_label_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, hipStream_t st) {
-  if (nj <= 0 || hypotheses <= 0) return hipSuccess;
-  hipLaunchKernelGGL(boot_error_kernel<true>, dim3(hypotheses), dim3(256), 0, st, jobs, hyp_end, nj, t);
+  if (same_label) hipLaunchKernelGGL(boot_error_kernel<true>, dim3(hypotheses), dim3(256), 0, st, jobs, hyp_end, nj, t);
+  else hipLaunchKernelGGL(boot_error_kernel<false>, dim3(hypotheses), dim3(256), 0, st, jobs, hyp_end, nj, t);
   return hipGetLastError();
 }
 

@@ -38,6 +38,7 @@
 
 #include "abi_barrier.hpp"
 #include "build_tree.h"
+#include "job_table.hpp"
 #include "kernels.h"
 #include "lm.hpp"
 #include "se3.hpp"
@@ -138,6 +139,19 @@ struct DevArena {
     FreeScope(const FreeScope&) = delete;
     FreeScope& operator=(const FreeScope&) = delete;
   };
+  // The device scratch of a feature call (or of a stream's covariance pass) going back to the arena: `idle` is its owner's
+  // word that every launch that used it has completed -- true only once the stream has been synchronised behind all of
+  // them, false after an error.  Then the frees skip the device-wide wait altogether, as inside a FreeScope (which waits
+  // once); otherwise, or without a device (nothing was reserved), every free waits as usual.  The scope a caller had is
+  // restored.
+  template <class... Bufs>
+  static void release_scratch(int device, bool idle, Bufs&... bufs) {
+    int& scope = scope_device();
+    const int prev = scope;
+    if (idle && device >= 0) scope = device;
+    (bufs.release(), ...);
+    scope = prev;
+  }
   void free(void* p, int device, int slab, size_t cls) {
     if (scope_device() != device) {
       int cur = -1;

@@ -17,8 +17,8 @@ constexpr int kGroupPairs = 256;
 constexpr long long kGroupBlocks = 1ll << 30;
 constexpr size_t kGroupResultBytes = (size_t)64 << 20;
 
-// A sweep's device scratch: it lives for the call, shared by its groups, and goes back to the arena at the end (as
-// pose_cov.cpp's: when every launch that used it has completed the arena's device-wide wait is skipped).
+// A sweep's device scratch: it lives for the call, shared by its groups, and goes back to the arena at the end
+// (DevArena::release_scratch: `idle` once the stream has been synchronised behind the sweep).
 struct EvalScratch {
   DevBuf<unsigned char> args, res;
   DevBuf<double> part_sum;
@@ -26,16 +26,7 @@ struct EvalScratch {
   DevBuf<float> nn_d2;
   int device = -1;
   bool idle = true;
-  EvalScratch() = default;
-  EvalScratch(const EvalScratch&) = delete;
-  EvalScratch& operator=(const EvalScratch&) = delete;
-  ~EvalScratch() {
-    int& scope = DevArena::scope_device();
-    const int prev = scope;
-    if (idle && device >= 0) scope = device;
-    args.release(); res.release(); part_sum.release(); part_cnt.release(); nn_idx.release(); nn_d2.release();
-    scope = prev;
-  }
+  ~EvalScratch() { DevArena::release_scratch(device, idle, args, res, part_sum, part_cnt, nn_idx, nn_d2); }
 };
 
 // the searches add to the handle's counters and timers (run_nn): an evaluation gives them back as they were
@@ -45,8 +36,6 @@ struct StatsKeeper {
   explicit StatsKeeper(sicp_context* ctx) : h(ctx), st(ctx->st) {}
   ~StatsKeeper() { h->st = st; }
 };
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // what a pair must pass before anything is queued for it
 int evaluate_ready(sicp_context* h, bool table) {
@@ -99,9 +88,10 @@ int evaluate_sweep(sicp_context* h, EvalScratch& X, HostBuf<unsigned char>& pin,
   }
   if (blocks_all > kGroupBlocks) return SICP_ERR_INTERNAL;
   const size_t cc = table ? (size_t)C * C : 0;
-  const size_t at_end = up256(sizeof(sicp::EvalJob) * (size_t)n), arg_bytes = at_end + up256(sizeof(int) * (size_t)n);
-  const size_t at_conf = up256(sizeof(sicp::EvalOut) * (size_t)n), res_bytes = at_conf + sizeof(long long) * cc * (size_t)n;
-  HIPCHECK(X.args.reserve(arg_bytes));
+  // the results: a row per pair | the tables; in `pin` they lie behind the job table
+  sicp::ArgBlock res_block;
+  const sicp::ArgBlock::Section s_out = res_block.add<sicp::EvalOut>((size_t)n), s_conf = res_block.add<unsigned long long>(cc * (size_t)n);
+  const size_t res_bytes = res_block.bytes();
   HIPCHECK(X.res.reserve(res_bytes));
   HIPCHECK(X.part_sum.reserve(std::max<size_t>(chunks_all, 1)));
   HIPCHECK(X.part_cnt.reserve(std::max<size_t>(chunks_all, 1) * 4));
@@ -109,21 +99,18 @@ int evaluate_sweep(sicp_context* h, EvalScratch& X, HostBuf<unsigned char>& pin,
     HIPCHECK(X.nn_idx.reserve((size_t)std::max(hs[0]->cloud(0).n, 1)));
     HIPCHECK(X.nn_d2.reserve((size_t)std::max(hs[0]->cloud(0).n, 1)));
   }
-  HIPCHECK(pin.resize(arg_bytes + res_bytes));
-  std::memset(pin.data(), 0, arg_bytes);
-  sicp::EvalJob* jobs = reinterpret_cast<sicp::EvalJob*>(pin.data());
-  int* blk_end = reinterpret_cast<int*>(pin.data() + at_end);
-  sicp::EvalOut* d_out = reinterpret_cast<sicp::EvalOut*>(X.res.p);
-  unsigned long long* d_conf = reinterpret_cast<unsigned long long*>(X.res.p + at_conf);
+  sicp::EvalOut* d_out = sicp::ArgBlock::dev<sicp::EvalOut>(s_out, X.res.p);
+  unsigned long long* d_conf = sicp::ArgBlock::dev<unsigned long long>(s_conf, X.res.p);
   X.device = h->device;
   X.idle = false;
+  sicp::JobTable<sicp::EvalJob> tab;  // (a pair without source points keeps its row: the finalize goes by position)
   size_t chunk_off = 0;
-  int blocks = 0;
   for (int k = 0; k < n; ++k) {
     sicp_context* g = hs[k];
     const Cloud &S = g->cloud(0), &T = g->cloud(1);
     const bool labels = S.has_label && T.has_label;
-    sicp::EvalJob& J = jobs[k];
+    sicp::EvalJob J;
+    std::memset(&J, 0, sizeof J);
     J.n_s = S.n; J.n_seg = T.n_seg();
     J.idx = g->ev_idx.p; J.d2 = g->ev_d2.p;
     J.slabel = labels ? S.label.p : nullptr; J.tlabel = labels ? T.label.p : nullptr;
@@ -137,18 +124,20 @@ int evaluate_sweep(sicp_context* h, EvalScratch& X, HostBuf<unsigned char>& pin,
     J.part_cnt = X.part_cnt.p + chunk_off * 4;
     J.out = d_out + k;
     chunk_off += (size_t)sicp::eval_chunks(S.n);
-    blocks += sicp::eval_blocks(S.n);
-    blk_end[k] = blocks;
+    tab.add(J, sicp::eval_blocks(S.n));
   }
+  const size_t arg_bytes = tab.bytes();
+  HIPCHECK(X.args.reserve(arg_bytes));
+  HIPCHECK(pin.resize(arg_bytes + res_bytes));
+  tab.pack(pin.data(), X.args.p);
   HIPCHECK(hipMemcpyAsync(X.args.p, pin.data(), arg_bytes, hipMemcpyHostToDevice, st));
   if (cc) HIPCHECK(hipMemsetAsync(d_conf, 0, sizeof(long long) * cc * (size_t)n, st));
-  HIPCHECK(sicp::launch_evaluate_jobs(reinterpret_cast<const sicp::EvalJob*>(X.args.p), reinterpret_cast<const int*>(X.args.p + at_end), n,
-                                      blocks, st));
-  HIPCHECK(sicp::launch_evaluate_finalize_jobs(reinterpret_cast<const sicp::EvalJob*>(X.args.p), n, st));
+  HIPCHECK(sicp::launch_evaluate_jobs(tab.d_jobs(), tab.d_end(), n, tab.blocks, st));
+  HIPCHECK(sicp::launch_evaluate_finalize_jobs(tab.d_jobs(), n, st));
   unsigned char* res = pin.data() + arg_bytes;
   HIPCHECK(hipMemcpyAsync(res, X.res.p, res_bytes, hipMemcpyDeviceToHost, st));
-  o->out = reinterpret_cast<const sicp::EvalOut*>(res);
-  o->conf = reinterpret_cast<const long long*>(res + at_conf);
+  o->out = sicp::ArgBlock::host<const sicp::EvalOut>(s_out, res);
+  o->conf = sicp::ArgBlock::host<const long long>(s_conf, res);
   return SICP_OK;
 }
 

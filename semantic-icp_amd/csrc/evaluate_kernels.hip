@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #define SICP_HD __host__ __device__
+#include "job_table.hpp"
 #include "kernels.h"
 
 namespace sicp {
@@ -37,17 +38,6 @@ namespace {
 template <class T>
 __device__ __forceinline__ SICP_GLOBAL T* dev(T* p) {
   return (SICP_GLOBAL T*)p;
-}
-
-// the job of workgroup b (blk_end: inclusive prefix of the per-job workgroup counts; a job without workgroups is never found)
-__device__ __forceinline__ int job_of(const int* __restrict__ blk_end, int nj, int b, int* local) {
-  int lo = 0, hi = nj - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (blk_end[mid] > b) hi = mid; else lo = mid + 1;
-  }
-  *local = b - (lo > 0 ? blk_end[lo - 1] : 0);
-  return lo;
 }
 
 __global__ __launch_bounds__(256) void evaluate_jobs_kernel(const EvalJob* __restrict__ jobs, const int* __restrict__ blk_end, int nj) {

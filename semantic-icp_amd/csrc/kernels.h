@@ -1,4 +1,4 @@
-// kernels.h -- argument blocks and launch wrappers of the gfx950 kernels (knn_kernels.hip, feature_kernels.hip, solve_kernels.hip).
+// kernels.h -- argument blocks and launch wrappers of the gfx950 kernels (every *_kernels.hip; the job-table convention: job_table.hpp).
 #ifndef SICP_KERNELS_H_
 #define SICP_KERNELS_H_
 
@@ -375,12 +375,11 @@ struct PoseCovArgs {
 };
 SICP_HD inline int pose_cov_blocks(int items) { return items > 0 ? (items + 255) / 256 : 0; }
 SICP_HD inline int pose_cov_tiles(int total) { return (total + kPoseCovTile - 1) / kPoseCovTile; }
-// Job form: one launch of each kernel over every pair of a group (a lone call is a group of one).  The jobs live in device
-// memory; job j owns the workgroups [blk_end[j - 1], blk_end[j]) of a launch (inclusive prefix of the per-job counts, as in
-// the bootstrap's job launches): pose_cov_blocks(n_s) of the source kernel, pose_cov_blocks(tiles) of the tile and the
-// owner kernel, 43 of the finalize.  A job keeps the column layout and the summation order of a launch of its own -- column
-// = workgroup within the job, the butterfly per wave, the four waves in order, the columns in order -- so its sums have
-// the same bits whatever else the launch holds.
+// Job form (job_table.hpp): one launch of each kernel over every pair of a group (a lone call is a group of one).  A job's
+// workgroups: pose_cov_blocks(n_s) of the source kernel, pose_cov_blocks(tiles) of the tile and the owner kernel, 43 of the
+// finalize (which indexes the jobs by position).  A job keeps the column layout and the summation order of a launch of
+// its own -- column = workgroup within the job, the butterfly per wave, the four waves in order, the columns in order -- so
+// its sums have the same bits whatever else the launch holds.
 // The keys of all jobs are sorted at once: key = job << (tgt_bits + slot_bits) | target << slot_bits | slot, target = n_t for a
 // gated-out slot (last within its job), the three widths those of the group's largest job.  Job j's keys occupy
 // [off_j, off_j + n_s K) of the key array before and after the sort, so a tile never spans two jobs.
@@ -396,9 +395,7 @@ struct PoseCovJob {
   int n_t, slot_bits, tgt_bits, pad_;
 };
 hipError_t launch_pose_cov_src_jobs(const PoseCovJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st);
-// ascending radix sort of bits [0, end_bit) (rocPRIM's convention: temp == nullptr asks for the bytes)
-hipError_t pose_cov_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long n, int end_bit,
-                              hipStream_t st);
+// (between the two: prim_sort_keys of the group's keys, bits [0, end_bit))
 hipError_t launch_pose_cov_tile_jobs(const PoseCovJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st);
 hipError_t launch_pose_cov_owner_jobs(const PoseCovJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st);
 // fixed-order sums of the partial columns -> out42, active of every job
@@ -407,8 +404,8 @@ hipError_t launch_pose_cov_finalize_jobs(const PoseCovJob* jobs, int nj, hipStre
 // ---- how well the clouds fit at a pose (evaluate_kernels.hip; driver: evaluate.cpp) ----
 // sicp_evaluate: per source point the nearest target of the whole target cloud (K = 1 searches, one per target segment, their
 // winners merged by (d^2, caller index)), the gate, and over the inliers: counts, the sum of d^2, the label confusion table.
-// Job form, as the pose covariance's: one launch over every pair of a group, job j owns the workgroups [blk_end[j - 1],
-// blk_end[j]) and indexes everything from its own origin, so a pair has the bits of its lone call in any group.
+// Job form (job_table.hpp): one launch over every pair of a group, eval_blocks(n_s) workgroups per job; the finalize indexes
+// the jobs by position.
 constexpr int kEvalChunk = 256;         // queries per partial sum: fixed, whatever the launch looks like
 constexpr int kEvalChunksPerBlock = 8;  // consecutive chunks one workgroup walks (what its LDS table collects before it is flushed)
 constexpr int kEvalLdsClasses = 64;     // confusion tables up to 64 x 64 are privatised in LDS (16 KB of 32-bit counts)
@@ -440,8 +437,7 @@ hipError_t launch_evaluate_finalize_jobs(const EvalJob* jobs, int nj, hipStream_
 // ---- posed clouds into one voxel-grid cloud (merge_kernels.hip; driver: merge.cpp) ----
 // sicp_merge_clouds: every finite point of every part, transformed as the search transforms its queries, cropped, keyed by
 // its voxel of an absolute grid, sorted (stable: the global indices ascend inside a voxel), and reduced per voxel in that
-// order.  All parts go through ONE key launch: part j owns the workgroups [blk_end[j - 1], blk_end[j]) (blk_end: inclusive
-// prefix of the parts' workgroup counts), so a workgroup never straddles two parts.
+// order.  All parts go through ONE key launch: the parts are its jobs (job_table.hpp), 256 points per workgroup.
 constexpr int kMergeBias = 1 << 20;  // |voxel coordinate| < 2^20: three biased 21-bit fields, z highest, bit 63 clear
 struct MergePart {
   const float *x, *y, *z;  // the part's finite points in caller order (Cloud::rx ...)
@@ -480,54 +476,40 @@ struct MergeReduceArgs {
   int* res;
 };
 hipError_t launch_merge_keys(const MergeKeyArgs& a, int blocks, hipStream_t st);
-// rocPRIM's convention: temp == nullptr asks for the bytes.  Keys: bits [begin_bit, 64).
-hipError_t merge_sort_pairs(void* temp, size_t& bytes, const unsigned long long* kin, unsigned long long* kout, const int* vin,
-                            int* vout, int n, int begin_bit, hipStream_t st);
-hipError_t merge_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, int n, hipStream_t st);
-hipError_t merge_scan(void* temp, size_t& bytes, const int* in, int* out, int n, hipStream_t st);
+// (the sorts and the scan between them: prim_kernels.hip)
 hipError_t launch_merge_heads(const MergeReduceArgs& a, hipStream_t st);    // flag
 hipError_t launch_merge_gather(const MergeReduceArgs& a, hipStream_t st);   // heads, res[kept, out], gx gy gz, lkey
 hipError_t launch_merge_centroids(const MergeReduceArgs& a, hipStream_t st);  // ox oy oz, ocount, res[max count]
 hipError_t launch_merge_labels(const MergeReduceArgs& a, hipStream_t st);   // olabel
 
 // ---- initial alignment without a pose prior (bootstrap_kernels.hip; driver: bootstrap.cpp) ----
-// The sort / scan wrappers follow rocPRIM's convention: temp == nullptr asks for the bytes.
 constexpr int kBootMaxK = 16;  // feature neighbours per source keypoint (k_correspondences)
 int boot_bounds_blocks(int n);
-// per workgroup of 256 points: min xyz, max xyz and count of the box-filtered points -> blk[block * 8 + 0..6]
-hipError_t launch_boot_bounds(int n, const float* x, const float* y, const float* z, double box_max, float* blk, hipStream_t st);
-// key[i] = voxel index << 32 | i for a kept point, ~0 otherwise
-hipError_t launch_boot_voxel_keys(int n, const float* x, const float* y, const float* z, double box_max, float inv_leaf,
-                                  const int* min_b, int dx, int dxy, unsigned long long* key, hipStream_t st);
 // the label forms (sicp_bootstrap_semantic): a point whose label is in the ignore list is dropped with the box filter
 constexpr int kBootMaxIgnore = 64;
 struct BootIgnore {  // a kernel argument: n <= kBootMaxIgnore labels
   int n;
   unsigned v[kBootMaxIgnore];
 };
-hipError_t launch_boot_bounds_ignore(int n, const float* x, const float* y, const float* z, const unsigned* label, const BootIgnore& ig,
-                                     double box_max, float* blk, hipStream_t st);
-hipError_t launch_boot_voxel_keys_ignore(int n, const float* x, const float* y, const float* z, const unsigned* label,
-                                         const BootIgnore& ig, double box_max, float inv_leaf, const int* min_b, int dx, int dxy,
-                                         unsigned long long* key, hipStream_t st);
+// Both take the label form as arguments: ig == nullptr launches the label-blind kernel (label is not read), otherwise the
+// kernel that also drops the points whose label[i] is in *ig.
+// per workgroup of 256 points: min xyz, max xyz and count of the box-filtered points -> blk[block * 8 + 0..6]
+hipError_t launch_boot_bounds(int n, const float* x, const float* y, const float* z, const unsigned* label, const BootIgnore* ig,
+                              double box_max, float* blk, hipStream_t st);
+// key[i] = voxel index << 32 | i for a kept point, ~0 otherwise
+hipError_t launch_boot_voxel_keys(int n, const float* x, const float* y, const float* z, const unsigned* label, const BootIgnore* ig,
+                                  double box_max, float inv_leaf, const int* min_b, int dx, int dxy, unsigned long long* key,
+                                  hipStream_t st);
 // klabel[k] = the most frequent label among voxel k's points (its range of the sorted keys), ties to the smallest label
 hipError_t launch_boot_label_vote(int n_kp, int n_kept, const int* heads, const unsigned long long* key, const unsigned* label,
                                   unsigned* klabel, hipStream_t st);
-hipError_t boot_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, int n, hipStream_t st);
-hipError_t boot_sort_pairs(void* temp, size_t& bytes, const unsigned long long* kin, unsigned long long* kout, const int* vin,
-                           int* vout, int n, hipStream_t st);
-hipError_t boot_scan_int(void* temp, size_t& bytes, const int* in, int* out, int n, hipStream_t st);
-hipError_t boot_scan_ll(void* temp, size_t& bytes, const long long* in, long long* out, int n, hipStream_t st);
-hipError_t boot_segmented_sort(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long total,
-                               int segments, const long long* off, hipStream_t st);
-// sorted voxel keys -> first entry of every voxel (heads[n_out]) and the keypoint count *n_out
+// sorted voxel keys -> first entry of every voxel (heads[n_out]) and the keypoint count *n_out (temp: prim_scan_int's)
 hipError_t launch_boot_voxel_compact(int n_kept, const unsigned long long* key, int* flag, int* pos, int* heads, int* n_out,
                                      void* temp, size_t temp_bytes, hipStream_t st);
 hipError_t launch_boot_centroids(int n_kp, int n_kept, const int* heads, const unsigned long long* key, const float* x,
                                  const float* y, const float* z, float* kx, float* ky, float* kz, hipStream_t st);
-// Job forms (one launch over every cloud or pair of a bootstrap batch): the jobs live in device memory, and job j owns the
-// blocks [blk_end[j - 1], blk_end[j]) of the launch -- blk_end is the inclusive prefix of the per-job block counts, in the
-// unit of the launch (256 items for radius / normals / k-NN, one keypoint for SPFH / FPFH, one hypothesis for the error).
+// Job forms (job_table.hpp; one launch over every cloud or pair of a bootstrap batch).  A workgroup is the unit of the
+// launch: 256 items for radius / normals / k-NN, one keypoint for SPFH / FPFH, one hypothesis for the error.
 // Per item every kernel runs what the lone launch ran, in the same order: a batch gives every job the bits of a batch of one.
 struct BootCloudJob {
   int m, pad_;                  // keypoints
@@ -570,14 +552,27 @@ hipError_t launch_boot_split(long long total, const unsigned long long* list, in
 hipError_t launch_boot_normal_jobs(const BootCloudJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st);
 // SPFH (into spfh) then FPFH; pt_end: prefix of the keypoint counts, points = all keypoints of the launch
 hipError_t launch_boot_fpfh_jobs(const BootCloudJob* jobs, const int* pt_end, int nj, int points, hipStream_t st);
-// out[n][k]: the k nearest target features of every source feature (-1: none / no feature)
-hipError_t launch_boot_feature_knn_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, hipStream_t st);
-// the same among the target keypoints with the source keypoint's label (sl / tl)
-hipError_t launch_boot_feature_knn_label_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, hipStream_t st);
-// err[h] = sum over the nt squared distances d2[h][.] of (e <= t ? e / t : 1); hyp_end: prefix of the hypothesis counts
-hipError_t launch_boot_error_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, hipStream_t st);
-// the same, where a distance counts as e / t only when the neighbour found has the source keypoint's label (sl / tl / nbr)
-hipError_t launch_boot_error_label_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, hipStream_t st);
+// out[n][k]: the k nearest target features of every source feature (-1: none / no feature); same_label: among the target
+// keypoints with the source keypoint's label (sl / tl)
+hipError_t launch_boot_feature_knn_jobs(const BootPairJob* jobs, const int* blk_end, int nj, int blocks, int k, bool same_label,
+                                        hipStream_t st);
+// err[h] = sum over the nt squared distances d2[h][.] of (e <= t ? e / t : 1); hyp_end: prefix of the hypothesis counts;
+// same_label: a distance counts as e / t only when the neighbour found has the source keypoint's label (sl / tl / nbr)
+hipError_t launch_boot_error_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, bool same_label,
+                                  hipStream_t st);
+
+// ---- the sorts and scans of the feature calls (prim_kernels.hip: the only rocPRIM instantiations besides build_tree.hip) ----
+// rocPRIM's convention: temp == nullptr asks for the bytes.  Ascending, stable; keys: bits [begin_bit, end_bit).
+hipError_t prim_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long n, int begin_bit,
+                          int end_bit, hipStream_t st);
+hipError_t prim_sort_pairs(void* temp, size_t& bytes, const unsigned long long* kin, unsigned long long* kout, const int* vin, int* vout,
+                           long long n, int begin_bit, int end_bit, hipStream_t st);
+// exclusive sums
+hipError_t prim_scan_int(void* temp, size_t& bytes, const int* in, int* out, long long n, hipStream_t st);
+hipError_t prim_scan_ll(void* temp, size_t& bytes, const long long* in, long long* out, long long n, hipStream_t st);
+// all 64 bits of the keys of every segment [off[s], off[s + 1]) on its own
+hipError_t prim_segmented_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long n,
+                                    int segments, const long long* off, hipStream_t st);
 
 }  // namespace sicp
 #endif

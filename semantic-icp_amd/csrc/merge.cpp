@@ -8,8 +8,8 @@ namespace sicp {
 namespace host {
 namespace {
 
-// A call's device scratch: taken from the arena, given back at the end (as evaluate.cpp's: when every launch that used it has
-// completed the arena's device-wide wait is skipped).
+// A call's device scratch: taken from the arena, given back at the end (DevArena::release_scratch: `idle` once the stream
+// has been synchronised behind the call's launches).
 struct MergeScratch {
   DevBuf<unsigned char> args, temp;
   DevBuf<float> tx, ty, tz, gx, gy, gz, ox, oy, oz;
@@ -18,22 +18,11 @@ struct MergeScratch {
   DevBuf<int> val, val2, flag, pos, heads, res;
   int device = -1;
   bool idle = true;
-  MergeScratch() = default;
-  MergeScratch(const MergeScratch&) = delete;
-  MergeScratch& operator=(const MergeScratch&) = delete;
   ~MergeScratch() {
-    int& scope = DevArena::scope_device();
-    const int prev = scope;
-    if (idle && device >= 0) scope = device;
-    args.release(); temp.release();
-    tx.release(); ty.release(); tz.release(); gx.release(); gy.release(); gz.release(); ox.release(); oy.release(); oz.release();
-    tl.release(); ol.release(); oc.release(); key.release(); key2.release();
-    val.release(); val2.release(); flag.release(); pos.release(); heads.release(); res.release();
-    scope = prev;
+    DevArena::release_scratch(device, idle, args, temp, tx, ty, tz, gx, gy, gz, ox, oy, oz, tl, ol, oc, key, key2, val, val2, flag, pos, heads, res);
   }
 };
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 bool slot_ok(int which) { return which == SICP_SOURCE || which == SICP_TARGET; }
 
 // developer aid (SICP_DEBUG + SICP_MERGE_LOG; tools/merge_timing.py reads it): HIP-event times of the stages on stderr
@@ -136,27 +125,26 @@ int merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_parts,
   StageLog log(log_env, st);
   if (n > 0) {
     const size_t m = (size_t)n;
-    const size_t at_end = up256(sizeof(sicp::MergePart) * (size_t)n_parts), arg_bytes = at_end + up256(sizeof(int) * (size_t)n_parts);
-    HIPCHECK(h->mg_stage.resize(arg_bytes + sizeof res));
-    std::memset(h->mg_stage.data(), 0, arg_bytes);
-    sicp::MergePart* tab = reinterpret_cast<sicp::MergePart*>(h->mg_stage.data());
-    int* blk_end = reinterpret_cast<int*>(h->mg_stage.data() + at_end);
+    sicp::JobTable<sicp::MergePart> tab;  // (a part without points stays in it: it owns no workgroup)
     const double ident[7] = {0, 0, 0, 1, 0, 0, 0};
-    int off = 0, blocks = 0;
+    int off = 0;
     for (int i = 0; i < n_parts; ++i) {
       const Cloud& c = parts[i]->cloud(part_which[i]);
-      sicp::MergePart& P = tab[i];
+      sicp::MergePart P;
+      std::memset(&P, 0, sizeof P);
       P.x = c.rx.p; P.y = c.ry.p; P.z = c.rz.p;
       P.label = has_label ? c.rl.p : nullptr;
       matrix34(qt ? qt + 7 * (size_t)i : ident, P.M);
       P.n = c.n; P.off = off;
       off += c.n;
-      blocks += (c.n + 255) / 256;
-      blk_end[i] = blocks;
+      tab.add(P, (c.n + 255) / 256);
     }
+    const size_t arg_bytes = tab.bytes();
+    HIPCHECK(h->mg_stage.resize(arg_bytes + sizeof res));  // behind the table: the counts' read-back
     X.device = h->device;
     X.idle = false;
     HIPCHECK(X.args.reserve(arg_bytes));
+    tab.pack(h->mg_stage.data(), X.args.p);
     HIPCHECK(X.tx.reserve(m)); HIPCHECK(X.ty.reserve(m)); HIPCHECK(X.tz.reserve(m));
     HIPCHECK(X.gx.reserve(m)); HIPCHECK(X.gy.reserve(m)); HIPCHECK(X.gz.reserve(m));
     HIPCHECK(X.ox.reserve(m)); HIPCHECK(X.oy.reserve(m)); HIPCHECK(X.oz.reserve(m));
@@ -168,14 +156,14 @@ int merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_parts,
     HIPCHECK(X.res.reserve(kMergeRes));
     const int begin_bit = voxel ? 0 : 63;  // without a grid the keys are 0 and ~0: one bit decides
     size_t pair_bytes = 0, key_bytes = 0, scan_bytes = 0;
-    HIPCHECK(sicp::merge_sort_pairs(nullptr, pair_bytes, X.key.p, X.key2.p, X.val.p, X.val2.p, n, begin_bit, st));
-    HIPCHECK(sicp::merge_sort_keys(nullptr, key_bytes, X.key.p, X.key2.p, n, st));
-    HIPCHECK(sicp::merge_scan(nullptr, scan_bytes, X.flag.p, X.pos.p, n, st));
+    HIPCHECK(sicp::prim_sort_pairs(nullptr, pair_bytes, X.key.p, X.key2.p, X.val.p, X.val2.p, n, begin_bit, 64, st));
+    HIPCHECK(sicp::prim_sort_keys(nullptr, key_bytes, X.key.p, X.key2.p, n, 0, 64, st));
+    HIPCHECK(sicp::prim_scan_int(nullptr, scan_bytes, X.flag.p, X.pos.p, n, st));
     HIPCHECK(X.temp.reserve(std::max(std::max(pair_bytes, key_bytes), scan_bytes) + 256));
 
     sicp::MergeKeyArgs K;
-    K.parts = reinterpret_cast<const sicp::MergePart*>(X.args.p);
-    K.blk_end = reinterpret_cast<const int*>(X.args.p + at_end);
+    K.parts = tab.d_jobs();
+    K.blk_end = tab.d_end();
     K.n_parts = n_parts;
     K.voxel = voxel ? 1 : 0; K.crop = crop ? 1 : 0;
     K.inv_leaf = voxel ? 1.0f / (float)p->leaf_size : 0.f;
@@ -200,18 +188,18 @@ int merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_parts,
     log.mark("begin");
     HIPCHECK(hipMemcpyAsync(X.args.p, h->mg_stage.data(), arg_bytes, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemsetAsync(X.res.p, 0, sizeof res, st));
-    HIPCHECK(sicp::launch_merge_keys(K, blocks, st));
+    HIPCHECK(sicp::launch_merge_keys(K, tab.blocks, st));
     log.mark("key");
-    HIPCHECK(sicp::merge_sort_pairs(X.temp.p, pair_bytes, X.key.p, X.key2.p, X.val.p, X.val2.p, n, begin_bit, st));
+    HIPCHECK(sicp::prim_sort_pairs(X.temp.p, pair_bytes, X.key.p, X.key2.p, X.val.p, X.val2.p, n, begin_bit, 64, st));
     log.mark("sort");
     HIPCHECK(sicp::launch_merge_heads(R, st));
-    HIPCHECK(sicp::merge_scan(X.temp.p, scan_bytes, X.flag.p, X.pos.p, n, st));
+    HIPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, X.flag.p, X.pos.p, n, st));
     HIPCHECK(sicp::launch_merge_gather(R, st));
     log.mark("compact_gather");
     HIPCHECK(sicp::launch_merge_centroids(R, st));
     log.mark("centroid");
     if (has_label) {
-      if (voxel) HIPCHECK(sicp::merge_sort_keys(X.temp.p, key_bytes, X.key.p, X.key2.p, n, st));
+      if (voxel) HIPCHECK(sicp::prim_sort_keys(X.temp.p, key_bytes, X.key.p, X.key2.p, n, 0, 64, st));
       HIPCHECK(sicp::launch_merge_labels(R, st));
       log.mark("label");
     }

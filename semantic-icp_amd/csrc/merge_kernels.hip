@@ -4,9 +4,8 @@
 // label.  No floating-point atomics: every sum runs in a fixed order, so every output is run-to-run bit-reproducible.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+#define SICP_HD __host__ __device__
+#include "job_table.hpp"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -16,18 +15,6 @@ namespace {
 
 typedef unsigned long long u64;
 constexpr u64 kDropped = ~0ull;
-
-// the part that owns workgroup b (the first whose blk_end exceeds b: parts without points own none), *local = its place
-// among the part's workgroups
-__device__ __forceinline__ int merge_part_of(const int* blk_end, int np, int b, int* local) {
-  int lo = 0, hi = np - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (blk_end[mid] > b) hi = mid; else lo = mid + 1;
-  }
-  *local = b - (lo > 0 ? blk_end[lo - 1] : 0);
-  return lo;
-}
 
 // pcl::transformPointCloud<PointT,double> as the search transforms its queries (knn_kernels.hip: xform_row):
 // (((m0*x + m1*y) + m2*z) + m3) in double, no contraction, then one rounding to float
@@ -45,7 +32,7 @@ __device__ __forceinline__ float merge_xform_row(const double* m, double x, doub
 // coordinate beyond the fields raises res[kMergeRange] (a plain store: every writer stores the same 1).
 __global__ __launch_bounds__(256) void merge_key_kernel(MergeKeyArgs a) {
   int lb;
-  const MergePart& P = a.parts[merge_part_of(a.blk_end, a.n_parts, blockIdx.x, &lb)];
+  const MergePart& P = a.parts[job_of(a.blk_end, a.n_parts, blockIdx.x, &lb)];
   const int i = lb * 256 + threadIdx.x;
   if (i >= P.n) return;
   const int g = P.off + i;
@@ -154,19 +141,6 @@ hipError_t launch_merge_keys(const MergeKeyArgs& a, int blocks, hipStream_t st) 
   if (a.n_parts <= 0 || blocks <= 0) return hipSuccess;
   hipLaunchKernelGGL(merge_key_kernel, dim3(blocks), dim3(256), 0, st, a);
   return hipGetLastError();
-}
-
-hipError_t merge_sort_pairs(void* temp, size_t& bytes, const unsigned long long* kin, unsigned long long* kout, const int* vin,
-                            int* vout, int n, int begin_bit, hipStream_t st) {
-  return rocprim::radix_sort_pairs(temp, bytes, kin, kout, vin, vout, (size_t)(n > 0 ? n : 1), begin_bit, 64, st);
-}
-
-hipError_t merge_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, int n, hipStream_t st) {
-  return rocprim::radix_sort_keys(temp, bytes, in, out, (size_t)(n > 0 ? n : 1), 0, 64, st);
-}
-
-hipError_t merge_scan(void* temp, size_t& bytes, const int* in, int* out, int n, hipStream_t st) {
-  return rocprim::exclusive_scan(temp, bytes, in, out, 0, (size_t)(n > 0 ? n : 1), rocprim::plus<int>(), st);
 }
 
 hipError_t launch_merge_heads(const MergeReduceArgs& a, hipStream_t st) {

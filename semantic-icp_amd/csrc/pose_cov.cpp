@@ -37,9 +37,8 @@ struct GroupBound {
 };
 
 // A sweep's device scratch.  Of a call: it lives for the call, shared by its groups, and goes back to the arena at the end
-// instead of staying with a handle (or with a parked one after sicp_destroy).  Of a stream: it stays with the stream.  When
-// every launch that used it has completed (`idle`: the stream was synchronised behind them) the arena's device-wide wait
-// is skipped, as inside a DevArena::FreeScope; after an error it is not.
+// instead of staying with a handle (or with a parked one after sicp_destroy).  Of a stream: it stays with the stream.
+// (`idle`: DevArena::release_scratch)
 struct PoseCovScratch {
   DevBuf<double> bq, piece, part_src, part_tgt, out;
   DevBuf<unsigned long long> key, key_sorted;
@@ -48,16 +47,8 @@ struct PoseCovScratch {
   DevBuf<unsigned char> sort_temp, args;
   int device = -1;
   bool idle = true;
-  PoseCovScratch() = default;
-  PoseCovScratch(const PoseCovScratch&) = delete;
-  PoseCovScratch& operator=(const PoseCovScratch&) = delete;
   ~PoseCovScratch() {
-    int& scope = DevArena::scope_device();
-    const int prev = scope;
-    if (idle && device >= 0) scope = device;
-    bq.release(); piece.release(); part_src.release(); part_tgt.release(); out.release();
-    key.release(); key_sorted.release(); flag.release(); part_active.release(); sort_temp.release(); args.release();
-    scope = prev;
+    DevArena::release_scratch(device, idle, bq, piece, part_src, part_tgt, out, key, key_sorted, flag, part_active, sort_temp, args);
   }
 };
 
@@ -73,8 +64,6 @@ struct SweepOut {
     r->active = active[pos[i]];
   }
 };
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // The sweep of a group: n pairs (distinct handles, one device, within a GroupBound) whose current correspondences are those
 // at qts[i], complete or queued on `st`.  Everything is queued on `st`, nothing is waited for: the accumulate kernel once per
@@ -115,26 +104,29 @@ int pose_cov_sweep(sicp_context* h, PoseCovScratch& X, HostBuf<unsigned char>& p
   HIPCHECK(X.out.reserve((size_t)n * 71));
   size_t sort_bytes = 0;
   if (slots > 0) {
-    HIPCHECK(sicp::pose_cov_sort_keys(nullptr, sort_bytes, X.key.p, X.key_sorted.p, (long long)slots, end_bit, st));
+    HIPCHECK(sicp::prim_sort_keys(nullptr, sort_bytes, X.key.p, X.key_sorted.p, (long long)slots, 0, end_bit, st));
     HIPCHECK(X.sort_temp.reserve(sort_bytes + 256));
   }
   // the argument block: headers | accumulate arguments | jobs | the two workgroup prefixes; behind it the results
-  const size_t at_batch = up256(sizeof(sicp::BatchHeader) * (size_t)n), at_jobs = at_batch + up256(sizeof(sicp::BatchArgs) * (size_t)n),
-               at_send = at_jobs + up256(sizeof(sicp::PoseCovJob) * (size_t)n), at_tend = at_send + up256(sizeof(int) * (size_t)n),
-               arg_bytes = at_tend + up256(sizeof(int) * (size_t)n), res_bytes = sizeof(double) * 71 * (size_t)n;
+  // (one job array under two prefixes -- the source kernel's workgroups and the tile / owner kernels')
+  typedef sicp::ArgBlock AB;
+  AB block;
+  const AB::Section s_hdr = block.add<sicp::BatchHeader>((size_t)n), s_batch = block.add<sicp::BatchArgs>((size_t)n),
+                    s_jobs = block.add<sicp::PoseCovJob>((size_t)n), s_send = block.add<int>((size_t)n), s_tend = block.add<int>((size_t)n);
+  const size_t arg_bytes = block.bytes(), res_bytes = sizeof(double) * 71 * (size_t)n;
   HIPCHECK(X.args.reserve(arg_bytes));
   HIPCHECK(pin.resize(arg_bytes + res_bytes));
   std::memset(pin.data(), 0, arg_bytes);
-  sicp::BatchHeader* hdr = reinterpret_cast<sicp::BatchHeader*>(pin.data());
-  sicp::BatchArgs* batch = reinterpret_cast<sicp::BatchArgs*>(pin.data() + at_batch);
-  sicp::PoseCovJob* jobs = reinterpret_cast<sicp::PoseCovJob*>(pin.data() + at_jobs);
-  int* src_end = reinterpret_cast<int*>(pin.data() + at_send);
-  int* tgt_end = reinterpret_cast<int*>(pin.data() + at_tend);
-  sicp::BatchHeader* d_hdr = reinterpret_cast<sicp::BatchHeader*>(X.args.p);
-  sicp::BatchArgs* d_batch = reinterpret_cast<sicp::BatchArgs*>(X.args.p + at_batch);
-  const sicp::PoseCovJob* d_jobs = reinterpret_cast<const sicp::PoseCovJob*>(X.args.p + at_jobs);
-  const int* d_src_end = reinterpret_cast<const int*>(X.args.p + at_send);
-  const int* d_tgt_end = reinterpret_cast<const int*>(X.args.p + at_tend);
+  sicp::BatchHeader* hdr = AB::host<sicp::BatchHeader>(s_hdr, pin.data());
+  sicp::BatchArgs* batch = AB::host<sicp::BatchArgs>(s_batch, pin.data());
+  sicp::PoseCovJob* jobs = AB::host<sicp::PoseCovJob>(s_jobs, pin.data());
+  int* src_end = AB::host<int>(s_send, pin.data());
+  int* tgt_end = AB::host<int>(s_tend, pin.data());
+  sicp::BatchHeader* d_hdr = AB::dev<sicp::BatchHeader>(s_hdr, X.args.p);
+  sicp::BatchArgs* d_batch = AB::dev<sicp::BatchArgs>(s_batch, X.args.p);
+  const sicp::PoseCovJob* d_jobs = AB::dev<sicp::PoseCovJob>(s_jobs, X.args.p);
+  const int* d_src_end = AB::dev<int>(s_send, X.args.p);
+  const int* d_tgt_end = AB::dev<int>(s_tend, X.args.p);
   double* d_out28 = X.out.p;
   double* d_out42 = X.out.p + 28 * (size_t)n;
   long long* d_active = reinterpret_cast<long long*>(X.out.p + 70 * (size_t)n);
@@ -190,7 +182,7 @@ int pose_cov_sweep(sicp_context* h, PoseCovScratch& X, HostBuf<unsigned char>& p
   }
   HIPCHECK(sicp::launch_finalize_batch(d_batch, n, d_out28, st));
   HIPCHECK(sicp::launch_pose_cov_src_jobs(d_jobs, d_src_end, n, src_blocks, st));
-  if (slots > 0) HIPCHECK(sicp::pose_cov_sort_keys(X.sort_temp.p, sort_bytes, X.key.p, X.key_sorted.p, (long long)slots, end_bit, st));
+  if (slots > 0) HIPCHECK(sicp::prim_sort_keys(X.sort_temp.p, sort_bytes, X.key.p, X.key_sorted.p, (long long)slots, 0, end_bit, st));
   HIPCHECK(sicp::launch_pose_cov_tile_jobs(d_jobs, d_tgt_end, n, tgt_blocks, st));
   HIPCHECK(sicp::launch_pose_cov_owner_jobs(d_jobs, d_tgt_end, n, tgt_blocks, st));
   HIPCHECK(sicp::launch_pose_cov_finalize_jobs(d_jobs, n, st));

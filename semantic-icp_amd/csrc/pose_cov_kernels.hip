@@ -9,7 +9,7 @@
 //   pose_cov_src_jobs       one lane per source point: its K slots (contiguous) -> G_j in registers, G_j G_j^T into a
 //                           fixed-order column of partials; every active slot's B^q stored once (144 bytes) with its sort
 //                           key job | target | slot
-//   (ONE rocPRIM radix sort of the keys of all jobs, over the bits in use: every target's slots become one run, in slot
+//   (ONE radix sort of the keys of all jobs, over the bits in use: every target's slots become one run, in slot
 //   order, inside the job's own range of the array)
 //   pose_cov_tile_jobs      one lane per tile of kPoseCovTile sorted slots: a run that lies inside the tile is summed and
 //                           squared at once; a run that crosses a tile edge leaves its part as a piece
@@ -24,9 +24,9 @@
 // per slot (the split rule of store-and-sum reductions with skewed destination counts).  Nothing here is GEMM shaped.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #define SICP_HD __host__ __device__
+#include "job_table.hpp"
 #include "kernels.h"
 
 namespace sicp {
@@ -150,18 +150,6 @@ __device__ __forceinline__ void block_sum21(double (&acc)[21], PartPtr part, int
 template <class T>
 __device__ __forceinline__ SICP_GLOBAL T* dev(T* p) {
   return (SICP_GLOBAL T*)p;
-}
-
-// the job of workgroup b (blk_end: inclusive prefix of the per-job workgroup counts), *local = its place among the job's
-// workgroups.  Wave-uniform: the bisection and the job's fields stay in scalar registers.
-__device__ __forceinline__ int job_of(const int* __restrict__ blk_end, int nj, int b, int* local) {
-  int lo = 0, hi = nj - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (blk_end[mid] > b) hi = mid; else lo = mid + 1;
-  }
-  *local = b - (lo > 0 ? blk_end[lo - 1] : 0);
-  return lo;
 }
 
 __global__ __launch_bounds__(256) void pose_cov_src_jobs_kernel(const PoseCovJob* __restrict__ jobs, const int* __restrict__ blk_end, int nj) {
@@ -361,11 +349,6 @@ hipError_t launch_pose_cov_src_jobs(const PoseCovJob* jobs, const int* blk_end, 
   if (nj <= 0 || blocks <= 0) return hipSuccess;
   hipLaunchKernelGGL(pose_cov_src_jobs_kernel, dim3(blocks), dim3(256), 0, st, jobs, blk_end, nj);
   return hipGetLastError();
-}
-
-hipError_t pose_cov_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long n, int end_bit,
-                              hipStream_t st) {
-  return rocprim::radix_sort_keys(temp, bytes, in, out, (size_t)(n > 0 ? n : 1), 0u, (unsigned)end_bit, st);
 }
 
 hipError_t launch_pose_cov_tile_jobs(const PoseCovJob* jobs, const int* blk_end, int nj, int blocks, hipStream_t st) {

@@ -299,3 +299,32 @@ def test_batch_rows_are_their_lone_calls():
     finally:
         for e in es:
             e.close()
+
+
+def test_a_batch_row_without_source_points_owns_no_workgroup():
+    """three pairs in one group, one whose source has no finite point -- a job without workgroups -- at position 0, 1 and 2:
+    every row and table is its lone call's, the empty pair's says so"""
+    src, sl, tgt, tl, qt, gate = cloud("lidar2000")
+    s3, sl3, t3, tl3, qt3, _ = cloud("three_labels")
+    full = [(src, sl, tgt, tl, qt), (s3, sl3, t3, tl3, qt3)]
+    empty = (np.full_like(s3, np.nan), sl3, tgt, tl, qt)
+    for at in range(3):
+        pairs = list(full)
+        pairs.insert(at, empty)
+        es = [_engine(G, a, al, b, bl) for a, al, b, bl, _ in pairs]
+        try:
+            qts = [q for *_, q in pairs]
+            lone = [_lone(e, q, gate, 11) for e, q in zip(es, qts)]
+            assert all(rc == sicp.OK for rc, _, _ in lone)
+            rc, status, out, conf = _batch(es, qts, gate, 11)
+            assert rc == sicp.OK and list(status) == [sicp.OK] * 3
+            for k in range(3):
+                assert out[k] == lone[k][1], (at, k)
+                assert np.array_equal(conf[k], lone[k][2]), (at, k)
+            r = sicp.SicpEvaluateResult.from_buffer_copy(out[at])
+            assert r.n_source == r.inliers == 0 and conf[at].sum() == 0
+            others = [sicp.SicpEvaluateResult.from_buffer_copy(out[k]) for k in range(3) if k != at]
+            assert all(o.inliers > 0 for o in others)
+        finally:
+            for e in es:
+                e.close()

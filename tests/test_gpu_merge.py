@@ -131,6 +131,32 @@ def test_one_cloud_as_two_parts_and_a_shared_cloud():
         e.close()
 
 
+@pytest.mark.parametrize("leaf", [0.25, 0.0], ids=["grid", "leaf0"])
+def test_a_part_without_finite_points_owns_no_workgroup(leaf):
+    """three parts, one of them all NaN -- no device point, no workgroup of the key launch -- as the first, the middle and the
+    last part: byte for byte the merge of the two others, and the restatement's"""
+    scans = [merge_cases.scan(310, 2000), merge_cases.scan(311, 2100)]
+    qts = merge_cases.track(3)
+    nothing = (np.full((700, 3), np.nan, np.float32), np.arange(700, dtype=np.uint32) % 5 + 1)
+    p = sicp.default_merge_params(leaf_size=leaf, crop_center=(0.5, 0, 0), crop_range=8.0)
+    two = _load(scans)
+    try:
+        for at in range(3):
+            keep = [k for k in range(3) if k != at]
+            parts = list(scans)
+            parts.insert(at, nothing)
+            hs = _load(parts)
+            try:
+                out = sicp.merge_clouds(hs, qts, p)
+                _same_out(out, sicp.merge_clouds(two, qts[keep], p))
+                _same(out, merge_ref.merge(parts, qts, leaf, (0.5, 0, 0), 8.0))
+                assert out["info"]["n_in"] == sum(e.cloud_size(w)[1] for e, w in two) and out["info"]["n_out"] > 0
+            finally:
+                _close(hs)
+    finally:
+        _close(two)
+
+
 # ---- dst ----------------------------------------------------------------------------------------------------------------------
 def _align_bits(e, init=IDENT):
     qt, st = e.align(init)
