@@ -581,11 +581,86 @@ int sicp_default_merge_params(sicp_merge_params* p);
  * points in all.  SICP_ERR_NOT_READY: a part's slot holds no cloud (or, on a SICP_MODE_SEMANTIC handle, a cloud that was never
  * uploaded because it has no labels).  No part's cloud, correspondences, features or statistics change, unless it is dst's
  * slot; parts already on the device are not uploaded again.  Bit-reproducible: a stable sort and fixed-order sums, no float
- * atomics.  Streams: merge on handles and pass the arrays to sicp_stream_add_cloud. */
+ * atomics.  Streams: merge on handles and pass the arrays to sicp_stream_add_cloud.  For a map that rolls on from scan to
+ * scan use a sicp_map (below): a merged cloud that goes back in as a part counts every point of it as one observation. */
 int sicp_merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_parts, const double* qt /* n_parts*7, NULL = identities */,
                       const sicp_merge_params* p, sicp_handle dst /* nullable */, int dst_which,
                       int32_t capacity, float* x, float* y, float* z, uint32_t* label, uint32_t* count /* all nullable */,
                       sicp_merge_info* info /* nullable */);
+
+/* ---- a persistent voxel map ---------------------------------------------------
+ * The map of scan-to-map odometry as an object that lives on the device between calls: per occupied voxel of the absolute
+ * grid of the merge above (v = floor(p * (1.0f / (float)leaf_size)), |v| < 2^20) its 63-bit key (three biased 21-bit
+ * coordinates, z highest), the float64 sums of its points, their number, and -- with num_classes > 0 -- a histogram of their
+ * labels 0..num_classes.  Integrating scans 1..n and extracting with the defaults gives the merge of parts 1..n under the same
+ * poses, leaf, centre and range bit for bit in x, y, z, count and label (every label <= num_classes), n_out and
+ * max_voxel_points included: a voxel's sums continue from the stored value with the new points in ascending point index, one
+ * add per point, which is the merge's own order.  Every call is synchronous; a map lives on one device and serves one thread at
+ * a time; a handle on another device is refused.  No float atomics: two maps built by the same calls are byte-identical. */
+typedef struct sicp_map_ctx* sicp_map;
+typedef struct sicp_map_params {
+  double leaf_size;     /* voxel edge, finite and > 0.  default 0.2 */
+  int32_t num_classes;  /* 0..255; 0 (default): the map keeps no labels and the clouds' labels are ignored */
+  int32_t reserved_;
+} sicp_map_params;
+int sicp_default_map_params(sicp_map_params* p);
+int sicp_map_create(int device_id, const sicp_map_params* p, sicp_map* out);
+int sicp_map_destroy(sicp_map m);
+int sicp_map_clear(sicp_map m);  /* no voxels; the buffers stay */
+int sicp_map_size(sicp_map m, int64_t* n_voxels, int64_t* n_points /* either nullable */);
+const char* sicp_map_last_error(sicp_map m);
+
+typedef struct sicp_map_integrate_info {
+  int64_t n_in;            /* finite points of the slot */
+  int64_t n_kept;          /* after the crop: the points added */
+  int32_t n_scan_voxels;   /* voxels the scan touches */
+  int32_t n_new_voxels;    /* ... of which the map did not hold */
+  int64_t n_voxels;        /* the map's voxels after the call */
+  double t_total_ms;       /* host wall clock */
+} sicp_map_integrate_info;
+/* Adds the finite points of slot `which` of h, in caller order whatever the handle's mode and device layout, transformed by qt
+ * and cropped about crop_center with crop_range exactly as steps 2 and 3 of sicp_merge_clouds say (the kernels share the
+ * arithmetic), to their voxels.  The handle is not modified -- cloud, features, correspondences and statistics stay, as with a
+ * merge part; a cloud that is not yet on the device is prepared as a merge part is.  The work is a sort of the SCAN's keys plus
+ * linear passes over the map; the map is never sorted.
+ * SICP_ERR_INVALID_ARGUMENT: a NULL map or handle; `which` outside the two slots; a pose or centre that is not finite; a range
+ * that is negative or NaN; a handle on another device; a cloud without labels into a map with num_classes > 0; a kept point
+ * whose voxel coordinate reaches 2^20 (the text names the leaf size); more than 2^31 - 1 voxels or 2^32 - 1 points in all.
+ * SICP_ERR_BAD_LABEL: a kept point's label above num_classes.  SICP_ERR_NOT_READY: the slot holds no cloud.
+ * SICP_ERR_OUT_OF_MEMORY: the arena refused (sicp_set_memory_limit applies).  After each of these the map is exactly what it
+ * was -- every extract output has the same bytes -- and stays usable, and info is not written.  A scan without a finite or kept
+ * point: SICP_OK, nothing changes. */
+int sicp_map_integrate(sicp_map m, sicp_handle h, int which, const double qt[7] /* NULL = identity */,
+                       const double crop_center[3] /* NULL = 0 0 0 */, double crop_range /* 0 = none */,
+                       sicp_map_integrate_info* info /* nullable */);
+/* Keeps the voxels whose centroid -- (float)(s / count) per axis -- passes step 3's crop test about center with range (> 0;
+ * +inf keeps everything); the survivors' state is unchanged bit for bit.  n_removed (nullable): voxels dropped. */
+int sicp_map_prune(sicp_map m, const double center[3], double range, int64_t* n_removed);
+
+typedef struct sicp_map_extract_params {
+  int32_t min_count;      /* voxels with fewer points are left out.  default 1 */
+  int32_t reserved_;
+  double crop_center[3];  /* default 0 0 0 */
+  double crop_range;      /* 0 = no crop (default); else prune's test on the centroid */
+} sicp_map_extract_params;
+typedef struct sicp_map_extract_info {
+  int64_t n_voxels;          /* of the map */
+  int32_t n_out;             /* voxels selected */
+  int32_t max_voxel_points;  /* largest count among them; 0 when n_out = 0 */
+  int32_t has_label, reserved_;
+  double t_total_ms;
+} sicp_map_extract_info;
+int sicp_default_map_extract_params(sicp_map_extract_params* p);
+/* One point per selected voxel in ascending key, i.e. ascending (vz, vy, vx): the centroid rounded once to float, count[j] the
+ * voxel's count, label[j] its fullest histogram bin (ties to the smallest label; untouched when num_classes = 0), hist
+ * (capacity * (num_classes + 1), refused when num_classes = 0) the row itself.  The map is not modified.  Capacity, dst and info
+ * follow sicp_merge_clouds: info (nullable) is written on success and on the capacity refusal; every array is nullable; a
+ * non-NULL array with capacity < n_out gives SICP_ERR_INVALID_ARGUMENT and nothing else happens; slot dst_which of dst
+ * (nullable) becomes the result exactly as sicp_set_cloud of the arrays would make it, and the result is complete before the
+ * slot lets go of its old cloud; n_out = 0 with a dst gives SICP_ERR_TOO_FEW_POINTS and dst is unchanged. */
+int sicp_map_extract(sicp_map m, const sicp_map_extract_params* p, sicp_handle dst /* nullable */, int dst_which, int32_t capacity,
+                     float* x, float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist,
+                     sicp_map_extract_info* info /* nullable */);
 
 /* test / bench hook: the keypoints of cloud `which` with their normals, FPFH features and feature-radius
  * neighbour lists (CSR: nbr_offsets[n + 1], nbr_idx sorted by (d^2, index)).  Counts are always written; an output

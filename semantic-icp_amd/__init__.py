@@ -238,6 +238,55 @@ class SicpMergeInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
 
 
+class SicpMapParams(C.Structure):
+    """sicp_map_params (include/sicp.h)"""
+    _fields_ = [
+        ("leaf_size", C.c_double),
+        ("num_classes", C.c_int32),
+        ("reserved_", C.c_int32),
+    ]
+
+
+class SicpMapIntegrateInfo(C.Structure):
+    """sicp_map_integrate_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_in", C.c_int64),
+        ("n_kept", C.c_int64),
+        ("n_scan_voxels", C.c_int32),
+        ("n_new_voxels", C.c_int32),
+        ("n_voxels", C.c_int64),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class SicpMapExtractParams(C.Structure):
+    """sicp_map_extract_params (include/sicp.h)"""
+    _fields_ = [
+        ("min_count", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("crop_center", C.c_double * 3),
+        ("crop_range", C.c_double),
+    ]
+
+
+class SicpMapExtractInfo(C.Structure):
+    """sicp_map_extract_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_voxels", C.c_int64),
+        ("n_out", C.c_int32),
+        ("max_voxel_points", C.c_int32),
+        ("has_label", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
+
+
 class SicpError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -283,6 +332,8 @@ def lib():
         _lib.sicp_version.restype = C.c_char_p
         _lib.sicp_stream_last_error.restype = C.c_char_p
         _lib.sicp_stream_last_error.argtypes = [C.c_void_p]
+        _lib.sicp_map_last_error.restype = C.c_char_p
+        _lib.sicp_map_last_error.argtypes = [C.c_void_p]
         for name, args in {
             "sicp_device_count": [C.POINTER(C.c_int)],
             "sicp_create": [C.c_int, C.POINTER(C.c_void_p)],
@@ -350,6 +401,16 @@ def lib():
             "sicp_default_merge_params": [C.POINTER(SicpMergeParams)],
             "sicp_merge_clouds": [C.POINTER(C.c_void_p), _ip, C.c_int32, _dp, C.POINTER(SicpMergeParams), C.c_void_p, C.c_int, C.c_int32,
                                   _fp, _fp, _fp, _up, _up, C.POINTER(SicpMergeInfo)],
+            "sicp_default_map_params": [C.POINTER(SicpMapParams)],
+            "sicp_default_map_extract_params": [C.POINTER(SicpMapExtractParams)],
+            "sicp_map_create": [C.c_int, C.POINTER(SicpMapParams), C.POINTER(C.c_void_p)],
+            "sicp_map_destroy": [C.c_void_p],
+            "sicp_map_clear": [C.c_void_p],
+            "sicp_map_size": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+            "sicp_map_integrate": [C.c_void_p, C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.POINTER(SicpMapIntegrateInfo)],
+            "sicp_map_prune": [C.c_void_p, _dp, C.c_double, C.POINTER(C.c_int64)],
+            "sicp_map_extract": [C.c_void_p, C.POINTER(SicpMapExtractParams), C.c_void_p, C.c_int, C.c_int32, _fp, _fp, _fp, _up, _up, _up,
+                                 C.POINTER(SicpMapExtractInfo)],
         }.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
@@ -433,6 +494,32 @@ def default_merge_params(**overrides) -> SicpMergeParams:
     st = lib().sicp_default_merge_params(C.byref(p))
     if st != OK:
         raise SicpError(st, "sicp_default_merge_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, (C.c_double * 3)(*v) if k == "crop_center" else v)
+    return p
+
+
+def default_map_params(**overrides) -> SicpMapParams:
+    """sicp_default_map_params (leaf 0.2, no labels), with any field overridden by keyword"""
+    p = SicpMapParams()
+    st = lib().sicp_default_map_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_map_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_map_extract_params(**overrides) -> SicpMapExtractParams:
+    """sicp_default_map_extract_params (min_count 1, no crop), with any field overridden by keyword (crop_center: 3 values)"""
+    p = SicpMapExtractParams()
+    st = lib().sicp_default_map_extract_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_map_extract_params")
     for k, v in overrides.items():
         if not hasattr(p, k):
             raise AttributeError(k)
@@ -878,6 +965,100 @@ def merge_clouds(parts, qts=None, params: SicpMergeParams | None = None, dst=Non
         "count": None if cnt is None else cnt[:m].copy(),
         "info": info.as_dict(),
     }
+
+
+class VoxelMap:
+    """sicp_map_*: a voxel map that lives on the device between calls -- per voxel of merge_clouds' grid the float64 sums, the
+    count and (num_classes > 0) the label histogram of every point integrated so far.  integrate() adds an Engine's cloud at a
+    pose; extract() gives the next target, to arrays and / or straight into an Engine's slot."""
+
+    def __init__(self, device: int = 0, params: SicpMapParams | None = None):
+        self._m = C.c_void_p()
+        p = params if params is not None else default_map_params()
+        self.num_classes = int(p.num_classes)
+        st = lib().sicp_map_create(device, C.byref(p), C.byref(self._m))
+        if st != OK:
+            self._m = C.c_void_p()
+            raise SicpError(st, "sicp_map_create")
+
+    def _check(self, st, where):
+        if st != OK:
+            raise SicpError(st, where, lib().sicp_map_last_error(self._m).decode())
+
+    def close(self):
+        if getattr(self, "_m", None) and self._m.value:
+            lib().sicp_map_destroy(self._m)
+            self._m = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def integrate(self, engine: "Engine", which: int = SOURCE, qt=None, crop_center=None, crop_range: float = 0.0):
+        """sicp_map_integrate: the finite points of engine's slot `which`, at pose qt (None: identity), cropped about crop_center
+        (None: the origin) with crop_range (0: no crop), into their voxels.  Returns SicpMapIntegrateInfo.as_dict()."""
+        q = None if qt is None else np.ascontiguousarray(qt, dtype=np.float64).reshape(7)
+        c = None if crop_center is None else np.ascontiguousarray(crop_center, dtype=np.float64).reshape(3)
+        info = SicpMapIntegrateInfo()
+        self._check(lib().sicp_map_integrate(self._m, engine._h, which, _ptr(q, _dp), _ptr(c, _dp), crop_range, C.byref(info)),
+                    "sicp_map_integrate")
+        return info.as_dict()
+
+    def extract(self, min_count: int = 1, crop_center=None, crop_range: float = 0.0, dst: "Engine | None" = None, dst_which: int = TARGET,
+                want_points: bool = True, want_hist: bool = False):
+        """sicp_map_extract: one point per voxel with at least min_count points whose centroid passes the crop, ascending key;
+        with dst that Engine's slot dst_which becomes the result as if it had been handed to set_cloud.  Returns {"xyz", "labels"
+        (None when the map keeps none), "count", "hist" ([n_out, num_classes + 1] with want_hist, else None), "info"}; with
+        want_points=False no arrays are asked for."""
+        p = default_map_extract_params(min_count=min_count, crop_range=crop_range,
+                                       crop_center=(0.0, 0.0, 0.0) if crop_center is None else tuple(crop_center))
+        cap = 0
+        x = y = z = lab = cnt = hist = None
+        if want_points or want_hist:
+            cap = self.size()[0]
+        if want_points:
+            x, y, z = (np.empty(max(cap, 1), dtype=np.float32) for _ in range(3))
+            lab, cnt = (np.empty(max(cap, 1), dtype=np.uint32) for _ in range(2))
+        if want_hist:
+            hist = np.empty((max(cap, 1), self.num_classes + 1), dtype=np.uint32)
+        info = SicpMapExtractInfo()
+        self._check(lib().sicp_map_extract(self._m, C.byref(p), None if dst is None else dst._h, dst_which, cap, _ptr(x, _fp), _ptr(y, _fp),
+                                           _ptr(z, _fp), _ptr(lab, _up), _ptr(cnt, _up), _ptr(hist, _up), C.byref(info)),
+                    "sicp_map_extract")
+        if dst is not None:
+            dst.n[dst_which] = info.n_out
+        m = info.n_out
+        return {
+            "xyz": None if x is None else np.stack([x[:m], y[:m], z[:m]], axis=1),
+            "labels": lab[:m].copy() if (lab is not None and info.has_label) else None,
+            "count": None if cnt is None else cnt[:m].copy(),
+            "hist": None if hist is None else hist[:m].copy(),
+            "info": info.as_dict(),
+        }
+
+    def prune(self, center, range):
+        """sicp_map_prune: drops the voxels whose centroid lies further than `range` from `center`; returns their number"""
+        c = np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+        n = C.c_int64(0)
+        self._check(lib().sicp_map_prune(self._m, _ptr(c, _dp), range, C.byref(n)), "sicp_map_prune")
+        return n.value
+
+    def clear(self):
+        self._check(lib().sicp_map_clear(self._m), "sicp_map_clear")
+
+    def size(self):
+        """(voxels, points)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(lib().sicp_map_size(self._m, C.byref(a), C.byref(b)), "sicp_map_size")
+        return a.value, b.value
 
 
 def accumulate_batch(engines, qts, repeat: int = 1):

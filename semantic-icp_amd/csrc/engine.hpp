@@ -9,6 +9,7 @@
 //   pose_cov.cpp  sicp_pose_covariance: the sweep over a group of pairs, the 6x6 algebra
 //   evaluate.cpp  sicp_evaluate: overlap, inlier RMSE and label agreement at a pose
 //   merge.cpp     sicp_merge_clouds: posed clouds into one voxel-grid cloud
+//   map.cpp       sicp_map_*: the persistent voxel map (integrate, prune, extract)
 //   sicp_api.cpp  the remaining C-ABI entry points
 // Every extern "C" entry runs inside abi_guard (abi_barrier.hpp): no exception crosses the boundary.
 #ifndef SICP_ENGINE_HPP_
@@ -517,6 +518,25 @@ struct sicp_stream_ctx {
   std::thread worker;
 };
 
+// ---- a persistent voxel map (sicp_map_*; map.cpp): the rows of kernels.h's MapRows, sorted by key, in two sets of arena
+// buffers -- a call that changes the map writes the spare set and swaps once nothing can refuse any more
+struct sicp_map_ctx {
+  int device = 0;
+  sicp_map_params params;
+  hipStream_t stream = nullptr;
+  struct Rows {
+    DevBuf<unsigned long long> key;
+    DevBuf<double> sx, sy, sz;
+    DevBuf<uint32_t> cnt, hist;
+  } rows[2];
+  int cur = 0;               // the set that holds the map
+  long long n_voxels = 0;    // <= 2^31 - 1
+  unsigned long long n_points = 0;  // <= 2^32 - 1: no row's count can overflow
+  HostBuf<unsigned char> stage;  // pinned: the counts' read-back
+  HostBuf<uint32_t> out;         // pinned: an extract's result (x | y | z | label | count | hist rows) on its way out
+  std::string last_error;
+};
+
 namespace sicp {
 namespace host {
 
@@ -534,6 +554,13 @@ inline int abi_guard(sicp_stream_ctx* S, Body&& body) noexcept {
     if (!S || !what) return;
     std::lock_guard<std::mutex> lock(S->m);
     S->api_error = std::string("internal: ") + what;
+  });
+}
+
+template <class Body>
+inline int abi_guard(sicp_map_ctx* m, Body&& body) noexcept {
+  return abi_guard_note(static_cast<Body&&>(body), [m](const char* what) {
+    if (m && what) m->last_error = std::string("internal: ") + what;
   });
 }
 
@@ -567,6 +594,34 @@ struct KernelTimer {
     if (hipEventSynchronize(h->ev1) != hipSuccess) return 0.0;
     if (hipEventElapsedTime(&ms, h->ev0, h->ev1) != hipSuccess) return 0.0;
     return (double)ms;
+  }
+};
+
+// developer aid of the feature calls (SICP_DEBUG + SICP_MERGE_LOG / SICP_MAP_LOG; tools/merge_timing.py and tools/map_timing.py
+// read it): HIP-event times of a call's stages on stderr
+struct StageLog {
+  static constexpr int kMax = 12;
+  bool on = false;
+  hipStream_t st = nullptr;
+  hipEvent_t ev[kMax] = {};
+  const char* name[kMax] = {};
+  int n = 0;
+  StageLog(bool enable, hipStream_t stream) : on(enable), st(stream) {}
+  ~StageLog() { for (int i = 0; i < n; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); }
+  void mark(const char* what) {  // the end of stage `what` (the first mark opens the first stage)
+    if (!on || n >= kMax) return;
+    if (hipEventCreate(&ev[n]) != hipSuccess) { on = false; return; }
+    (void)hipEventRecord(ev[n], st);
+    name[n++] = what;
+  }
+  void print(std::string s) {  // `s`: the line's head ("sicp_merge: n_in=... n_out=...")
+    if (!on || n < 2) return;
+    for (int i = 1; i < n; ++i) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, ev[i - 1], ev[i]) != hipSuccess) return;
+      s += std::string(" ") + name[i] + "_ms=" + std::to_string(ms);
+    }
+    std::fprintf(stderr, "%s\n", s.c_str());
   }
 };
 
@@ -786,6 +841,16 @@ void merge_default_params(sicp_merge_params* p);
 int merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_parts, const double* qt, const sicp_merge_params* p,
                  sicp_context* dst, int dst_which, int32_t capacity, float* x, float* y, float* z, uint32_t* label, uint32_t* count,
                  sicp_merge_info* info);
+// sicp_map_* (map.cpp): the persistent voxel map
+void map_default_params(sicp_map_params* p);
+void map_default_extract_params(sicp_map_extract_params* p);
+int map_create(int device_id, const sicp_map_params* p, sicp_map_ctx** out);
+int map_destroy(sicp_map_ctx* m);
+int map_integrate(sicp_map_ctx* m, sicp_context* h, int which, const double* qt, const double* crop_center, double crop_range,
+                  sicp_map_integrate_info* info);
+int map_prune(sicp_map_ctx* m, const double* center, double range, int64_t* n_removed);
+int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
+                float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info);
 
 }  // namespace host
 }  // namespace sicp

@@ -482,6 +482,72 @@ hipError_t launch_merge_gather(const MergeReduceArgs& a, hipStream_t st);   // h
 hipError_t launch_merge_centroids(const MergeReduceArgs& a, hipStream_t st);  // ox oy oz, ocount, res[max count]
 hipError_t launch_merge_labels(const MergeReduceArgs& a, hipStream_t st);   // olabel
 
+// ---- the persistent voxel map (map_kernels.hip; driver: map.cpp) ----
+// sicp_map_*: per occupied voxel of merge's grid one row -- key, f64 sums, count, label histogram -- in arrays sorted by key.
+// An integrate keys and sorts the SCAN (the key arithmetic of voxel_key.hpp, merge's heads and gather launches), finds every
+// scan voxel in the map by binary search, moves the map's rows once into the spare buffers with the new voxels' rows opened
+// between them, and continues every touched row's sums in point order by the one lane that owns it.  The map is never sorted.
+struct MapRows {
+  unsigned long long* key;  // ascending
+  double *sx, *sy, *sz;
+  uint32_t* cnt;
+  uint32_t* hist;           // [rows][stride], nullptr when the map keeps no labels
+};
+// the words of an integrate's read-back; the first two are merge's (launch_merge_gather writes them)
+enum { kMapKept = kMergeKept, kMapScanVoxels = kMergeOut, kMapRange = 2, kMapBadLabel = 3, kMapNew = 4, kMapOut = 5, kMapMaxCount = 6, kMapRes = 8 };
+struct MapKeyArgs {
+  const float *x, *y, *z;   // the scan's finite points in caller order (Cloud::rx ...)
+  const uint32_t* label;    // nullptr when the map keeps no labels
+  double M[12];
+  int n, crop, num_classes;
+  float inv_leaf, cx, cy, cz;
+  double range_sq;
+  float *tx, *ty, *tz;      // [n] transformed points
+  unsigned long long* key;  // [n] voxel key, ~0 for a dropped point
+  int* val;                 // [n] point index
+  int* res;                 // kMapRes words, zeroed before the launch
+};
+struct MapFoldArgs {
+  int n;                           // scan points: the bound of its voxels (their number is res[kMapScanVoxels])
+  int n_map, n_new;                // rows before the call; rows it opens (known after the first read-back)
+  int stride;                      // num_classes + 1; 0 without labels
+  const unsigned long long* skey;  // the scan's sorted keys
+  const int* heads;                // first sorted position of every scan voxel
+  const float *gx, *gy, *gz;       // the transformed points in sorted order
+  const unsigned long long* lkey;  // low word: the label in sorted order
+  int *rank, *miss, *mpos;         // [n] per scan voxel: lower bound among the map's keys; 1 when absent; exclusive scan of that
+  unsigned long long* miss_key;    // [n_new] the absent keys, ascending
+  int* miss_rank;                  // [n_new] their lower bounds
+  int* src_of;                     // [n_map + n_new] the old row a new row continues, -1 for an opened one
+  int* res;
+  MapRows from, to;
+};
+hipError_t launch_map_keys(const MapKeyArgs& a, hipStream_t st);
+hipError_t launch_map_lookup(const MapFoldArgs& a, hipStream_t st);   // rank, miss
+hipError_t launch_map_misses(const MapFoldArgs& a, hipStream_t st);   // miss_key, miss_rank, res[kMapNew]
+hipError_t launch_map_scatter(const MapFoldArgs& a, hipStream_t st);  // to.{key, sums, cnt}, src_of
+// to[r][*] = src_of[r] >= 0 ? from[src_of[r]][*] : 0 for `rows` histogram rows of `stride` bins
+hipError_t launch_map_move_hist(const uint32_t* from, uint32_t* to, const int* src_of, long long rows, int stride, hipStream_t st);
+hipError_t launch_map_fold(const MapFoldArgs& a, hipStream_t st);     // to.{sums, cnt, hist} of the touched rows
+// prune and extract: a flag per row, its scan (prim_scan_int), a gather
+struct MapSelectArgs {
+  int n_map, stride;
+  long long min_count;
+  int crop;
+  float cx, cy, cz;
+  double range_sq;
+  MapRows rows;
+  int *flag, *pos, *src_of;             // [n_map]
+  MapRows to;                           // prune: the survivors' rows
+  unsigned long long* kept_points;      // prune: the sum of the survivors' counts (zeroed before the launch)
+  float *ox, *oy, *oz;                  // extract: [n_map] centroids, counts, arg-max labels (nullptr without labels)
+  uint32_t *ocount, *olabel;
+  int* res;                             // res[kMapOut]: selected rows; res[kMapMaxCount]: extract's largest count
+};
+hipError_t launch_map_select(const MapSelectArgs& a, hipStream_t st);
+hipError_t launch_map_prune(const MapSelectArgs& a, hipStream_t st);
+hipError_t launch_map_extract(const MapSelectArgs& a, hipStream_t st);
+
 // ---- initial alignment without a pose prior (bootstrap_kernels.hip; driver: bootstrap.cpp) ----
 constexpr int kBootMaxK = 16;  // feature neighbours per source keypoint (k_correspondences)
 int boot_bounds_blocks(int n);

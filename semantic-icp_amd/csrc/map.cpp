@@ -1,0 +1,468 @@
+// map.cpp -- sicp_map_* (include/sicp.h): a voxel map that lives on the device between calls.  Its rows (kernels.h: MapRows)
+// lie sorted by key in one of two sets of arena buffers.  A call that changes the map -- integrate, prune -- computes into the
+// spare set and swaps only once the counts and flags have been read back clean, so a refused call leaves the map as it was by
+// construction.  The kernels: map_kernels.hip, merge's heads and gather launches, the rocPRIM wrappers.
+#include "engine.hpp"
+
+namespace sicp {
+namespace host {
+namespace {
+
+#define MAPCHECK(expr)                                                                         \
+  do {                                                                                         \
+    hipError_t _e = (expr);                                                                    \
+    if (_e != hipSuccess) {                                                                    \
+      m->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);                       \
+      return _e == hipErrorOutOfMemory ? SICP_ERR_OUT_OF_MEMORY : SICP_ERR_HIP;                \
+    }                                                                                          \
+  } while (0)
+
+// A call's device scratch: taken from the arena, given back at the end (`idle`: the stream has been synchronised behind the
+// call's launches).
+struct MapScratch {
+  DevBuf<unsigned char> temp;
+  DevBuf<float> tx, ty, tz, gx, gy, gz, ox, oy, oz;
+  DevBuf<uint32_t> ol, oc, ohist;
+  DevBuf<unsigned long long> key, key2, miss_key, total;
+  DevBuf<int> val, val2, flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res;
+  int device = -1;
+  bool idle = true;
+  ~MapScratch() {
+    DevArena::release_scratch(device, idle, temp, tx, ty, tz, gx, gy, gz, ox, oy, oz, ol, oc, ohist, key, key2, miss_key, total, val, val2,
+                              flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res);
+  }
+};
+
+bool slot_ok(int which) { return which == SICP_SOURCE || which == SICP_TARGET; }
+
+bool log_enabled() {
+  static const bool on = debug_enabled() && std::getenv("SICP_MAP_LOG") != nullptr;
+  return on;
+}
+
+int stride_of(const sicp_map_ctx* m) { return m->params.num_classes > 0 ? m->params.num_classes + 1 : 0; }
+
+sicp::MapRows rows_of(sicp_map_ctx::Rows& r, bool hist) {
+  sicp::MapRows R;
+  R.key = r.key.p; R.sx = r.sx.p; R.sy = r.sy.p; R.sz = r.sz.p; R.cnt = r.cnt.p;
+  R.hist = hist ? r.hist.p : nullptr;
+  return R;
+}
+
+// room for `n` rows in a set (its contents are lost when it grows: only ever the spare set)
+hipError_t reserve_rows(sicp_map_ctx::Rows& r, size_t n, int stride) {
+  hipError_t e = r.key.reserve(n);
+  if (e == hipSuccess) e = r.sx.reserve(n);
+  if (e == hipSuccess) e = r.sy.reserve(n);
+  if (e == hipSuccess) e = r.sz.reserve(n);
+  if (e == hipSuccess) e = r.cnt.reserve(n);
+  if (e == hipSuccess && stride > 0) e = r.hist.reserve(n * (size_t)stride);
+  return e;
+}
+
+// crop arguments shared by the three calls: c = (float)centre, range^2 in double
+struct Crop {
+  int on;
+  float c[3];
+  double range_sq;
+};
+Crop make_crop(const double* center, double range) {
+  Crop k;
+  k.on = range > 0.0 ? 1 : 0;
+  for (int d = 0; d < 3; ++d) k.c[d] = center ? (float)center[d] : 0.f;
+  k.range_sq = range * range;
+  return k;
+}
+
+}  // namespace
+
+void map_default_params(sicp_map_params* p) {
+  std::memset(p, 0, sizeof *p);
+  p->leaf_size = 0.2;
+}
+
+void map_default_extract_params(sicp_map_extract_params* p) {
+  std::memset(p, 0, sizeof *p);
+  p->min_count = 1;
+}
+
+int map_create(int device_id, const sicp_map_params* p, sicp_map_ctx** out) {
+  if (!out) return SICP_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  if (!p || !(p->leaf_size > 0.0) || !std::isfinite(p->leaf_size) || p->num_classes < 0 || p->num_classes > 255) return SICP_ERR_INVALID_ARGUMENT;
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return SICP_ERR_NO_DEVICE;
+  if (device_id < 0 || device_id >= n) return SICP_ERR_INVALID_ARGUMENT;
+  sicp_map_ctx* m = new (std::nothrow) sicp_map_ctx();
+  if (!m) return SICP_ERR_OUT_OF_MEMORY;
+  m->device = device_id;
+  m->params = *p;
+  m->params.reserved_ = 0;
+  if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete m;
+    return SICP_ERR_NO_DEVICE;
+  }
+  *out = m;
+  return SICP_OK;
+}
+
+int map_destroy(sicp_map_ctx* m) {
+  if (!m) return SICP_OK;
+  (void)hipSetDevice(m->device);
+  if (m->stream) {
+    (void)hipStreamSynchronize(m->stream);
+    (void)hipStreamDestroy(m->stream);
+  }
+  {
+    DevArena::FreeScope once(m->device);  // one wait for the device, not one per buffer
+    delete m;
+  }
+  return SICP_OK;
+}
+
+int map_integrate(sicp_map_ctx* m, sicp_context* h, int which, const double* qt, const double* crop_center, double crop_range,
+                  sicp_map_integrate_info* info) {
+  if (!m) return SICP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const std::string& why) {
+    m->last_error = "sicp_map_integrate: " + why + "; the map is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (!h) return refuse("the handle is NULL");
+  if (!slot_ok(which)) return refuse("`which` is neither SICP_SOURCE nor SICP_TARGET");
+  if (h->device != m->device) return refuse("the handle is on device " + std::to_string(h->device) + ", the map on " + std::to_string(m->device));
+  if (!(crop_range >= 0.0)) return refuse("crop_range must be >= 0 (+inf is allowed)");
+  if (crop_center)
+    for (int d = 0; d < 3; ++d)
+      if (!std::isfinite(crop_center[d])) return refuse("crop_center must be finite");
+  if (qt)
+    for (int k = 0; k < 7; ++k)
+      if (!std::isfinite(qt[k])) return refuse("the pose is not finite");
+  Cloud& c = h->cloud(which);
+  if (!c.is_set) {
+    m->last_error = "sicp_map_integrate: the slot has no cloud";
+    return SICP_ERR_NOT_READY;
+  }
+  const int C = m->params.num_classes, stride = stride_of(m);
+  if (C > 0 && !c.has_label) return refuse("the cloud has no labels and the map keeps " + std::to_string(C) + " classes");
+  const double t_begin = now_ms();
+  MAPCHECK(hipSetDevice(m->device));
+  // the scan's device copy: the finite points in caller order (Cloud::rx ..., valid in every layout), prepared as a merge part is
+  if (c.layout < 0) {
+    const int rc = prepare_cloud(h, c);
+    if (rc != SICP_OK) {
+      m->last_error = "sicp_map_integrate: the cloud: " + (h->last_error.empty() ? std::string("not ready") : h->last_error);
+      return rc;
+    }
+  }
+  if (c.pending && c.ready_ev) {  // (the upload runs on the handle's stream, the kernels below on the map's)
+    MAPCHECK(hipEventSynchronize(c.ready_ev));
+    c.pending = false;
+  }
+  const int n = c.n;
+  const int n_map = (int)m->n_voxels;
+  sicp_map_integrate_info I;
+  std::memset(&I, 0, sizeof I);
+  I.n_in = n;
+  I.n_voxels = m->n_voxels;
+  if (n == 0) {
+    I.t_total_ms = now_ms() - t_begin;
+    if (info) *info = I;
+    return SICP_OK;
+  }
+  hipStream_t st = m->stream;
+  StageLog log(log_enabled(), st);
+  MapScratch X;
+  X.device = m->device;
+  X.idle = false;
+  const size_t np = (size_t)n;
+  MAPCHECK(m->stage.resize(sizeof(int) * sicp::kMapRes));
+  MAPCHECK(X.tx.reserve(np)); MAPCHECK(X.ty.reserve(np)); MAPCHECK(X.tz.reserve(np));
+  MAPCHECK(X.gx.reserve(np)); MAPCHECK(X.gy.reserve(np)); MAPCHECK(X.gz.reserve(np));
+  MAPCHECK(X.key.reserve(np)); MAPCHECK(X.key2.reserve(np));
+  MAPCHECK(X.val.reserve(np)); MAPCHECK(X.val2.reserve(np));
+  MAPCHECK(X.flag.reserve(np)); MAPCHECK(X.pos.reserve(np)); MAPCHECK(X.heads.reserve(np));
+  MAPCHECK(X.rank.reserve(np)); MAPCHECK(X.miss.reserve(np)); MAPCHECK(X.mpos.reserve(np));
+  MAPCHECK(X.miss_key.reserve(np)); MAPCHECK(X.miss_rank.reserve(np));
+  MAPCHECK(X.res.reserve(sicp::kMapRes));
+  size_t pair_bytes = 0, scan_bytes = 0;
+  MAPCHECK(sicp::prim_sort_pairs(nullptr, pair_bytes, X.key.p, X.key2.p, X.val.p, X.val2.p, n, 0, 64, st));
+  MAPCHECK(sicp::prim_scan_int(nullptr, scan_bytes, X.flag.p, X.pos.p, n, st));
+  MAPCHECK(X.temp.reserve(std::max(pair_bytes, scan_bytes) + 256));
+
+  const Crop crop = make_crop(crop_center, crop_range);
+  const double ident[7] = {0, 0, 0, 1, 0, 0, 0};
+  sicp::MapKeyArgs K;
+  std::memset(&K, 0, sizeof K);
+  K.x = c.rx.p; K.y = c.ry.p; K.z = c.rz.p;
+  K.label = C > 0 ? c.rl.p : nullptr;
+  matrix34(qt ? qt : ident, K.M);
+  K.n = n; K.crop = crop.on; K.num_classes = C;
+  K.inv_leaf = 1.0f / (float)m->params.leaf_size;
+  K.cx = crop.c[0]; K.cy = crop.c[1]; K.cz = crop.c[2];
+  K.range_sq = crop.range_sq;
+  K.tx = X.tx.p; K.ty = X.ty.p; K.tz = X.tz.p;
+  K.key = X.key.p; K.val = X.val.p; K.res = X.res.p;
+  // the scan's runs of equal keys: merge's heads and gather (the labels ride in the low word of its rank | label keys)
+  sicp::MergeReduceArgs R;
+  std::memset(&R, 0, sizeof R);
+  R.n = n; R.voxel = 1; R.labels = C > 0 ? 1 : 0;
+  R.skey = X.key2.p; R.sval = X.val2.p;
+  R.flag = X.flag.p; R.pos = X.pos.p; R.heads = X.heads.p;
+  R.tx = X.tx.p; R.ty = X.ty.p; R.tz = X.tz.p; R.tlabel = K.label;
+  R.gx = X.gx.p; R.gy = X.gy.p; R.gz = X.gz.p;
+  R.lkey = X.key.p;  // (the unsorted keys are dead once sorted)
+  R.res = X.res.p;
+  sicp_map_ctx::Rows& cur = m->rows[m->cur];
+  sicp_map_ctx::Rows& spare = m->rows[m->cur ^ 1];
+  sicp::MapFoldArgs F;
+  std::memset(&F, 0, sizeof F);
+  F.n = n; F.n_map = n_map; F.n_new = 0; F.stride = stride;
+  F.skey = X.key2.p; F.heads = X.heads.p;
+  F.gx = X.gx.p; F.gy = X.gy.p; F.gz = X.gz.p; F.lkey = X.key.p;
+  F.rank = X.rank.p; F.miss = X.miss.p; F.mpos = X.mpos.p;
+  F.miss_key = X.miss_key.p; F.miss_rank = X.miss_rank.p;
+  F.res = X.res.p;
+  F.from = rows_of(cur, stride > 0);
+
+  log.mark("begin");
+  MAPCHECK(hipMemsetAsync(X.res.p, 0, sizeof(int) * sicp::kMapRes, st));
+  MAPCHECK(sicp::launch_map_keys(K, st));
+  log.mark("key");
+  MAPCHECK(sicp::prim_sort_pairs(X.temp.p, pair_bytes, X.key.p, X.key2.p, X.val.p, X.val2.p, n, 0, 64, st));
+  log.mark("sort");
+  MAPCHECK(sicp::launch_merge_heads(R, st));
+  MAPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, X.flag.p, X.pos.p, n, st));
+  MAPCHECK(sicp::launch_merge_gather(R, st));
+  log.mark("runs");
+  MAPCHECK(sicp::launch_map_lookup(F, st));
+  MAPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, X.miss.p, X.mpos.p, n, st));
+  MAPCHECK(sicp::launch_map_misses(F, st));
+  log.mark("lookup");
+  int res[sicp::kMapRes];
+  MAPCHECK(hipMemcpyAsync(m->stage.data(), X.res.p, sizeof res, hipMemcpyDeviceToHost, st));
+  MAPCHECK(hipStreamSynchronize(st));
+  std::memcpy(res, m->stage.data(), sizeof res);
+  X.idle = true;
+  // every refusal lies before the first write to a row
+  if (res[sicp::kMapRange])
+    return refuse("leaf size " + std::to_string(m->params.leaf_size) + " is too small for the points: a voxel coordinate reaches 2^20");
+  if (res[sicp::kMapBadLabel]) {
+    m->last_error = "sicp_map_integrate: a label above num_classes = " + std::to_string(C) + "; the map is unchanged";
+    return SICP_ERR_BAD_LABEL;
+  }
+  const int n_kept = res[sicp::kMapKept], n_scan_vox = res[sicp::kMapScanVoxels], n_new = res[sicp::kMapNew];
+  I.n_kept = n_kept;
+  I.n_scan_voxels = n_scan_vox;
+  I.n_new_voxels = n_new;
+  if (n_kept == 0) {
+    I.t_total_ms = now_ms() - t_begin;
+    if (info) *info = I;
+    return SICP_OK;
+  }
+  if (m->n_voxels + (long long)n_new > 0x7fffffffll) return refuse("the map would hold more than 2^31 - 1 voxels");
+  if (m->n_points + (unsigned long long)n_kept > 0xffffffffull) return refuse("the map would hold more than 2^32 - 1 points");
+  const size_t rows = (size_t)n_map + (size_t)n_new;
+  X.idle = false;
+  MAPCHECK(reserve_rows(spare, rows, stride));
+  MAPCHECK(X.src_of.reserve(rows));
+  F.n_new = n_new;
+  F.src_of = X.src_of.p;
+  F.to = rows_of(spare, stride > 0);
+  MAPCHECK(sicp::launch_map_scatter(F, st));
+  if (stride > 0) MAPCHECK(sicp::launch_map_move_hist(F.from.hist, F.to.hist, F.src_of, (long long)rows, stride, st));
+  log.mark("scatter");
+  MAPCHECK(sicp::launch_map_fold(F, st));
+  log.mark("fold");
+  MAPCHECK(hipStreamSynchronize(st));
+  X.idle = true;
+  m->cur ^= 1;
+  m->n_voxels = (long long)rows;
+  m->n_points += (unsigned long long)n_kept;
+  I.n_voxels = m->n_voxels;
+  log.print("sicp_map_integrate: n_in=" + std::to_string(n) + " n_map=" + std::to_string(n_map) + " n_new=" + std::to_string(n_new));
+  I.t_total_ms = now_ms() - t_begin;
+  if (info) *info = I;
+  return SICP_OK;
+}
+
+int map_prune(sicp_map_ctx* m, const double* center, double range, int64_t* n_removed) {
+  if (!m) return SICP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const std::string& why) {
+    m->last_error = "sicp_map_prune: " + why + "; the map is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (!center) return refuse("the centre is NULL");
+  for (int d = 0; d < 3; ++d)
+    if (!std::isfinite(center[d])) return refuse("the centre must be finite");
+  if (!(range > 0.0)) return refuse("the range must be > 0 (+inf keeps everything)");
+  if (n_removed) *n_removed = 0;
+  const int n_map = (int)m->n_voxels, stride = stride_of(m);
+  if (n_map == 0) return SICP_OK;
+  MAPCHECK(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  MapScratch X;
+  X.device = m->device;
+  X.idle = false;
+  const size_t nr = (size_t)n_map;
+  sicp_map_ctx::Rows& cur = m->rows[m->cur];
+  sicp_map_ctx::Rows& spare = m->rows[m->cur ^ 1];
+  MAPCHECK(m->stage.resize(sizeof(int) * sicp::kMapRes + sizeof(unsigned long long)));
+  MAPCHECK(reserve_rows(spare, nr, stride));
+  MAPCHECK(X.flag.reserve(nr)); MAPCHECK(X.pos.reserve(nr)); MAPCHECK(X.src_of.reserve(nr));
+  MAPCHECK(X.res.reserve(sicp::kMapRes)); MAPCHECK(X.total.reserve(1));
+  size_t scan_bytes = 0;
+  MAPCHECK(sicp::prim_scan_int(nullptr, scan_bytes, X.flag.p, X.pos.p, n_map, st));
+  MAPCHECK(X.temp.reserve(scan_bytes + 256));
+  const Crop crop = make_crop(center, range);
+  sicp::MapSelectArgs S;
+  std::memset(&S, 0, sizeof S);
+  S.n_map = n_map; S.stride = stride; S.min_count = 0; S.crop = 1;
+  S.cx = crop.c[0]; S.cy = crop.c[1]; S.cz = crop.c[2]; S.range_sq = crop.range_sq;
+  S.rows = rows_of(cur, stride > 0);
+  S.to = rows_of(spare, stride > 0);
+  S.flag = X.flag.p; S.pos = X.pos.p; S.src_of = X.src_of.p;
+  S.kept_points = X.total.p; S.res = X.res.p;
+  MAPCHECK(hipMemsetAsync(X.res.p, 0, sizeof(int) * sicp::kMapRes, st));
+  MAPCHECK(hipMemsetAsync(X.total.p, 0, sizeof(unsigned long long), st));
+  MAPCHECK(sicp::launch_map_select(S, st));
+  MAPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, X.flag.p, X.pos.p, n_map, st));
+  MAPCHECK(sicp::launch_map_prune(S, st));
+  int res[sicp::kMapRes];
+  unsigned long long kept_points = 0;
+  MAPCHECK(hipMemcpyAsync(m->stage.data(), X.res.p, sizeof res, hipMemcpyDeviceToHost, st));
+  MAPCHECK(hipMemcpyAsync(m->stage.data() + sizeof res, X.total.p, sizeof kept_points, hipMemcpyDeviceToHost, st));
+  MAPCHECK(hipStreamSynchronize(st));
+  std::memcpy(res, m->stage.data(), sizeof res);
+  std::memcpy(&kept_points, m->stage.data() + sizeof res, sizeof kept_points);
+  const int n_keep = res[sicp::kMapOut];
+  if (stride > 0 && n_keep > 0) {  // (the rows' places are known: their histograms follow)
+    MAPCHECK(sicp::launch_map_move_hist(S.rows.hist, S.to.hist, S.src_of, n_keep, stride, st));
+    MAPCHECK(hipStreamSynchronize(st));
+  }
+  X.idle = true;
+  m->cur ^= 1;
+  m->n_voxels = n_keep;
+  m->n_points = kept_points;
+  if (n_removed) *n_removed = (int64_t)n_map - n_keep;
+  return SICP_OK;
+}
+
+int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
+                float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info) {
+  if (!m) return SICP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const std::string& why) {
+    m->last_error = "sicp_map_extract: " + why + "; nothing was done";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (!p) return refuse("the params are NULL");
+  if (dst && !slot_ok(dst_which)) return refuse("dst_which is neither SICP_SOURCE nor SICP_TARGET");
+  if (dst && dst->device != m->device) return refuse("dst is on device " + std::to_string(dst->device) + ", the map on " + std::to_string(m->device));
+  if (!(p->crop_range >= 0.0)) return refuse("crop_range must be >= 0 (+inf is allowed)");
+  for (int d = 0; d < 3; ++d)
+    if (!std::isfinite(p->crop_center[d])) return refuse("crop_center must be finite");
+  const int C = m->params.num_classes, stride = stride_of(m);
+  if (hist && C == 0) return refuse("the map keeps no labels: there are no histograms");
+  const double t_begin = now_ms();
+  MAPCHECK(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  StageLog log(log_enabled(), st);
+  const int n_map = (int)m->n_voxels;
+  const size_t nr = (size_t)n_map;
+  int res[sicp::kMapRes] = {};
+  MapScratch X;
+  sicp::MapSelectArgs S;
+  std::memset(&S, 0, sizeof S);
+  if (n_map > 0) {
+    X.device = m->device;
+    X.idle = false;
+    MAPCHECK(m->stage.resize(sizeof res));
+    MAPCHECK(X.flag.reserve(nr)); MAPCHECK(X.pos.reserve(nr)); MAPCHECK(X.src_of.reserve(nr));
+    MAPCHECK(X.ox.reserve(nr)); MAPCHECK(X.oy.reserve(nr)); MAPCHECK(X.oz.reserve(nr)); MAPCHECK(X.oc.reserve(nr));
+    if (C > 0) MAPCHECK(X.ol.reserve(nr));
+    MAPCHECK(X.res.reserve(sicp::kMapRes));
+    size_t scan_bytes = 0;
+    MAPCHECK(sicp::prim_scan_int(nullptr, scan_bytes, X.flag.p, X.pos.p, n_map, st));
+    MAPCHECK(X.temp.reserve(scan_bytes + 256));
+    const Crop crop = make_crop(p->crop_center, p->crop_range);
+    S.n_map = n_map; S.stride = stride; S.min_count = p->min_count; S.crop = crop.on;
+    S.cx = crop.c[0]; S.cy = crop.c[1]; S.cz = crop.c[2]; S.range_sq = crop.range_sq;
+    S.rows = rows_of(m->rows[m->cur], stride > 0);
+    S.flag = X.flag.p; S.pos = X.pos.p; S.src_of = X.src_of.p;
+    S.ox = X.ox.p; S.oy = X.oy.p; S.oz = X.oz.p; S.ocount = X.oc.p;
+    S.olabel = C > 0 ? X.ol.p : nullptr;
+    S.res = X.res.p;
+    log.mark("begin");
+    MAPCHECK(hipMemsetAsync(X.res.p, 0, sizeof res, st));
+    MAPCHECK(sicp::launch_map_select(S, st));
+    MAPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, X.flag.p, X.pos.p, n_map, st));
+    MAPCHECK(sicp::launch_map_extract(S, st));
+    log.mark("select_gather");
+    MAPCHECK(hipMemcpyAsync(m->stage.data(), X.res.p, sizeof res, hipMemcpyDeviceToHost, st));
+    MAPCHECK(hipStreamSynchronize(st));
+    std::memcpy(res, m->stage.data(), sizeof res);
+    X.idle = true;
+  }
+  const int n_out = res[sicp::kMapOut];
+  sicp_map_extract_info I;
+  std::memset(&I, 0, sizeof I);
+  I.n_voxels = m->n_voxels;
+  I.n_out = n_out;
+  I.max_voxel_points = res[sicp::kMapMaxCount];
+  I.has_label = C > 0 ? 1 : 0;
+  const bool want_arrays = x || y || z || label || count || hist;
+  if (want_arrays && capacity < n_out) {
+    I.t_total_ms = now_ms() - t_begin;
+    if (info) *info = I;
+    m->last_error = "sicp_map_extract: the result has " + std::to_string(n_out) + " points, the output arrays hold " + std::to_string(capacity);
+    return SICP_ERR_INVALID_ARGUMENT;
+  }
+  if (dst && n_out == 0) {
+    m->last_error = "sicp_map_extract: the result is empty; dst keeps its cloud";
+    return SICP_ERR_TOO_FEW_POINTS;
+  }
+  // the result -> pinned memory: the whole of it is on the host before dst's slot lets go of its old cloud
+  const size_t mo = (size_t)n_out;
+  if (n_out > 0 && (want_arrays || dst)) {
+    X.idle = false;
+    const size_t hist_words = hist ? mo * (size_t)stride : 0;
+    MAPCHECK(m->out.resize(mo * 5 + hist_words));
+    uint32_t* o = m->out.data();
+    if (hist) {
+      MAPCHECK(X.ohist.reserve(hist_words));
+      MAPCHECK(sicp::launch_map_move_hist(S.rows.hist, X.ohist.p, S.src_of, n_out, stride, st));
+      MAPCHECK(hipMemcpyAsync(o + 5 * mo, X.ohist.p, 4 * hist_words, hipMemcpyDeviceToHost, st));
+    }
+    MAPCHECK(hipMemcpyAsync(o, X.ox.p, 4 * mo, hipMemcpyDeviceToHost, st));
+    MAPCHECK(hipMemcpyAsync(o + mo, X.oy.p, 4 * mo, hipMemcpyDeviceToHost, st));
+    MAPCHECK(hipMemcpyAsync(o + 2 * mo, X.oz.p, 4 * mo, hipMemcpyDeviceToHost, st));
+    if (C > 0) MAPCHECK(hipMemcpyAsync(o + 3 * mo, X.ol.p, 4 * mo, hipMemcpyDeviceToHost, st));
+    MAPCHECK(hipMemcpyAsync(o + 4 * mo, X.oc.p, 4 * mo, hipMemcpyDeviceToHost, st));
+    log.mark("result");
+    MAPCHECK(hipStreamSynchronize(st));
+    X.idle = true;
+  }
+  log.print("sicp_map_extract: n_map=" + std::to_string(n_map) + " n_out=" + std::to_string(n_out));
+  const uint32_t* o = m->out.data();
+  if (dst) {
+    const StridedCloud in = {(const char*)o, (const char*)(o + mo), (const char*)(o + 2 * mo), C > 0 ? (const char*)(o + 3 * mo) : nullptr, 4, 4};
+    const int rc = set_cloud_common(dst, dst_which, n_out, in);
+    if (rc != SICP_OK) {
+      m->last_error = "sicp_map_extract: dst: " + dst->last_error;
+      return rc;
+    }
+  }
+  if (n_out > 0) {
+    if (x) std::memcpy(x, o, 4 * mo);
+    if (y) std::memcpy(y, o + mo, 4 * mo);
+    if (z) std::memcpy(z, o + 2 * mo, 4 * mo);
+    if (label && C > 0) std::memcpy(label, o + 3 * mo, 4 * mo);
+    if (count) std::memcpy(count, o + 4 * mo, 4 * mo);
+    if (hist) std::memcpy(hist, o + 5 * mo, 4 * mo * (size_t)stride);
+  }
+  I.t_total_ms = now_ms() - t_begin;
+  if (info) *info = I;
+  return SICP_OK;
+}
+
+}  // namespace host
+}  // namespace sicp

@@ -1,0 +1,272 @@
+// map_kernels.hip -- sicp_map_*: the persistent voxel map (driver: map.cpp; the rules: INTEGRATION.md, "A persistent voxel
+// map").  The map's rows lie sorted by voxel key.  An integrate keys the scan's points with merge's arithmetic
+// (voxel_key.hpp), sorts THEM (a stable radix sort: point indices ascend inside a voxel), and merges by rank: a lower-bound
+// search of every scan voxel among the map's keys, a search of every map row among the few absent keys, one pass that moves
+// the rows to their new places in the spare buffers, and one lane per scan voxel that continues its row's f64 sums in point
+// order.  A lane owns its row: plain stores, no float atomics, so every byte is run-to-run reproducible.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#define SICP_HD __host__ __device__
+#include "kernels.h"
+#include "voxel_key.hpp"
+
+#pragma clang fp contract(off)
+
+namespace sicp {
+namespace {
+
+typedef unsigned long long u64;
+
+// the number of keys below k in the ascending keys[n]
+__device__ __forceinline__ int map_lower_bound(const u64* keys, int n, u64 k) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (keys[mid] < k) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// per point of the scan: transform, crop, voxel key (~0 for a dropped point); a coordinate beyond the key's fields and a label
+// beyond the histogram raise their flags (plain stores: every writer stores the same 1)
+__global__ __launch_bounds__(256) void map_key_kernel(MapKeyArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const double x = a.x[i], y = a.y[i], z = a.z[i];
+  const float px = voxel_xform_row(a.M + 0, x, y, z);
+  const float py = voxel_xform_row(a.M + 4, x, y, z);
+  const float pz = voxel_xform_row(a.M + 8, x, y, z);
+  a.tx[i] = px; a.ty[i] = py; a.tz[i] = pz;
+  u64 k = kVoxelDropped;
+  if (!a.crop || voxel_crop_keeps(px, py, pz, a.cx, a.cy, a.cz, a.range_sq)) {
+    if (!voxel_key(px, py, pz, a.inv_leaf, &k)) {
+      k = kVoxelDropped;
+      a.res[kMapRange] = 1;
+    }
+    if (a.label && a.label[i] > (uint32_t)a.num_classes) a.res[kMapBadLabel] = 1;
+  }
+  a.key[i] = k;
+  a.val[i] = i;
+}
+
+// one lane per scan voxel: where its key stands among the map's, and whether it is there
+__global__ __launch_bounds__(256) void map_lookup_kernel(MapFoldArgs a) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= a.n) return;
+  int miss = 0;
+  if (k < a.res[kMapScanVoxels]) {
+    const u64 key = a.skey[a.heads[k]];
+    const int r = map_lower_bound(a.from.key, a.n_map, key);
+    a.rank[k] = r;
+    miss = (r < a.n_map && a.from.key[r] == key) ? 0 : 1;
+  }
+  a.miss[k] = miss;
+}
+
+// the absent keys, compacted (ascending, as the scan's voxels are), and their number
+__global__ __launch_bounds__(256) void map_miss_kernel(MapFoldArgs a) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= a.n) return;
+  const int f = a.miss[k], p = a.mpos[k];
+  if (f) {
+    a.miss_key[p] = a.skey[a.heads[k]];
+    a.miss_rank[p] = a.rank[k];
+  }
+  if (k == a.n - 1) a.res[kMapNew] = p + f;
+}
+
+// one lane per row of the grown map: an old row i moves up by the absent keys below it, absent key j opens the row
+// j + (old keys below it), empty
+__global__ __launch_bounds__(256) void map_scatter_kernel(MapFoldArgs a) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t < a.n_map) {
+    const u64 key = a.from.key[t];
+    const int r = t + map_lower_bound(a.miss_key, a.n_new, key);
+    a.to.key[r] = key;
+    a.to.sx[r] = a.from.sx[t]; a.to.sy[r] = a.from.sy[t]; a.to.sz[r] = a.from.sz[t];
+    a.to.cnt[r] = a.from.cnt[t];
+    a.src_of[r] = t;
+  } else if (t - a.n_map < a.n_new) {
+    const int j = t - a.n_map;
+    const int r = j + a.miss_rank[j];
+    a.to.key[r] = a.miss_key[j];
+    a.to.sx[r] = 0.0; a.to.sy[r] = 0.0; a.to.sz[r] = 0.0;
+    a.to.cnt[r] = 0u;
+    a.src_of[r] = -1;
+  }
+}
+
+// histogram rows to their new places (consecutive lanes write consecutive words)
+__global__ __launch_bounds__(256) void map_move_hist_kernel(const uint32_t* from, uint32_t* to, const int* src_of, long long total, int stride) {
+  const long long step = (long long)gridDim.x * 256;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += step) {
+    const long long r = e / stride;
+    const int s = src_of[r];
+    to[e] = s >= 0 ? from[(long long)s * stride + (e - r * stride)] : 0u;
+  }
+}
+
+// one lane per scan voxel: its row's sums continued with the voxel's points in ascending point index -- s += (double)p, one
+// add per point, from the stored value (the order is the specification: a voxel's run is not split across lanes) -- and its
+// count and histogram bins.  Scan voxel k's row: its rank among the old keys plus the absent keys below it.
+__global__ __launch_bounds__(256) void map_fold_kernel(MapFoldArgs a) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  const int n_vox = a.res[kMapScanVoxels], n_kept = a.res[kMapKept];
+  if (k >= a.n || k >= n_vox) return;
+  const int r = a.rank[k] + a.mpos[k];
+  if (r >= a.n_map + a.n_new) return;  // (cannot happen; a row beyond the buffers is never written)
+  const int b = a.heads[k], e = k + 1 < n_vox ? a.heads[k + 1] : n_kept;
+  double sx = a.to.sx[r], sy = a.to.sy[r], sz = a.to.sz[r];
+  uint32_t* const h = a.stride > 0 ? a.to.hist + (size_t)r * (size_t)a.stride : nullptr;
+  for (int j = b; j < e; ++j) {
+    sx += (double)a.gx[j]; sy += (double)a.gy[j]; sz += (double)a.gz[j];
+    if (h) {
+      const uint32_t l = (uint32_t)(a.lkey[j] & 0xffffffffull);
+      if (l < (uint32_t)a.stride) h[l] += 1u;  // (labels beyond the bins were refused before this launch)
+    }
+  }
+  a.to.sx[r] = sx; a.to.sy[r] = sy; a.to.sz[r] = sz;
+  a.to.cnt[r] += (uint32_t)(e - b);
+}
+
+// a row's centroid as the caller sees it: (float)(s / count) per axis
+__device__ __forceinline__ void map_centroid(const MapRows& R, int i, float* cx, float* cy, float* cz) {
+  const double c = (double)R.cnt[i];
+  *cx = (float)(R.sx[i] / c); *cy = (float)(R.sy[i] / c); *cz = (float)(R.sz[i] / c);
+}
+
+// flag[i]: row i has at least min_count points and its centroid passes the crop
+__global__ __launch_bounds__(256) void map_select_kernel(MapSelectArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_map) return;
+  bool keep = (long long)a.rows.cnt[i] >= a.min_count;
+  if (keep && a.crop) {
+    float px, py, pz;
+    map_centroid(a.rows, i, &px, &py, &pz);
+    keep = voxel_crop_keeps(px, py, pz, a.cx, a.cy, a.cz, a.range_sq);
+  }
+  a.flag[i] = keep ? 1 : 0;
+}
+
+// the surviving rows, bit for bit, to the spare buffers; their number and the sum of their counts (one integer atomic a wave)
+__global__ __launch_bounds__(256) void map_prune_kernel(MapSelectArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  u64 c = 0;
+  if (i < a.n_map) {
+    const int f = a.flag[i], p = a.pos[i];
+    if (f) {
+      a.to.key[p] = a.rows.key[i];
+      a.to.sx[p] = a.rows.sx[i]; a.to.sy[p] = a.rows.sy[i]; a.to.sz[p] = a.rows.sz[i];
+      a.to.cnt[p] = a.rows.cnt[i];
+      a.src_of[p] = i;
+      c = a.rows.cnt[i];
+    }
+    if (i == a.n_map - 1) a.res[kMapOut] = p + f;
+  }
+  unsigned lo = (unsigned)c, carry = 0;  // (64 counts below 2^32: the wave's sum in two words)
+  for (int w = 32; w > 0; w >>= 1) {
+    const unsigned olo = (unsigned)__shfl_xor((int)lo, w, 64), oc = (unsigned)__shfl_xor((int)carry, w, 64);
+    const unsigned s = lo + olo;
+    carry += oc + (s < lo ? 1u : 0u);
+    lo = s;
+  }
+  const u64 sum = ((u64)carry << 32) | lo;
+  if ((threadIdx.x & 63) == 0 && sum) atomicAdd(a.kept_points, sum);
+}
+
+// the selected rows as points, ascending key: centroid, count, the arg-max bin (ties to the smallest label); their number and
+// the largest count
+__global__ __launch_bounds__(256) void map_extract_kernel(MapSelectArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  int cnt = 0;
+  if (i < a.n_map) {
+    const int f = a.flag[i], p = a.pos[i];
+    if (f) {
+      float px, py, pz;
+      map_centroid(a.rows, i, &px, &py, &pz);
+      a.ox[p] = px; a.oy[p] = py; a.oz[p] = pz;
+      const uint32_t c = a.rows.cnt[i];
+      a.ocount[p] = c;
+      cnt = (int)(c > 0x7fffffffu ? 0x7fffffffu : c);
+      a.src_of[p] = i;
+      if (a.olabel) {
+        const uint32_t* h = a.rows.hist + (size_t)i * (size_t)a.stride;
+        uint32_t best = 0, best_n = h[0];
+        for (int l = 1; l < a.stride; ++l) {
+          const uint32_t m = h[l];
+          if (m > best_n) { best_n = m; best = (uint32_t)l; }
+        }
+        a.olabel[p] = best;
+      }
+    }
+    if (i == a.n_map - 1) a.res[kMapOut] = p + f;
+  }
+  int m = cnt;
+  for (int w = 32; w > 0; w >>= 1) m = max(m, __shfl_xor(m, w, 64));
+  if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(&a.res[kMapMaxCount], m);
+}
+
+inline dim3 map_grid(long long n) { return dim3((unsigned)((n + 255) / 256)); }
+
+}  // namespace
+
+hipError_t launch_map_keys(const MapKeyArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_key_kernel, map_grid(a.n), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_lookup(const MapFoldArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_lookup_kernel, map_grid(a.n), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_misses(const MapFoldArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_miss_kernel, map_grid(a.n), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_scatter(const MapFoldArgs& a, hipStream_t st) {
+  const long long rows = (long long)a.n_map + a.n_new;
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_scatter_kernel, map_grid(rows), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_move_hist(const uint32_t* from, uint32_t* to, const int* src_of, long long rows, int stride, hipStream_t st) {
+  const long long total = rows * stride;
+  if (total <= 0) return hipSuccess;
+  const long long blocks = std::min<long long>((total + 255) / 256, 1 << 16);  // (the rest by the kernel's stride loop)
+  hipLaunchKernelGGL(map_move_hist_kernel, dim3((unsigned)blocks), dim3(256), 0, st, from, to, src_of, total, stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_fold(const MapFoldArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_fold_kernel, map_grid(a.n), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_select(const MapSelectArgs& a, hipStream_t st) {
+  if (a.n_map <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_select_kernel, map_grid(a.n_map), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_prune(const MapSelectArgs& a, hipStream_t st) {
+  if (a.n_map <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_prune_kernel, map_grid(a.n_map), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_extract(const MapSelectArgs& a, hipStream_t st) {
+  if (a.n_map <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_extract_kernel, map_grid(a.n_map), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace sicp

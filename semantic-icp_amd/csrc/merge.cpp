@@ -25,34 +25,6 @@ struct MergeScratch {
 
 bool slot_ok(int which) { return which == SICP_SOURCE || which == SICP_TARGET; }
 
-// developer aid (SICP_DEBUG + SICP_MERGE_LOG; tools/merge_timing.py reads it): HIP-event times of the stages on stderr
-struct StageLog {
-  static constexpr int kMax = 10;
-  bool on = false;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[kMax] = {};
-  const char* name[kMax] = {};
-  int n = 0;
-  StageLog(bool enable, hipStream_t stream) : on(enable), st(stream) {}
-  ~StageLog() { for (int i = 0; i < n; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); }
-  void mark(const char* what) {  // the end of stage `what` (the first mark opens the first stage)
-    if (!on || n >= kMax) return;
-    if (hipEventCreate(&ev[n]) != hipSuccess) { on = false; return; }
-    (void)hipEventRecord(ev[n], st);
-    name[n++] = what;
-  }
-  void print(long long n_in, int n_out) {
-    if (!on || n < 2) return;
-    std::string s = "sicp_merge: n_in=" + std::to_string(n_in) + " n_out=" + std::to_string(n_out);
-    for (int i = 1; i < n; ++i) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, ev[i - 1], ev[i]) != hipSuccess) return;
-      s += std::string(" ") + name[i] + "_ms=" + std::to_string(ms);
-    }
-    std::fprintf(stderr, "%s\n", s.c_str());
-  }
-};
-
 }  // namespace
 
 void merge_default_params(sicp_merge_params* p) {
@@ -247,7 +219,7 @@ int merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_parts,
     HIPCHECK(hipStreamSynchronize(st));
   }
   X.idle = true;
-  log.print(n_in, n_out);
+  log.print("sicp_merge: n_in=" + std::to_string(n_in) + " n_out=" + std::to_string(n_out));
   const uint32_t* o = h->mg_out.data();
   if (dst) {
     const StridedCloud in = {(const char*)o, (const char*)(o + mo), (const char*)(o + 2 * mo), has_label ? (const char*)(o + 3 * mo) : nullptr, 4, 4};

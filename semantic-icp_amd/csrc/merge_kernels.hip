@@ -7,6 +7,7 @@
 #define SICP_HD __host__ __device__
 #include "job_table.hpp"
 #include "kernels.h"
+#include "voxel_key.hpp"
 
 #pragma clang fp contract(off)
 
@@ -14,22 +15,12 @@ namespace sicp {
 namespace {
 
 typedef unsigned long long u64;
-constexpr u64 kDropped = ~0ull;
+constexpr u64 kDropped = kVoxelDropped;
 
-// pcl::transformPointCloud<PointT,double> as the search transforms its queries (knn_kernels.hip: xform_row):
-// (((m0*x + m1*y) + m2*z) + m3) in double, no contraction, then one rounding to float
-__device__ __forceinline__ float merge_xform_row(const double* m, double x, double y, double z) {
-#pragma clang fp contract(off)
-  double a = __dmul_rn(m[0], x);
-  a = __dadd_rn(a, __dmul_rn(m[1], y));
-  a = __dadd_rn(a, __dmul_rn(m[2], z));
-  a = __dadd_rn(a, m[3]);
-  return __double2float_rn(a);
-}
-
-// per point: transform, crop (exec/filter_range.h in f32 about a centre), voxel key.  key = three biased 21-bit voxel
-// coordinates, z highest, so ascending keys are ascending (vz, vy, vx); 0 without a grid; ~0 for a cropped point.  A
-// coordinate beyond the fields raises res[kMergeRange] (a plain store: every writer stores the same 1).
+// per point: transform, crop (exec/filter_range.h in f32 about a centre), voxel key -- the arithmetic of voxel_key.hpp, which the
+// voxel map shares.  key = three biased 21-bit voxel coordinates, z highest, so ascending keys are ascending (vz, vy, vx); 0
+// without a grid; ~0 for a cropped point.  A coordinate beyond the fields raises res[kMergeRange] (a plain store: every writer
+// stores the same 1).
 __global__ __launch_bounds__(256) void merge_key_kernel(MergeKeyArgs a) {
   int lb;
   const MergePart& P = a.parts[job_of(a.blk_end, a.n_parts, blockIdx.x, &lb)];
@@ -37,32 +28,18 @@ __global__ __launch_bounds__(256) void merge_key_kernel(MergeKeyArgs a) {
   if (i >= P.n) return;
   const int g = P.off + i;
   const double x = P.x[i], y = P.y[i], z = P.z[i];
-  const float px = merge_xform_row(P.M + 0, x, y, z);
-  const float py = merge_xform_row(P.M + 4, x, y, z);
-  const float pz = merge_xform_row(P.M + 8, x, y, z);
+  const float px = voxel_xform_row(P.M + 0, x, y, z);
+  const float py = voxel_xform_row(P.M + 4, x, y, z);
+  const float pz = voxel_xform_row(P.M + 8, x, y, z);
   a.tx[g] = px; a.ty[g] = py; a.tz[g] = pz;
   if (a.tlabel) a.tlabel[g] = P.label[i];
-  bool keep = true;
-  if (a.crop) {
-    const float dx = __fsub_rn(px, a.cx), dy = __fsub_rn(py, a.cy), dz = __fsub_rn(pz, a.cz);
-    float d2 = __fmul_rn(dx, dx);
-    d2 = __fadd_rn(d2, __fmul_rn(dy, dy));
-    d2 = __fadd_rn(d2, __fmul_rn(dz, dz));
-    keep = (double)d2 <= a.range_sq;
-  }
+  const bool keep = !a.crop || voxel_crop_keeps(px, py, pz, a.cx, a.cy, a.cz, a.range_sq);
   u64 k = kDropped;
   if (keep) {
     k = 0;
-    if (a.voxel) {
-      const float v0 = floorf(__fmul_rn(px, a.inv_leaf)), v1 = floorf(__fmul_rn(py, a.inv_leaf)), v2 = floorf(__fmul_rn(pz, a.inv_leaf));
-      const float lim = (float)kMergeBias;
-      if (fabsf(v0) < lim && fabsf(v1) < lim && fabsf(v2) < lim) {  // (a NaN fails)
-        k = ((u64)(unsigned)((int)v2 + kMergeBias) << 42) | ((u64)(unsigned)((int)v1 + kMergeBias) << 21) |
-            (u64)(unsigned)((int)v0 + kMergeBias);
-      } else {
-        k = kDropped;
-        a.res[kMergeRange] = 1;
-      }
+    if (a.voxel && !voxel_key(px, py, pz, a.inv_leaf, &k)) {
+      k = kDropped;
+      a.res[kMergeRange] = 1;
     }
   }
   a.key[g] = k;

@@ -864,6 +864,66 @@ int sicp_merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_p
   });
 }
 
+int sicp_default_map_params(sicp_map_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    map_default_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_default_map_extract_params(sicp_map_extract_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    map_default_extract_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_map_create(int device_id, const sicp_map_params* p, sicp_map* out) {
+  return abi_guard([&]() -> int { return map_create(device_id, p, out); });
+}
+
+int sicp_map_destroy(sicp_map m) {
+  return abi_guard([&]() -> int { return map_destroy(m); });
+}
+
+int sicp_map_clear(sicp_map m) {
+  return abi_guard(m, [&]() -> int {
+    if (!m) return SICP_ERR_INVALID_ARGUMENT;
+    m->n_voxels = 0;
+    m->n_points = 0;
+    return SICP_OK;
+  });
+}
+
+int sicp_map_size(sicp_map m, int64_t* n_voxels, int64_t* n_points) {
+  return abi_guard(m, [&]() -> int {
+    if (!m) return SICP_ERR_INVALID_ARGUMENT;
+    if (n_voxels) *n_voxels = m->n_voxels;
+    if (n_points) *n_points = (int64_t)m->n_points;
+    return SICP_OK;
+  });
+}
+
+const char* sicp_map_last_error(sicp_map m) { return m ? m->last_error.c_str() : ""; }
+
+int sicp_map_integrate(sicp_map m, sicp_handle h, int which, const double qt[7], const double crop_center[3], double crop_range,
+                       sicp_map_integrate_info* info) {
+  return abi_guard(m, [&]() -> int { return map_integrate(m, h, which, qt, crop_center, crop_range, info); });
+}
+
+int sicp_map_prune(sicp_map m, const double center[3], double range, int64_t* n_removed) {
+  return abi_guard(m, [&]() -> int { return map_prune(m, center, range, n_removed); });
+}
+
+int sicp_map_extract(sicp_map m, const sicp_map_extract_params* p, sicp_handle dst, int dst_which, int32_t capacity, float* x,
+                     float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info) {
+  return abi_guard(m, [&]() -> int {
+    return map_extract(m, p, dst, dst_which, capacity, x, y, z, label, count, hist, info);
+  });
+}
+
 int sicp_solve(sicp_handle h, const double init_qt[7], double out_qt[7], int32_t* lm_iters, int32_t* evals,
                double* final_cost) {
   return abi_guard(h, [&]() -> int {
