@@ -168,12 +168,19 @@ int sicp_device_count(int* count);
 /* replaces the three class constructors (em_icp.h:42-48, gicp.h:34-40,
  * semantic_icp.h:35-39); mode and tunables follow via sicp_set_params */
 int sicp_create(int device_id, sicp_handle* out);
+/* Ends the caller's use of `h`: everything it queued is waited for and its clouds are let go.  The handle itself is
+ * PARKED, not freed: up to 32 per device stay in a pool with their streams, events, pinned mirrors, device buffers and
+ * tick graphs (a batch leader or a stream's slot holds tens of MB), and the next sicp_create on that device hands one
+ * out again, reset to what a new handle is.  Only sicp_release_pool gives a parked handle's memory back.
+ * A second sicp_destroy of a handle that is still parked returns SICP_ERR_INVALID_ARGUMENT and changes nothing.  The
+ * check can only work while the handle is parked: once sicp_create has handed it out again it is another caller's live
+ * handle, and once sicp_release_pool has freed it the pointer dangles -- as after any free. */
 int sicp_destroy(sicp_handle h);
 /* Uploaded clouds (device buffers, search structures, pinned staging memory) are recycled through a
  * per-device pool when their last handle lets go of them, and all device buffers are carved from a
  * per-device arena that is not returned to the driver by itself; this frees what the pool of
- * `device_id` currently holds and every arena slab no live buffer sits in (it waits for the device
- * first).  Never required. */
+ * `device_id` currently holds -- the recycled clouds and the handles parked by sicp_destroy, with all they retain --
+ * and every arena slab no live buffer sits in (it waits for the device first).  Never required. */
 int sicp_release_pool(int device_id);
 /* Device memory the library may hold on `device_id`, in bytes (0 = no limit, the default): the arena takes no new
  * slab from the driver beyond it, and whatever then cannot be allocated -- a cloud, a handle's buffers -- fails with

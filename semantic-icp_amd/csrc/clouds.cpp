@@ -217,7 +217,7 @@ int prepare_cloud(sicp_context* h, Cloud& c) {
   // no synchronisation here: every staging buffer is pinned memory owned by the cloud, and the next
   // user of the cloud waits for ready_ev (cloud_wait).  A sequence driver can therefore queue the
   // uploads of a whole batch of scans back to back, beside the registrations of the previous batch.
-  if (!c.ready_ev) HIPCHECK(hipEventCreateWithFlags(&c.ready_ev, hipEventDisableTiming));
+  HIPCHECK(c.ready_ev.create());
   HIPCHECK(hipEventRecord(c.ready_ev, h->stream));
   c.pending = true;
   c.layout = want;

@@ -216,11 +216,13 @@ struct DevBuf {
 };
 
 // pinned host memory: uploads and read-backs through it are real asynchronous DMA copies
+// (flags: hipHostMallocCoherent for memory a running kernel writes while the host polls it)
 template <class T>
 struct HostBuf {
   T* p = nullptr;
   size_t cap = 0, n = 0;
-  HostBuf() = default;
+  unsigned flags = hipHostMallocDefault;
+  explicit HostBuf(unsigned alloc_flags = hipHostMallocDefault) : flags(alloc_flags) {}
   HostBuf(const HostBuf&) = delete;
   HostBuf& operator=(const HostBuf&) = delete;
   ~HostBuf() { if (p) (void)hipHostFree(p); }
@@ -229,7 +231,7 @@ struct HostBuf {
       if (p) (void)hipHostFree(p);
       p = nullptr; cap = 0;
       const size_t want = count + count / 8 + 64;
-      hipError_t e = hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault);
+      hipError_t e = hipHostMalloc((void**)&p, want * sizeof(T), flags);
       if (e != hipSuccess) { p = nullptr; n = 0; return e; }
       cap = want;
     }
@@ -246,6 +248,29 @@ struct HostBuf {
   size_t size() const { return n; }
   T& operator[](size_t i) { return p[i]; }
   const T& operator[](size_t i) const { return p[i]; }
+};
+
+// A HIP stream / event its holder owns: move-only, destroyed with the holder, used wherever the raw type is.  create()
+// makes the object unless it is there already.
+struct OwnedStream {
+  hipStream_t s = nullptr;
+  OwnedStream() = default;
+  OwnedStream(OwnedStream&& o) noexcept { std::swap(s, o.s); }
+  OwnedStream& operator=(OwnedStream&& o) noexcept { std::swap(s, o.s); return *this; }
+  ~OwnedStream() { if (s) (void)hipStreamDestroy(s); }
+  hipError_t create(unsigned flags = hipStreamNonBlocking) { return s ? hipSuccess : hipStreamCreateWithFlags(&s, flags); }
+  hipStream_t get() const { return s; }
+  operator hipStream_t() const { return s; }
+};
+struct OwnedEvent {
+  hipEvent_t e = nullptr;
+  OwnedEvent() = default;
+  OwnedEvent(OwnedEvent&& o) noexcept { std::swap(e, o.e); }
+  OwnedEvent& operator=(OwnedEvent&& o) noexcept { std::swap(e, o.e); return *this; }
+  ~OwnedEvent() { if (e) (void)hipEventDestroy(e); }
+  hipError_t create(unsigned flags = hipEventDisableTiming) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+  hipEvent_t get() const { return e; }
+  operator hipEvent_t() const { return e; }
 };
 
 struct Cloud {
@@ -315,11 +340,10 @@ struct Cloud {
   unsigned long long proj_cm_id = 0;
   // the upload + tree build is left running on the uploading handle's stream: whoever uses the cloud
   // next (any handle, any stream, or the host reading `perm`) waits for this event first
-  hipEvent_t ready_ev = nullptr;
+  OwnedEvent ready_ev;
   // set by the uploading thread, cleared by whoever waits first (a sequence driver uploads the next
   // batch's scans on a second host thread while the main thread registers clouds that share them)
   std::atomic<bool> pending{false};
-  ~Cloud() { if (ready_ev) (void)hipEventDestroy(ready_ev); }
   int n_seg() const { return (int)seg_label.size(); }
   int caller_index(int d) const { return keep.empty() ? perm[d] : keep[perm[d]]; }
 };
@@ -366,17 +390,25 @@ struct JobCollector {
 // the argument buffers of one stream of ticks (run_tick): argument array + header in HBM with pinned
 // mirrors, and the instantiated [accumulate, LM step] x lm_batch graph that reads them
 struct TickSet {
+  // resources, and the cache that lives as long as they do: `cap`, the capacity in pairs (steps of 32) that keys the graphs
+  // and caps the launches
   DevBuf<sicp::BatchArgs> d_batch;
   DevBuf<sicp::BatchHeader> d_bhdr;
-  sicp::BatchHeader* h_bhdr = nullptr;
-  sicp::BatchArgs* h_batch = nullptr;
-  sicp::LmJoin* h_join = nullptr;  // pinned: the pairs that join with the next tick
+  HostBuf<sicp::BatchHeader> h_bhdr;
+  HostBuf<sicp::BatchArgs> h_batch;
+  HostBuf<sicp::LmJoin> h_join;  // pinned: the pairs that join with the next tick
   DevBuf<sicp::LmJoin> d_join;
   int cap = 0;
   sicp::BatchGraph graph[2];   // [1]: the accumulate nodes carry kAccStaticRanges (static_ranges below)
+  // state of the current use (invalidate(): what a recycled handle starts from)
   bool static_ranges = false;  // the next ticks' large accumulate launches keep equal chunk ranges (a stream while scans are being uploaded)
   std::vector<int> tick_act;  // the pairs whose arguments d_batch currently holds
   bool tick_valid = false;
+  TickSet() = default;
+  TickSet(const TickSet&) = delete;
+  TickSet& operator=(const TickSet&) = delete;
+  ~TickSet() { sicp::batch_graph_destroy(graph[0]); sicp::batch_graph_destroy(graph[1]); }
+  void invalidate() { tick_valid = false; tick_act.clear(); static_ranges = false; }
 };
 
 }  // namespace host
@@ -384,38 +416,67 @@ struct TickSet {
 
 using namespace sicp::host;  // (internal header: only the library's own translation units include it)
 
-struct sicp_context {
-  int device = 0;
+// A handle's members are of three kinds, declared apart:
+//   * the state of the current use (sicp_use_state): what sicp_set_* / align() leave behind.  A recycled handle gets a
+//     default-constructed one, so a member added here needs no edit anywhere else;
+//   * resources a parked handle keeps (streams, events, pinned mirrors, device buffers, tick graphs), each held by an
+//     owner that frees it when the handle is deleted;
+//   * caches that describe the contents of a resource and live exactly as long as it does, each next to its resource.
+struct sicp_use_state {
   JobCollector* collect = nullptr;
-  hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;  // second cloud's feature kernels run beside the first's
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_join = nullptr;
   sicp_params params;
-  std::shared_ptr<Cloud> cl[2];
-  Cloud& cloud(int which) { return *cl[which]; }
-  const Cloud& cloud(int which) const { return *cl[which]; }
   unsigned long long epoch = 0;  // id of the running align() / align_batch() call
   int C = 0;
   std::vector<double> cm;
   unsigned long long cm_id = 0;  // changes with every sicp_set_confusion
-  DevBuf<double> d_cm, d_hval;
-  int hval_k = 0;
-  // correspondences of the last search
-  DevBuf<int> idx;
-  DevBuf<float> d2;
-  DevBuf<double> w;
+  // correspondences of the last search (in idx / d2 / w)
   int corr_n = 0, corr_K = 0;
   bool corr_valid = false, corr_weighted = false;
   bool hint_ok = false;  // idx holds this align()'s previous search: usable as the next search's seed hint
+  // the persistent solve (solve_one_kernel) of the last pair still iterating
+  int solo_pair = 0;  // the pair's state slot
+  bool solo_was_init = false, solo_failed = false;  // the launch in flight starts a solve / the last one did not run to its end
+  int solo_skip = 0, solo_penalty = 0;  // after a persistent launch timed out: solves that stay with the tick graph before the next try (doubling)
+  bool count_stats = false;           // the align() in progress reports statistics: every search also counts its live slots
+  bool counted_in_search = false;     // ... and the search kernel of the current correspondences did so itself
+  // a slot of a registration stream: an upload that is still in flight (queued by the submitting thread on
+  // the stream's upload stream) is waited for ON THE DEVICE, by the stream the slot's kernels run on
+  bool wait_on_device = false;
+  std::string last_error;
+  sicp_stats st = {};
+  sicp_use_state() { sicp_default_params(SICP_MODE_GICP, &params); }
+};
+
+struct sicp_context : sicp_use_state {
+  int device = 0;
+  bool parked = false;  // in the handle pool (sicp_destroy ... sicp_create): not the caller's any more
+  std::shared_ptr<Cloud> cl[2];
+  Cloud& cloud(int which) { return *cl[which]; }
+  const Cloud& cloud(int which) const { return *cl[which]; }
+  // ---- resources.  Members go in reverse order of declaration: graphs and pinned mirrors, then events, then streams.
+  OwnedStream own_stream, own_stream2;  // (the second cloud's feature kernels run beside the first's)
+  OwnedStream side_stream;              // batch leader: searches of the pairs between two inner solves
+  OwnedStream feat_stream;              // batch leader: the start-up pipelines (features + first search) of a large batch
+  OwnedStream part_stream[kParts];
+  // the streams this handle launches on: its own, or the ones it borrows while it is part of a batch (BatchGuard) or a
+  // slot of a registration stream (the leader's side stream).  Never destroyed through these.
+  hipStream_t stream = nullptr, stream2 = nullptr;
+  OwnedEvent ev0, ev1, ev_join;
+  OwnedEvent side_done, side_done2, main_done;
+  std::vector<OwnedEvent> chunk_ev;  // one per start-up chunk
+  OwnedEvent part_fork, part_done[kParts];
+  DevBuf<double> d_cm, d_hval;
+  int hval_k = 0;  // cache: the k that d_hval was filled for
+  DevBuf<int> idx;
+  DevBuf<float> d2;
+  DevBuf<double> w;
   DevBuf<unsigned long long> part;
   DevBuf<double> partials, out28;
   DevBuf<long long> d_count;
   DevBuf<sicp::LmState> d_lm;
-  // one batch of the device-resident solve ([accumulate, lm_step] x lm_batch) captured as a graph:
-  // a single launch call per batch instead of 2 x lm_batch trips through the runtime's launch path
-  sicp::LmState* h_lm = nullptr;  // pinned mirror of the device-resident LM state
-  double* h_out28 = nullptr;      // pinned, 28 doubles
-  long long* h_count = nullptr;   // pinned
+  HostBuf<sicp::LmState> h_lm;  // pinned mirror of the device-resident LM state
+  HostBuf<double> h_out28;      // pinned, 28 doubles
+  HostBuf<long long> h_count;   // pinned
   DevBuf<float> tmpx, tmpy, tmpz;
   DevBuf<double> tmp9;  // sicp_covariances: the 3x3 matrices in the caller's order on their way out
   DevBuf<uint32_t> tmpl;
@@ -434,29 +495,27 @@ struct sicp_context {
   // state per pair, pinned mirrors, and the captured [accumulate_batch, lm_step_batch] x lm_batch graph
   TickSet ts[2];  // two sets: the halves of a batch alternate, one's tick runs while the host turns the other around
   DevBuf<sicp::LmState> d_bstates;
-  DevBuf<unsigned> d_solo_sync;       // the last pair still iterating: hand-off words of the persistent solve (solve_one_kernel)
-  unsigned solo_tag = 0;              // its tags so far (a launch uses solo_tag + 1 ...: the words are never zeroed in between)
-  int solo_seq = 0, solo_pair = 0;    // launch counter (the state's pad_ word echoes it at a regular end) and the pair's state slot
-  bool solo_was_init = false, solo_failed = false;  // the launch in flight starts a solve / the last one did not run to its end
-  int solo_skip = 0, solo_penalty = 0;  // after a persistent launch timed out: solves that stay with the tick graph before the next try (doubling)
-  bool count_stats = false;           // the align() in progress reports statistics: every search also counts its live slots
-  bool counted_in_search = false;     // ... and the search kernel of the current correspondences did so itself
   DevBuf<double> d_bout28;
-  sicp::LmState* h_bstates = nullptr;
-  int* h_solo_flag = nullptr;  // pinned: the persistent solve's master writes its launch number here at a regular end (solve.cpp: solo_wait)
-  double* h_bout28 = nullptr;
-  int h_batch_cap = 0;  // capacity of the per-pair state mirrors (h_bstates, h_bout28)
-  hipStream_t side_stream = nullptr;  // batch leader: searches of the pairs between two inner solves
-  hipEvent_t side_done = nullptr, side_done2 = nullptr, main_done = nullptr;
-  hipStream_t feat_stream = nullptr;          // batch leader: the start-up pipelines (features + first search) of a large batch
-  std::vector<hipEvent_t> chunk_ev;           // one per start-up chunk
-  hipStream_t part_stream[kParts] = {};
-  hipEvent_t part_fork = nullptr, part_done[kParts] = {};
-  // a slot of a registration stream: an upload that is still in flight (queued by the submitting thread on
-  // the stream's upload stream) is waited for ON THE DEVICE, by the stream the slot's kernels run on
-  bool wait_on_device = false;
-  std::string last_error;
-  sicp_stats st;
+  // per-pair state mirrors, sized in steps of 32 pairs (batch_reserve).  h_bstates is also written by the persistent solve's
+  // master while the host polls: coherent
+  HostBuf<sicp::LmState> h_bstates{hipHostMallocCoherent};
+  HostBuf<double> h_bout28;
+  DevBuf<unsigned> d_solo_sync;  // hand-off words of the persistent solve
+  // caches of d_solo_sync: the tags used so far (a launch uses solo_tag + 1 ...: the words are never zeroed in between), and
+  // the launch counter (the state's pad_ word echoes it at a regular end; process-wide, so never stale)
+  unsigned solo_tag = 0;
+  int solo_seq = 0;
+  // pinned, coherent: the persistent solve's master writes its launch number here at a regular end (solve.cpp: solo_wait);
+  // behind the word, the landing area of the fallback copy
+  HostBuf<int> h_solo_flag{hipHostMallocCoherent};
+
+  // what a new handle is, for one that has been used: the resources and their caches stay
+  void reset_use() {
+    static_cast<sicp_use_state&>(*this) = sicp_use_state();
+    stream = own_stream;
+    stream2 = own_stream2;
+    for (TickSet& S : ts) S.invalidate();
+  }
 };
 
 // ---- a registration stream (sicp_stream_*): the continuous batching of sicp_align_batch without the closed
@@ -480,7 +539,6 @@ struct sicp_stream_ctx {
   int C = 0;
   std::vector<double> cm;
   std::vector<sicp_context*> slots;      // slots[0] leads: tick sets, LM states, side stream
-  std::vector<hipStream_t> own1, own2;   // the slots' own streams (restored before the handles are destroyed)
   sicp_context* uploader = nullptr;      // runs the uploads + search-tree builds (caller's thread, own stream)
   std::mutex up_m;                       // one upload at a time
   // ---- shared between the caller's threads and the worker, under `m`
@@ -512,7 +570,7 @@ struct sicp_stream_ctx {
   std::vector<long long> slot_ticket;
   std::vector<double> slot_t0;
   std::vector<unsigned> slot_flags;
-  std::vector<hipEvent_t> slot_ev;  // SICP_SUBMIT_FUSED_LABELS: recorded behind the label kernel + read-back of the slot
+  std::vector<OwnedEvent> slot_ev;  // SICP_SUBMIT_FUSED_LABELS: recorded behind the label kernel + read-back of the slot
   PoseCovStream* cov = nullptr;     // SICP_SUBMIT_POSE_COVARIANCE: reserved with the first flagged registration, released with the stream
   std::vector<int> slot_cov_stage, slot_cov_row;  // the stage of the slot's covariance pass and its row there
   std::thread worker;
@@ -523,7 +581,7 @@ struct sicp_stream_ctx {
 struct sicp_map_ctx {
   int device = 0;
   sicp_map_params params;
-  hipStream_t stream = nullptr;
+  OwnedStream stream;
   struct Rows {
     DevBuf<unsigned long long> key;
     DevBuf<double> sx, sy, sz;
@@ -603,14 +661,13 @@ struct StageLog {
   static constexpr int kMax = 12;
   bool on = false;
   hipStream_t st = nullptr;
-  hipEvent_t ev[kMax] = {};
+  OwnedEvent ev[kMax];
   const char* name[kMax] = {};
   int n = 0;
   StageLog(bool enable, hipStream_t stream) : on(enable), st(stream) {}
-  ~StageLog() { for (int i = 0; i < n; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); }
   void mark(const char* what) {  // the end of stage `what` (the first mark opens the first stage)
     if (!on || n >= kMax) return;
-    if (hipEventCreate(&ev[n]) != hipSuccess) { on = false; return; }
+    if (ev[n].create(hipEventDefault) != hipSuccess) { on = false; return; }
     (void)hipEventRecord(ev[n], st);
     name[n++] = what;
   }
@@ -655,7 +712,8 @@ struct WeightFold {
 int run_nn(sicp_context* h, int K, const Cloud& Qc, int q_begin, int q_count, const double* M34, const Cloud& Tc,
            int tseg, bool self, float gate_sq, int* out_i, float* out_d, int timer_bit, hipStream_t stream, int out_stride = 0,
            const WeightFold* fold = nullptr);
-int ensure_hval(sicp_context* h, int k);
+int ensure_hval(sicp_context* h, int k, hipStream_t st = nullptr);  // (st: the handle's stream unless given)
+int set_confusion(sicp_context* h, int32_t C, const double* cm, hipStream_t st);  // sicp_set_confusion, uploading on st
 int ensure_proj(sicp_context* h, Cloud& c);
 int compute_features(sicp_context* h, Cloud& c, bool with_hist, hipStream_t stream = nullptr);
 bool features_current(const sicp_context* h, const Cloud& c, bool with_hist);
@@ -691,7 +749,7 @@ struct SolveResult {
   double cost = 0;
 };
 
-hipError_t create_side_stream(hipStream_t* st);  // the stream of a batch's / a stream's searches and feature kernels
+int side_reserve(sicp_context* h);  // the leader's side stream (a batch's / a stream's searches and feature kernels) and its events
 bool solo_allowed(sicp_context* h);
 bool general_covariances(const sicp_context* h);  // either cloud carries caller covariances of general form
 int align_host_loop(sicp_context* h, const double* init_qt, double* out_qt, int32_t* outer_iters, sicp_stats* stats);

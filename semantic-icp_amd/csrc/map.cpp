@@ -98,7 +98,7 @@ int map_create(int device_id, const sicp_map_params* p, sicp_map_ctx** out) {
   m->device = device_id;
   m->params = *p;
   m->params.reserved_ = 0;
-  if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) {
+  if (hipSetDevice(device_id) != hipSuccess || m->stream.create() != hipSuccess) {
     delete m;
     return SICP_ERR_NO_DEVICE;
   }
@@ -109,10 +109,7 @@ int map_create(int device_id, const sicp_map_params* p, sicp_map_ctx** out) {
 int map_destroy(sicp_map_ctx* m) {
   if (!m) return SICP_OK;
   (void)hipSetDevice(m->device);
-  if (m->stream) {
-    (void)hipStreamSynchronize(m->stream);
-    (void)hipStreamDestroy(m->stream);
-  }
+  if (m->stream) (void)hipStreamSynchronize(m->stream);
   {
     DevArena::FreeScope once(m->device);  // one wait for the device, not one per buffer
     delete m;

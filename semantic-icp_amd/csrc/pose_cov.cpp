@@ -459,7 +459,7 @@ int pose_covariance_batch(sicp_handle* hs, int32_t n, const double* qt, double s
 struct PoseCovStage {
   HostBuf<unsigned char> pin;
   SweepOut o;
-  hipEvent_t ev = nullptr;
+  OwnedEvent ev;
   int waiting = 0;  // slots that have not taken their sums yet
 };
 struct PoseCovStream {
@@ -485,7 +485,7 @@ int stream_cov_pass(sicp_stream_ctx* S, const std::vector<int>& slots, const std
       if (C.stages[k]->waiting == 0) si = (int)k;
     if (si < 0) { C.stages.emplace_back(new PoseCovStage()); si = (int)C.stages.size() - 1; }
     PoseCovStage& G = *C.stages[(size_t)si];
-    if (!G.ev) HIPCHECK(hipEventCreateWithFlags(&G.ev, hipEventDisableTiming));
+    HIPCHECK(G.ev.create());
     std::vector<sicp_context*> gh;
     for (size_t k = b; k < e; ++k) gh.push_back(S->slots[(size_t)slots[k]]);
     SICPCHECK(pose_cov_sweep(h, C.X, G.pin, gh.data(), qts.data() + b, (int)(e - b), side, &G.o));
@@ -507,8 +507,6 @@ void stream_cov_take(sicp_stream_ctx* S, int slot, PoseCovSums* out) {
 
 void stream_cov_destroy(sicp_stream_ctx* S, bool idle) {
   if (!S->cov) return;
-  for (auto& g : S->cov->stages)
-    if (g->ev) (void)hipEventDestroy(g->ev);
   S->cov->X.idle = idle;
   delete S->cov;
   S->cov = nullptr;

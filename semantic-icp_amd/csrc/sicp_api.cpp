@@ -33,6 +33,24 @@ int sicp::host::align_host_loop(sicp_context* h, const double* init_qt, double* 
   return SICP_OK;
 }
 
+// sicp_set_confusion, uploading on `st` and waiting for it (a stream's slot: on its own stream, not the one it borrows)
+int sicp::host::set_confusion(sicp_context* h, int32_t C, const double* cm, hipStream_t st) {
+  if (C < 1 || C > 255 || !cm) return SICP_ERR_INVALID_ARGUMENT;
+  SICPCHECK(set_device(h));
+  h->C = C;
+  h->cm.assign(cm, cm + (size_t)C * C);
+  {  // FNV-1a of the contents: handles holding the same matrix share the projections of a shared cloud
+    unsigned long long id = 1469598103934665603ull ^ (unsigned long long)C;
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(h->cm.data());
+    for (size_t i = 0; i < sizeof(double) * h->cm.size(); ++i) id = (id ^ b[i]) * 1099511628211ull;
+    h->cm_id = id;
+  }
+  HIPCHECK(h->d_cm.reserve((size_t)C * C));
+  HIPCHECK(hipMemcpyAsync(h->d_cm.p, h->cm.data(), sizeof(double) * C * C, hipMemcpyHostToDevice, st));
+  HIPCHECK(hipStreamSynchronize(st));
+  return SICP_OK;
+}
+
 // =================================================================================================
 // C ABI
 // =================================================================================================
@@ -126,23 +144,6 @@ HandlePool& handle_pool() {
 }
 constexpr size_t kHandlePoolCap = 32;  // per device (a parked handle keeps its buffers: ~12 MB at 100K x 4 slots)
 
-// what a new handle is, for one that has been used
-void reset_handle(sicp_context* h) {
-  h->collect = nullptr;
-  sicp_default_params(SICP_MODE_GICP, &h->params);
-  h->epoch = 0;
-  h->C = 0; h->cm.clear(); h->cm_id = 0;
-  h->corr_n = h->corr_K = 0;
-  h->corr_valid = h->corr_weighted = h->hint_ok = false;
-  for (TickSet& S : h->ts) { S.tick_valid = false; S.tick_act.clear(); }
-  h->solo_skip = h->solo_penalty = 0;
-  h->solo_was_init = h->solo_failed = false;
-  h->count_stats = h->counted_in_search = false;
-  h->wait_on_device = false;
-  h->last_error.clear();
-  std::memset(&h->st, 0, sizeof h->st);
-}
-
 int destroy_for_real(sicp_context* h);
 }  // namespace
 
@@ -163,6 +164,7 @@ int sicp_create(int device_id, sicp_handle* out) {
           if (v[i]->device == device_id) { h = v[i]; v.erase(v.begin() + (long)i); break; }
       }
       if (h) {
+        h->parked = false;
         h->cl[0] = acquire_cloud(device_id);
         h->cl[1] = acquire_cloud(device_id);
         *out = h;
@@ -174,20 +176,14 @@ int sicp_create(int device_id, sicp_handle* out) {
     h->device = device_id;
     h->cl[0] = acquire_cloud(device_id);
     h->cl[1] = acquire_cloud(device_id);
-    sicp_default_params(SICP_MODE_GICP, &h->params);
-    std::memset(&h->st, 0, sizeof h->st);
-    bool ok = hipSetDevice(device_id) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreate(&h->ev0) == hipSuccess && hipEventCreate(&h->ev1) == hipSuccess &&
-              hipHostMalloc((void**)&h->h_out28, sizeof(double) * 28, hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void**)&h->h_count, sizeof(long long) * sicp::kLiveCounters, hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void**)&h->h_lm, sizeof(sicp::LmState), hipHostMallocDefault) == hipSuccess;
+    bool ok = hipSetDevice(device_id) == hipSuccess && h->own_stream.create() == hipSuccess && h->own_stream2.create() == hipSuccess &&
+              h->ev_join.create() == hipSuccess && h->ev0.create(hipEventDefault) == hipSuccess && h->ev1.create(hipEventDefault) == hipSuccess &&
+              h->h_out28.resize(28) == hipSuccess && h->h_count.resize(sicp::kLiveCounters) == hipSuccess && h->h_lm.resize(1) == hipSuccess;
     if (!ok) {
-      destroy_for_real(h);
+      delete h;
       return SICP_ERR_NO_DEVICE;
     }
+    h->reset_use();  // (the streams it launches on: its own)
     *out = h;
     return SICP_OK;
   });
@@ -196,10 +192,11 @@ int sicp_create(int device_id, sicp_handle* out) {
 int sicp_destroy(sicp_handle h) {
   return abi_guard(h, [&]() -> int {
     if (!h) return SICP_OK;
+    if (h->parked) return SICP_ERR_INVALID_ARGUMENT;  // destroyed already: the pool's, until sicp_create hands it out again
     // park it: everything it queued has ended, its clouds go back to their pool (or stay with whoever shares them), and
     // what remains is a handle as sicp_create makes them -- with its streams, mirrors, buffers and graphs in place
-    bool clean = h->stream && h->stream2 && hipSetDevice(h->device) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess &&
-                 hipStreamSynchronize(h->stream2) == hipSuccess;
+    bool clean = h->own_stream && h->own_stream2 && hipSetDevice(h->device) == hipSuccess && hipStreamSynchronize(h->own_stream) == hipSuccess &&
+                 hipStreamSynchronize(h->own_stream2) == hipSuccess;
     if (clean && h->side_stream) clean = hipStreamSynchronize(h->side_stream) == hipSuccess;
     if (clean && h->feat_stream) clean = hipStreamSynchronize(h->feat_stream) == hipSuccess;
     for (int s2 = 1; clean && s2 < kParts; ++s2)
@@ -207,11 +204,11 @@ int sicp_destroy(sicp_handle h) {
     if (clean) {
       for (auto& c : h->cl)
         if (c) { settle_cloud(*c); c.reset(); }
-      reset_handle(h);
+      h->reset_use();
       HandlePool& pool = handle_pool();
       std::lock_guard<std::mutex> lock(pool.m);
       auto& v = pool.parked[h->device % kPoolDevices];
-      if (v.size() < kHandlePoolCap) { v.push_back(h); return SICP_OK; }
+      if (v.size() < kHandlePoolCap) { h->parked = true; v.push_back(h); return SICP_OK; }
     }
     return destroy_for_real(h);
   });
@@ -221,41 +218,13 @@ namespace {
 int destroy_for_real(sicp_context* h) {
   {
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
+    if (h->own_stream2) (void)hipStreamSynchronize(h->own_stream2);
     for (auto& c : h->cl)
       if (c) settle_cloud(*c);  // before the streams go (see settle_cloud)
-    if (h->h_out28) (void)hipHostFree(h->h_out28);
-    if (h->h_count) (void)hipHostFree(h->h_count);
-    if (h->h_lm) (void)hipHostFree(h->h_lm);
-    for (TickSet& S : h->ts) {
-      if (S.h_batch) (void)hipHostFree(S.h_batch);
-      if (S.h_join) (void)hipHostFree(S.h_join);
-      if (S.h_bhdr) (void)hipHostFree(S.h_bhdr);
-      sicp::batch_graph_destroy(S.graph[0]);
-      sicp::batch_graph_destroy(S.graph[1]);
-    }
-    if (h->h_bstates) (void)hipHostFree(h->h_bstates);
-    if (h->h_solo_flag) (void)hipHostFree(h->h_solo_flag);
-    if (h->h_bout28) (void)hipHostFree(h->h_bout28);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->side_done) (void)hipEventDestroy(h->side_done);
-    if (h->side_done2) (void)hipEventDestroy(h->side_done2);
-    if (h->main_done) (void)hipEventDestroy(h->main_done);
-    if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
-    if (h->feat_stream) (void)hipStreamDestroy(h->feat_stream);
-    for (hipEvent_t e : h->chunk_ev) (void)hipEventDestroy(e);
-    if (h->part_fork) (void)hipEventDestroy(h->part_fork);
-    for (int s = 1; s < kParts; ++s) {
-      if (h->part_done[s]) (void)hipEventDestroy(h->part_done[s]);
-      if (h->part_stream[s]) (void)hipStreamDestroy(h->part_stream[s]);
-    }
-    if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     {
       DevArena::FreeScope once(h->device);  // one wait for the device, not one per buffer of the handle
-      delete h;
+      delete h;  // graphs and pinned mirrors, then events, then streams (engine.hpp: the order of the members)
     }
     return SICP_OK;
   }
@@ -411,22 +380,7 @@ int sicp_cloud_size(sicp_handle h, int which, int32_t* n_points, int32_t* n_inde
 }
 
 int sicp_set_confusion(sicp_handle h, int32_t C, const double* cm) {
-  return abi_guard(h, [&]() -> int {
-    if (!h || C < 1 || C > 255 || !cm) return SICP_ERR_INVALID_ARGUMENT;
-    SICPCHECK(set_device(h));
-    h->C = C;
-    h->cm.assign(cm, cm + (size_t)C * C);
-    {  // FNV-1a of the contents: handles holding the same matrix share the projections of a shared cloud
-      unsigned long long id = 1469598103934665603ull ^ (unsigned long long)C;
-      const unsigned char* b = reinterpret_cast<const unsigned char*>(h->cm.data());
-      for (size_t i = 0; i < sizeof(double) * h->cm.size(); ++i) id = (id ^ b[i]) * 1099511628211ull;
-      h->cm_id = id;
-    }
-    HIPCHECK(h->d_cm.reserve((size_t)C * C));
-    HIPCHECK(hipMemcpyAsync(h->d_cm.p, h->cm.data(), sizeof(double) * C * C, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    return SICP_OK;
-  });
+  return abi_guard(h, [&]() -> int { return h ? set_confusion(h, C, cm, h->stream) : SICP_ERR_INVALID_ARGUMENT; });
 }
 
 int sicp_align(sicp_handle h, const double init_qt[7], double out_qt[7], int32_t* outer_iters, sicp_stats* stats) {
@@ -472,9 +426,9 @@ int sicp_accumulate_batch(sicp_handle* hs, int32_t n, const double* qt, double* 
       h->ts[0].h_batch[p].nb = nb;
       HIPCHECK(hipStreamSynchronize(g->stream));  // the pair's correspondences are complete
     }
-    *h->ts[0].h_bhdr = sicp::BatchHeader{n, 0u, 0u, 0};
-    HIPCHECK(hipMemcpyAsync(h->ts[0].d_bhdr.p, h->ts[0].h_bhdr, sizeof(sicp::BatchHeader), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(h->ts[0].d_batch.p, h->ts[0].h_batch, sizeof(sicp::BatchArgs) * n, hipMemcpyHostToDevice, h->stream));
+    *h->ts[0].h_bhdr.p = sicp::BatchHeader{n, 0u, 0u, 0};
+    HIPCHECK(hipMemcpyAsync(h->ts[0].d_bhdr.p, h->ts[0].h_bhdr.p, sizeof(sicp::BatchHeader), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->ts[0].d_batch.p, h->ts[0].h_batch.p, sizeof(sicp::BatchArgs) * n, hipMemcpyHostToDevice, h->stream));
     if (repeat < 1) repeat = 1;
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     for (int r = 0; r < repeat; ++r)
@@ -482,9 +436,9 @@ int sicp_accumulate_batch(sicp_handle* hs, int32_t n, const double* qt, double* 
                                              h->stream));
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     HIPCHECK(sicp::launch_finalize_batch(h->ts[0].d_batch.p, n, h->d_bout28.p, h->stream));
-    HIPCHECK(hipMemcpyAsync(h->h_bout28, h->d_bout28.p, sizeof(double) * 28 * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->h_bout28.p, h->d_bout28.p, sizeof(double) * 28 * n, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
-    std::memcpy(out28, h->h_bout28, sizeof(double) * 28 * n);
+    std::memcpy(out28, h->h_bout28.p, sizeof(double) * 28 * n);
     if (kernel_ms) {
       float ms = 0.f;
       HIPCHECK(hipEventElapsedTime(&ms, h->ev0, h->ev1));

@@ -82,14 +82,12 @@ int tickset_reserve(sicp_context* h, TickSet& S, int n) {
   n = std::max(32, (n + 31) / 32 * 32);  // capacity in steps of 32: the tick graph is keyed on it
   HIPCHECK(S.d_batch.reserve(n));
   HIPCHECK(S.d_bhdr.reserve(1));
-  if (!S.h_bhdr) HIPCHECK(hipHostMalloc((void**)&S.h_bhdr, sizeof(sicp::BatchHeader), hipHostMallocDefault));
+  HIPCHECK(S.h_bhdr.resize(1));
   HIPCHECK(S.d_join.reserve(n));
   if (S.cap < n) {
-    if (S.h_batch) (void)hipHostFree(S.h_batch);
-    if (S.h_join) (void)hipHostFree(S.h_join);
-    S.h_batch = nullptr; S.h_join = nullptr; S.cap = 0;
-    HIPCHECK(hipHostMalloc((void**)&S.h_batch, sizeof(sicp::BatchArgs) * n, hipHostMallocDefault));
-    HIPCHECK(hipHostMalloc((void**)&S.h_join, sizeof(sicp::LmJoin) * n, hipHostMallocDefault));
+    S.cap = 0;
+    HIPCHECK(S.h_batch.resize(n));
+    HIPCHECK(S.h_join.resize(n));
     S.cap = n;
   }
   return SICP_OK;
@@ -101,20 +99,21 @@ int batch_reserve(sicp_context* h, int n) {
   n = std::max(32, (n + 31) / 32 * 32);
   HIPCHECK(h->d_bstates.reserve(n));
   HIPCHECK(h->d_bout28.reserve((size_t)28 * n));
-  if (h->h_batch_cap < n) {
-    if (h->h_bstates) (void)hipHostFree(h->h_bstates);
-    if (h->h_bout28) (void)hipHostFree(h->h_bout28);
-    h->h_bstates = nullptr; h->h_bout28 = nullptr; h->h_batch_cap = 0;
-    HIPCHECK(hipHostMalloc((void**)&h->h_bstates, sizeof(sicp::LmState) * n, hipHostMallocCoherent));  // (also written by the persistent solve's master)
-    HIPCHECK(hipHostMalloc((void**)&h->h_bout28, sizeof(double) * 28 * n, hipHostMallocDefault));
-    h->h_batch_cap = n;
+  if (h->h_bstates.size() < (size_t)n) {  // (never shrunk: a smaller batch keeps the mirrors of a larger one)
+    HIPCHECK(h->h_bstates.resize(n));
+    HIPCHECK(h->h_bout28.resize((size_t)28 * n));
   }
   return SICP_OK;
 }
 
 // The searches / weights / feature kernels of the pairs between two solves run on a stream of their own beside the ticks
 // (with the device's lowest or highest queue priority it measured 10-13 % slower: DESIGN.md 3.1).
-hipError_t create_side_stream(hipStream_t* st) { return hipStreamCreateWithFlags(st, hipStreamNonBlocking); }
+int side_reserve(sicp_context* h) {
+  HIPCHECK(h->side_stream.create());
+  HIPCHECK(h->side_done.create());
+  HIPCHECK(h->main_done.create());
+  return SICP_OK;
+}
 
 // One TICK of a batch: `len` LM evaluations of every pair in `act` (pair indices), in one graph launch:
 // the accumulate kernel evaluates all of them at their current LM poses, lm_step_batch_kernel
@@ -132,7 +131,7 @@ int tick_launch(sicp_context* h, TickSet& S, hipStream_t M, sicp_handle* hs, int
       std::memcpy(J.start, start[p], sizeof J.start);
       J.opt = lm_options(hs[p]->params);
     }
-    HIPCHECK(hipMemcpyAsync(S.d_join.p, S.h_join, sizeof(sicp::LmJoin) * joining.size(), hipMemcpyHostToDevice, M));
+    HIPCHECK(hipMemcpyAsync(S.d_join.p, S.h_join.p, sizeof(sicp::LmJoin) * joining.size(), hipMemcpyHostToDevice, M));
     HIPCHECK(sicp::launch_lm_init(S.d_join.p, (int)joining.size(), h->d_bstates.p, M));
   }
   if (solo_evals > 0) {
@@ -166,13 +165,13 @@ int tick_launch(sicp_context* h, TickSet& S, hipStream_t M, sicp_handle* hs, int
     A.opt = lm_options(g->params);
     // the state also lands in the pinned mirror by the master's own stores, and the launch number in a pinned word the host
     // polls (solo_wait); the copy queued behind the kernel stays as the fallback (a launch that gave up writes neither)
-    if (!h->h_solo_flag) {
+    if (!h->h_solo_flag.p) {
       // fine-grained: visible to the CPU while the kernel runs.  Behind the word: the landing area of the fallback copy
-      HIPCHECK(hipHostMalloc((void**)&h->h_solo_flag, kSoloFallbackOffset + sizeof(sicp::LmState), hipHostMallocCoherent));
-      *h->h_solo_flag = 0;
+      HIPCHECK(h->h_solo_flag.resize((kSoloFallbackOffset + sizeof(sicp::LmState)) / sizeof(int)));
+      *h->h_solo_flag.p = 0;
     }
-    A.host_state = static_cast<sicp::LmCore*>(h->h_bstates + p);
-    A.host_flag = h->h_solo_flag;
+    A.host_state = static_cast<sicp::LmCore*>(h->h_bstates.p + p);
+    A.host_flag = h->h_solo_flag.p;
     h->solo_pair = p;
     h->solo_was_init = A.init != 0;
     S.tick_valid = false;  // (the argument array in HBM was not refreshed)
@@ -180,7 +179,7 @@ int tick_launch(sicp_context* h, TickSet& S, hipStream_t M, sicp_handle* hs, int
     // The fallback read-back lands in an area of its OWN: the host reads h_bstates[p] as soon as the polled word has changed,
     // while this copy may still be in flight behind the kernel -- it must not rewrite what the host is reading (solo_wait
     // moves it over when the poll did not see the word: a launch that gave up).
-    HIPCHECK(hipMemcpyAsync(reinterpret_cast<char*>(h->h_solo_flag) + kSoloFallbackOffset, h->d_bstates.p + p, sizeof(sicp::LmState), hipMemcpyDeviceToHost, M));
+    HIPCHECK(hipMemcpyAsync(reinterpret_cast<char*>(h->h_solo_flag.p) + kSoloFallbackOffset, h->d_bstates.p + p, sizeof(sicp::LmState), hipMemcpyDeviceToHost, M));
     return SICP_OK;
   }
   // the argument array in HBM only changes when the set of pairs inside a solve does
@@ -198,9 +197,9 @@ int tick_launch(sicp_context* h, TickSet& S, hipStream_t M, sicp_handle* hs, int
     B.nb = nb;
   }
   if (!same_set) {
-    *S.h_bhdr = sicp::BatchHeader{(int)act.size(), 0u, 0u, 0};
-    HIPCHECK(hipMemcpyAsync(S.d_bhdr.p, S.h_bhdr, sizeof(sicp::BatchHeader), hipMemcpyHostToDevice, M));
-    HIPCHECK(hipMemcpyAsync(S.d_batch.p, S.h_batch, sizeof(sicp::BatchArgs) * act.size(), hipMemcpyHostToDevice, M));
+    *S.h_bhdr.p = sicp::BatchHeader{(int)act.size(), 0u, 0u, 0};
+    HIPCHECK(hipMemcpyAsync(S.d_bhdr.p, S.h_bhdr.p, sizeof(sicp::BatchHeader), hipMemcpyHostToDevice, M));
+    HIPCHECK(hipMemcpyAsync(S.d_batch.p, S.h_batch.p, sizeof(sicp::BatchArgs) * act.size(), hipMemcpyHostToDevice, M));
     S.tick_act = act;
     S.tick_valid = true;
   }
@@ -225,7 +224,7 @@ int tick_launch(sicp_context* h, TickSet& S, hipStream_t M, sicp_handle* hs, int
     h->st.graph_builds += built;
     HIPCHECK(hipGraphLaunch(graph.exec, M));
   }
-  HIPCHECK(hipMemcpyAsync(h->h_bstates + lo, h->d_bstates.p + lo, sizeof(sicp::LmState) * (hi - lo), hipMemcpyDeviceToHost, M));
+  HIPCHECK(hipMemcpyAsync(h->h_bstates.p + lo, h->d_bstates.p + lo, sizeof(sicp::LmState) * (hi - lo), hipMemcpyDeviceToHost, M));
   return SICP_OK;
 }
 
@@ -240,8 +239,8 @@ int tick_wait(sicp_context* h, hipStream_t M) {
 // word (SoloArgs::host_flag) -- the host polls that word (bounded) instead of waiting for the read-back copy queued behind
 // the kernel; whatever the poll does not see (a launch that gave up) the stream wait catches.
 int solo_wait(sicp_context* h, hipStream_t M) {
-  if (h->h_solo_flag) {
-    volatile int* flag = h->h_solo_flag;
+  if (h->h_solo_flag.p) {
+    volatile int* flag = h->h_solo_flag.p;
     for (int spins = 0; *flag != h->solo_seq; ++spins) {
       // every ~20 us: has everything queued on M ended without the word changing?  Then the launch gave up (or the
       // word is not coming): stop polling.
@@ -259,8 +258,8 @@ int solo_wait(sicp_context* h, hipStream_t M) {
     }
   }
   HIPCHECK(hipStreamSynchronize(M));
-  if (h->h_solo_flag && h->solo_pair >= 0)
-    std::memcpy(static_cast<void*>(h->h_bstates + h->solo_pair), reinterpret_cast<const char*>(h->h_solo_flag) + kSoloFallbackOffset, sizeof(sicp::LmState));
+  if (h->h_solo_flag.p && h->solo_pair >= 0)
+    std::memcpy(static_cast<void*>(h->h_bstates.p + h->solo_pair), reinterpret_cast<const char*>(h->h_solo_flag.p) + kSoloFallbackOffset, sizeof(sicp::LmState));
   return SICP_OK;
 }
 
@@ -521,11 +520,7 @@ int align_batch(sicp_handle* hs, int32_t n, const double* init_qt, double* out_q
     sicp_context* h = L;
     SICPCHECK(batch_reserve(h, n));
     h->ts[0].tick_valid = false;
-    if (!h->side_stream) {
-      HIPCHECK(create_side_stream(&h->side_stream));
-      HIPCHECK(hipEventCreateWithFlags(&h->side_done, hipEventDisableTiming));
-      HIPCHECK(hipEventCreateWithFlags(&h->main_done, hipEventDisableTiming));
-    }
+    SICPCHECK(side_reserve(h));
   }
   BatchRun run;
   run.L = L; run.hs = hs; run.P = P; run.one_launch = one_launch; run.want_stats = stats != nullptr;
@@ -542,13 +537,10 @@ int align_batch(sicp_handle* hs, int32_t n, const double* init_qt, double* out_q
     }
   if (staged) {
     sicp_context* h = L;
-    if (!h->feat_stream) HIPCHECK(hipStreamCreateWithFlags(&h->feat_stream, hipStreamNonBlocking));
+    HIPCHECK(h->feat_stream.create());
     const int n_chunks = (n + kStartChunk - 1) / kStartChunk;
-    while ((int)h->chunk_ev.size() < n_chunks) {
-      hipEvent_t e = nullptr;
-      HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      h->chunk_ev.push_back(e);
-    }
+    if ((int)h->chunk_ev.size() < n_chunks) h->chunk_ev.resize((size_t)n_chunks);
+    for (int c = 0; c < n_chunks; ++c) HIPCHECK(h->chunk_ev[(size_t)c].create());
     run.chunk_ev.assign(h->chunk_ev.begin(), h->chunk_ev.begin() + n_chunks);
     guard.retarget(h->feat_stream);
     for (int c = 0; c < n_chunks; ++c) {
@@ -593,7 +585,7 @@ int align_batch(sicp_handle* hs, int32_t n, const double* init_qt, double* out_q
       grp[g].S = &h->ts[g];
       SICPCHECK(tickset_reserve(h, h->ts[g], grp[g].hi - grp[g].lo));
       h->ts[g].tick_valid = false;
-      if (g == 1 && !h->side_done2) HIPCHECK(hipEventCreateWithFlags(&h->side_done2, hipEventDisableTiming));
+      if (g == 1) HIPCHECK(h->side_done2.create());
       grp[g].side_done = g == 0 ? h->side_done : h->side_done2;
     }
   }

@@ -136,15 +136,16 @@ int run_nn(sicp_context* h, int K, const Cloud& Qc, int q_begin, int q_count, co
 }
 
 // ---- per-point normals (+ label histograms) ----------------------------------------------------
-int ensure_hval(sicp_context* h, int k) {
+int ensure_hval(sicp_context* h, int k, hipStream_t st) {
+  if (!st) st = h->stream;
   if (h->hval_k == k && h->d_hval.p) return SICP_OK;
   std::vector<double> hv(k + 1);
   const double increment = 1.0 / (double)k;  // em_icp.hpp:279
   double acc = 0.0;
   for (int c = 0; c <= k; ++c) { hv[c] = acc; acc += increment; }  // em_icp.hpp:301, repeated +=
   HIPCHECK(h->d_hval.reserve(k + 1));
-  HIPCHECK(hipMemcpyAsync(h->d_hval.p, hv.data(), sizeof(double) * (k + 1), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
+  HIPCHECK(hipMemcpyAsync(h->d_hval.p, hv.data(), sizeof(double) * (k + 1), hipMemcpyHostToDevice, st));
+  HIPCHECK(hipStreamSynchronize(st));
   h->hval_k = k;
   return SICP_OK;
 }
@@ -433,9 +434,9 @@ int eval28(sicp_context* h, const double* qt, double* out28) {
   fill_acc(h, B.a);
   fill_pose(qt, B.a.pose);
   B.nb = nb;
-  *h->ts[0].h_bhdr = sicp::BatchHeader{1, 0u, 0u, 0};
-  HIPCHECK(hipMemcpyAsync(h->ts[0].d_bhdr.p, h->ts[0].h_bhdr, sizeof(sicp::BatchHeader), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipMemcpyAsync(h->ts[0].d_batch.p, h->ts[0].h_batch, sizeof(sicp::BatchArgs), hipMemcpyHostToDevice, h->stream));
+  *h->ts[0].h_bhdr.p = sicp::BatchHeader{1, 0u, 0u, 0};
+  HIPCHECK(hipMemcpyAsync(h->ts[0].d_bhdr.p, h->ts[0].h_bhdr.p, sizeof(sicp::BatchHeader), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->ts[0].d_batch.p, h->ts[0].h_batch.p, sizeof(sicp::BatchArgs), hipMemcpyHostToDevice, h->stream));
   if (general_covariances(h)) {
     // caller covariances of general form: the literal cost function on full 3x3 matrices, the same columns for the same sum
     sicp::GenAccArgs g;
@@ -454,9 +455,9 @@ int eval28(sicp_context* h, const double* qt, double* out28) {
     h->st.acc_kernel_ms += kt.stop();
   }
   HIPCHECK(sicp::launch_finalize_batch(h->ts[0].d_batch.p, 1, h->d_bout28.p, h->stream));
-  HIPCHECK(hipMemcpyAsync(h->h_bout28, h->d_bout28.p, sizeof(double) * 28, hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->h_bout28.p, h->d_bout28.p, sizeof(double) * 28, hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
-  std::memcpy(out28, h->h_bout28, sizeof(double) * 28);
+  std::memcpy(out28, h->h_bout28.p, sizeof(double) * 28);
   h->st.total_evals++;
   return SICP_OK;
 }
@@ -525,7 +526,7 @@ void outer_finish(const sicp_params& P, OuterState& o) {
 int align_end(sicp_context* h, const OuterState& o, double t_begin, int32_t* outer_iters, sicp_stats* stats) {
   h->count_stats = false;
   if (stats) {
-    HIPCHECK(hipMemcpyAsync(h->h_count, h->d_count.p, sizeof(long long) * sicp::kLiveCounters, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->h_count.p, h->d_count.p, sizeof(long long) * sicp::kLiveCounters, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     h->st.total_active = 0;
     for (int k = 0; k < sicp::kLiveCounters; ++k) h->st.total_active += h->h_count[k];
@@ -563,11 +564,11 @@ int flush_jobs(sicp_context* h, JobCollector& jc, hipStream_t base) {
   const bool fork = n_used > 1 || (n_used == 1 && !used[0]);
   if (fork) {
     for (int s = 1; s < kParts; ++s)
-      if (used[s] && !h->part_stream[s]) {
-        HIPCHECK(hipStreamCreateWithFlags(&h->part_stream[s], hipStreamNonBlocking));
-        HIPCHECK(hipEventCreateWithFlags(&h->part_done[s], hipEventDisableTiming));
+      if (used[s]) {
+        HIPCHECK(h->part_stream[s].create());
+        HIPCHECK(h->part_done[s].create());
       }
-    if (!h->part_fork) HIPCHECK(hipEventCreateWithFlags(&h->part_fork, hipEventDisableTiming));
+    HIPCHECK(h->part_fork.create());
     HIPCHECK(hipEventRecord(h->part_fork, base));
   }
   for (int s = 0; s < kParts; ++s) {

@@ -42,7 +42,7 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
   run.len = std::min(S->params.lm_batch > 0 ? S->params.lm_batch : 8, sicp::kMaxBatchLen);
   run.side = L->side_stream;
   TickGroup G;
-  G.lo = 0; G.hi = S->cap; G.M = S->own1[0]; G.S = &L->ts[0]; G.side_done = L->side_done;
+  G.lo = 0; G.hi = S->cap; G.M = L->own_stream; G.S = &L->ts[0]; G.side_done = L->side_done;
   JobCollector jc;
   for (sicp_context* g : S->slots) g->collect = &jc;
   std::vector<int> free_slots;
@@ -65,7 +65,7 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
   constexpr int kMaxOvertaken = 48;  // worker turns (a turn = one tick of ~4 LM evaluations)
   std::unordered_set<const Cloud*> held, round_clouds;  // (hash sets: the scan below runs under S->m once per worker turn)
   bool round_rewrites = false, order_needed = false;
-  hipEvent_t tick_ev = nullptr;  // recorded on M behind the tick in flight when a rewrite has to wait for it
+  OwnedEvent tick_ev;  // recorded on M behind the tick in flight when a rewrite has to wait for it
   auto release_users = [&](const Cloud* a, const Cloud* b) {
     for (const Cloud* c : {a, b}) {
       auto it = users.find(c);
@@ -86,7 +86,6 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
       std::unique_lock<std::mutex> lock(S->m);
       S->cv_work.wait(lock, [&] { return S->stop || !S->queue.empty() || S->in_flight > 0; });
       if (S->stop) {
-        if (tick_ev) (void)hipEventDestroy(tick_ev);
         for (size_t i = 0; i < dbg_log.size(); i += std::max<size_t>(1, dbg_log.size() / 40))
           std::fprintf(stderr, "[stream] t %.1f ms completed %.0f ticks %.0f waited %.1f ms pairs-per-tick %.1f solo-allowed %.0f | host ms: admit %.1f flush %.1f turn %.1f (of which waited; searches %.1f, tick launch %.1f)\n",
                        dbg_log[i][0], dbg_log[i][1], dbg_log[i][2], dbg_log[i][3], dbg_log[i][4], dbg_log[i][5], dbg_log[i][6], dbg_log[i][7], dbg_log[i][8], dbg_log[i][9], dbg_log[i][10]);
@@ -190,7 +189,7 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
     dbg_admit_ms += t_flush0 - t_admit0;
     if (!fresh.empty()) {
       if (order_needed) {  // the rewrite waits for the tick that may be reading the shared cloud ...
-        hipError_t e = tick_ev ? hipSuccess : hipEventCreateWithFlags(&tick_ev, hipEventDisableTiming);
+        hipError_t e = tick_ev.create();
         if (e == hipSuccess) e = hipEventRecord(tick_ev, G.M);
         if (e == hipSuccess) e = hipStreamWaitEvent(run.side, tick_ev, 0);
         if (e != hipSuccess) { stream_fail(S, SICP_ERR_HIP, std::string("stream: ordering a feature rewrite: ") + hipGetErrorString(e)); return; }
@@ -269,7 +268,7 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
           hipError_t e = rc == SICP_OK ? h->h_labels.resize((size_t)(n > 0 ? n : 1)) : hipSuccess;
           if (rc == SICP_OK && e == hipSuccess && n > 0)
             e = hipMemcpyAsync(h->h_labels.data(), h->tmpl.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, run.side);
-          if (rc == SICP_OK && e == hipSuccess && !S->slot_ev[p]) e = hipEventCreateWithFlags(&S->slot_ev[p], hipEventDisableTiming);
+          if (rc == SICP_OK && e == hipSuccess) e = S->slot_ev[p].create();
           if (rc == SICP_OK && e == hipSuccess) e = hipEventRecord(S->slot_ev[p], run.side);
           if (rc != SICP_OK || e != hipSuccess) { stream_fail(S, rc != SICP_OK ? rc : SICP_ERR_HIP, rc != SICP_OK ? h->last_error : std::string("fused labels: ") + hipGetErrorString(e)); return; }
         }
@@ -294,7 +293,7 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
       if (run.phase[p] == PAIR_PASS) {
         // (one stream carries both passes, the covariance sweep last: its event covers the labels of the same slot)
         const bool with_cov = (S->slot_flags[p] & SICP_SUBMIT_POSE_COVARIANCE) != 0, with_labels = (S->slot_flags[p] & SICP_SUBMIT_FUSED_LABELS) != 0;
-        const hipEvent_t ev = with_cov ? stream_cov_event(S, p) : S->slot_ev[p];
+        const hipEvent_t ev = with_cov ? stream_cov_event(S, p) : S->slot_ev[p].get();
         const hipError_t q = hipEventQuery(ev);
         if (q == hipErrorNotReady) { if (!pass_waiting) pass_waiting = ev; continue; }
         if (q != hipSuccess) { stream_fail(S, SICP_ERR_HIP, std::string(with_cov ? "pose covariance: " : "fused labels: ") + hipGetErrorString(q)); return; }
@@ -398,11 +397,7 @@ int sicp_stream_create(int device_id, const sicp_params* params, int32_t max_in_
     S->params.reuse_features = 1;  // a stream's cloud keeps its normals / histograms: computed with its first registration
     S->params.lm_on_device = params->lm_on_device == 2 ? 2 : 1;  // (2: never the persistent solve)
     auto cleanup = [&](int rc) {
-      for (size_t k = 0; k < S->slots.size(); ++k) {
-        sicp_context* g = S->slots[k];
-        g->collect = nullptr; g->stream = S->own1[k]; g->stream2 = S->own2[k];
-        sicp_destroy(g);
-      }
+      for (sicp_context* g : S->slots) sicp_destroy(g);
       if (S->uploader) sicp_destroy(S->uploader);
       return rc;
     };
@@ -415,8 +410,6 @@ int sicp_stream_create(int device_id, const sicp_params* params, int32_t max_in_
       rc = sicp_create(device_id, &g);
       if (rc != SICP_OK) return cleanup(rc);
       S->slots.push_back(g);
-      S->own1.push_back(g->stream);
-      S->own2.push_back(g->stream2);
       rc = sicp_set_params(g, &S->params);
       if (rc != SICP_OK) return cleanup(rc);
     }
@@ -425,19 +418,16 @@ int sicp_stream_create(int device_id, const sicp_params* params, int32_t max_in_
       rc = batch_reserve(h, S->cap);
       if (rc != SICP_OK) return cleanup(rc);
       h->ts[0].tick_valid = false;
-      if (!h->side_stream) {
-        if (create_side_stream(&h->side_stream) != hipSuccess ||
-            hipEventCreateWithFlags(&h->side_done, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h->main_done, hipEventDisableTiming) != hipSuccess)
-          return cleanup(SICP_ERR_HIP);
-      }
-      // every slot's own launches (memsets of the semantic search, cloud waits) go to the side stream
+      rc = side_reserve(h);
+      if (rc != SICP_OK) return cleanup(rc);
+      // every slot's own launches (memsets of the semantic search, cloud waits) go to the side stream, borrowed until the
+      // slot is destroyed (sicp_context::reset_use)
       for (sicp_context* g : S->slots) { g->stream = h->side_stream; g->stream2 = h->side_stream; g->wait_on_device = true; }
     }
     S->slot_ticket.assign(S->cap, 0);
     S->slot_t0.assign(S->cap, 0.0);
     S->slot_flags.assign(S->cap, 0u);
-    S->slot_ev.assign(S->cap, nullptr);
+    S->slot_ev.resize((size_t)S->cap);
     S->slot_cov_stage.assign(S->cap, -1);
     S->slot_cov_row.assign(S->cap, 0);
     S->worker = std::thread(stream_worker, S.get());
@@ -459,18 +449,12 @@ int sicp_stream_destroy(sicp_stream S) {
     if (S->worker.joinable()) S->worker.join();
     (void)hipSetDevice(S->device);
     if (!S->slots.empty() && S->slots[0]->side_stream) (void)hipStreamSynchronize(S->slots[0]->side_stream);
-    for (size_t k = 0; k < S->slots.size(); ++k) (void)hipStreamSynchronize(S->own1[k]);
+    for (sicp_context* g : S->slots) (void)hipStreamSynchronize(g->own_stream);
     if (S->uploader) (void)hipStreamSynchronize(S->uploader->stream);
     // the clouds go back to the pool once nothing refers to them: settle their uploads while the upload stream exists
     for (auto& kv : S->clouds) settle_cloud(*kv.second);
     for (auto& q : S->queue) { settle_cloud(*q.src); settle_cloud(*q.tgt); }
-    for (size_t k = 0; k < S->slots.size(); ++k) {
-      sicp_context* g = S->slots[k];
-      g->collect = nullptr; g->stream = S->own1[k]; g->stream2 = S->own2[k];
-      sicp_destroy(g);
-    }
-    for (hipEvent_t e : S->slot_ev)
-      if (e) (void)hipEventDestroy(e);
+    for (sicp_context* g : S->slots) sicp_destroy(g);
     stream_cov_destroy(S, true);  // (the side stream has been waited for)
     S->clouds.clear();
     S->queue.clear();
@@ -500,14 +484,10 @@ int sicp_stream_set_confusion(sicp_stream S, int32_t C, const double* cm) {
       std::lock_guard<std::mutex> lock(S->m);
       if (S->submitted > 0) return SICP_ERR_INVALID_ARGUMENT;  // before the first registration
     }
-    for (size_t k = 0; k < S->slots.size(); ++k) {
-      // (sicp_set_confusion uploads on the handle's stream and waits for it: the slot's own stream, not the side stream)
-      sicp_context* g = S->slots[k];
-      hipStream_t keep = g->stream;
-      g->stream = S->own1[k];
-      int rc = sicp_set_confusion(g, C, cm);
-      if (rc == SICP_OK) rc = ensure_hval(g, S->params.k_cov);  // (one small upload + wait per slot, here rather than in the worker)
-      g->stream = keep;
+    for (sicp_context* g : S->slots) {
+      // (the uploads run on the slot's own stream and are waited for: not on the side stream it launches on)
+      int rc = set_confusion(g, C, cm, g->own_stream);
+      if (rc == SICP_OK) rc = ensure_hval(g, S->params.k_cov, g->own_stream);  // (one small upload + wait per slot, here rather than in the worker)
       if (rc != SICP_OK) return rc;
     }
     return sicp_set_confusion(S->uploader, C, cm);
