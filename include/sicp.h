@@ -669,6 +669,46 @@ int sicp_map_extract(sicp_map m, const sicp_map_extract_params* p, sicp_handle d
                      float* x, float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist,
                      sicp_map_extract_info* info /* nullable */);
 
+/* ---- the map's labels through the confusion matrix ------------------------------
+ * sicp_map_extract's label is a majority vote.  With a confusion matrix the map gives the maximum a-posteriori class of a
+ * voxel under a uniform prior, and its posterior probability: for a histogram row h[0..C] and L[r][s] = log cm[r*C + s],
+ *     score_s = 0.0;  for r = 1..C ascending, where h[r] > 0:  score_s = score_s + (double)h[r] * L[r-1][s-1]
+ * (product and sum rounded once each, no contraction; the order is the specification).  Bin 0, "unlabelled", never
+ * contributes.  No evidence: no term was added, or the largest score is -inf (every class is ruled out by a zero entry).
+ * Otherwise the fused label is the smallest s whose score is the largest, and
+ *     confidence = 1 / sum_s exp(score_s - max)
+ * in double, summed in this fixed tree: the scoring lanes' own classes (lane j of the map's 64, or of the power of two >= C
+ * when C < 64, owns s = j+1, j+1+64, ...) in ascending s, then pairs of lanes at distance 1, 2, 4, ...  No float atomics: two
+ * runs give the same bytes.
+ *
+ * sicp_map_set_confusion: cm[r*C + s] as sicp_set_confusion has it (observed label r+1, class s+1).  May be called at any
+ * time and replaces the previous matrix.  Zero entries are allowed (log 0 = -inf).  SICP_ERR_INVALID_ARGUMENT, the map and any
+ * earlier matrix unchanged: a NULL pointer; a map with num_classes = 0; C != num_classes; an entry that is negative or not
+ * finite (sicp_map_last_error names it).  The logarithms are taken on the host (double, libm) and only they go to the device,
+ * into an arena buffer (sicp_set_memory_limit applies). */
+int sicp_map_set_confusion(sicp_map m, int32_t C, const double* cm_rowmajor);
+/* sicp_map_extract with the fused label in label[j] and its confidence in confidence[j] (0 and 0.0 for a voxel without
+ * evidence): the same selection and order under the same p, the same x, y, z, count and info, the same capacity, dst (the slot
+ * becomes what sicp_set_cloud of these arrays makes it) and n_out = 0 rules, the same refusals.  SICP_ERR_NOT_READY: no matrix
+ * has been set.  SICP_ERR_INVALID_ARGUMENT: num_classes = 0.  The map is not modified. */
+int sicp_map_extract_fused(sicp_map m, const sicp_map_extract_params* p, sicp_handle dst /* nullable */, int dst_which,
+                           int32_t capacity, float* x, float* y, float* z, uint32_t* label, uint32_t* count,
+                           double* confidence, sicp_map_extract_info* info /* arrays and info nullable */);
+/* getFusedLabels against the map: a label and a confidence for every one of the slot's n_points (sicp_cloud_size), in caller
+ * order whatever the handle's mode and layout.  A point that is not finite gets label 0 and confidence 0 (sicp_fused_labels'
+ * rule).  A finite point is transformed by qt and keyed exactly as sicp_map_integrate does, without a crop; a coordinate beyond
+ * the key's range means "not in the map", it is not an error.  Evidence: the row of the point's voxel when the map holds it
+ * with count >= min_count; then, added last, the one term L[own-1][s-1] when include_own_label is 1, the cloud has labels and
+ * the point's label is in 1..C (the reference multiplies source and target distributions; this is the analogue).  With
+ * evidence: the fused label and confidence as above.  Without: the point's own label (0 when the cloud has none) and
+ * confidence 0.  SICP_ERR_BAD_LABEL, nothing written: include_own_label is set and a finite point's label is above
+ * num_classes.  SICP_ERR_INVALID_ARGUMENT, nothing written: a NULL map, handle or out_labels; `which` outside the two slots;
+ * a flag that is neither 0 nor 1; min_count < 1; a pose that is not finite; a handle on another device; num_classes = 0.
+ * SICP_ERR_NOT_READY: no matrix has been set, or the slot holds no cloud.  Neither the handle nor the map changes. */
+int sicp_map_fused_labels(sicp_map m, sicp_handle h, int which, const double qt[7] /* NULL = identity */,
+                          int32_t include_own_label, int32_t min_count, uint32_t* out_labels,
+                          double* out_confidence /* nullable */);
+
 /* test / bench hook: the keypoints of cloud `which` with their normals, FPFH features and feature-radius
  * neighbour lists (CSR: nbr_offsets[n + 1], nbr_idx sorted by (d^2, index)).  Counts are always written; an output
  * array is written when it is non-NULL and its capacity (points / neighbour entries) suffices, otherwise the call

@@ -411,6 +411,10 @@ def lib():
             "sicp_map_prune": [C.c_void_p, _dp, C.c_double, C.POINTER(C.c_int64)],
             "sicp_map_extract": [C.c_void_p, C.POINTER(SicpMapExtractParams), C.c_void_p, C.c_int, C.c_int32, _fp, _fp, _fp, _up, _up, _up,
                                  C.POINTER(SicpMapExtractInfo)],
+            "sicp_map_set_confusion": [C.c_void_p, C.c_int32, _dp],
+            "sicp_map_extract_fused": [C.c_void_p, C.POINTER(SicpMapExtractParams), C.c_void_p, C.c_int, C.c_int32, _fp, _fp, _fp, _up, _up,
+                                       _dp, C.POINTER(SicpMapExtractInfo)],
+            "sicp_map_fused_labels": [C.c_void_p, C.c_void_p, C.c_int, _dp, C.c_int32, C.c_int32, _up, _dp],
         }.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
@@ -1043,6 +1047,57 @@ class VoxelMap:
             "hist": None if hist is None else hist[:m].copy(),
             "info": info.as_dict(),
         }
+
+    def set_confusion(self, cm):
+        """sicp_map_set_confusion: cm[r, s] = how often a point of class s + 1 is observed with label r + 1 ([C, C], C the map's
+        num_classes; zero entries allowed).  Replaces the matrix set before."""
+        cm = np.ascontiguousarray(cm, dtype=np.float64)
+        if cm.ndim != 2 or cm.shape[0] != cm.shape[1]:
+            raise ValueError("the confusion matrix must be square")
+        self._check(lib().sicp_map_set_confusion(self._m, cm.shape[0], _ptr(cm, _dp)), "sicp_map_set_confusion")
+
+    def extract_fused(self, min_count: int = 1, crop_center=None, crop_range: float = 0.0, dst: "Engine | None" = None,
+                      dst_which: int = TARGET, want_points: bool = True):
+        """sicp_map_extract_fused: extract()'s selection, order, points and counts, with the maximum a-posteriori class under the
+        confusion matrix as the label and its posterior probability (0 and 0.0 for a voxel without evidence).  Returns {"xyz",
+        "labels", "count", "confidence", "info"}; with want_points=False no arrays are asked for."""
+        p = default_map_extract_params(min_count=min_count, crop_range=crop_range,
+                                       crop_center=(0.0, 0.0, 0.0) if crop_center is None else tuple(crop_center))
+        cap = 0
+        x = y = z = lab = cnt = conf = None
+        if want_points:
+            cap = self.size()[0]
+            x, y, z = (np.empty(max(cap, 1), dtype=np.float32) for _ in range(3))
+            lab, cnt = (np.empty(max(cap, 1), dtype=np.uint32) for _ in range(2))
+            conf = np.empty(max(cap, 1), dtype=np.float64)
+        info = SicpMapExtractInfo()
+        self._check(lib().sicp_map_extract_fused(self._m, C.byref(p), None if dst is None else dst._h, dst_which, cap, _ptr(x, _fp),
+                                                 _ptr(y, _fp), _ptr(z, _fp), _ptr(lab, _up), _ptr(cnt, _up), _ptr(conf, _dp), C.byref(info)),
+                    "sicp_map_extract_fused")
+        if dst is not None:
+            dst.n[dst_which] = info.n_out
+        m = info.n_out
+        return {
+            "xyz": None if x is None else np.stack([x[:m], y[:m], z[:m]], axis=1),
+            "labels": None if lab is None else lab[:m].copy(),
+            "count": None if cnt is None else cnt[:m].copy(),
+            "confidence": None if conf is None else conf[:m].copy(),
+            "info": info.as_dict(),
+        }
+
+    def fused_labels(self, engine: "Engine", which: int = SOURCE, qt=None, include_own: bool = True, min_count: int = 1,
+                     want_confidence: bool = True):
+        """sicp_map_fused_labels: every point of engine's slot `which` (caller order), at pose qt (None: identity), relabelled
+        from the voxel it falls into -- the voxel's histogram (when it has min_count points) and, with include_own, the point's
+        own label as one more observation, through the confusion matrix.  Returns (labels, confidence); confidence is None
+        with want_confidence=False.  A point without evidence keeps its own label with confidence 0."""
+        q = None if qt is None else np.ascontiguousarray(qt, dtype=np.float64).reshape(7)
+        n = engine.cloud_size(which)[0]
+        labels = np.empty(max(n, 1), dtype=np.uint32)
+        conf = np.empty(max(n, 1), dtype=np.float64) if want_confidence else None
+        self._check(lib().sicp_map_fused_labels(self._m, engine._h, which, _ptr(q, _dp), int(bool(include_own)), min_count,
+                                                _ptr(labels, _up), _ptr(conf, _dp)), "sicp_map_fused_labels")
+        return labels[:n].copy(), None if conf is None else conf[:n].copy()
 
     def prune(self, center, range):
         """sicp_map_prune: drops the voxels whose centroid lies further than `range` from `center`; returns their number"""

@@ -590,8 +590,10 @@ struct sicp_map_ctx {
   int cur = 0;               // the set that holds the map
   long long n_voxels = 0;    // <= 2^31 - 1
   unsigned long long n_points = 0;  // <= 2^32 - 1: no row's count can overflow
+  DevBuf<double> logcm;      // sicp_map_set_confusion: log cm[r][s], num_classes^2 doubles (the host takes the logarithms)
+  bool has_cm = false;
   HostBuf<unsigned char> stage;  // pinned: the counts' read-back
-  HostBuf<uint32_t> out;         // pinned: an extract's result (x | y | z | label | count | hist rows) on its way out
+  HostBuf<uint32_t> out;         // pinned: an extract's result (x | y | z | label | count | hist rows | confidence) on its way out
   std::string last_error;
 };
 
@@ -909,6 +911,11 @@ int map_integrate(sicp_map_ctx* m, sicp_context* h, int which, const double* qt,
 int map_prune(sicp_map_ctx* m, const double* center, double range, int64_t* n_removed);
 int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
                 float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info);
+int map_set_confusion(sicp_map_ctx* m, int32_t C, const double* cm);
+int map_extract_fused(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
+                      float* y, float* z, uint32_t* label, uint32_t* count, double* confidence, sicp_map_extract_info* info);
+int map_fused_labels(sicp_map_ctx* m, sicp_context* h, int which, const double* qt, int32_t include_own_label, int32_t min_count,
+                     uint32_t* out_labels, double* out_confidence);
 
 }  // namespace host
 }  // namespace sicp

@@ -547,6 +547,39 @@ struct MapSelectArgs {
 hipError_t launch_map_select(const MapSelectArgs& a, hipStream_t st);
 hipError_t launch_map_prune(const MapSelectArgs& a, hipStream_t st);
 hipError_t launch_map_extract(const MapSelectArgs& a, hipStream_t st);
+// label fusion through the confusion matrix (sicp_map_extract_fused, sicp_map_fused_labels).  logcm[r * C + s] = log cm[r][s]
+// (observed label r + 1, class s + 1; -inf for a zero entry).  A histogram row's score of class s is the sum over its
+// non-zero bins r = 1..C, ascending, of (double)h[r] * logcm[r - 1][s - 1], each product and each sum rounded once.  An item
+// (a voxel, a point) is scored by map_fuse_width(C) neighbouring lanes of a wave, lane j of them owning the classes j + 1,
+// j + 1 + 64, ...: it walks the row's non-zero bins, never C^2 products.  Up to kMapFuseLdsClasses classes every workgroup
+// stages logcm in LDS (8 * 64 * 64 bytes = 32 KiB); above, it reads it from global memory.  The same arithmetic either way.
+constexpr int kMapFuseLdsClasses = 64;
+inline int map_fuse_width(int C) {  // lanes per item: the power of two >= C in 4..64
+  int w = 4;
+  while (w < C && w < 64) w <<= 1;
+  return w;
+}
+struct MapFuseArgs {
+  const double* logcm;      // [C][C]
+  int C, stride;            // stride = C + 1
+  MapRows rows;
+  int n_map;
+  // extract: the selected rows (src_of[j] for j < res[kMapOut], written by launch_map_extract on the same stream)
+  const int* src_of;
+  const int* res_in;
+  // relabel: the scan's finite points in caller order, their labels (nullptr: none), the pose
+  const float *x, *y, *z;
+  const uint32_t* label;
+  double M[12];
+  int n, include_own;
+  long long min_count;
+  float inv_leaf;
+  int* res;                 // relabel: res[kMapBadLabel] (zeroed before the launch)
+  uint32_t* olabel;         // [items] the fused label; without evidence 0 (extract) / the point's own label (relabel)
+  double* oconf;            // [items] its posterior probability; 0 without evidence
+};
+hipError_t launch_map_posterior(const MapFuseArgs& a, hipStream_t st);  // olabel, oconf of the selected rows
+hipError_t launch_map_relabel(const MapFuseArgs& a, hipStream_t st);    // olabel, oconf of the n points; res[kMapBadLabel]
 
 // ---- initial alignment without a pose prior (bootstrap_kernels.hip; driver: bootstrap.cpp) ----
 constexpr int kBootMaxK = 16;  // feature neighbours per source keypoint (k_correspondences)

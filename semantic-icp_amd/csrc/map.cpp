@@ -23,13 +23,14 @@ struct MapScratch {
   DevBuf<unsigned char> temp;
   DevBuf<float> tx, ty, tz, gx, gy, gz, ox, oy, oz;
   DevBuf<uint32_t> ol, oc, ohist;
+  DevBuf<double> oconf;
   DevBuf<unsigned long long> key, key2, miss_key, total;
   DevBuf<int> val, val2, flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res;
   int device = -1;
   bool idle = true;
   ~MapScratch() {
-    DevArena::release_scratch(device, idle, temp, tx, ty, tz, gx, gy, gz, ox, oy, oz, ol, oc, ohist, key, key2, miss_key, total, val, val2,
-                              flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res);
+    DevArena::release_scratch(device, idle, temp, tx, ty, tz, gx, gy, gz, ox, oy, oz, ol, oc, ohist, oconf, key, key2, miss_key, total, val,
+                              val2, flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res);
   }
 };
 
@@ -344,11 +345,15 @@ int map_prune(sicp_map_ctx* m, const double* center, double range, int64_t* n_re
   return SICP_OK;
 }
 
-int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
-                float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info) {
+// sicp_map_extract and sicp_map_extract_fused (`confidence_wanted`): the selection, the order, the centroids and counts, the
+// capacity rule, dst and info are one code; the fused call replaces the arg-max label by the posterior's and adds its probability
+static int extract_rows(sicp_map_ctx* m, const char* call, bool fused, const sicp_map_extract_params* p, sicp_context* dst, int dst_which,
+                        int32_t capacity, float* x, float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist,
+                        double* confidence, sicp_map_extract_info* info) {
   if (!m) return SICP_ERR_INVALID_ARGUMENT;
+  const std::string name = call;
   auto refuse = [&](const std::string& why) {
-    m->last_error = "sicp_map_extract: " + why + "; nothing was done";
+    m->last_error = name + ": " + why + "; nothing was done";
     return SICP_ERR_INVALID_ARGUMENT;
   };
   if (!p) return refuse("the params are NULL");
@@ -359,6 +364,11 @@ int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context*
     if (!std::isfinite(p->crop_center[d])) return refuse("crop_center must be finite");
   const int C = m->params.num_classes, stride = stride_of(m);
   if (hist && C == 0) return refuse("the map keeps no labels: there are no histograms");
+  if (fused && C == 0) return refuse("the map keeps no labels: there is nothing to fuse");
+  if (fused && !m->has_cm) {
+    m->last_error = name + ": no confusion matrix has been set (sicp_map_set_confusion)";
+    return SICP_ERR_NOT_READY;
+  }
   const double t_begin = now_ms();
   MAPCHECK(hipSetDevice(m->device));
   hipStream_t st = m->stream;
@@ -376,6 +386,7 @@ int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context*
     MAPCHECK(X.flag.reserve(nr)); MAPCHECK(X.pos.reserve(nr)); MAPCHECK(X.src_of.reserve(nr));
     MAPCHECK(X.ox.reserve(nr)); MAPCHECK(X.oy.reserve(nr)); MAPCHECK(X.oz.reserve(nr)); MAPCHECK(X.oc.reserve(nr));
     if (C > 0) MAPCHECK(X.ol.reserve(nr));
+    if (fused) MAPCHECK(X.oconf.reserve(nr));
     MAPCHECK(X.res.reserve(sicp::kMapRes));
     size_t scan_bytes = 0;
     MAPCHECK(sicp::prim_scan_int(nullptr, scan_bytes, X.flag.p, X.pos.p, n_map, st));
@@ -394,6 +405,16 @@ int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context*
     MAPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, X.flag.p, X.pos.p, n_map, st));
     MAPCHECK(sicp::launch_map_extract(S, st));
     log.mark("select_gather");
+    if (fused) {  // (the rows' number is on the device: the kernel reads it there)
+      sicp::MapFuseArgs A;
+      std::memset(&A, 0, sizeof A);
+      A.logcm = m->logcm.p; A.C = C; A.stride = stride;
+      A.rows = S.rows; A.n_map = n_map;
+      A.src_of = X.src_of.p; A.res_in = X.res.p;
+      A.olabel = X.ol.p; A.oconf = X.oconf.p;
+      MAPCHECK(sicp::launch_map_posterior(A, st));
+      log.mark("posterior");
+    }
     MAPCHECK(hipMemcpyAsync(m->stage.data(), X.res.p, sizeof res, hipMemcpyDeviceToHost, st));
     MAPCHECK(hipStreamSynchronize(st));
     std::memcpy(res, m->stage.data(), sizeof res);
@@ -406,24 +427,26 @@ int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context*
   I.n_out = n_out;
   I.max_voxel_points = res[sicp::kMapMaxCount];
   I.has_label = C > 0 ? 1 : 0;
-  const bool want_arrays = x || y || z || label || count || hist;
+  const bool want_arrays = x || y || z || label || count || hist || confidence;
   if (want_arrays && capacity < n_out) {
     I.t_total_ms = now_ms() - t_begin;
     if (info) *info = I;
-    m->last_error = "sicp_map_extract: the result has " + std::to_string(n_out) + " points, the output arrays hold " + std::to_string(capacity);
+    m->last_error = name + ": the result has " + std::to_string(n_out) + " points, the output arrays hold " + std::to_string(capacity);
     return SICP_ERR_INVALID_ARGUMENT;
   }
   if (dst && n_out == 0) {
-    m->last_error = "sicp_map_extract: the result is empty; dst keeps its cloud";
+    m->last_error = name + ": the result is empty; dst keeps its cloud";
     return SICP_ERR_TOO_FEW_POINTS;
   }
   // the result -> pinned memory: the whole of it is on the host before dst's slot lets go of its old cloud
   const size_t mo = (size_t)n_out;
+  const size_t hist_words = hist ? mo * (size_t)stride : 0;
+  const size_t conf_at = (mo * 5 + hist_words + 1) & ~(size_t)1;  // (doubles: an even word)
   if (n_out > 0 && (want_arrays || dst)) {
     X.idle = false;
-    const size_t hist_words = hist ? mo * (size_t)stride : 0;
-    MAPCHECK(m->out.resize(mo * 5 + hist_words));
+    MAPCHECK(m->out.resize(conf_at + (fused ? 2 * mo : 0)));
     uint32_t* o = m->out.data();
+    if (fused) MAPCHECK(hipMemcpyAsync(o + conf_at, X.oconf.p, 8 * mo, hipMemcpyDeviceToHost, st));
     if (hist) {
       MAPCHECK(X.ohist.reserve(hist_words));
       MAPCHECK(sicp::launch_map_move_hist(S.rows.hist, X.ohist.p, S.src_of, n_out, stride, st));
@@ -438,13 +461,13 @@ int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context*
     MAPCHECK(hipStreamSynchronize(st));
     X.idle = true;
   }
-  log.print("sicp_map_extract: n_map=" + std::to_string(n_map) + " n_out=" + std::to_string(n_out));
+  log.print(name + ": n_map=" + std::to_string(n_map) + " n_out=" + std::to_string(n_out));
   const uint32_t* o = m->out.data();
   if (dst) {
     const StridedCloud in = {(const char*)o, (const char*)(o + mo), (const char*)(o + 2 * mo), C > 0 ? (const char*)(o + 3 * mo) : nullptr, 4, 4};
     const int rc = set_cloud_common(dst, dst_which, n_out, in);
     if (rc != SICP_OK) {
-      m->last_error = "sicp_map_extract: dst: " + dst->last_error;
+      m->last_error = name + ": dst: " + dst->last_error;
       return rc;
     }
   }
@@ -455,9 +478,146 @@ int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context*
     if (label && C > 0) std::memcpy(label, o + 3 * mo, 4 * mo);
     if (count) std::memcpy(count, o + 4 * mo, 4 * mo);
     if (hist) std::memcpy(hist, o + 5 * mo, 4 * mo * (size_t)stride);
+    if (confidence) std::memcpy(confidence, o + conf_at, 8 * mo);
   }
   I.t_total_ms = now_ms() - t_begin;
   if (info) *info = I;
+  return SICP_OK;
+}
+
+int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
+                float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info) {
+  return extract_rows(m, "sicp_map_extract", false, p, dst, dst_which, capacity, x, y, z, label, count, hist, nullptr, info);
+}
+
+int map_extract_fused(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
+                      float* y, float* z, uint32_t* label, uint32_t* count, double* confidence, sicp_map_extract_info* info) {
+  return extract_rows(m, "sicp_map_extract_fused", true, p, dst, dst_which, capacity, x, y, z, label, count, nullptr, confidence, info);
+}
+
+int map_set_confusion(sicp_map_ctx* m, int32_t C, const double* cm) {
+  if (!m) return SICP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const std::string& why) {
+    m->last_error = "sicp_map_set_confusion: " + why + "; the map keeps the matrix it had";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (!cm) return refuse("the matrix is NULL");
+  const int classes = m->params.num_classes;
+  if (classes == 0) return refuse("the map keeps no labels");
+  if (C != classes) return refuse("the matrix has " + std::to_string(C) + " classes, the map " + std::to_string(classes));
+  const size_t nn = (size_t)C * (size_t)C;
+  for (size_t e = 0; e < nn; ++e)
+    if (!std::isfinite(cm[e]) || cm[e] < 0.0)
+      return refuse("entry [" + std::to_string(e / (size_t)C) + "][" + std::to_string(e % (size_t)C) + "] = " + std::to_string(cm[e]) +
+                    " is negative or not finite");
+  MAPCHECK(hipSetDevice(m->device));
+  MAPCHECK(m->stage.resize(sizeof(double) * nn));
+  MAPCHECK(m->logcm.reserve(nn));
+  double* L = reinterpret_cast<double*>(m->stage.data());
+  for (size_t e = 0; e < nn; ++e) L[e] = std::log(cm[e]);  // (log 0 = -inf: a class that never shows as that label)
+  m->has_cm = false;  // (nothing can refuse any more; a failed copy leaves no matrix)
+  MAPCHECK(hipMemcpyAsync(m->logcm.p, L, sizeof(double) * nn, hipMemcpyHostToDevice, m->stream));
+  MAPCHECK(hipStreamSynchronize(m->stream));
+  m->has_cm = true;
+  return SICP_OK;
+}
+
+int map_fused_labels(sicp_map_ctx* m, sicp_context* h, int which, const double* qt, int32_t include_own_label, int32_t min_count,
+                     uint32_t* out_labels, double* out_confidence) {
+  if (!m) return SICP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const std::string& why) {
+    m->last_error = "sicp_map_fused_labels: " + why + "; nothing was written";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (!h) return refuse("the handle is NULL");
+  if (!out_labels) return refuse("out_labels is NULL");
+  if (!slot_ok(which)) return refuse("`which` is neither SICP_SOURCE nor SICP_TARGET");
+  if (include_own_label != 0 && include_own_label != 1) return refuse("include_own_label is neither 0 nor 1");
+  if (min_count < 1) return refuse("min_count must be >= 1");
+  if (qt)
+    for (int k = 0; k < 7; ++k)
+      if (!std::isfinite(qt[k])) return refuse("the pose is not finite");
+  if (h->device != m->device) return refuse("the handle is on device " + std::to_string(h->device) + ", the map on " + std::to_string(m->device));
+  const int C = m->params.num_classes, stride = stride_of(m);
+  if (C == 0) return refuse("the map keeps no labels: there is nothing to fuse");
+  if (!m->has_cm) {
+    m->last_error = "sicp_map_fused_labels: no confusion matrix has been set (sicp_map_set_confusion)";
+    return SICP_ERR_NOT_READY;
+  }
+  Cloud& c = h->cloud(which);
+  if (!c.is_set) {
+    m->last_error = "sicp_map_fused_labels: the slot has no cloud";
+    return SICP_ERR_NOT_READY;
+  }
+  MAPCHECK(hipSetDevice(m->device));
+  if (c.layout < 0) {  // (prepared as a merge part is: sicp_map_integrate's rule)
+    const int rc = prepare_cloud(h, c);
+    if (rc != SICP_OK) {
+      m->last_error = "sicp_map_fused_labels: the cloud: " + (h->last_error.empty() ? std::string("not ready") : h->last_error);
+      return rc;
+    }
+  }
+  if (c.pending && c.ready_ev) {
+    MAPCHECK(hipEventSynchronize(c.ready_ev));
+    c.pending = false;
+  }
+  const int n = c.n;
+  const size_t np = (size_t)n, n_caller = (size_t)c.n_caller;
+  hipStream_t st = m->stream;
+  StageLog log(log_enabled(), st);
+  MapScratch X;
+  if (n > 0) {
+    X.device = m->device;
+    X.idle = false;
+    MAPCHECK(m->stage.resize(sizeof(int) * sicp::kMapRes));
+    MAPCHECK(m->out.resize(3 * np));  // confidence (doubles first) | labels
+    MAPCHECK(X.ol.reserve(np)); MAPCHECK(X.oconf.reserve(np)); MAPCHECK(X.res.reserve(sicp::kMapRes));
+    const double ident[7] = {0, 0, 0, 1, 0, 0, 0};
+    sicp::MapFuseArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.logcm = m->logcm.p; A.C = C; A.stride = stride;
+    A.rows = rows_of(m->rows[m->cur], true); A.n_map = (int)m->n_voxels;
+    A.x = c.rx.p; A.y = c.ry.p; A.z = c.rz.p;
+    A.label = c.has_label ? c.rl.p : nullptr;
+    matrix34(qt ? qt : ident, A.M);
+    A.n = n; A.include_own = include_own_label; A.min_count = min_count;
+    A.inv_leaf = 1.0f / (float)m->params.leaf_size;
+    A.res = X.res.p; A.olabel = X.ol.p; A.oconf = X.oconf.p;
+    log.mark("begin");
+    MAPCHECK(hipMemsetAsync(X.res.p, 0, sizeof(int) * sicp::kMapRes, st));
+    MAPCHECK(sicp::launch_map_relabel(A, st));
+    log.mark("relabel");
+    uint32_t* o = m->out.data();
+    MAPCHECK(hipMemcpyAsync(m->stage.data(), X.res.p, sizeof(int) * sicp::kMapRes, hipMemcpyDeviceToHost, st));
+    MAPCHECK(hipMemcpyAsync(o, X.oconf.p, 8 * np, hipMemcpyDeviceToHost, st));
+    MAPCHECK(hipMemcpyAsync(o + 2 * np, X.ol.p, 4 * np, hipMemcpyDeviceToHost, st));
+    log.mark("result");
+    MAPCHECK(hipStreamSynchronize(st));
+    X.idle = true;
+    log.print("sicp_map_fused_labels: n=" + std::to_string(n) + " n_map=" + std::to_string(m->n_voxels));
+    int res[sicp::kMapRes];
+    std::memcpy(res, m->stage.data(), sizeof res);
+    if (res[sicp::kMapBadLabel]) {
+      m->last_error = "sicp_map_fused_labels: a label above num_classes = " + std::to_string(C) + "; nothing was written";
+      return SICP_ERR_BAD_LABEL;
+    }
+  }
+  // caller order: a point that is not finite (it is not on the device) keeps label 0 and confidence 0
+  const uint32_t* o = m->out.data();
+  const double* conf = reinterpret_cast<const double*>(o);
+  if (np == n_caller) {
+    if (n > 0) {
+      std::memcpy(out_labels, o + 2 * np, 4 * np);
+      if (out_confidence) std::memcpy(out_confidence, conf, 8 * np);
+    }
+  } else {
+    std::memset(out_labels, 0, 4 * n_caller);
+    if (out_confidence) std::fill(out_confidence, out_confidence + n_caller, 0.0);
+    for (size_t i = 0; i < np; ++i) {
+      out_labels[c.keep[i]] = o[2 * np + i];
+      if (out_confidence) out_confidence[c.keep[i]] = conf[i];
+    }
+  }
   return SICP_OK;
 }
 

@@ -208,6 +208,154 @@ __global__ __launch_bounds__(256) void map_extract_kernel(MapSelectArgs a) {
   if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(&a.res[kMapMaxCount], m);
 }
 
+// ---- label fusion through the confusion matrix (kernels.h: MapFuseArgs) -------------------------------------------------------
+constexpr int kFuseSlots = 4;  // classes a lane owns at most: ceil(255 / 64)
+
+// One item -- a histogram row h (nullptr: none) and, added last, the single observation `own` (0: none) -- scored by the
+// `width` neighbouring lanes it belongs to; lane j of them owns the classes j + 1, j + 1 + width, ...  EVERY lane of the wave
+// calls this, from wave-uniform control flow (a ballot and shuffles inside); items differ between the groups of a wave.
+// The groups' lanes read the row's bins `width` at a time, and the non-zero ones are walked in ascending r: every lane
+// continues its classes' scores with (double)h[r] * L[r - 1][s - 1], product and sum rounded once each -- the per-class
+// order of kernels.h whatever the lane mapping.  The arg-max (the smallest class among equals) goes through a butterfly;
+// the denominator of the confidence is each lane's terms in ascending class, then a butterfly over lane distance 1, 2, 4 ...
+// Returns whether there was evidence: a term was added and the best score is not -inf.
+template <int SLOTS>
+__device__ __forceinline__ bool map_fuse(const uint32_t* h, uint32_t own, const double* L, int C, int width, uint32_t* label,
+                                         double* conf) {
+  const int lane = threadIdx.x & 63, sub = lane & (width - 1), base = lane - sub;
+  const u64 group = width == 64 ? ~0ull : ((1ull << width) - 1ull);
+  double sc[SLOTS];
+#pragma unroll
+  for (int k = 0; k < SLOTS; ++k) sc[k] = 0.0;
+  bool added = false;
+#pragma unroll
+  for (int c = 0; c < SLOTS; ++c) {
+    const int r0 = c * width;  // this round: the bins r0 + 1 ... r0 + width
+    if (r0 >= C) break;
+    const int r = r0 + sub + 1;
+    const uint32_t v = (h && r <= C) ? h[r] : 0u;
+    u64 live = (__ballot(v > 0u) >> base) & group;
+    while (__any(live != 0ull)) {
+      const int b = live ? __ffsll((unsigned long long)live) - 1 : 0;
+      const uint32_t n = (uint32_t)__shfl((int)v, base + b, 64);
+      if (live) {
+        const double* row = L + (size_t)(r0 + b) * (size_t)C;
+        const double w = (double)n;
+#pragma unroll
+        for (int k = 0; k < SLOTS; ++k) {
+          const int s = sub + 1 + k * width;
+          if (s <= C) sc[k] = __dadd_rn(sc[k], __dmul_rn(w, row[s - 1]));
+        }
+        added = true;
+        live &= live - 1ull;
+      }
+    }
+  }
+  if (own >= 1u && own <= (uint32_t)C) {
+    const double* row = L + (size_t)(own - 1u) * (size_t)C;
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) {
+      const int s = sub + 1 + k * width;
+      if (s <= C) sc[k] = __dadd_rn(sc[k], row[s - 1]);
+    }
+    added = true;
+  }
+  const double ninf = -__builtin_inf();
+  double best = ninf;
+  int best_s = 0x7fffffff;
+#pragma unroll
+  for (int k = 0; k < SLOTS; ++k) {
+    const int s = sub + 1 + k * width;
+    if (s <= C && sc[k] > best) { best = sc[k]; best_s = s; }
+  }
+  for (int w = width >> 1; w > 0; w >>= 1) {
+    const double os = __shfl_xor(best, w, 64);
+    const int ol = __shfl_xor(best_s, w, 64);
+    if (os > best || (os == best && ol < best_s)) { best = os; best_s = ol; }
+  }
+  const bool evidence = added && best > ninf;
+  double t = 0.0;
+#pragma unroll
+  for (int k = 0; k < SLOTS; ++k) {
+    const int s = sub + 1 + k * width;
+    if (s <= C) t = __dadd_rn(t, exp(sc[k] - best));
+  }
+  for (int w = 1; w < width; w <<= 1) t = __dadd_rn(t, __shfl_xor(t, w, 64));
+  *label = evidence ? (uint32_t)best_s : 0u;
+  *conf = evidence ? 1.0 / t : 0.0;
+  return evidence;
+}
+
+// log cm where the lanes read it: a copy in LDS (SLOTS == 1: C <= kMapFuseLdsClasses) or the global array
+template <int SLOTS>
+__device__ __forceinline__ const double* map_fuse_stage(const MapFuseArgs& a, double* lds) {
+  if (SLOTS != 1) return a.logcm;
+  for (int e = threadIdx.x; e < a.C * a.C; e += 256) lds[e] = a.logcm[e];
+  __syncthreads();
+  return lds;
+}
+
+// the selected rows' posteriors: `width` lanes per row, 256 / width rows per workgroup and turn (no lane leaves early)
+template <int SLOTS>
+__global__ __launch_bounds__(256) void map_posterior_kernel(MapFuseArgs a, int width) {
+  __shared__ double lds[SLOTS == 1 ? kMapFuseLdsClasses * kMapFuseLdsClasses : 1];
+  const double* L = map_fuse_stage<SLOTS>(a, lds);
+  const int n = a.res_in[kMapOut];
+  const int per_block = 256 / width, mine = threadIdx.x / width;
+  for (long long j0 = (long long)blockIdx.x * per_block; j0 < n; j0 += (long long)gridDim.x * per_block) {
+    const long long j = j0 + mine;
+    const bool valid = j < n;
+    const uint32_t* h = valid ? a.rows.hist + (size_t)a.src_of[j] * (size_t)a.stride : nullptr;
+    uint32_t lab;
+    double cf;
+    map_fuse<SLOTS>(h, 0u, L, a.C, width, &lab, &cf);
+    if (valid && (threadIdx.x & (width - 1)) == 0) { a.olabel[j] = lab; a.oconf[j] = cf; }
+  }
+}
+
+// per point of a scan: transform and key as map_key_kernel does (no crop), its voxel among the map's keys, the posterior of
+// that row (when it has min_count points) with the point's own label added last; a label beyond the classes raises its flag
+template <int SLOTS>
+__global__ __launch_bounds__(256) void map_relabel_kernel(MapFuseArgs a, int width) {
+  __shared__ double lds[SLOTS == 1 ? kMapFuseLdsClasses * kMapFuseLdsClasses : 1];
+  const double* L = map_fuse_stage<SLOTS>(a, lds);
+  const int per_block = 256 / width, mine = threadIdx.x / width;
+  for (long long i0 = (long long)blockIdx.x * per_block; i0 < a.n; i0 += (long long)gridDim.x * per_block) {
+    const long long i = i0 + mine;
+    const bool valid = i < a.n;
+    const uint32_t* h = nullptr;
+    uint32_t own_label = 0u, own = 0u;
+    if (valid) {
+      const double x = a.x[i], y = a.y[i], z = a.z[i];
+      const float px = voxel_xform_row(a.M + 0, x, y, z);
+      const float py = voxel_xform_row(a.M + 4, x, y, z);
+      const float pz = voxel_xform_row(a.M + 8, x, y, z);
+      u64 k;
+      if (voxel_key(px, py, pz, a.inv_leaf, &k)) {  // (beyond the key's range: not in the map)
+        const int r = map_lower_bound(a.rows.key, a.n_map, k);
+        if (r < a.n_map && a.rows.key[r] == k && (long long)a.rows.cnt[r] >= a.min_count) h = a.rows.hist + (size_t)r * (size_t)a.stride;
+      }
+      if (a.label) {
+        own_label = a.label[i];
+        if (a.include_own) {
+          if (own_label > (uint32_t)a.C) a.res[kMapBadLabel] = 1; else own = own_label;
+        }
+      }
+    }
+    uint32_t lab;
+    double cf;
+    const bool evidence = map_fuse<SLOTS>(h, own, L, a.C, width, &lab, &cf);
+    if (valid && (threadIdx.x & (width - 1)) == 0) { a.olabel[i] = evidence ? lab : own_label; a.oconf[i] = cf; }
+  }
+}
+
+// workgroups for `items` scored `width` lanes each: eight turns a workgroup where there is that much (the LDS copy of log cm
+// is paid once a workgroup), 2048 at the most
+inline dim3 fuse_grid(long long items, int width) {
+  const long long per_turn = 256 / width;
+  return dim3((unsigned)std::max<long long>(1, std::min<long long>((items + per_turn * 8 - 1) / (per_turn * 8), 2048)));
+}
+
 inline dim3 map_grid(long long n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
@@ -266,6 +414,24 @@ hipError_t launch_map_prune(const MapSelectArgs& a, hipStream_t st) {
 hipError_t launch_map_extract(const MapSelectArgs& a, hipStream_t st) {
   if (a.n_map <= 0) return hipSuccess;
   hipLaunchKernelGGL(map_extract_kernel, map_grid(a.n_map), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_posterior(const MapFuseArgs& a, hipStream_t st) {
+  if (a.n_map <= 0) return hipSuccess;
+  if (a.C < 1 || a.C > 255 || a.stride != a.C + 1) return hipErrorInvalidValue;
+  const int width = map_fuse_width(a.C);
+  if (a.C <= kMapFuseLdsClasses) hipLaunchKernelGGL(map_posterior_kernel<1>, fuse_grid(a.n_map, width), dim3(256), 0, st, a, width);
+  else hipLaunchKernelGGL(map_posterior_kernel<kFuseSlots>, fuse_grid(a.n_map, width), dim3(256), 0, st, a, width);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_relabel(const MapFuseArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (a.C < 1 || a.C > 255 || a.stride != a.C + 1) return hipErrorInvalidValue;
+  const int width = map_fuse_width(a.C);
+  if (a.C <= kMapFuseLdsClasses) hipLaunchKernelGGL(map_relabel_kernel<1>, fuse_grid(a.n, width), dim3(256), 0, st, a, width);
+  else hipLaunchKernelGGL(map_relabel_kernel<kFuseSlots>, fuse_grid(a.n, width), dim3(256), 0, st, a, width);
   return hipGetLastError();
 }
 

@@ -878,6 +878,24 @@ int sicp_map_extract(sicp_map m, const sicp_map_extract_params* p, sicp_handle d
   });
 }
 
+int sicp_map_set_confusion(sicp_map m, int32_t C, const double* cm_rowmajor) {
+  return abi_guard(m, [&]() -> int { return map_set_confusion(m, C, cm_rowmajor); });
+}
+
+int sicp_map_extract_fused(sicp_map m, const sicp_map_extract_params* p, sicp_handle dst, int dst_which, int32_t capacity, float* x,
+                           float* y, float* z, uint32_t* label, uint32_t* count, double* confidence, sicp_map_extract_info* info) {
+  return abi_guard(m, [&]() -> int {
+    return map_extract_fused(m, p, dst, dst_which, capacity, x, y, z, label, count, confidence, info);
+  });
+}
+
+int sicp_map_fused_labels(sicp_map m, sicp_handle h, int which, const double qt[7], int32_t include_own_label, int32_t min_count,
+                          uint32_t* out_labels, double* out_confidence) {
+  return abi_guard(m, [&]() -> int {
+    return map_fused_labels(m, h, which, qt, include_own_label, min_count, out_labels, out_confidence);
+  });
+}
+
 int sicp_solve(sicp_handle h, const double init_qt[7], double out_qt[7], int32_t* lm_iters, int32_t* evals,
                double* final_cost) {
   return abi_guard(h, [&]() -> int {
