@@ -97,6 +97,63 @@ __device__ __forceinline__ void corr_eval(const Pose& P, double one_m_eps, doubl
   }
 }
 
+// r and det A for Probability() AS A DOUBLE (quirk Q1 off), by the reference's own sequence of operations on the full
+// matrices (gicp_cost_function.h:75-87: R C_s R^T, + C_t, the cofactor inverse, res^T (M res)) with C = I - (1-eps) n n^T
+// formed entry by entry as sicp_covariances reports it.  A has condition 2 / eps: the closed form above and this sequence are
+// both right to about (2 / eps) * 2^-52 * r, which exp(-r / 2) turns into a RELATIVE difference of 3e-11 between them at
+// r = 774, eps = 1e-3 -- beyond the 1e-11 the double is held to.  The bool only asks whether the product is 0 and keeps
+// the closed form; the solve never calls this.
+__device__ __forceinline__ void corr_eval_literal(const Pose& P, double one_m_eps, double psx, double psy, double psz,
+                                                  double nsx, double nsy, double nsz, double ptx, double pty, double ptz,
+                                                  double ntx, double nty, double ntz, Corr& o) {
+#pragma clang fp contract(off)
+  const double* R = P.R;
+  const double ns[3] = {nsx, nsy, nsz}, nt[3] = {ntx, nty, ntz};
+  double Cs[3][3], A[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = a; b < 3; ++b) {
+      const double d = a == b ? 1.0 : 0.0;
+      Cs[a][b] = Cs[b][a] = d - one_m_eps * ns[a] * ns[b];
+      A[a][b] = A[b][a] = d - one_m_eps * nt[a] * nt[b];  // C_t, for now
+    }
+  double RC[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) RC[i][j] = R[3 * i] * Cs[0][j] + R[3 * i + 1] * Cs[1][j] + R[3 * i + 2] * Cs[2][j];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) A[i][j] = A[i][j] + (RC[i][0] * R[3 * j] + RC[i][1] * R[3 * j + 1] + RC[i][2] * R[3 * j + 2]);
+  // Eigen Matrix3d::inverse(): cofactors / determinant, all nine entries (A is symmetric only up to rounding)
+  const double c00 = A[1][1] * A[2][2] - A[1][2] * A[2][1];
+  const double c10 = A[1][2] * A[2][0] - A[1][0] * A[2][2];
+  const double c20 = A[1][0] * A[2][1] - A[1][1] * A[2][0];
+  const double inv = 1.0 / (A[0][0] * c00 + A[0][1] * c10 + A[0][2] * c20);
+  const double m00 = c00 * inv;
+  const double m01 = (A[0][2] * A[2][1] - A[0][1] * A[2][2]) * inv;
+  const double m02 = (A[0][1] * A[1][2] - A[0][2] * A[1][1]) * inv;
+  const double m10 = c10 * inv;
+  const double m11 = (A[0][0] * A[2][2] - A[0][2] * A[2][0]) * inv;
+  const double m12 = (A[0][2] * A[1][0] - A[0][0] * A[1][2]) * inv;
+  const double m20 = c20 * inv;
+  const double m21 = (A[0][1] * A[2][0] - A[0][0] * A[2][1]) * inv;
+  const double m22 = (A[0][0] * A[1][1] - A[0][1] * A[1][0]) * inv;
+  double tx = R[0] * psx + R[1] * psy + R[2] * psz;
+  double ty = R[3] * psx + R[4] * psy + R[5] * psz;
+  double tz = R[6] * psx + R[7] * psy + R[8] * psz;
+  tx += P.t[0]; ty += P.t[1]; tz += P.t[2];
+  const double rx = ptx - tx, ry = pty - ty, rz = ptz - tz;
+  const double dx = m00 * rx + m01 * ry + m02 * rz;
+  const double dy = m10 * rx + m11 * ry + m12 * rz;
+  const double dz = m20 * rx + m21 * ry + m22 * rz;
+  o.r = rx * dx + ry * dy + rz * dz;
+  o.detA = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+           A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+}
+
 // GICPCostFunction::Probability as the reference uses it (gicp_cost_function.h:75-87 through em_icp.hpp:108):
 // the density det(2 pi A)^-1/2 exp(-r/2), converted to bool (quirk Q1: 1 unless the product underflows to
 // exactly 0; NaN -> 1).  pow() and exp() cost ~300 instructions to answer a question that is decided long
@@ -115,6 +172,19 @@ __device__ __forceinline__ double geometric_gate(const Corr& c, int bool_probabi
     return (probability != 0.0) ? 1.0 : 0.0;  // quirk Q1: double -> bool (NaN -> true)
   }
   return pow(two_pi * two_pi * two_pi * c.detA, -0.5) * exp(-0.5 * c.r);
+}
+
+// the geometric factor of one slot: the closed form decides the bool, the literal sequence gives the double.  LITERAL is a
+// template parameter, not only a run-time flag: with both forms compiled in, the K = 4 packet search needs 66 VGPRs instead of
+// 54 (8 -> 7 waves per SIMD) and em_weight_rows4_kernel 156 instead of 126 (4 -> 3), whichever form runs.  The launchers
+// pick the LITERAL kernels only for handles with quirk_bool_probability = 0; every other launch runs the code it always ran.
+// (A job launch takes them when any of its jobs is such a handle; em_weight_hist4_body, a developer switch, keeps the closed form.)
+template <bool LITERAL>
+__device__ __forceinline__ double slot_gate(const Pose& P, double one_m_eps, const PointRec& s, const PointRec& t, int bool_probability) {
+  Corr c;
+  if (LITERAL && !bool_probability) corr_eval_literal(P, one_m_eps, s.x, s.y, s.z, s.nx, s.ny, s.nz, t.x, t.y, t.z, t.nx, t.ny, t.nz, c);
+  else corr_eval<false>(P, one_m_eps, s.x, s.y, s.z, s.nx, s.ny, s.nz, t.x, t.y, t.z, t.nx, t.ny, t.nz, c);
+  return geometric_gate(c, bool_probability);
 }
 
 }  // namespace sicp

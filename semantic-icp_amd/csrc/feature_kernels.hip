@@ -212,7 +212,7 @@ typedef double v2d_t __attribute__((ext_vector_type(2)));
 // prob = sum_s (t_dist . CM[:, s]) * (s_dist . CM[:, s]), accumulated in ascending s, every product rounded
 // on its own -- the same operations in the same order as before, hence the same bits.
 constexpr int WEIGHT_CMAX = 16;  // classes the register-resident row holds; beyond, the generic kernel below
-template <int K>
+template <int K, bool LITERAL>  // LITERAL: Probability() as a double by the reference's own operations (slot_gate)
 __device__ __forceinline__ void em_weight_rows_body(const WeightArgs& a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n_s) return;
@@ -241,9 +241,7 @@ __device__ __forceinline__ void em_weight_rows_body(const WeightArgs& a) {
         if (2 * k < C) { double temp = t[k].x; temp *= ps[k].x; prob += temp; }
         if (2 * k + 1 < C) { double temp = t[k].y; temp *= ps[k].y; prob += temp; }
       }
-      Corr cr;
-      corr_eval<false>(a.pose, a.one_m_eps, sr.x, sr.y, sr.z, sr.nx, sr.ny, sr.nz, tr.x, tr.y, tr.z, tr.nx, tr.ny, tr.nz, cr);
-      w[c] = prob * geometric_gate(cr, a.bool_probability);  // em_icp.hpp:108
+      w[c] = prob * slot_gate<LITERAL>(a.pose, a.one_m_eps, sr, tr, a.bool_probability);  // em_icp.hpp:108
     }
   }
 #pragma unroll
@@ -316,9 +314,8 @@ __device__ __forceinline__ void em_weight_hist4_body(const WeightArgs& a) {
         temp *= s_ps[s * 256 + threadIdx.x];  // em_icp.hpp:86-88
         prob += temp;
       }
-      Corr cr;
-      corr_eval<false>(a.pose, a.one_m_eps, sr.x, sr.y, sr.z, sr.nx, sr.ny, sr.nz, tr.x, tr.y, tr.z, tr.nx, tr.ny, tr.nz, cr);
-      w = prob * geometric_gate(cr, a.bool_probability);  // em_icp.hpp:108
+      // (the developer switch keeps corr_eval's closed form for Probability() as a double too: slot_gate)
+      w = prob * slot_gate<false>(a.pose, a.one_m_eps, sr, tr, a.bool_probability);  // em_icp.hpp:108
     }
     w0 = c == 0 ? w : w0; w1 = c == 1 ? w : w1; w2 = c == 2 ? w : w2; w3 = c == 3 ? w : w3;
   }
@@ -329,6 +326,7 @@ __device__ __forceinline__ void em_weight_hist4_body(const WeightArgs& a) {
 }
 
 // any K and C: one lane per slot
+template <bool LITERAL>
 __device__ __forceinline__ void em_weight_body(const WeightArgs& a) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= a.n_s * a.K) return;
@@ -344,18 +342,21 @@ __device__ __forceinline__ void em_weight_body(const WeightArgs& a) {
     temp *= ps[s];
     prob += temp;
   }
-  Corr c;
   const PointRec sr = a.srec[i], tr = a.trec[j];
-  corr_eval<false>(a.pose, a.one_m_eps, sr.x, sr.y, sr.z, sr.nx, sr.ny, sr.nz, tr.x, tr.y, tr.z, tr.nx, tr.ny, tr.nz, c);
-  a.w[e] = prob * geometric_gate(c, a.bool_probability);
+  a.w[e] = prob * slot_gate<LITERAL>(a.pose, a.one_m_eps, sr, tr, a.bool_probability);
 }
 
-__global__ __launch_bounds__(256) void em_weight_kernel(WeightArgs a) { em_weight_body(a); }
-__global__ __launch_bounds__(256) void em_weight_jobs_kernel(WeightJobs jobs) { em_weight_body(jobs.job[blockIdx.y]); }
-__global__ __launch_bounds__(256) void em_weight_rows4_kernel(WeightArgs a) { em_weight_rows_body<4>(a); }
-__global__ __launch_bounds__(256) void em_weight_rows4_jobs_kernel(WeightJobs jobs) { em_weight_rows_body<4>(jobs.job[blockIdx.y]); }
+__global__ __launch_bounds__(256) void em_weight_kernel(WeightArgs a) { em_weight_body<false>(a); }
+__global__ __launch_bounds__(256) void em_weight_jobs_kernel(WeightJobs jobs) { em_weight_body<false>(jobs.job[blockIdx.y]); }
+__global__ __launch_bounds__(256) void em_weight_rows4_kernel(WeightArgs a) { em_weight_rows_body<4, false>(a); }
+__global__ __launch_bounds__(256) void em_weight_rows4_jobs_kernel(WeightJobs jobs) { em_weight_rows_body<4, false>(jobs.job[blockIdx.y]); }
 __global__ __launch_bounds__(256) void em_weight_hist4_kernel(WeightArgs a) { em_weight_hist4_body(a); }
 __global__ __launch_bounds__(256) void em_weight_hist4_jobs_kernel(WeightJobs jobs) { em_weight_hist4_body(jobs.job[blockIdx.y]); }
+// the same kernels for handles with quirk_bool_probability = 0 (a launch of jobs: for any such job)
+__global__ __launch_bounds__(256) void em_weight_literal_kernel(WeightArgs a) { em_weight_body<true>(a); }
+__global__ __launch_bounds__(256) void em_weight_literal_jobs_kernel(WeightJobs jobs) { em_weight_body<true>(jobs.job[blockIdx.y]); }
+__global__ __launch_bounds__(256) void em_weight_rows4_literal_kernel(WeightArgs a) { em_weight_rows_body<4, true>(a); }
+__global__ __launch_bounds__(256) void em_weight_rows4_literal_jobs_kernel(WeightJobs jobs) { em_weight_rows_body<4, true>(jobs.job[blockIdx.y]); }
 
 __global__ void transform_float_kernel(int n, const float* x, const float* y, const float* z, Mat4f M,
                                        float* ox, float* oy, float* oz) {
@@ -369,7 +370,8 @@ __global__ void transform_float_kernel(int n, const float* x, const float* y, co
 }
 
 // fused label = arg max_s sum_c prob_c * (t_c . CM[:,s]) (s_i . CM[:,s])   (em_icp.hpp:224-266)
-__global__ __launch_bounds__(256) void fused_label_kernel(WeightArgs a, uint32_t* out_labels) {
+template <bool LITERAL>
+__device__ __forceinline__ void fused_label_body(const WeightArgs& a, uint32_t* out_labels) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n_s) return;
   // the geometric factor of each of the K correspondences does not depend on s
@@ -382,10 +384,8 @@ __global__ __launch_bounds__(256) void fused_label_kernel(WeightArgs a, uint32_t
     jj[c] = j;
     gprob[c] = 0.0;
     if (j >= 0) {
-      Corr cr;
       const PointRec tr = a.trec[j];
-      corr_eval<false>(a.pose, a.one_m_eps, sr.x, sr.y, sr.z, sr.nx, sr.ny, sr.nz, tr.x, tr.y, tr.z, tr.nx, tr.ny, tr.nz, cr);
-      gprob[c] = geometric_gate(cr, a.bool_probability);
+      gprob[c] = slot_gate<LITERAL>(a.pose, a.one_m_eps, sr, tr, a.bool_probability);
     }
   }
   const int PS = proj_stride(a.C);
@@ -405,6 +405,8 @@ __global__ __launch_bounds__(256) void fused_label_kernel(WeightArgs a, uint32_t
   }
   out_labels[i] = (uint32_t)(max_s + 1);
 }
+__global__ __launch_bounds__(256) void fused_label_kernel(WeightArgs a, uint32_t* out_labels) { fused_label_body<false>(a, out_labels); }
+__global__ __launch_bounds__(256) void fused_label_literal_kernel(WeightArgs a, uint32_t* out_labels) { fused_label_body<true>(a, out_labels); }
 
 // statistics: number of live correspondence slots (integer atomics: order independent)
 __global__ __launch_bounds__(256) void count_active_kernel(const int* idx, int n, unsigned long long* out) {
@@ -492,9 +494,10 @@ hipError_t launch_proj(const ProjArgs& a, hipStream_t st) {
 hipError_t launch_em_weight(const WeightArgs& a, hipStream_t st) {
   const int total = a.n_s * a.K;
   if (total <= 0) return hipSuccess;
+  const bool lit = !a.bool_probability;
   if (a.s_hist && a.K == 4 && a.C <= HW_CMAX) hipLaunchKernelGGL(em_weight_hist4_kernel, dim3((a.n_s + 255) / 256), dim3(256), 0, st, a);
-  else if (a.K == 4 && a.C <= WEIGHT_CMAX) hipLaunchKernelGGL(em_weight_rows4_kernel, dim3((a.n_s + 255) / 256), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(em_weight_kernel, dim3((total + 255) / 256), dim3(256), 0, st, a);
+  else if (a.K == 4 && a.C <= WEIGHT_CMAX) hipLaunchKernelGGL((lit ? em_weight_rows4_literal_kernel : em_weight_rows4_kernel), dim3((a.n_s + 255) / 256), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((lit ? em_weight_literal_kernel : em_weight_kernel), dim3((total + 255) / 256), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -533,25 +536,26 @@ hipError_t launch_em_weight_jobs(const WeightArgs* jobs, int n, hipStream_t st) 
     const int cnt = n - b < kMaxKnnJobs ? n - b : kMaxKnnJobs;
     WeightJobs J;
     int mx = 0, mx_n = 0;
-    bool rows = true, hist = true;
+    bool rows = true, hist = true, lit = false;
     for (int i = 0; i < cnt; ++i) {
       J.job[i] = jobs[b + i];
       const int t = jobs[b + i].n_s * jobs[b + i].K;
       mx = t > mx ? t : mx; mx_n = jobs[b + i].n_s > mx_n ? jobs[b + i].n_s : mx_n;
       rows = rows && jobs[b + i].K == 4 && jobs[b + i].C <= WEIGHT_CMAX;
       hist = hist && jobs[b + i].s_hist != nullptr && jobs[b + i].K == 4 && jobs[b + i].C <= HW_CMAX;
+      lit = lit || !jobs[b + i].bool_probability;
     }
     if (mx <= 0) continue;
     if (hist) hipLaunchKernelGGL(em_weight_hist4_jobs_kernel, dim3((mx_n + 255) / 256, cnt), dim3(256), 0, st, J);
-    else if (rows) hipLaunchKernelGGL(em_weight_rows4_jobs_kernel, dim3((mx_n + 255) / 256, cnt), dim3(256), 0, st, J);
-    else hipLaunchKernelGGL(em_weight_jobs_kernel, dim3((mx + 255) / 256, cnt), dim3(256), 0, st, J);
+    else if (rows) hipLaunchKernelGGL((lit ? em_weight_rows4_literal_jobs_kernel : em_weight_rows4_jobs_kernel), dim3((mx_n + 255) / 256, cnt), dim3(256), 0, st, J);
+    else hipLaunchKernelGGL((lit ? em_weight_literal_jobs_kernel : em_weight_jobs_kernel), dim3((mx + 255) / 256, cnt), dim3(256), 0, st, J);
   }
   return hipGetLastError();
 }
 
 hipError_t launch_fused_labels(const WeightArgs& a, uint32_t* out, hipStream_t st) {
   if (a.n_s <= 0) return hipSuccess;
-  hipLaunchKernelGGL(fused_label_kernel, dim3((a.n_s + 255) / 256), dim3(256), 0, st, a, out);
+  hipLaunchKernelGGL((a.bool_probability ? fused_label_kernel : fused_label_literal_kernel), dim3((a.n_s + 255) / 256), dim3(256), 0, st, a, out);
   return hipGetLastError();
 }
 

@@ -658,7 +658,7 @@ __device__ __forceinline__ void lds_leaf_points(const KNN_LDS knn_v4f* buf, unsi
 
 // WPB waves (packets) per workgroup: one-wave workgroups are launched too slowly to fill the chip
 // (6250 of them at 100K queries: ~1.5 waves per SIMD resident on average)
-template <int K, int WPB>
+template <int K, int WPB, bool LITERAL = false>  // LITERAL: the epilogue's weights with Probability() as a double (slot_gate)
 __device__ __forceinline__ void knn_packet_body(const KnnArgs& a, int wg, int n_wg) {
   // One wave-private LDS region: s_lb[L][lane] = lane (q, c)'s lower bound of query q to child c of the node of
   // level L + 1 the walk is below -- the bounds of the siblings that wait on every level of the current path.
@@ -900,9 +900,7 @@ __device__ __forceinline__ void knn_packet_body(const KnnArgs& a, int wg, int n_
               P.R[3 * r + 0] = a.M[4 * r + 0]; P.R[3 * r + 1] = a.M[4 * r + 1]; P.R[3 * r + 2] = a.M[4 * r + 2];
               P.t[r] = a.M[4 * r + 3];
             }
-            Corr cr;
-            corr_eval<false>(P, a.w_one_m_eps, sr.x, sr.y, sr.z, sr.nx, sr.ny, sr.nz, tr.x, tr.y, tr.z, tr.nx, tr.ny, tr.nz, cr);
-            w = prob * geometric_gate(cr, a.w_bool_probability);
+            w = prob * slot_gate<LITERAL>(P, a.w_one_m_eps, sr, tr, a.w_bool_probability);
           }
           if (mine) a.w_out[o + k * ks] = w;
         }
@@ -912,9 +910,9 @@ __device__ __forceinline__ void knn_packet_body(const KnnArgs& a, int wg, int n_
   }
 }
 
-template <int K, int WPB>
+template <int K, int WPB, bool LITERAL = false>
 __global__ __launch_bounds__(64 * WPB) void bvh_knn_packet_kernel(KnnArgs a) {
-  knn_packet_body<K, WPB>(a, (int)blockIdx.x, (int)gridDim.x);
+  knn_packet_body<K, WPB, LITERAL>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // Several searches in one launch (lock-step batch: all pairs' searches of a phase): blockIdx.y picks
@@ -926,12 +924,12 @@ __global__ __launch_bounds__(64 * WPB) void bvh_knn_packet_kernel(KnnArgs a) {
 #ifndef SICP_KNN20_WAVES
 #define SICP_KNN20_WAVES 1
 #endif
-template <int K, int WPB>
+template <int K, int WPB, bool LITERAL = false>
 __global__ __launch_bounds__(64 * WPB, (K >= 16 ? SICP_KNN20_WAVES : 1)) void bvh_knn_packet_jobs_kernel(KnnJobs jobs) {
   const KnnArgs& a = jobs.job[blockIdx.y];
   const int n_wg = ((a.q_count + 15) / 16 + WPB - 1) / WPB;
   if ((int)blockIdx.x >= n_wg) return;
-  knn_packet_body<K, WPB>(a, (int)blockIdx.x, n_wg);
+  knn_packet_body<K, WPB, LITERAL>(a, (int)blockIdx.x, n_wg);
 }
 
 
@@ -988,12 +986,15 @@ hipError_t launch_bvh_knn_quad(int K, const KnnArgs& a, hipStream_t st) {
 hipError_t launch_bvh_knn_packet(int K, const KnnArgs& a, hipStream_t st) {
   if (a.q_count <= 0) return hipSuccess;
   const int packets = (a.q_count + 15) / 16;
-#define SICP_PK(KK, W) hipLaunchKernelGGL((bvh_knn_packet_kernel<KK, W>), dim3((packets + W - 1) / W), dim3(64 * W), 0, st, a)
+#define SICP_PK(KK, W, LIT) hipLaunchKernelGGL((bvh_knn_packet_kernel<KK, W, LIT>), dim3((packets + W - 1) / W), dim3(64 * W), 0, st, a)
   switch (K) {
-    case 1: SICP_PK(1, 4); break;
-    case 4: SICP_PK(4, 4); break;
-    case 20: SICP_PK(20, 2); break;
-    case 32: SICP_PK(32, 2); break;
+    case 1: SICP_PK(1, 4, false); break;
+    case 4:
+      if (a.w_out != nullptr && !a.w_bool_probability) SICP_PK(4, 4, true);  // the epilogue's weights with Probability() as a double
+      else SICP_PK(4, 4, false);
+      break;
+    case 20: SICP_PK(20, 2, false); break;
+    case 32: SICP_PK(32, 2, false); break;
     default: return hipErrorInvalidValue;
   }
 #undef SICP_PK
@@ -1011,12 +1012,17 @@ hipError_t launch_bvh_knn_packet_jobs(int K, const KnnArgs* jobs, int n, hipStre
     for (int i = 0; i < cnt; ++i) { J.job[i] = jobs[b + i]; max_q = jobs[b + i].q_count > max_q ? jobs[b + i].q_count : max_q; }
     if (max_q <= 0) continue;
     const int packets = (max_q + 15) / 16;
-#define SICP_PKJ(KK, W) hipLaunchKernelGGL((bvh_knn_packet_jobs_kernel<KK, W>), dim3((packets + W - 1) / W, cnt), dim3(64 * W), 0, st, J)
+    bool literal = false;  // a job whose epilogue writes weights with Probability() as a double
+    for (int i = 0; i < cnt; ++i) literal = literal || (J.job[i].w_out != nullptr && !J.job[i].w_bool_probability);
+#define SICP_PKJ(KK, W, LIT) hipLaunchKernelGGL((bvh_knn_packet_jobs_kernel<KK, W, LIT>), dim3((packets + W - 1) / W, cnt), dim3(64 * W), 0, st, J)
     switch (K) {
-      case 1: SICP_PKJ(1, 4); break;
-      case 4: SICP_PKJ(4, 4); break;
-      case 20: SICP_PKJ(20, 2); break;
-      case 32: SICP_PKJ(32, 2); break;
+      case 1: SICP_PKJ(1, 4, false); break;
+      case 4:
+        if (literal) SICP_PKJ(4, 4, true);
+        else SICP_PKJ(4, 4, false);
+        break;
+      case 20: SICP_PKJ(20, 2, false); break;
+      case 32: SICP_PKJ(32, 2, false); break;
       default: return hipErrorInvalidValue;
     }
 #undef SICP_PKJ
