@@ -637,13 +637,13 @@ int score_stage(sicp_context* h, const sicp_bootstrap_params& p, const sicp_boot
   std::unique_ptr<BootTable<BootPairJob>> tab(new BootTable<BootPairJob>);
   long long used = 0;
   auto flush = [&]() -> int {
-    if (jc.knn[0].empty()) return SICP_OK;
-    HIPCHECK(sicp::launch_bvh_knn_packet_jobs(jc.knn_K[0], jc.knn[0].data(), (int)jc.knn[0].size(), st));
+    if (jc.part[0].knn.empty()) return SICP_OK;
+    HIPCHECK(sicp::launch_bvh_knn_packet_jobs(jc.part[0].knn_K, jc.part[0].knn.data(), (int)jc.part[0].knn.size(), st));
     HIPCHECK(tab->upload(st));
     HIPCHECK(launch_boot_error_jobs(tab->d_jobs(), tab->d_end(), tab->nj(), tab->blocks, t, same_label, st));
     tables.push_back(std::move(tab));
     tab.reset(new BootTable<BootPairJob>);
-    jc.knn[0].clear();
+    jc.part[0].knn.clear();
     used = 0;
     return SICP_OK;
   };

@@ -256,7 +256,7 @@ __global__ __launch_bounds__(256) void boot_normal_kernel(const BootCloudJob* jo
   }
   double A[3][3] = {{c00 / cnt, c01 / cnt, c02 / cnt}, {c01 / cnt, c11 / cnt, c12 / cnt}, {c02 / cnt, c12 / cnt, c22 / cnt}};
   double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int sweep = 0; sweep < 30; ++sweep) {  // the sweep of cov_kernel (feature_kernels.hip)
+  for (int sweep = 0; sweep < 30; ++sweep) {  // the sweep of cov_body (feature_kernels.hip)
     const double offd = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
     const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
     if (offd <= 1e-300 || offd <= 1e-34 * dia) break;

@@ -7,7 +7,7 @@
 namespace sicp {
 
 // one rotation of the cyclic Jacobi eigensolver of a symmetric 3x3 matrix (A := J^T A J, V := V J): the normal
-// estimation of cov_kernel and of the bootstrap's normal kernel
+// estimation of cov_body and of the bootstrap's normal kernel
 __device__ __forceinline__ void jacobi_rotate(double (&A)[3][3], double (&V)[3][3], int p, int q) {
   const double apq = A[p][q];
   if (apq == 0.0) return;
@@ -176,7 +176,7 @@ __device__ __forceinline__ double geometric_gate(const Corr& c, int bool_probabi
 
 // the geometric factor of one slot: the closed form decides the bool, the literal sequence gives the double.  LITERAL is a
 // template parameter, not only a run-time flag: with both forms compiled in, the K = 4 packet search needs 66 VGPRs instead of
-// 54 (8 -> 7 waves per SIMD) and em_weight_rows4_kernel 156 instead of 126 (4 -> 3), whichever form runs.  The launchers
+// 54 (8 -> 7 waves per SIMD) and em_weight_rows4_jobs_kernel 156 instead of 126 (4 -> 3), whichever form runs.  The launchers
 // pick the LITERAL kernels only for handles with quirk_bool_probability = 0; every other launch runs the code it always ran.
 // (A job launch takes them when any of its jobs is such a handle; em_weight_hist4_body, a developer switch, keeps the closed form.)
 template <bool LITERAL>

@@ -368,8 +368,26 @@ double now_ms();
 // SICP_DEBUG is set in the environment: without it the library never prints (include/sicp.h)
 bool debug_enabled();
 
-// lock-step batch: instead of launching, the per-pair stages append their jobs here; the batch driver
-// launches each kind once for all pairs (kernels.h: *_jobs launchers), in dependency order
+// The stage jobs of one launch sequence -- searches, covariances, projections, weights, counts, one job launch per kind
+// (kernels.h: launch_*_jobs) in that order on one stream (stages.cpp: launch_slice).  A stage a handle launches for itself
+// is such a sequence of one job.
+struct JobSlice {
+  int knn_K = 0;  // list length of the searches (one launch: one length)
+  std::vector<sicp::KnnArgs> knn;
+  std::vector<sicp::CovArgs> cov;
+  std::vector<sicp::ProjArgs> proj;
+  std::vector<sicp::WeightArgs> weight;
+  std::vector<sicp::CountJob> count;
+  struct Sizes { size_t knn = 0, cov = 0, proj = 0, weight = 0, count = 0; };
+  Sizes sizes() const { return {knn.size(), cov.size(), proj.size(), weight.size(), count.size()}; }
+  // drops the jobs appended since sizes() returned `s`
+  void shrink_to(const Sizes& s) { knn.resize(s.knn); cov.resize(s.cov); proj.resize(s.proj); weight.resize(s.weight); count.resize(s.count); }
+  void clear() { shrink_to(Sizes()); }
+  bool empty() const { return knn.empty() && cov.empty() && proj.empty() && weight.empty() && count.empty(); }
+};
+
+// lock-step batch: instead of launching, the per-pair stages append their jobs here (stages.cpp: hand_off); the batch driver
+// launches each kind once for all pairs of a slice (flush_jobs)
 constexpr int kParts = 4;  // slices of a batch whose stage sequences run on their own streams
 
 struct JobCollector {
@@ -378,13 +396,8 @@ struct JobCollector {
   // 1.98 ms).  Not by larger batches and streams: there the separate weight kernel runs hidden beside the accumulate launches
   // and the longer search does not (measured, profiles/r05/weights_in_search_epilogue.json: 256-pair step 184.4 against 185.3 ms).
   bool fold_weights = false;
-  int knn_K[kParts] = {};  // list length of a slice's searches (one launch per slice: one length)
   int slice = 0;  // slice of the batch the pair whose stage is running belongs to (set by the driver)
-  std::vector<sicp::KnnArgs> knn[kParts];
-  std::vector<sicp::CovArgs> cov[kParts];
-  std::vector<sicp::ProjArgs> proj[kParts];
-  std::vector<sicp::WeightArgs> weight[kParts];
-  std::vector<sicp::CountJob> count[kParts];
+  JobSlice part[kParts];
 };
 
 // the argument buffers of one stream of ticks (run_tick): argument array + header in HBM with pinned
@@ -458,6 +471,7 @@ struct sicp_context : sicp_use_state {
   OwnedStream side_stream;              // batch leader: searches of the pairs between two inner solves
   OwnedStream feat_stream;              // batch leader: the start-up pipelines (features + first search) of a large batch
   OwnedStream part_stream[kParts];
+  JobSlice own_jobs;  // the stage job this handle is launching for itself (stages.cpp: hand_off; kept for its vectors' capacity)
   // the streams this handle launches on: its own, or the ones it borrows while it is part of a batch (BatchGuard) or a
   // slot of a registration stream (the leader's side stream).  Never destroyed through these.
   hipStream_t stream = nullptr, stream2 = nullptr;
@@ -759,7 +773,9 @@ int run_solve(sicp_context* h, const double* init_qt, double* out_qt, SolveResul
 bool same_solver(const sicp_params& a, const sicp_params& b);
 int tickset_reserve(sicp_context* h, TickSet& S, int n);
 int batch_reserve(sicp_context* h, int n);
-// while a lock-step batch runs, all its handles work on the leader's stream and collect their jobs
+// while a lock-step batch runs, all its handles work on the leader's stream and collect their jobs.  A handle that collects
+// has ONE stream (stream2 == stream, here and for the slots of a registration stream): align_begin reads that as "nothing runs
+// side by side" and queues no join.
 struct BatchGuard {
   sicp_handle* hs; int n;
   std::vector<hipStream_t> s1, s2;

@@ -1,7 +1,7 @@
 // feature_kernels.hip -- per-point covariance normals and label histograms, the EM label-posterior
 // weights, fused labels and the small utility kernels (gfx950, wave64).
 //
-//   cov_kernel       : ComputeCovariances body                 em_icp.hpp:298-340
+//   cov_body         : ComputeCovariances body                 em_icp.hpp:298-340
 //   proj / em_weight : label posterior * Probability           em_icp.hpp:77-89,108
 //   fused_label      : getFusedLabels                          em_icp.hpp:224-266
 //   transform_float  : the final_cloud of align()              em_icp.hpp:192-198
@@ -139,13 +139,12 @@ __device__ __forceinline__ void cov_body(const CovArgs& a) {
   }
 }
 
+__global__ __launch_bounds__(256) void cov_jobs_kernel(CovJobs jobs) { cov_body(jobs.job[blockIdx.y]); }
+
 // per-point projections of the label distribution through the confusion matrix:
 //   proj[i][s] = dist_i^T * CM[:, s]   (the two factors of em_icp.hpp:86-87), dist = counts * 1/k
 // accumulated over r in ascending order exactly like the reference's dot product.  Computed once per
 // align() per cloud, so the per-correspondence weight is a C-term product-sum of two such rows.
-__global__ __launch_bounds__(256) void cov_kernel(CovArgs a) { cov_body(a); }
-__global__ __launch_bounds__(256) void cov_jobs_kernel(CovJobs jobs) { cov_body(jobs.job[blockIdx.y]); }
-
 __device__ __forceinline__ void proj_body(const ProjArgs& a) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= a.n * a.C) return;
@@ -194,14 +193,12 @@ __device__ __forceinline__ void proj_rows_body(const ProjArgs& a) {
   for (int k = threadIdx.x; k < valid; k += 256) out[k] = s_out[k];
 }
 
+__global__ __launch_bounds__(256) void proj_jobs_kernel(ProjJobs jobs) { proj_body(jobs.job[blockIdx.y]); }
+__global__ __launch_bounds__(256) void proj_rows_jobs_kernel(ProjJobs jobs) { proj_rows_body(jobs.job[blockIdx.y]); }
+
 // ------------------------------------------------------------------------------------------
 // EM weight: label posterior from the confusion matrix x the (bool) geometric gate
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void proj_kernel(ProjArgs a) { proj_body(a); }
-__global__ __launch_bounds__(256) void proj_jobs_kernel(ProjJobs jobs) { proj_body(jobs.job[blockIdx.y]); }
-__global__ __launch_bounds__(256) void proj_rows_kernel(ProjArgs a) { proj_rows_body(a); }
-__global__ __launch_bounds__(256) void proj_rows_jobs_kernel(ProjJobs jobs) { proj_rows_body(jobs.job[blockIdx.y]); }
-
 // one 16-byte piece of a projection row (rows are padded to an even number of doubles: proj_stride)
 typedef double v2d_t __attribute__((ext_vector_type(2)));
 
@@ -252,7 +249,7 @@ __device__ __forceinline__ void em_weight_rows_body(const WeightArgs& a) {
 // projection row -- 8 (C + C % 2) = 96 bytes at C = 11 -- and is bound by exactly that gather traffic (77 MB through the
 // L1s per 100K x 4 search).  A point's label distribution is 16 BYTES of neighbour counts; here a lane gathers those
 // and forms the projections it needs itself: proj[s] = sum_r hval[count[r]] * CM[r][s], r ascending, every product rounded
-// on its own -- the very sums proj_kernel forms (same operations, same order: same bits), with CM^T and the count table in
+// on its own -- the very sums proj_body forms (same operations, same order: same bits), with CM^T and the count table in
 // LDS (broadcast reads).  The source point's projections are formed once and parked in LDS (they are indexed by the class
 // loop's counter), then slot after slot: counts -> table values, class after class the target's projection, times the
 // source's, added up in the reference's order (em_icp.hpp:84-89).  ~300 float64 operations per slot instead of a
@@ -277,7 +274,7 @@ __device__ __forceinline__ void em_weight_hist4_body(const WeightArgs& a) {
   __syncthreads();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n_s) return;
-  // ---- the source point: its own projections (what proj_kernel would have stored for it)
+  // ---- the source point: its own projections (what proj_body would have stored for it)
   {
     const uint4 row = *reinterpret_cast<const uint4*>(a.s_hist + (size_t)i * 16);
     double hv[HW_CMAX];
@@ -307,7 +304,7 @@ __device__ __forceinline__ void em_weight_hist4_body(const WeightArgs& a) {
       double prob = 0.0;
       for (int s = 0; s < C; ++s) {
         const double* cm = s_cmT + s * HW_CMAX;
-        double temp = 0.0;  // the target's projection on class s (proj_kernel's sum)
+        double temp = 0.0;  // the target's projection on class s (proj_body's sum)
 #pragma unroll
         for (int r = 0; r < HW_CMAX; ++r)
           if (r < C) temp += hv[r] * cm[r];
@@ -346,16 +343,11 @@ __device__ __forceinline__ void em_weight_body(const WeightArgs& a) {
   a.w[e] = prob * slot_gate<LITERAL>(a.pose, a.one_m_eps, sr, tr, a.bool_probability);
 }
 
-__global__ __launch_bounds__(256) void em_weight_kernel(WeightArgs a) { em_weight_body<false>(a); }
 __global__ __launch_bounds__(256) void em_weight_jobs_kernel(WeightJobs jobs) { em_weight_body<false>(jobs.job[blockIdx.y]); }
-__global__ __launch_bounds__(256) void em_weight_rows4_kernel(WeightArgs a) { em_weight_rows_body<4, false>(a); }
 __global__ __launch_bounds__(256) void em_weight_rows4_jobs_kernel(WeightJobs jobs) { em_weight_rows_body<4, false>(jobs.job[blockIdx.y]); }
-__global__ __launch_bounds__(256) void em_weight_hist4_kernel(WeightArgs a) { em_weight_hist4_body(a); }
 __global__ __launch_bounds__(256) void em_weight_hist4_jobs_kernel(WeightJobs jobs) { em_weight_hist4_body(jobs.job[blockIdx.y]); }
 // the same kernels for handles with quirk_bool_probability = 0 (a launch of jobs: for any such job)
-__global__ __launch_bounds__(256) void em_weight_literal_kernel(WeightArgs a) { em_weight_body<true>(a); }
 __global__ __launch_bounds__(256) void em_weight_literal_jobs_kernel(WeightJobs jobs) { em_weight_body<true>(jobs.job[blockIdx.y]); }
-__global__ __launch_bounds__(256) void em_weight_rows4_literal_kernel(WeightArgs a) { em_weight_rows_body<4, true>(a); }
 __global__ __launch_bounds__(256) void em_weight_rows4_literal_jobs_kernel(WeightJobs jobs) { em_weight_rows_body<4, true>(jobs.job[blockIdx.y]); }
 
 __global__ void transform_float_kernel(int n, const float* x, const float* y, const float* z, Mat4f M,
@@ -407,25 +399,6 @@ __device__ __forceinline__ void fused_label_body(const WeightArgs& a, uint32_t* 
 }
 __global__ __launch_bounds__(256) void fused_label_kernel(WeightArgs a, uint32_t* out_labels) { fused_label_body<false>(a, out_labels); }
 __global__ __launch_bounds__(256) void fused_label_literal_kernel(WeightArgs a, uint32_t* out_labels) { fused_label_body<true>(a, out_labels); }
-
-// statistics: number of live correspondence slots (integer atomics: order independent)
-__global__ __launch_bounds__(256) void count_active_kernel(const int* idx, int n, unsigned long long* out) {
-  __shared__ unsigned cnt[4];
-  unsigned c = 0;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) c += idx[e] >= 0 ? 1u : 0u;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-  if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, (unsigned long long)(cnt[0] + cnt[1] + cnt[2] + cnt[3]));
-}
-
-
-hipError_t launch_cov(const CovArgs& a, hipStream_t st) {
-  if (a.n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(cov_kernel, dim3((a.n + 255) / 256), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
 
 // sicp_set_covariances: the records of a cloud whose normals the caller supplied (device order), written like cov_body's
 __global__ __launch_bounds__(256) void set_normals_kernel(int n, const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
@@ -483,73 +456,39 @@ hipError_t launch_set_normals(int n, const float* x, const float* y, const float
   return hipGetLastError();
 }
 
-hipError_t launch_proj(const ProjArgs& a, hipStream_t st) {
-  const int total = a.n * a.C;
-  if (total <= 0) return hipSuccess;
-  if (a.C <= PROJ_CMAX) hipLaunchKernelGGL(proj_rows_kernel, dim3((a.n + 255) / 256), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(proj_kernel, dim3((total + 255) / 256), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_em_weight(const WeightArgs& a, hipStream_t st) {
-  const int total = a.n_s * a.K;
-  if (total <= 0) return hipSuccess;
-  const bool lit = !a.bool_probability;
-  if (a.s_hist && a.K == 4 && a.C <= HW_CMAX) hipLaunchKernelGGL(em_weight_hist4_kernel, dim3((a.n_s + 255) / 256), dim3(256), 0, st, a);
-  else if (a.K == 4 && a.C <= WEIGHT_CMAX) hipLaunchKernelGGL((lit ? em_weight_rows4_literal_kernel : em_weight_rows4_kernel), dim3((a.n_s + 255) / 256), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((lit ? em_weight_literal_kernel : em_weight_kernel), dim3((total + 255) / 256), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-// job-array launches (lock-step batch): every job of one launch, grid.y = job
+// job-array launches: every job of one launch, grid.y = job (for_job_chunks: kernels.h)
 hipError_t launch_cov_jobs(const CovArgs* jobs, int n, hipStream_t st) {
-  for (int b = 0; b < n; b += kMaxSmallJobs) {
-    const int cnt = n - b < kMaxSmallJobs ? n - b : kMaxSmallJobs;
-    CovJobs J;
-    int mx = 0;
-    for (int i = 0; i < cnt; ++i) { J.job[i] = jobs[b + i]; mx = jobs[b + i].n > mx ? jobs[b + i].n : mx; }
-    if (mx <= 0) continue;
+  for_job_chunks<CovJobs>(jobs, n, [](const CovArgs& a) { return a.n; }, [&](const CovJobs& J, int cnt, int mx) {
     hipLaunchKernelGGL(cov_jobs_kernel, dim3((mx + 255) / 256, cnt), dim3(256), 0, st, J);
-  }
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_proj_jobs(const ProjArgs* jobs, int n, hipStream_t st) {
-  for (int b = 0; b < n; b += kMaxSmallJobs) {
-    const int cnt = n - b < kMaxSmallJobs ? n - b : kMaxSmallJobs;
-    ProjJobs J;
-    int mx = 0, mx_n = 0, mx_c = 0;
-    for (int i = 0; i < cnt; ++i) {
-      J.job[i] = jobs[b + i];
-      const int t = jobs[b + i].n * jobs[b + i].C;
-      mx = t > mx ? t : mx; mx_n = jobs[b + i].n > mx_n ? jobs[b + i].n : mx_n; mx_c = jobs[b + i].C > mx_c ? jobs[b + i].C : mx_c;
-    }
-    if (mx <= 0) continue;
+  for_job_chunks<ProjJobs>(jobs, n, [](const ProjArgs& a) { return a.n * a.C; }, [&](const ProjJobs& J, int cnt, int mx) {
+    int mx_n = 0, mx_c = 0;
+    for (int i = 0; i < cnt; ++i) { mx_n = J.job[i].n > mx_n ? J.job[i].n : mx_n; mx_c = J.job[i].C > mx_c ? J.job[i].C : mx_c; }
     if (mx_c <= PROJ_CMAX) hipLaunchKernelGGL(proj_rows_jobs_kernel, dim3((mx_n + 255) / 256, cnt), dim3(256), 0, st, J);
     else hipLaunchKernelGGL(proj_jobs_kernel, dim3((mx + 255) / 256, cnt), dim3(256), 0, st, J);
-  }
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_em_weight_jobs(const WeightArgs* jobs, int n, hipStream_t st) {
-  for (int b = 0; b < n; b += kMaxKnnJobs) {
-    const int cnt = n - b < kMaxKnnJobs ? n - b : kMaxKnnJobs;
-    WeightJobs J;
-    int mx = 0, mx_n = 0;
+  for_job_chunks<WeightJobs>(jobs, n, [](const WeightArgs& a) { return a.n_s * a.K; }, [&](const WeightJobs& J, int cnt, int mx) {
+    int mx_n = 0;
     bool rows = true, hist = true, lit = false;
     for (int i = 0; i < cnt; ++i) {
-      J.job[i] = jobs[b + i];
-      const int t = jobs[b + i].n_s * jobs[b + i].K;
-      mx = t > mx ? t : mx; mx_n = jobs[b + i].n_s > mx_n ? jobs[b + i].n_s : mx_n;
-      rows = rows && jobs[b + i].K == 4 && jobs[b + i].C <= WEIGHT_CMAX;
-      hist = hist && jobs[b + i].s_hist != nullptr && jobs[b + i].K == 4 && jobs[b + i].C <= HW_CMAX;
-      lit = lit || !jobs[b + i].bool_probability;
+      const WeightArgs& a = J.job[i];
+      mx_n = a.n_s > mx_n ? a.n_s : mx_n;
+      rows = rows && a.K == 4 && a.C <= WEIGHT_CMAX;
+      hist = hist && a.s_hist != nullptr && a.K == 4 && a.C <= HW_CMAX;
+      lit = lit || !a.bool_probability;
     }
-    if (mx <= 0) continue;
     if (hist) hipLaunchKernelGGL(em_weight_hist4_jobs_kernel, dim3((mx_n + 255) / 256, cnt), dim3(256), 0, st, J);
     else if (rows) hipLaunchKernelGGL((lit ? em_weight_rows4_literal_jobs_kernel : em_weight_rows4_jobs_kernel), dim3((mx_n + 255) / 256, cnt), dim3(256), 0, st, J);
     else hipLaunchKernelGGL((lit ? em_weight_literal_jobs_kernel : em_weight_jobs_kernel), dim3((mx + 255) / 256, cnt), dim3(256), 0, st, J);
-  }
+  });
   return hipGetLastError();
 }
 
@@ -569,21 +508,10 @@ __global__ __launch_bounds__(256) void count_active_jobs_kernel(CountJobs jobs) 
 }
 
 hipError_t launch_count_active_jobs(const CountJob* jobs, int n, hipStream_t st) {
-  for (int b = 0; b < n; b += kMaxSmallJobs) {
-    const int cnt = n - b < kMaxSmallJobs ? n - b : kMaxSmallJobs;
-    CountJobs J;
-    int mx = 0;
-    for (int i = 0; i < cnt; ++i) { J.job[i] = jobs[b + i]; mx = jobs[b + i].n > mx ? jobs[b + i].n : mx; }
-    if (mx <= 0) continue;
+  for_job_chunks<CountJobs>(jobs, n, [](const CountJob& a) { return a.n; }, [&](const CountJobs& J, int cnt, int mx) {
     const int gx = (mx + 255) / 256 < 256 ? (mx + 255) / 256 : 256;
     hipLaunchKernelGGL(count_active_jobs_kernel, dim3(gx, cnt), dim3(256), 0, st, J);
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_count_active(const int* idx, int n, unsigned long long* out, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(count_active_kernel, dim3(min(256, (n + 255) / 256)), dim3(256), 0, st, idx, n, out);
+  });
   return hipGetLastError();
 }
 

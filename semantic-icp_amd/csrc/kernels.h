@@ -25,7 +25,7 @@ struct Mat4f {
 
 // One point as the weight / accumulate kernels gather it: position (the float32 the search ran on) and
 // the unit normal of its k-neighbourhood in double (its covariance is I - (1-eps) n n^T), 48 bytes =
-// three loads instead of one load from each of six arrays.  Written by cov_kernel.
+// three loads instead of one load from each of six arrays.  Written by cov_jobs_kernel.
 // Field order: the batched accumulate kernel moves a record into LDS with three LDS-DMA loads of
 // 16 + 16 + 4 bytes (the 36 bytes that carry data).
 struct alignas(16) PointRec {
@@ -133,7 +133,7 @@ struct KnnArgs {
   unsigned long long* live_cnt;  // nullable, packet kernel: kLiveCounters partial counters; every wave adds the number of
                                  // neighbours it wrote that passed the gate (statistics: sicp_stats.total_active)
   // EM weights in the search's epilogue (packet kernel, K = 4, at most 16 classes; w_out == nullptr: not wanted).  The lane
-  // that writes a neighbour's index already holds everything em_weight_rows4_kernel would re-read -- the index, the query's
+  // that writes a neighbour's index already holds everything em_weight_rows4_jobs_kernel would re-read -- the index, the query's
   // place -- so it gathers the two records and projection rows and writes the slot's weight beside the index: the same
   // operations in the same order as that kernel (em_icp.hpp:84-89,108), hence the same bits.  The pose is M (rows [R | t]).
   const PointRec *w_srec, *w_trec;
@@ -187,9 +187,9 @@ struct WeightArgs {
   int n_s, K, C;
   const int* idx;
   const PointRec *srec, *trec;
-  const double *s_proj, *t_proj;  // [n][proj_stride(C)] label distributions projected through CM (proj_kernel); unused with histograms
+  const double *s_proj, *t_proj;  // [n][proj_stride(C)] label distributions projected through CM (proj_*_jobs_kernel); unused with histograms
   // K = 4, C <= 16: the weights straight from the label histograms (rows of hist_stride(C) = 16 bytes), the projections
-  // formed in the kernel -- the same sums in the same order as proj_kernel's, so the same bits -- from cm / hval
+  // formed in the kernel -- the same sums in the same order as proj_body's, so the same bits -- from cm / hval
   const uint8_t *s_hist, *t_hist;  // nullable: then s_proj / t_proj are read
   const double *cm, *hval;         // C*C row-major; hval[c] = c additions of 1/k
   Pose pose;
@@ -224,8 +224,8 @@ struct GenAccArgs {
 };
 hipError_t launch_accumulate_general(const GenAccArgs& g, hipStream_t st);
 
-// job arrays passed by value to one launch (lock-step batch); sized to stay inside the 4 KB of
-// kernel arguments
+// job arrays passed by value to one launch (every stage job of a lock-step batch's slice; one job when a handle launches a
+// stage for itself); sized to stay inside the 4 KB of kernel arguments
 constexpr int kMaxKnnJobs = 8;
 constexpr int kMaxSmallJobs = 16;
 struct KnnJobs { KnnArgs job[kMaxKnnJobs]; };
@@ -235,6 +235,23 @@ struct WeightJobs { WeightArgs job[kMaxKnnJobs]; };
 struct CountJob { const int* idx; int n; unsigned long long* out; };
 struct CountJobs { CountJob job[kMaxSmallJobs]; };
 static_assert(sizeof(KnnJobs) <= 4000 && sizeof(WeightJobs) <= 4000 && sizeof(CovJobs) <= 4000, "kernel argument segment");
+// What every launch_*_jobs wrapper does with its n jobs: chunk after chunk of at most as many as one array holds, copied
+// into it, handed to launch(array, jobs in it, largest work(job) among them) -- unless none of them has any work.
+template <class Jobs, class Job, class Work, class Launch>
+inline void for_job_chunks(const Job* jobs, int n, Work work, Launch launch) {
+  constexpr int cap = (int)(sizeof(Jobs) / sizeof(Job));
+  for (int b = 0; b < n; b += cap) {
+    const int cnt = n - b < cap ? n - b : cap;
+    Jobs J;
+    int mx = 0;
+    for (int i = 0; i < cnt; ++i) {
+      J.job[i] = jobs[b + i];
+      const int w = work(J.job[i]);
+      mx = w > mx ? w : mx;
+    }
+    if (mx > 0) launch(J, cnt, mx);
+  }
+}
 
 // one pair of a lock-step batch (sicp_align_batch); an array of these lives in HBM
 struct BatchArgs {
@@ -286,18 +303,20 @@ int nn_queries_per_thread(int K);
 hipError_t launch_nn_partial(int K, const NNArgs& a, int n_chunks, hipStream_t st);
 hipError_t launch_nn_merge(int K, const MergeArgs& m, hipStream_t st);
 hipError_t launch_bvh_knn_quad(int K, const KnnArgs& a, hipStream_t st);
-hipError_t launch_bvh_knn_packet(int K, const KnnArgs& a, hipStream_t st);
-hipError_t launch_cov(const CovArgs& a, hipStream_t st);
-hipError_t launch_proj(const ProjArgs& a, hipStream_t st);
 // sicp_covariances' fast path: the n 3x3 matrices (row-major) in the CALLER's point order, formed on the device from the records'
 // normals (C = I - (1 - eps) n n^T) or from the caller's own general matrices (cov6 != nullptr); perm = device -> caller index
 hipError_t launch_cov9_caller_order(int n, const PointRec* rec, const double* cov6, const int* perm, double one_m_eps, double* out9, hipStream_t st);
-// caller-supplied normals (sicp_set_covariances): the point records and their dense copy, as cov_kernel writes them
+// caller-supplied normals (sicp_set_covariances): the point records and their dense copy, as cov_jobs_kernel writes them
 hipError_t launch_set_normals(int n, const float* x, const float* y, const float* z, const double* normal3, PointRec* rec, char* rec_dense,
                               int rec_dense_n, hipStream_t st);
-hipError_t launch_em_weight(const WeightArgs& a, hipStream_t st);
 hipError_t launch_fused_labels(const WeightArgs& a, uint32_t* out, hipStream_t st);
 hipError_t launch_bvh_knn_packet_jobs(int K, const KnnArgs* jobs, int n, hipStream_t st);
+// The one stage that keeps a single-job kernel: a search with a list longer than 1 (K = 4, 20 or 32) that a handle launches
+// for itself.  As one job of the job kernel the K = 4 search of a 100K-point pair took 56.2-57.3 us against 54.4-54.8, the
+// k = 20 self-search 76.9-79.0 against 76.2-76.7 (profiles/single_job_launches/ab.json, the block of the earlier builds; an
+// earlier set of k = 20 rounds, 77.3-78.1 against 76.2-77.5, was still inside the parent's range; K = 32 is k = 20's two-wave
+// form and goes with it, unmeasured); the K = 1 search and every other stage measure the same either way.
+hipError_t launch_bvh_knn_packet(int K, const KnnArgs& a, hipStream_t st);
 hipError_t launch_cov_jobs(const CovArgs* jobs, int n, hipStream_t st);
 hipError_t launch_proj_jobs(const ProjArgs* jobs, int n, hipStream_t st);
 hipError_t launch_em_weight_jobs(const WeightArgs* jobs, int n, hipStream_t st);
@@ -346,7 +365,6 @@ struct SoloArgs {
 };
 hipError_t launch_solve_one(int K, int use_sqloss, const SoloArgs& args, int n_chunks, hipStream_t st);
 int solo_wait_ticks();
-hipError_t launch_count_active(const int* idx, int n, unsigned long long* out, hipStream_t st);
 // test hook: csrc/se3.hpp on the device, one lane per item (op = SICP_SE3_*; in/out strides per op)
 // op 5 / 6: the trust-region machine fed with a given sequence of evaluations, as the kernels run it (a whole wave) / as the host
 // runs it (one lane): in = n x kLmSeqIn (start pose | kLmSeqEvals x 28 sums), out = n x kLmSeqOut (the final state)

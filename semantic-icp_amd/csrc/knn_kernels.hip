@@ -875,7 +875,7 @@ __device__ __forceinline__ void knn_packet_body(const KnnArgs& a, int wg, int n_
       }
       if (a.live_cnt) live += (unsigned)__popcll(__ballot(mine && keep));
       if constexpr (K == 4) {
-        // The slot's EM weight, here rather than in a kernel of its own (em_weight_rows4_kernel: one more launch per
+        // The slot's EM weight, here rather than in a kernel of its own (em_weight_rows4_jobs_kernel: one more launch per
         // search that re-reads the indices and is bound by its gathers): prob = sum_s (t_dist . CM[:, s]) (s_dist .
         // CM[:, s]) from the two projection rows, in ascending s with every product rounded on its own
         // (em_icp.hpp:84-89), times Probability()'s bool (:108) -- operation for operation what that kernel does.
@@ -910,12 +910,13 @@ __device__ __forceinline__ void knn_packet_body(const KnnArgs& a, int wg, int n_
   }
 }
 
+// One search in one launch: instantiated for the lists longer than 1 (launch_bvh_knn_packet, kernels.h says why it stays)
 template <int K, int WPB, bool LITERAL = false>
 __global__ __launch_bounds__(64 * WPB) void bvh_knn_packet_kernel(KnnArgs a) {
   knn_packet_body<K, WPB, LITERAL>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
-// Several searches in one launch (lock-step batch: all pairs' searches of a phase): blockIdx.y picks
+// The searches of one launch (all pairs' searches of a phase of a batch; one search when a handle launches for itself): blockIdx.y picks
 // the job from an array passed BY VALUE -- kernel arguments keep their pointers typed as HBM and
 // are read with scalar loads.  The jobs' long tails overlap inside the one launch.
 // (SICP_KNN20_WAVES, build-time experiment: waves per SIMD the long-list kernels are compiled for.  Their 122 VGPRs give 4;
@@ -983,12 +984,14 @@ hipError_t launch_bvh_knn_quad(int K, const KnnArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+bool nn_k_supported(int K) { return K == 1 || K == 4 || K == 20; }  // correspondences per source point (accumulate kernels)
+int nn_list_len(int k) { return k < 1 ? 0 : (k == 1 ? 1 : (k <= 4 ? 4 : (k <= 20 ? 20 : (k <= 32 ? 32 : 0)))); }
+
 hipError_t launch_bvh_knn_packet(int K, const KnnArgs& a, hipStream_t st) {
   if (a.q_count <= 0) return hipSuccess;
   const int packets = (a.q_count + 15) / 16;
 #define SICP_PK(KK, W, LIT) hipLaunchKernelGGL((bvh_knn_packet_kernel<KK, W, LIT>), dim3((packets + W - 1) / W), dim3(64 * W), 0, st, a)
   switch (K) {
-    case 1: SICP_PK(1, 4, false); break;
     case 4:
       if (a.w_out != nullptr && !a.w_bool_probability) SICP_PK(4, 4, true);  // the epilogue's weights with Probability() as a double
       else SICP_PK(4, 4, false);
@@ -1001,16 +1004,9 @@ hipError_t launch_bvh_knn_packet(int K, const KnnArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-bool nn_k_supported(int K) { return K == 1 || K == 4 || K == 20; }  // correspondences per source point (accumulate kernels)
-int nn_list_len(int k) { return k < 1 ? 0 : (k == 1 ? 1 : (k <= 4 ? 4 : (k <= 20 ? 20 : (k <= 32 ? 32 : 0)))); }
-
 hipError_t launch_bvh_knn_packet_jobs(int K, const KnnArgs* jobs, int n, hipStream_t st) {
-  for (int b = 0; b < n; b += kMaxKnnJobs) {
-    const int cnt = n - b < kMaxKnnJobs ? n - b : kMaxKnnJobs;
-    KnnJobs J;
-    int max_q = 0;
-    for (int i = 0; i < cnt; ++i) { J.job[i] = jobs[b + i]; max_q = jobs[b + i].q_count > max_q ? jobs[b + i].q_count : max_q; }
-    if (max_q <= 0) continue;
+  bool bad_K = false;
+  for_job_chunks<KnnJobs>(jobs, n, [](const KnnArgs& a) { return a.q_count; }, [&](const KnnJobs& J, int cnt, int max_q) {
     const int packets = (max_q + 15) / 16;
     bool literal = false;  // a job whose epilogue writes weights with Probability() as a double
     for (int i = 0; i < cnt; ++i) literal = literal || (J.job[i].w_out != nullptr && !J.job[i].w_bool_probability);
@@ -1023,11 +1019,11 @@ hipError_t launch_bvh_knn_packet_jobs(int K, const KnnArgs* jobs, int n, hipStre
         break;
       case 20: SICP_PKJ(20, 2, false); break;
       case 32: SICP_PKJ(32, 2, false); break;
-      default: return hipErrorInvalidValue;
+      default: bad_K = true;
     }
 #undef SICP_PKJ
-  }
-  return hipGetLastError();
+  });
+  return bad_K ? hipErrorInvalidValue : hipGetLastError();
 }
 
 }  // namespace sicp

@@ -491,13 +491,13 @@ int sicp_search_batch(sicp_handle* hs, int32_t n, const double* qt, int32_t what
       }
     }
     if (repeat < 1) repeat = 1;
-    const int L = jc.knn_K[0];
+    const int L = jc.part[0].knn_K;
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     for (int r = 0; r < repeat; ++r)
-      if (!jc.knn[0].empty()) HIPCHECK(sicp::launch_bvh_knn_packet_jobs(L, jc.knn[0].data(), (int)jc.knn[0].size(), h->stream));
+      if (!jc.part[0].knn.empty()) HIPCHECK(sicp::launch_bvh_knn_packet_jobs(L, jc.part[0].knn.data(), (int)jc.part[0].knn.size(), h->stream));
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     // whatever consumes the searches (covariances, histograms, projections) runs once, so the handles stay consistent
-    jc.knn[0].clear();
+    jc.part[0].knn.clear();
     SICPCHECK(flush_jobs(h, jc, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     if (kernel_ms) {

@@ -5,6 +5,41 @@
 namespace sicp {
 namespace host {
 
+// one launch per kind of what a slice holds, in dependency order: searches, then the kernels that consume them
+static int launch_slice(sicp_context* h, JobSlice& s, hipStream_t st) {
+  if (!s.knn.empty()) HIPCHECK(sicp::launch_bvh_knn_packet_jobs(s.knn_K, s.knn.data(), (int)s.knn.size(), st));
+  if (!s.cov.empty()) HIPCHECK(sicp::launch_cov_jobs(s.cov.data(), (int)s.cov.size(), st));
+  if (!s.proj.empty()) HIPCHECK(sicp::launch_proj_jobs(s.proj.data(), (int)s.proj.size(), st));
+  if (!s.weight.empty()) HIPCHECK(sicp::launch_em_weight_jobs(s.weight.data(), (int)s.weight.size(), st));
+  if (!s.count.empty()) HIPCHECK(sicp::launch_count_active_jobs(s.count.data(), (int)s.count.size(), st));
+  s.clear();
+  return SICP_OK;
+}
+
+// Where every stage driver hands its job: add(slice) appends it.  Inside a batch or a stream that slice is the current
+// one of the collector the driver installed, and flush_jobs launches it with the other pairs' jobs.  A handle on its own
+// launches it at once on `stream`, as a slice of that one job, between the events of `timer_bit` when the stream is the
+// handle's (KernelTimer), and says so in *own.
+struct OwnLaunch {
+  bool launched = false;  // by the handle for itself (what nn_launches / cov_launches count)
+  double ms = 0.0;        // its time (0 without profiling)
+};
+template <class Add>
+static int hand_off(sicp_context* h, hipStream_t stream, int timer_bit, Add add, OwnLaunch* own = nullptr) {
+  if (h->collect) return add(h->collect->part[h->collect->slice]);
+  JobSlice& one = h->own_jobs;
+  one.clear();  // (a launch that failed may have left its job behind)
+  SICPCHECK(add(one));
+  KernelTimer kt(h, stream == h->stream ? timer_bit : 0);
+  if (!one.knn.empty() && one.knn_K > 1) {  // the one single-job kernel that stays (kernels.h)
+    HIPCHECK(sicp::launch_bvh_knn_packet(one.knn_K, one.knn[0], stream));
+    one.knn.clear();
+  }
+  SICPCHECK(launch_slice(h, one, stream));
+  if (own) { own->launched = true; own->ms = kt.stop(); }
+  return SICP_OK;
+}
+
 // queries: points [q_begin, q_begin+q_count) of cloud Q (device order), optionally transformed
 // by M34; targets: segment `tseg` of cloud T.  Writes device indices of T (or -1) and distances.
 int run_nn(sicp_context* h, int K, const Cloud& Qc, int q_begin, int q_count, const double* M34, const Cloud& Tc,
@@ -57,20 +92,25 @@ int run_nn(sicp_context* h, int K, const Cloud& Qc, int q_begin, int q_count, co
       a.live_cnt = (unsigned long long*)h->d_count.p;
       h->counted_in_search = true;
     }
-    if (h->collect) {  // lock-step batch (packet search, no profiling: checked by the driver)
-      JobCollector& jc = *h->collect;
-      if (!jc.knn[jc.slice].empty() && jc.knn_K[jc.slice] != L) {
-        h->last_error = "internal: searches of two list lengths collected into one slice";
-        return SICP_ERR_INVALID_ARGUMENT;
-      }
-      jc.knn_K[jc.slice] = L;
-      jc.knn[jc.slice].push_back(a);
-      return SICP_OK;
+    OwnLaunch own;
+    if (h->params.nn_method == 2) {
+      KernelTimer kt(h, stream == h->stream ? timer_bit : 0);
+      HIPCHECK(sicp::launch_bvh_knn_quad(L, a, stream));
+      own.launched = true;
+      own.ms = kt.stop();
+    } else {  // (a batch collects packet searches only: checked by its driver)
+      SICPCHECK(hand_off(h, stream, timer_bit, [&](JobSlice& js) -> int {
+        if (!js.knn.empty() && js.knn_K != L) {
+          h->last_error = "internal: searches of two list lengths collected into one slice";
+          return SICP_ERR_INVALID_ARGUMENT;
+        }
+        js.knn_K = L;
+        js.knn.push_back(a);
+        return SICP_OK;
+      }, &own));
     }
-    KernelTimer kt(h, stream == h->stream ? timer_bit : 0);
-    if (h->params.nn_method == 2) HIPCHECK(sicp::launch_bvh_knn_quad(L, a, stream));
-    else HIPCHECK(sicp::launch_bvh_knn_packet(L, a, stream));
-    account(kt.stop());
+    if (!own.launched) return SICP_OK;
+    account(own.ms);
     if (want_dbg) {
       std::vector<int> hd((size_t)2 * q_count);
       HIPCHECK(hipMemcpy(hd.data(), dbg.p, sizeof(int) * hd.size(), hipMemcpyDeviceToHost));
@@ -162,8 +202,7 @@ int ensure_proj(sicp_context* h, Cloud& c) {
   sicp::ProjArgs a;
   a.n = c.n; a.C = P.num_classes;
   a.hist = c.hist.p; a.cm = h->d_cm.p; a.hval = h->d_hval.p; a.proj = c.proj.p;
-  if (h->collect) h->collect->proj[h->collect->slice].push_back(a);
-  else HIPCHECK(sicp::launch_proj(a, h->stream));
+  SICPCHECK(hand_off(h, h->stream, 0, [&](JobSlice& js) -> int { js.proj.push_back(a); return SICP_OK; }));
   c.proj_valid = true;
   c.proj_cm_id = want_id;
   return SICP_OK;
@@ -217,8 +256,7 @@ int compute_features(sicp_context* h, Cloud& c, bool with_hist, hipStream_t stre
     a.rec_dense = c.rec_dense.p; a.rec_dense_n = n;
     c.rec_dense_n = n;
   }
-  if (h->collect) h->collect->cov[h->collect->slice].push_back(a);
-  else HIPCHECK(sicp::launch_cov(a, stream));
+  SICPCHECK(hand_off(h, stream, 0, [&](JobSlice& js) -> int { js.cov.push_back(a); return SICP_OK; }));
   c.feat_valid = true;
   c.cov_general = false;  // (what the engine computes is of its own form)
   c.proj_valid = false;
@@ -277,7 +315,7 @@ int run_correspondences(sicp_context* h, const double* qt, int K, bool weights) 
   const bool sem = P.mode == SICP_MODE_SEMANTIC;
   h->counted_in_search = false;
   // EM-ICP, K = 4, at most 16 classes, packet search: the weights are written by the search's own epilogue
-  // (knn_kernels.hip: KnnArgs::w_*; the same operations as em_weight_rows4_kernel, which then does not run) -- for a handle
+  // (knn_kernels.hip: KnnArgs::w_*; the same operations as em_weight_rows4_jobs_kernel, which then does not run) -- for a handle
   // on its own and in batches of at most 4 pairs (JobCollector::fold_weights says why not in larger ones).  Only when
   // the projections it reads are already there -- computed by an EARLIER flush, not waiting in this one (a flush launches
   // its searches first).
@@ -290,7 +328,7 @@ int run_correspondences(sicp_context* h, const double* qt, int K, bool weights) 
               S.proj_valid && T.proj_valid && S.proj_cm_id == want_id && T.proj_cm_id == want_id;
     if (ok && h->collect) {
       ok = h->collect->fold_weights;
-      for (int s = 0; s < kParts; ++s) ok = ok && h->collect->cov[s].empty() && h->collect->proj[s].empty();
+      for (const JobSlice& js : h->collect->part) ok = ok && js.cov.empty() && js.proj.empty();
     }
     if (ok) {
       fold_args.srec = S.rec.p; fold_args.trec = T.rec.p;
@@ -370,7 +408,6 @@ int run_weights(sicp_context* h, const double* qt) {
   Cloud &S = h->cloud(0), &T = h->cloud(1);
   const int K = h->corr_K;
   if (P.mode == SICP_MODE_EM) {
-    KernelTimer kt(h, SICP_PROFILE_WEIGHT);
     const double t0 = now_ms();
     sicp::WeightArgs a{};
     a.n_s = S.n; a.K = K; a.C = P.num_classes;
@@ -389,10 +426,10 @@ int run_weights(sicp_context* h, const double* qt) {
     a.one_m_eps = 1.0 - P.epsilon;
     a.bool_probability = P.quirk_bool_probability;
     a.w = h->w.p;
-    if (h->collect) h->collect->weight[h->collect->slice].push_back(a);
-    else HIPCHECK(sicp::launch_em_weight(a, h->stream));
+    OwnLaunch own;
+    SICPCHECK(hand_off(h, h->stream, SICP_PROFILE_WEIGHT, [&](JobSlice& js) -> int { js.weight.push_back(a); return SICP_OK; }, &own));
     h->st.weight_launches += 1;
-    h->st.weight_kernel_ms += kt.stop();
+    h->st.weight_kernel_ms += own.ms;
     h->st.t_weight_ms += now_ms() - t0;
     h->corr_weighted = true;
   }
@@ -407,7 +444,7 @@ void fill_acc(sicp_context* h, sicp::AccArgs& a) {
   a.w = h->corr_weighted ? h->w.p : nullptr;
   a.srec = S.rec.p; a.trec = T.rec.p;
   a.srec_dense = (S.rec_dense_n == S.n && S.n > 0 && S.n == h->corr_n) ? S.rec_dense.p : nullptr;
-  // the gathers come from the target's dense arrays whenever they are current: rec_dense_n is set where rec is written (cov_kernel,
+  // the gathers come from the target's dense arrays whenever they are current: rec_dense_n is set where rec is written (cov_jobs_kernel,
   // set_normals_kernel) and cleared wherever feat_valid is (a cloud that is re-set, re-laid out or recycled by the pool)
   a.trec_dense = (T.feat_valid && T.rec_dense_n == T.n && T.n > 0 && T.n <= sicp::kDenseGatherMaxPoints) ? T.rec_dense.p : nullptr;
   a.n_t = T.n; a.pad_ = 0;
@@ -479,7 +516,8 @@ int align_begin(sicp_context* h, bool want_stats) {
   const double t0 = now_ms();
   // the two clouds' feature kernels are independent and latency bound: run them side by side
   // (not with brute force, which shares one scratch buffer, nor while those kernels are timed)
-  const bool side_by_side = P.nn_method >= 1 && !(P.profile & SICP_PROFILE_COV);
+  // (nor inside a batch or a stream, where the handle's two streams are one borrowed stream)
+  const bool side_by_side = P.nn_method >= 1 && !(P.profile & SICP_PROFILE_COV) && h->stream2 != h->stream;
   // A cloud is searched at most once per align() / align_batch() call (it may be shared by two
   // handles of a batch: one scan is the source of a pair and the target of the next), and not at
   // all when reuse_features is set and the features already belong to this cloud, k and C.
@@ -491,7 +529,7 @@ int align_begin(sicp_context* h, bool want_stats) {
   if (stale(S)) SICPCHECK(compute_features(h, S, em));
   if (stale(T)) {
     SICPCHECK(compute_features(h, T, em, side_by_side ? h->stream2 : h->stream));
-    if (side_by_side && !h->collect) {
+    if (side_by_side) {
       HIPCHECK(hipEventRecord(h->ev_join, h->stream2));
       HIPCHECK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
     }
@@ -549,7 +587,7 @@ int batch_slice(int p, int n, int knn) {
   return (int)((long long)p * parts / n);
 }
 
-// launches what the pairs' stages collected: searches, then the kernels that consume them
+// launches what the pairs' stages collected
 int flush_jobs(sicp_context* h, JobCollector& jc, hipStream_t base) {
   if (!base) base = h->stream;
   // The slices of the batch run their stage sequences (searches -> covariances -> projections ->
@@ -558,7 +596,7 @@ int flush_jobs(sicp_context* h, JobCollector& jc, hipStream_t base) {
   bool used[kParts];
   int n_used = 0;
   for (int s = 0; s < kParts; ++s) {
-    used[s] = !jc.knn[s].empty() || !jc.cov[s].empty() || !jc.proj[s].empty() || !jc.weight[s].empty() || !jc.count[s].empty();
+    used[s] = !jc.part[s].empty();
     n_used += used[s];
   }
   const bool fork = n_used > 1 || (n_used == 1 && !used[0]);
@@ -575,12 +613,7 @@ int flush_jobs(sicp_context* h, JobCollector& jc, hipStream_t base) {
     if (!used[s]) continue;
     hipStream_t st = s ? h->part_stream[s] : base;
     if (s) HIPCHECK(hipStreamWaitEvent(st, h->part_fork, 0));
-    if (!jc.knn[s].empty()) HIPCHECK(sicp::launch_bvh_knn_packet_jobs(jc.knn_K[s], jc.knn[s].data(), (int)jc.knn[s].size(), st));
-    if (!jc.cov[s].empty()) HIPCHECK(sicp::launch_cov_jobs(jc.cov[s].data(), (int)jc.cov[s].size(), st));
-    if (!jc.proj[s].empty()) HIPCHECK(sicp::launch_proj_jobs(jc.proj[s].data(), (int)jc.proj[s].size(), st));
-    if (!jc.weight[s].empty()) HIPCHECK(sicp::launch_em_weight_jobs(jc.weight[s].data(), (int)jc.weight[s].size(), st));
-    if (!jc.count[s].empty()) HIPCHECK(sicp::launch_count_active_jobs(jc.count[s].data(), (int)jc.count[s].size(), st));
-    jc.knn[s].clear(); jc.cov[s].clear(); jc.proj[s].clear(); jc.weight[s].clear(); jc.count[s].clear();
+    SICPCHECK(launch_slice(h, jc.part[s], st));
     if (s) {
       HIPCHECK(hipEventRecord(h->part_done[s], st));
       HIPCHECK(hipStreamWaitEvent(base, h->part_done[s], 0));
@@ -623,12 +656,8 @@ int labels_launch(sicp_context* h, const double* qt, hipStream_t st) {
 
 // statistics only: add the number of live slots of the current search to the device counter (run_correspondences)
 int count_active(sicp_context* h) {
-  if (h->collect) {
-    h->collect->count[h->collect->slice].push_back(sicp::CountJob{h->idx.p, h->corr_n * h->corr_K, (unsigned long long*)h->d_count.p});
-    return SICP_OK;
-  }
-  HIPCHECK(sicp::launch_count_active(h->idx.p, h->corr_n * h->corr_K, (unsigned long long*)h->d_count.p, h->stream));
-  return SICP_OK;
+  const sicp::CountJob job{h->idx.p, h->corr_n * h->corr_K, (unsigned long long*)h->d_count.p};
+  return hand_off(h, h->stream, 0, [&](JobSlice& js) -> int { js.count.push_back(job); return SICP_OK; });
 }
 
 }  // namespace host

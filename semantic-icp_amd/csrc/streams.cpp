@@ -141,11 +141,7 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
       S->slot_t0[p] = now_ms();
       S->slot_flags[p] = fresh[k].flags;
       jc.slice = batch_slice(p, S->cap, S->params.knn);
-      size_t mark[5][kParts];  // what the collector held before this registration queued anything
-      for (int q = 0; q < kParts; ++q) {
-        mark[0][q] = jc.knn[q].size(); mark[1][q] = jc.cov[q].size(); mark[2][q] = jc.proj[q].size();
-        mark[3][q] = jc.weight[q].size(); mark[4][q] = jc.count[q].size();
-      }
+      const JobSlice::Sizes mark = jc.part[jc.slice].sizes();  // what its slice held before this registration queued anything
       FeatureMarks before[2] = {FeatureMarks(h->cl[0].get()), FeatureMarks(h->cl[1].get())};
       int rc = check_ready(h, false);
       if (rc == SICP_OK && general_covariances(h)) rc = SICP_ERR_INVALID_ARGUMENT;  // (caller covariances of general form: sicp_align, one pair at a time)
@@ -164,10 +160,7 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
         if (rc == SICP_ERR_HIP) { stream_fail(S, rc, h->last_error); return; }
         // nothing of it runs: the jobs it had queued are dropped, its clouds go back (a released cloud's memory must not
         // stay pinned by an idle slot), and the registrations waiting for those clouds may come in
-        for (int q = 0; q < kParts; ++q) {
-          jc.knn[q].resize(mark[0][q]); jc.cov[q].resize(mark[1][q]); jc.proj[q].resize(mark[2][q]);
-          jc.weight[q].resize(mark[3][q]); jc.count[q].resize(mark[4][q]);
-        }
+        jc.part[jc.slice].shrink_to(mark);
         // ... and with the jobs goes what they would have written: compute_features / ensure_proj mark a cloud's records,
         // histograms and projections current when they QUEUE the kernels, so a registration that failed on its second cloud
         // (an arena that is full: SICP_ERR_OUT_OF_MEMORY) would leave its first cloud marked current with nothing computed,

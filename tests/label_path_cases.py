@@ -17,7 +17,7 @@ from np_ref import mat_to_qt
 K_COV, EPS = 20, 1e-3
 
 # cov_body keeps the counts of up to 16 classes in two 64-bit registers (classes 1-8 | 9-16) and walks bytes in global memory
-# beyond; launch_proj and the weight kernels change at 16 as well; 32 | 33 for no reason the code knows of; 255 is the most
+# beyond; launch_proj_jobs and the weight kernels change at 16 as well; 32 | 33 for no reason the code knows of; 255 is the most
 HIST_CLASSES = (1, 2, 8, 9, 15, 16, 17, 20, 32, 33, 255)
 FUSED_CLASSES = (9, 16, 17, 20)
 BATCH_SIZES = (3000, 2999, 1500, 257, 256)

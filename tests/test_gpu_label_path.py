@@ -1,5 +1,5 @@
 """GPU tests of EM-ICP's label path -- cov_body's label counts, proj_body / proj_rows_body, em_weight_rows_body<4> /
-em_weight_body / the search's weight epilogue, geometric_gate, fused_label_kernel and their job-array twins -- against
+em_weight_body / the search's weight epilogue, geometric_gate, fused_label_kernel, in job launches of one and of many -- against
 tests/label_path_ref.py on both sides of every branch on the class count C and on the slots per point K:
   counts        exactly, on the engine's own neighbour lists (which equal the oracle's), C on both sides of the register
                 borders (8 | 9, 16 | 17) and up to 255, 32 neighbours in one byte, non-finite points left out;
@@ -11,9 +11,9 @@ tests/label_path_ref.py on both sides of every branch on the class count C and o
                 literal formula turns 0: w > 0 exactly where the reference's Probability() is true;
   fused labels  exactly as the oracle's, with the distance gate wide and tight (points with 0, 1-3 and 4 live slots); with the
                 gate as a double, exactly as the restatement's scores say;
-  batch twins   align_batch of five pairs of ragged sizes at C = 17 equals the lone aligns bit for bit; so do batches of
+  batches       align_batch of five pairs of ragged sizes at C = 17 equals the lone aligns bit for bit; so do batches of
                 handles with Probability() as a double (3 and 5 pairs, C on both sides of 16) and batches that mix them with
-                bool handles -- the job-array twins of the kernels that hold both forms of the gate.
+                bool handles -- job launches of many of the kernels that hold both forms of the gate.
 Every case prints its figures (run with -s); profiles/label_path/figures.txt holds them."""
 import importlib
 
@@ -240,10 +240,10 @@ def test_fused_labels_with_the_probability_as_a_double(C, gate_sq):
     assert (got != as_bool).sum() > 0   # (the density weighs the slots differently: the branch changes labels)
 
 
-# ---- 5. batch twins ---------------------------------------------------------------------------------------------------------------
+# ---- 5. batches -------------------------------------------------------------------------------------------------------------------
 def test_align_batch_at_17_classes_equals_the_lone_aligns():
     """five pairs in one batch (more than four: the weights stay in em_weight_jobs_kernel), sources of ragged sizes: the byte-walk
-    side of cov_jobs_kernel, proj_jobs_kernel and the generic em_weight_jobs_kernel against their single-launch twins"""
+    side of cov_jobs_kernel, proj_jobs_kernel and the generic em_weight_jobs_kernel in launches of several jobs against launches of one"""
     src, sl, tgt, tl, _ = cases.labelled_pair(17)
     engines, singles = [], []
     try:
@@ -276,7 +276,7 @@ Q1_OFF_BATCHES = [   # (id, C, quirk_bool_probability per pair)
 
 @pytest.mark.parametrize("C,quirks", [c[1:] for c in Q1_OFF_BATCHES], ids=[c[0] for c in Q1_OFF_BATCHES])
 def test_align_batch_with_the_probability_as_a_double_equals_the_lone_aligns(C, quirks):
-    """the job-array twins of the kernels that compute Probability() as a double, and the rule that one such job in a launch
+    """job launches of the kernels that compute Probability() as a double, and the rule that one such job in a launch
     takes the whole launch to them: per pair the batch gives the lone align's bits, whatever its neighbours in the batch are"""
     src, sl, tgt, tl, _ = cases.labelled_pair(C)
     engines, singles = [], []

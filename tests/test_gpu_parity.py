@@ -245,7 +245,7 @@ def test_weights_and_accumulate_vs_oracle(pair1, mode, nn, lm):
 @pytest.mark.parametrize("C,bool_q", [(11, 1), (4, 1), (16, 1), (13, 0)])
 def test_em_weights_from_the_search_epilogue_equal_the_weight_kernel(lidar20k, C, bool_q):
     """EM-ICP, K = 4, at most 16 classes: the packet search writes the slots' weights in its epilogue (KnnArgs::w_*) instead
-    of em_weight_rows4_kernel running behind it -- the same operations in the same order (em_icp.hpp:84-89,108), so the same
+    of em_weight_rows4_jobs_kernel running behind it -- the same operations in the same order (em_icp.hpp:84-89,108), so the same
     bits.  A handle with a profiling mask takes the separate kernel: both, on the same correspondences, compared bit for bit
     (odd and even class counts: padded projection rows; quirk Q1 on and off: the literal pow / exp path)."""
     src, sl, tgt, tl, T, _ = lidar20k

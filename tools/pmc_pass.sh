@@ -15,7 +15,7 @@ for r in csv.DictReader(open(sys.argv[1])):
     acc[r["Kernel_Name"][:48]][r["Counter_Name"]].append(float(r["Counter_Value"]))
 for k, d in acc.items():
     n = max(len(v) for v in d.values())
-    if not any(s in k for s in ("knn", "accumulate", "lm_step", "cov_kernel", "weight")):
+    if not any(s in k for s in ("knn", "accumulate", "lm_step", "cov_jobs", "weight")):
         continue
     print(k, "dispatches", n, " ".join(f"{c}={sum(v)/len(v):.4g}" for c, v in sorted(d.items())))
 PY
