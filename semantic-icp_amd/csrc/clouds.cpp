@@ -149,24 +149,24 @@ int prepare_cloud(sicp_context* h, Cloud& c) {
   const int n_seg = (int)c.seg_label.size();
   c.seg_off.assign(n_seg + 1, 0);
   c.trees.assign(n_seg, Cloud::SegTree());
-  std::vector<sicp::BuildSegment> segs(n_seg);
+  HIPCHECK(c.h_segs.resize((size_t)std::max(n_seg, 1)));  // the build's segment table (build_tree.h), filled in place
   int pt_total = 0, node_total = 0, code_total = 0, max_cnt = 1;
   for (int sg = 0; sg < n_seg; ++sg) {
-    sicp::BuildSegment& g = segs[sg];
+    sicp::BuildSegment& g = c.h_segs[sg];
+    Cloud::SegTree& st = c.trees[sg];
     g.off = c.seg_off[sg]; g.cnt = counts[sg];
     c.seg_off[sg + 1] = g.off + g.cnt;
-    g.lv = sicp::make_levels(g.cnt);
-    g.padded = g.lv.cnt[0] * sicp::kLeaf;  // every leaf of the complete tree owns 16 point slots (sentinels beyond the real points)
+    st.lv = sicp::make_levels(g.cnt);
+    g.n_leaf = st.lv.cnt[0]; g.top = st.lv.n_levels - 1;
+    g.padded = g.n_leaf * sicp::kLeaf;  // every leaf of the complete tree owns 16 point slots (sentinels beyond the real points)
     g.pt_begin = pt_total; g.node_begin = node_total; g.code_begin = code_total;
-    pt_total += g.padded; node_total += sicp::total_nodes(g.lv); code_total += g.lv.cnt[0];
+    pt_total += g.padded; node_total += sicp::total_nodes(st.lv); code_total += g.n_leaf;
     float ext = 0.f;
-    for (int d = 0; d < 3; ++d) { g.lo[d] = g.cnt > 0 ? lo[3 * sg + d] : 0.f; if (g.cnt > 0) ext = std::max(ext, hi[3 * sg + d] - lo[3 * sg + d]); }
+    for (int d = 0; d < 3; ++d) { st.lo[d] = g.cnt > 0 ? lo[3 * sg + d] : 0.f; if (g.cnt > 0) ext = std::max(ext, hi[3 * sg + d] - lo[3 * sg + d]); }
     if (!(ext > 0.f) || !std::isfinite(ext)) ext = 1.f;
-    g.scale = 2097151.f / ext;
+    g.lox = st.lo[0]; g.loy = st.lo[1]; g.loz = st.lo[2]; g.scale = st.scale = 2097151.f / ext;
     max_cnt = std::max(max_cnt, g.cnt);
-    Cloud::SegTree& st = c.trees[sg];
-    st.lv = g.lv; st.n = g.cnt; st.pt_begin = g.pt_begin; st.node_begin = g.node_begin; st.code_begin = g.code_begin;
-    st.lo[0] = g.lo[0]; st.lo[1] = g.lo[1]; st.lo[2] = g.lo[2]; st.scale = g.scale;
+    st.n = g.cnt; st.pt_begin = g.pt_begin; st.node_begin = g.node_begin; st.code_begin = g.code_begin;
   }
   HostBuf<int>& ids = c.h_ids;
   if (want) {  // caller indices grouped by segment, cloud order inside a segment
@@ -178,18 +178,12 @@ int prepare_cloud(sicp_context* h, Cloud& c) {
   const size_t m = (size_t)(n > 0 ? n : 1);
   HIPCHECK(c.rx.reserve(m)); HIPCHECK(c.ry.reserve(m)); HIPCHECK(c.rz.reserve(m)); HIPCHECK(c.rl.reserve(m));
   HIPCHECK(c.ids.reserve(m)); HIPCHECK(c.d_perm.reserve(m));
-  // one segment: sort buffers of its size; several: every segment sorts its own range of buffers that hold all points (and the
-  // segments' descriptions go to the device: the other stages are ONE launch over all segments)
-  const bool together = want && n_seg > 1;
-  const size_t sort_n = together ? m : (size_t)max_cnt;
-  HIPCHECK(c.keys_in.reserve(sort_n)); HIPCHECK(c.keys_out.reserve(sort_n));
-  HIPCHECK(c.vals_in.reserve(sort_n)); HIPCHECK(c.vals_out.reserve(sort_n));
+  // every segment sorts its own range of buffers that hold all points; the segment table goes to the device with them
+  HIPCHECK(c.keys_in.reserve(m)); HIPCHECK(c.keys_out.reserve(m));
+  HIPCHECK(c.vals_in.reserve(m)); HIPCHECK(c.vals_out.reserve(m));
   const size_t temp_bytes = sicp::build_sort_temp_bytes(max_cnt);
   HIPCHECK(c.sort_temp.reserve(temp_bytes + 256));
-  if (together) {
-    HIPCHECK(c.d_segs.reserve((size_t)n_seg)); HIPCHECK(c.d_seg_begin.reserve((size_t)n_seg)); HIPCHECK(c.d_seg_end.reserve((size_t)n_seg));
-    HIPCHECK(c.h_segs.resize((size_t)n_seg)); HIPCHECK(c.h_seg_begin.resize((size_t)n_seg)); HIPCHECK(c.h_seg_end.resize((size_t)n_seg));
-  }
+  HIPCHECK(c.d_segs.reserve(c.h_segs.size()));
   HIPCHECK(c.x.reserve(m)); HIPCHECK(c.y.reserve(m)); HIPCHECK(c.z.reserve(m));
   HIPCHECK(c.label.reserve(m)); HIPCHECK(c.inv.reserve(m));
   HIPCHECK(c.pts4.reserve((size_t)pt_total + 1)); HIPCHECK(c.box_lo.reserve((size_t)node_total + 1));
@@ -206,12 +200,10 @@ int prepare_cloud(sicp_context* h, Cloud& c) {
   b.rx = c.rx.p; b.ry = c.ry.p; b.rz = c.rz.p; b.rl = c.has_label ? c.rl.p : nullptr; b.ids = want ? c.ids.p : nullptr;
   b.keys_in = c.keys_in.p; b.keys_out = c.keys_out.p; b.vals_in = c.vals_in.p; b.vals_out = c.vals_out.p;
   b.sort_temp = c.sort_temp.p; b.sort_temp_bytes = temp_bytes;
-  b.d_segs = together ? c.d_segs.p : nullptr; b.h_segs = together ? c.h_segs.data() : nullptr;
-  b.d_seg_begin = together ? c.d_seg_begin.p : nullptr; b.d_seg_end = together ? c.d_seg_end.p : nullptr;
-  b.h_seg_begin = together ? c.h_seg_begin.data() : nullptr; b.h_seg_end = together ? c.h_seg_end.data() : nullptr;
+  b.d_segs = c.d_segs.p; b.h_segs = c.h_segs.data();
   b.x = c.x.p; b.y = c.y.p; b.z = c.z.p; b.label = c.label.p; b.perm = c.d_perm.p; b.inv = c.inv.p;
   b.pts4 = c.pts4.p; b.box_lo = c.box_lo.p; b.box_hi = c.box_hi.p; b.leaf_code = c.leaf_code.p;
-  HIPCHECK(sicp::build_tree_device(b, segs.data(), n_seg, h->stream));
+  HIPCHECK(sicp::build_tree_device(b, n_seg, h->stream));
   HIPCHECK(c.perm.resize(n));  // device -> caller order, for returning results in the caller's order
   if (n > 0) HIPCHECK(hipMemcpyAsync(c.perm.data(), c.d_perm.p, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
   // no synchronisation here: every staging buffer is pinned memory owned by the cloud, and the next
