@@ -644,6 +644,75 @@ int sicp_map_integrate(sicp_map m, sicp_handle h, int which, const double qt[7] 
  * +inf keeps everything); the survivors' state is unchanged bit for bit.  n_removed (nullable): voxels dropped. */
 int sicp_map_prune(sicp_map m, const double center[3], double range, int64_t* n_removed);
 
+/* ---- free-space carving: remove map voxels a new scan sees through ----------------
+ * Every ray of a scan, from the sensor to its return, shows that the voxels it passes through are empty.  A map voxel that
+ * enough rays of ONE scan pass through, and in which no return of that scan lands, is removed: the car that stood in scan 3
+ * and drove off.  The intended order in a loop is align -> carve(scan, pose) -> integrate(scan, pose).  The rules:
+ *  1. Points and origin.  The points are the finite points the slot holds, in caller order, whatever the handle's mode and
+ *     device layout; each is transformed by qt exactly as sicp_map_integrate does, giving float p.  The origin o is
+ *     (float)sensor_origin put through the same arithmetic, as a point of the scan would be.  Both are keyed with the grid's float
+ *     arithmetic, v = floor(p * inv_leaf) with inv_leaf = 1.0f / (float)leaf_size: vo, vp.  An origin with |v| >= 2^20 on an axis
+ *     is refused; a point with such a voxel takes no part (it is not an error).
+ *  2. Hits.  Every point with a valid key marks its voxel's row as hit, if the map holds that voxel.  The range test plays no
+ *     part here.
+ *  3. Rays.  A point casts a ray when its key is valid and either max_range = 0 or step 3's crop test of sicp_merge_clouds
+ *     holds for p about the centre o with the range max_range (all in float, as there).
+ *  4. The walk runs in double, every operation rounded on its own, no contraction.  Per axis a: u = (double)o_a * (double)
+ *     inv_leaf and w = (double)p_a * (double)inv_leaf (both products are exact); rem_a = |vp_a - vo_a| and step_a the sign of
+ *     vp_a - vo_a.  For an axis with rem_a > 0: du = w - u, tmax_a = ((double)(vo_a + (step_a > 0 ? 1 : 0)) - u) / du and
+ *     tdelta_a = (double)step_a / du.  The ray visits v_0 = vo and then takes exactly n = rem_x + rem_y + rem_z steps; a step
+ *     picks, among the axes with rem_a > 0, the one with the smallest tmax_a (ties: x before y before z) and sets v_a +=
+ *     step_a, rem_a -= 1, tmax_a = tmax_a + tdelta_a.  So v_n = vp by construction, whatever the rounding: the trip count is an
+ *     integer known before the loop and nothing loops on a floating-point condition.  The carve candidates of the ray are v_i for
+ *     0 <= i < n - end_margin (none when n <= end_margin; the return's own voxel v_n is never one).
+ *  5. Miss counts.  miss[row] += 1 for every candidate the map holds.  A ray visits a voxel at most once; the counts are
+ *     integers, so the result does not depend on the order of the updates.
+ *  6. Removal.  A row is removed when miss >= min_rays, it is not hit, and its fullest histogram bin -- sicp_map_extract's label:
+ *     ties to the smallest label, bin 0 can win -- is not in protect.  The survivors keep their state bit for bit and stay in
+ *     ascending key; the map's point count follows, as in sicp_map_prune.
+ *  7. Outputs.  miss (nullable, capacity elements): one count per row of the map BEFORE the call in ascending key, the order of
+ *     sicp_map_extract with its defaults; written when non-NULL and capacity >= that row count.  A smaller capacity gives
+ *     SICP_ERR_INVALID_ARGUMENT with info written (n_removed: the rows that would have gone) and nothing else happens.  info
+ *     (nullable) is written on success and on that one refusal.
+ *  8. Contracts: those of sicp_map_integrate.  The call computes into the spare set and swaps last, so every refusal leaves
+ *     every extract byte as it was.  SICP_ERR_INVALID_ARGUMENT: a NULL map, handle or params; `which` outside the two slots; a
+ *     pose or origin that is not finite; an origin beyond the key's range; max_range negative or NaN (+inf: every ray);
+ *     min_rays < 1; end_margin < 0; dry_run neither 0 nor 1; n_protect outside 0..SICP_MAP_MAX_PROTECT, or > 0 on a map with
+ *     num_classes = 0; a protected label above num_classes; a handle on another device.  SICP_ERR_NOT_READY: the slot holds no
+ *     cloud.  An empty map, or a scan without rays: SICP_OK, nothing changes.  The handle is not modified; the cloud's labels are
+ *     not read.  No float atomics: two maps driven alike are byte-identical, whatever the launch shape.
+ * Cost: one lookup among the map's keys per candidate, a ray's candidates one after the other.  max_range is what bounds a
+ * ray's length, n <= 3 * max_range / leaf_size + 3; with max_range = 0 a stray far return walks all the way (up to 3 * 2^21
+ * steps), so a loop that feeds raw scans should set it.
+ * The counts do not persist: a voxel must be seen through min_rays times by one scan.  The default min_rays = 3 is a choice; it
+ * has not been tuned on real data. */
+#define SICP_MAP_MAX_PROTECT 64
+typedef struct sicp_map_carve_params {
+  double  max_range;      /* 0 (default) = every ray; else only rays whose return passes step 3's crop test about the origin */
+  int32_t min_rays;       /* a voxel goes when at least this many rays of THIS scan pass through it.  default 3, >= 1 */
+  int32_t end_margin;     /* voxels before the return's voxel that a ray spares.  default 1, >= 0 */
+  int32_t dry_run;        /* 1: count, remove nothing.  default 0 */
+  int32_t n_protect;      /* 0 (default) .. SICP_MAP_MAX_PROTECT */
+  uint32_t protect[SICP_MAP_MAX_PROTECT]; /* a voxel whose fullest histogram bin (extract's label rule) is one of these is never removed */
+} sicp_map_carve_params;
+typedef struct sicp_map_carve_info {
+  int64_t n_in;           /* finite points of the slot */
+  int64_t n_rays;         /* points that cast a ray */
+  int64_t n_steps;        /* carve candidates visited by all rays (map or not) */
+  int64_t n_voxels;       /* the map's voxels after the call */
+  int32_t n_touched;      /* map rows with miss > 0 */
+  int32_t n_hit;          /* map rows that hold a return of this scan */
+  int32_t n_removed;      /* rows removed (dry_run: rows that would be) */
+  int32_t n_spared_hit, n_spared_label;  /* rows with miss >= min_rays kept by the hit rule / by protect (hit first) */
+  int32_t reserved_;
+  double t_total_ms;      /* host wall clock */
+} sicp_map_carve_info;
+int sicp_default_map_carve_params(sicp_map_carve_params* p);
+int sicp_map_carve(sicp_map m, sicp_handle h, int which, const double qt[7] /* NULL = identity */,
+                   const double sensor_origin[3] /* in the scan's own frame; NULL = 0 0 0 */,
+                   const sicp_map_carve_params* p, int32_t capacity, uint32_t* miss /* nullable */,
+                   sicp_map_carve_info* info /* nullable */);
+
 typedef struct sicp_map_extract_params {
   int32_t min_count;      /* voxels with fewer points are left out.  default 1 */
   int32_t reserved_;

@@ -287,6 +287,41 @@ class SicpMapExtractInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
 
 
+MAP_MAX_PROTECT = 64
+
+
+class SicpMapCarveParams(C.Structure):
+    """sicp_map_carve_params (include/sicp.h)"""
+    _fields_ = [
+        ("max_range", C.c_double),
+        ("min_rays", C.c_int32),
+        ("end_margin", C.c_int32),
+        ("dry_run", C.c_int32),
+        ("n_protect", C.c_int32),
+        ("protect", C.c_uint32 * MAP_MAX_PROTECT),
+    ]
+
+
+class SicpMapCarveInfo(C.Structure):
+    """sicp_map_carve_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_in", C.c_int64),
+        ("n_rays", C.c_int64),
+        ("n_steps", C.c_int64),
+        ("n_voxels", C.c_int64),
+        ("n_touched", C.c_int32),
+        ("n_hit", C.c_int32),
+        ("n_removed", C.c_int32),
+        ("n_spared_hit", C.c_int32),
+        ("n_spared_label", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
+
+
 class SicpError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -409,6 +444,9 @@ def lib():
             "sicp_map_size": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
             "sicp_map_integrate": [C.c_void_p, C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.POINTER(SicpMapIntegrateInfo)],
             "sicp_map_prune": [C.c_void_p, _dp, C.c_double, C.POINTER(C.c_int64)],
+            "sicp_default_map_carve_params": [C.POINTER(SicpMapCarveParams)],
+            "sicp_map_carve": [C.c_void_p, C.c_void_p, C.c_int, _dp, _dp, C.POINTER(SicpMapCarveParams), C.c_int32, _up,
+                               C.POINTER(SicpMapCarveInfo)],
             "sicp_map_extract": [C.c_void_p, C.POINTER(SicpMapExtractParams), C.c_void_p, C.c_int, C.c_int32, _fp, _fp, _fp, _up, _up, _up,
                                  C.POINTER(SicpMapExtractInfo)],
             "sicp_map_set_confusion": [C.c_void_p, C.c_int32, _dp],
@@ -528,6 +566,28 @@ def default_map_extract_params(**overrides) -> SicpMapExtractParams:
         if not hasattr(p, k):
             raise AttributeError(k)
         setattr(p, k, (C.c_double * 3)(*v) if k == "crop_center" else v)
+    return p
+
+
+def default_map_carve_params(**overrides) -> SicpMapCarveParams:
+    """sicp_default_map_carve_params (every ray, min_rays 3, end_margin 1, nothing protected), with any field overridden by
+    keyword; protect takes the labels themselves and sets n_protect with them"""
+    p = SicpMapCarveParams()
+    st = lib().sicp_default_map_carve_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_map_carve_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        if k == "protect":
+            labels = [int(l) for l in v]
+            if len(labels) > MAP_MAX_PROTECT:
+                raise ValueError(f"at most {MAP_MAX_PROTECT} protected labels")
+            p.protect = (C.c_uint32 * MAP_MAX_PROTECT)(*labels)
+            if "n_protect" not in overrides:
+                p.n_protect = len(labels)
+        else:
+            setattr(p, k, v)
     return p
 
 
@@ -1098,6 +1158,22 @@ class VoxelMap:
         self._check(lib().sicp_map_fused_labels(self._m, engine._h, which, _ptr(q, _dp), int(bool(include_own)), min_count,
                                                 _ptr(labels, _up), _ptr(conf, _dp)), "sicp_map_fused_labels")
         return labels[:n].copy(), None if conf is None else conf[:n].copy()
+
+    def carve(self, engine: "Engine", which: int = SOURCE, qt=None, sensor_origin=None, params: SicpMapCarveParams | None = None,
+              want_miss: bool = False):
+        """sicp_map_carve: removes the voxels that at least params.min_rays rays of engine's slot `which` -- from sensor_origin (in
+        the scan's own frame; None: 0 0 0) to every finite point, at pose qt (None: identity) -- pass through, that hold no return
+        of the scan and whose label is not protected.  Returns {"miss": with want_miss the rays through every row the map had
+        before the call, ascending key (extract's default order), else None; "info": SicpMapCarveInfo.as_dict()}."""
+        q = None if qt is None else np.ascontiguousarray(qt, dtype=np.float64).reshape(7)
+        o = None if sensor_origin is None else np.ascontiguousarray(sensor_origin, dtype=np.float64).reshape(3)
+        p = params if params is not None else default_map_carve_params()
+        cap = self.size()[0] if want_miss else 0
+        miss = np.zeros(max(cap, 1), dtype=np.uint32) if want_miss else None
+        info = SicpMapCarveInfo()
+        self._check(lib().sicp_map_carve(self._m, engine._h, which, _ptr(q, _dp), _ptr(o, _dp), C.byref(p), cap, _ptr(miss, _up),
+                                         C.byref(info)), "sicp_map_carve")
+        return {"miss": None if miss is None else miss[:cap].copy(), "info": info.as_dict()}
 
     def prune(self, center, range):
         """sicp_map_prune: drops the voxels whose centroid lies further than `range` from `center`; returns their number"""

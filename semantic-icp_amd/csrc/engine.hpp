@@ -9,7 +9,7 @@
 //   pose_cov.cpp  sicp_pose_covariance: the sweep over a group of pairs, the 6x6 algebra
 //   evaluate.cpp  sicp_evaluate: overlap, inlier RMSE and label agreement at a pose
 //   merge.cpp     sicp_merge_clouds: posed clouds into one voxel-grid cloud
-//   map.cpp       sicp_map_*: the persistent voxel map (integrate, prune, extract)
+//   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, prune, extract)
 //   sicp_api.cpp  the remaining C-ABI entry points
 // Every extern "C" entry runs inside abi_guard (abi_barrier.hpp): no exception crosses the boundary.
 #ifndef SICP_ENGINE_HPP_
@@ -923,6 +923,9 @@ int map_destroy(sicp_map_ctx* m);
 int map_integrate(sicp_map_ctx* m, sicp_context* h, int which, const double* qt, const double* crop_center, double crop_range,
                   sicp_map_integrate_info* info);
 int map_prune(sicp_map_ctx* m, const double* center, double range, int64_t* n_removed);
+void map_default_carve_params(sicp_map_carve_params* p);
+int map_carve(sicp_map_ctx* m, sicp_context* h, int which, const double* qt, const double* sensor_origin, const sicp_map_carve_params* p,
+              int32_t capacity, uint32_t* miss, sicp_map_carve_info* info);
 int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
                 float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info);
 int map_set_confusion(sicp_map_ctx* m, int32_t C, const double* cm);

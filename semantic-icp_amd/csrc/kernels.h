@@ -565,6 +565,43 @@ struct MapSelectArgs {
 hipError_t launch_map_select(const MapSelectArgs& a, hipStream_t st);
 hipError_t launch_map_prune(const MapSelectArgs& a, hipStream_t st);
 hipError_t launch_map_extract(const MapSelectArgs& a, hipStream_t st);
+// free-space carving (sicp_map_carve): every ray of a scan, from the sensor's voxel to its return's, walks the grid by the
+// arithmetic of voxel_key.hpp (VoxelRay) and looks every candidate voxel up among the map's keys; a row counts the rays that
+// pass through it (integer atomics: any order gives the same counts) and is flagged when a return lands in it.  A wave owns
+// kCarveRaysPerWave consecutive rays and hands them to its lanes as they fall idle, so a long ray does not hold 63 finished
+// lanes; a step along x finds its row beside the previous one (the key moves by 1), a step along y gallops from it.  The rows
+// to keep then go through prune's scan and compaction.
+constexpr int kCarveRaysPerWave = 128;
+constexpr int kMapMaxProtect = 64;  // SICP_MAP_MAX_PROTECT
+enum { kCarveRays = 0, kCarveSteps, kCarveTouched, kCarveHit, kCarveRemoved, kCarveSparedHit, kCarveSparedLabel, kCarveStats = 8 };
+struct MapCarveArgs {
+  const float *x, *y, *z;   // the scan's finite points in caller order (Cloud::rx ...)
+  double M[12];
+  int n;
+  float inv_leaf;
+  float sx, sy, sz;         // (float)sensor_origin, transformed in the kernels as a point is
+  int ranged;               // max_range > 0
+  double range_sq;
+  int end_margin;
+  const unsigned long long* key;  // the map's keys, ascending
+  int n_map;
+  int* hit;                 // [n_map] zeroed: 1 where a return lands
+  uint32_t* miss;           // [n_map] zeroed: rays that pass through
+  unsigned long long* stat; // kCarveStats words, zeroed
+  int* res;                 // res[kMapRange]: the origin lies beyond the key's range (zeroed before the launch)
+};
+struct MapCarveSelectArgs {
+  int n_map, stride, min_rays, n_protect;
+  uint32_t protect[kMapMaxProtect];
+  const uint32_t* hist;     // nullptr when the map keeps no labels
+  const int* hit;
+  const uint32_t* miss;
+  int* flag;                // [n_map] 1: the row stays
+  unsigned long long* stat;
+};
+hipError_t launch_map_carve_hits(const MapCarveArgs& a, hipStream_t st);    // hit, res[kMapRange] (launched for n = 0 too)
+hipError_t launch_map_carve_walk(const MapCarveArgs& a, hipStream_t st);    // miss, stat[rays, steps]
+hipError_t launch_map_carve_select(const MapCarveSelectArgs& a, hipStream_t st);  // flag, stat[touched ... spared]
 // label fusion through the confusion matrix (sicp_map_extract_fused, sicp_map_fused_labels).  logcm[r * C + s] = log cm[r][s]
 // (observed label r + 1, class s + 1; -inf for a zero entry).  A histogram row's score of class s is the sum over its
 // non-zero bins r = 1..C, ascending, of (double)h[r] * logcm[r - 1][s - 1], each product and each sum rounded once.  An item

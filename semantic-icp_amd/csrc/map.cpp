@@ -24,13 +24,14 @@ struct MapScratch {
   DevBuf<float> tx, ty, tz, gx, gy, gz, ox, oy, oz;
   DevBuf<uint32_t> ol, oc, ohist;
   DevBuf<double> oconf;
-  DevBuf<unsigned long long> key, key2, miss_key, total;
-  DevBuf<int> val, val2, flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res;
+  DevBuf<unsigned long long> key, key2, miss_key, total, stat;
+  DevBuf<int> val, val2, flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res, ray_hit;
+  DevBuf<uint32_t> ray_miss;
   int device = -1;
   bool idle = true;
   ~MapScratch() {
-    DevArena::release_scratch(device, idle, temp, tx, ty, tz, gx, gy, gz, ox, oy, oz, ol, oc, ohist, oconf, key, key2, miss_key, total, val,
-                              val2, flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res);
+    DevArena::release_scratch(device, idle, temp, tx, ty, tz, gx, gy, gz, ox, oy, oz, ol, oc, ohist, oconf, key, key2, miss_key, total, stat,
+                              val, val2, flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res, ray_hit, ray_miss);
   }
 };
 
@@ -75,6 +76,35 @@ Crop make_crop(const double* center, double range) {
   return k;
 }
 
+// The rows whose S.flag is 1 become the map (prune and carve): the flags' scan, the survivors bit for bit into the spare set
+// (S.to, reserved by the caller for n_map rows, as are X.pos, X.src_of, X.res -- zeroed --, X.total and X.temp for the scan),
+// their histograms behind them, and the swap.  Takes the stream as it is, leaves it idle.
+int keep_flagged_rows(sicp_map_ctx* m, MapScratch& X, const sicp::MapSelectArgs& S, size_t scan_bytes) {
+  hipStream_t st = m->stream;
+  X.idle = false;
+  MAPCHECK(m->stage.resize(sizeof(int) * sicp::kMapRes + sizeof(unsigned long long)));
+  MAPCHECK(hipMemsetAsync(X.total.p, 0, sizeof(unsigned long long), st));
+  MAPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, S.flag, S.pos, S.n_map, st));
+  MAPCHECK(sicp::launch_map_prune(S, st));
+  int res[sicp::kMapRes];
+  unsigned long long kept_points = 0;
+  MAPCHECK(hipMemcpyAsync(m->stage.data(), X.res.p, sizeof res, hipMemcpyDeviceToHost, st));
+  MAPCHECK(hipMemcpyAsync(m->stage.data() + sizeof res, X.total.p, sizeof kept_points, hipMemcpyDeviceToHost, st));
+  MAPCHECK(hipStreamSynchronize(st));
+  std::memcpy(res, m->stage.data(), sizeof res);
+  std::memcpy(&kept_points, m->stage.data() + sizeof res, sizeof kept_points);
+  const int n_keep = res[sicp::kMapOut];
+  if (S.stride > 0 && n_keep > 0) {  // (the rows' places are known: their histograms follow)
+    MAPCHECK(sicp::launch_map_move_hist(S.rows.hist, S.to.hist, S.src_of, n_keep, S.stride, st));
+    MAPCHECK(hipStreamSynchronize(st));
+  }
+  X.idle = true;
+  m->cur ^= 1;
+  m->n_voxels = n_keep;
+  m->n_points = kept_points;
+  return SICP_OK;
+}
+
 }  // namespace
 
 void map_default_params(sicp_map_params* p) {
@@ -85,6 +115,12 @@ void map_default_params(sicp_map_params* p) {
 void map_default_extract_params(sicp_map_extract_params* p) {
   std::memset(p, 0, sizeof *p);
   p->min_count = 1;
+}
+
+void map_default_carve_params(sicp_map_carve_params* p) {
+  std::memset(p, 0, sizeof *p);
+  p->min_rays = 3;
+  p->end_margin = 1;
 }
 
 int map_create(int device_id, const sicp_map_params* p, sicp_map_ctx** out) {
@@ -321,27 +357,172 @@ int map_prune(sicp_map_ctx* m, const double* center, double range, int64_t* n_re
   S.flag = X.flag.p; S.pos = X.pos.p; S.src_of = X.src_of.p;
   S.kept_points = X.total.p; S.res = X.res.p;
   MAPCHECK(hipMemsetAsync(X.res.p, 0, sizeof(int) * sicp::kMapRes, st));
-  MAPCHECK(hipMemsetAsync(X.total.p, 0, sizeof(unsigned long long), st));
   MAPCHECK(sicp::launch_map_select(S, st));
-  MAPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, X.flag.p, X.pos.p, n_map, st));
-  MAPCHECK(sicp::launch_map_prune(S, st));
-  int res[sicp::kMapRes];
-  unsigned long long kept_points = 0;
-  MAPCHECK(hipMemcpyAsync(m->stage.data(), X.res.p, sizeof res, hipMemcpyDeviceToHost, st));
-  MAPCHECK(hipMemcpyAsync(m->stage.data() + sizeof res, X.total.p, sizeof kept_points, hipMemcpyDeviceToHost, st));
-  MAPCHECK(hipStreamSynchronize(st));
-  std::memcpy(res, m->stage.data(), sizeof res);
-  std::memcpy(&kept_points, m->stage.data() + sizeof res, sizeof kept_points);
-  const int n_keep = res[sicp::kMapOut];
-  if (stride > 0 && n_keep > 0) {  // (the rows' places are known: their histograms follow)
-    MAPCHECK(sicp::launch_map_move_hist(S.rows.hist, S.to.hist, S.src_of, n_keep, stride, st));
-    MAPCHECK(hipStreamSynchronize(st));
+  const int rc = keep_flagged_rows(m, X, S, scan_bytes);
+  if (rc == SICP_OK && n_removed) *n_removed = (int64_t)n_map - m->n_voxels;
+  return rc;
+}
+
+int map_carve(sicp_map_ctx* m, sicp_context* h, int which, const double* qt, const double* sensor_origin, const sicp_map_carve_params* p,
+              int32_t capacity, uint32_t* miss, sicp_map_carve_info* info) {
+  if (!m) return SICP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const std::string& why) {
+    m->last_error = "sicp_map_carve: " + why + "; the map is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (!h) return refuse("the handle is NULL");
+  if (!p) return refuse("the params are NULL");
+  if (!slot_ok(which)) return refuse("`which` is neither SICP_SOURCE nor SICP_TARGET");
+  if (h->device != m->device) return refuse("the handle is on device " + std::to_string(h->device) + ", the map on " + std::to_string(m->device));
+  if (!(p->max_range >= 0.0)) return refuse("max_range must be >= 0 (+inf is allowed)");
+  if (p->min_rays < 1) return refuse("min_rays must be >= 1");
+  if (p->end_margin < 0) return refuse("end_margin must be >= 0");
+  if (p->dry_run != 0 && p->dry_run != 1) return refuse("dry_run is neither 0 nor 1");
+  const int C = m->params.num_classes, stride = stride_of(m);
+  if (p->n_protect < 0 || p->n_protect > SICP_MAP_MAX_PROTECT) return refuse("n_protect must be 0.." + std::to_string(SICP_MAP_MAX_PROTECT));
+  if (p->n_protect > 0 && C == 0) return refuse("the map keeps no labels: there is nothing to protect");
+  for (int j = 0; j < p->n_protect; ++j)
+    if (p->protect[j] > (uint32_t)C) return refuse("protect[" + std::to_string(j) + "] = " + std::to_string(p->protect[j]) + " is above num_classes = " + std::to_string(C));
+  if (sensor_origin)
+    for (int d = 0; d < 3; ++d)
+      if (!std::isfinite(sensor_origin[d])) return refuse("sensor_origin must be finite");
+  if (qt)
+    for (int k = 0; k < 7; ++k)
+      if (!std::isfinite(qt[k])) return refuse("the pose is not finite");
+  Cloud& c = h->cloud(which);
+  if (!c.is_set) {
+    m->last_error = "sicp_map_carve: the slot has no cloud";
+    return SICP_ERR_NOT_READY;
   }
-  X.idle = true;
-  m->cur ^= 1;
-  m->n_voxels = n_keep;
-  m->n_points = kept_points;
-  if (n_removed) *n_removed = (int64_t)n_map - n_keep;
+  const double t_begin = now_ms();
+  MAPCHECK(hipSetDevice(m->device));
+  if (c.layout < 0) {  // (prepared as a merge part is: sicp_map_integrate's rule)
+    const int rc = prepare_cloud(h, c);
+    if (rc != SICP_OK) {
+      m->last_error = "sicp_map_carve: the cloud: " + (h->last_error.empty() ? std::string("not ready") : h->last_error);
+      return rc;
+    }
+  }
+  if (c.pending && c.ready_ev) {
+    MAPCHECK(hipEventSynchronize(c.ready_ev));
+    c.pending = false;
+  }
+  const int n = c.n;
+  const int n_map = (int)m->n_voxels;
+  const size_t nr = (size_t)n_map;
+  sicp_map_carve_info I;
+  std::memset(&I, 0, sizeof I);
+  I.n_in = n;
+  I.n_voxels = m->n_voxels;
+  const bool short_miss = miss && capacity < n_map;
+  auto capacity_refusal = [&]() {
+    I.t_total_ms = now_ms() - t_begin;
+    if (info) *info = I;
+    m->last_error = "sicp_map_carve: the map has " + std::to_string(n_map) + " rows, miss holds " + std::to_string(capacity) + "; the map is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  hipStream_t st = m->stream;
+  StageLog log(log_enabled(), st);
+  MapScratch X;
+  unsigned long long stat[sicp::kCarveStats] = {};
+  size_t scan_bytes = 0;
+  sicp::MapSelectArgs S;
+  std::memset(&S, 0, sizeof S);
+  {  // (a slot without a finite point goes the same way: its origin is checked, its counts are zero)
+    X.device = m->device;
+    X.idle = false;
+    const size_t head = sizeof(int) * sicp::kMapRes + sizeof stat;
+    MAPCHECK(m->stage.resize(head));
+    MAPCHECK(X.res.reserve(sicp::kMapRes)); MAPCHECK(X.stat.reserve(sicp::kCarveStats));
+    if (n_map > 0) {
+      MAPCHECK(X.ray_hit.reserve(nr)); MAPCHECK(X.ray_miss.reserve(nr)); MAPCHECK(X.flag.reserve(nr));
+      MAPCHECK(hipMemsetAsync(X.ray_hit.p, 0, sizeof(int) * nr, st));
+      MAPCHECK(hipMemsetAsync(X.ray_miss.p, 0, sizeof(uint32_t) * nr, st));
+    }
+    const double ident[7] = {0, 0, 0, 1, 0, 0, 0};
+    sicp::MapCarveArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.x = c.rx.p; A.y = c.ry.p; A.z = c.rz.p;
+    matrix34(qt ? qt : ident, A.M);
+    A.n = n;
+    A.inv_leaf = 1.0f / (float)m->params.leaf_size;
+    A.sx = sensor_origin ? (float)sensor_origin[0] : 0.f;
+    A.sy = sensor_origin ? (float)sensor_origin[1] : 0.f;
+    A.sz = sensor_origin ? (float)sensor_origin[2] : 0.f;
+    A.ranged = p->max_range > 0.0 ? 1 : 0;
+    A.range_sq = p->max_range * p->max_range;
+    A.end_margin = p->end_margin;
+    A.key = m->rows[m->cur].key.p; A.n_map = n_map;
+    A.hit = X.ray_hit.p; A.miss = X.ray_miss.p; A.stat = X.stat.p; A.res = X.res.p;
+    sicp::MapCarveSelectArgs Q;
+    std::memset(&Q, 0, sizeof Q);
+    Q.n_map = n_map; Q.stride = stride; Q.min_rays = p->min_rays; Q.n_protect = p->n_protect;
+    for (int j = 0; j < p->n_protect; ++j) Q.protect[j] = p->protect[j];
+    Q.hist = stride > 0 ? m->rows[m->cur].hist.p : nullptr;
+    Q.hit = X.ray_hit.p; Q.miss = X.ray_miss.p; Q.flag = X.flag.p; Q.stat = X.stat.p;
+    log.mark("begin");
+    MAPCHECK(hipMemsetAsync(X.res.p, 0, sizeof(int) * sicp::kMapRes, st));
+    MAPCHECK(hipMemsetAsync(X.stat.p, 0, sizeof stat, st));
+    MAPCHECK(sicp::launch_map_carve_hits(A, st));
+    log.mark("hits");
+    MAPCHECK(sicp::launch_map_carve_walk(A, st));
+    log.mark("walk");
+    MAPCHECK(sicp::launch_map_carve_select(Q, st));
+    log.mark("select");
+    int res[sicp::kMapRes];
+    MAPCHECK(hipMemcpyAsync(m->stage.data(), X.res.p, sizeof res, hipMemcpyDeviceToHost, st));
+    MAPCHECK(hipMemcpyAsync(m->stage.data() + sizeof res, X.stat.p, sizeof stat, hipMemcpyDeviceToHost, st));
+    MAPCHECK(hipStreamSynchronize(st));
+    std::memcpy(res, m->stage.data(), sizeof res);
+    std::memcpy(stat, m->stage.data() + sizeof res, sizeof stat);
+    X.idle = true;
+    if (res[sicp::kMapRange])
+      return refuse("leaf size " + std::to_string(m->params.leaf_size) + " is too small for the sensor origin: a voxel coordinate reaches 2^20");
+  }
+  I.n_rays = (int64_t)stat[sicp::kCarveRays];
+  I.n_steps = (int64_t)stat[sicp::kCarveSteps];
+  I.n_touched = (int32_t)stat[sicp::kCarveTouched];
+  I.n_hit = (int32_t)stat[sicp::kCarveHit];
+  I.n_removed = (int32_t)stat[sicp::kCarveRemoved];
+  I.n_spared_hit = (int32_t)stat[sicp::kCarveSparedHit];
+  I.n_spared_label = (int32_t)stat[sicp::kCarveSparedLabel];
+  if (short_miss) return capacity_refusal();  // (every refusal lies before the first write to a row)
+  const bool carve = !p->dry_run && I.n_removed > 0;
+  if (carve) {  // prune's compaction of the rows the select kernel flagged
+    sicp_map_ctx::Rows& cur = m->rows[m->cur];
+    sicp_map_ctx::Rows& spare = m->rows[m->cur ^ 1];
+    X.idle = false;
+    MAPCHECK(reserve_rows(spare, nr, stride));
+    MAPCHECK(X.pos.reserve(nr)); MAPCHECK(X.src_of.reserve(nr)); MAPCHECK(X.total.reserve(1));
+    MAPCHECK(sicp::prim_scan_int(nullptr, scan_bytes, X.flag.p, X.pos.p, n_map, st));
+    MAPCHECK(X.temp.reserve(scan_bytes + 256));
+    if (miss) MAPCHECK(m->out.resize(nr));
+    S.n_map = n_map; S.stride = stride;
+    S.rows = rows_of(cur, stride > 0);
+    S.to = rows_of(spare, stride > 0);
+    S.flag = X.flag.p; S.pos = X.pos.p; S.src_of = X.src_of.p;
+    S.kept_points = X.total.p; S.res = X.res.p;
+  } else if (miss && n_map > 0) {
+    MAPCHECK(m->out.resize(nr));
+  }
+  if (miss && n_map > 0) {  // (on the host before the map changes: a failed copy leaves the map as it was)
+    X.idle = false;
+    MAPCHECK(hipMemcpyAsync(m->out.data(), X.ray_miss.p, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, st));
+    log.mark("result");
+    MAPCHECK(hipStreamSynchronize(st));
+    X.idle = true;
+  }
+  if (carve) {
+    const int rc = keep_flagged_rows(m, X, S, scan_bytes);
+    if (rc != SICP_OK) return rc;
+    log.mark("compact");
+    if (log.on) MAPCHECK(hipStreamSynchronize(st));  // (the log reads the mark's event)
+  }
+  if (miss && n_map > 0) std::memcpy(miss, m->out.data(), sizeof(uint32_t) * nr);
+  I.n_voxels = m->n_voxels;
+  log.print("sicp_map_carve: n_in=" + std::to_string(n) + " n_map=" + std::to_string(n_map) + " n_removed=" + std::to_string(I.n_removed));
+  I.t_total_ms = now_ms() - t_begin;
+  if (info) *info = I;
   return SICP_OK;
 }
 

@@ -176,6 +176,16 @@ __global__ __launch_bounds__(256) void map_prune_kernel(MapSelectArgs a) {
   if ((threadIdx.x & 63) == 0 && sum) atomicAdd(a.kept_points, sum);
 }
 
+// a histogram row's fullest bin: ties to the smallest label, bin 0 can win
+__device__ __forceinline__ uint32_t map_fullest_bin(const uint32_t* h, int stride) {
+  uint32_t best = 0, best_n = h[0];
+  for (int l = 1; l < stride; ++l) {
+    const uint32_t m = h[l];
+    if (m > best_n) { best_n = m; best = (uint32_t)l; }
+  }
+  return best;
+}
+
 // the selected rows as points, ascending key: centroid, count, the arg-max bin (ties to the smallest label); their number and
 // the largest count
 __global__ __launch_bounds__(256) void map_extract_kernel(MapSelectArgs a) {
@@ -191,21 +201,185 @@ __global__ __launch_bounds__(256) void map_extract_kernel(MapSelectArgs a) {
       a.ocount[p] = c;
       cnt = (int)(c > 0x7fffffffu ? 0x7fffffffu : c);
       a.src_of[p] = i;
-      if (a.olabel) {
-        const uint32_t* h = a.rows.hist + (size_t)i * (size_t)a.stride;
-        uint32_t best = 0, best_n = h[0];
-        for (int l = 1; l < a.stride; ++l) {
-          const uint32_t m = h[l];
-          if (m > best_n) { best_n = m; best = (uint32_t)l; }
-        }
-        a.olabel[p] = best;
-      }
+      if (a.olabel) a.olabel[p] = map_fullest_bin(a.rows.hist + (size_t)i * (size_t)a.stride, a.stride);
     }
     if (i == a.n_map - 1) a.res[kMapOut] = p + f;
   }
   int m = cnt;
   for (int w = 32; w > 0; w >>= 1) m = max(m, __shfl_xor(m, w, 64));
   if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(&a.res[kMapMaxCount], m);
+}
+
+// ---- free-space carving (kernels.h: MapCarveArgs) ------------------------------------------------------------------------------
+// the lower bound of k in keys[lo, hi): every key below lo is known to be < k, every key from hi on >= k
+__device__ __forceinline__ int map_lower_bound_in(const u64* keys, int lo, int hi, u64 k) {
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (keys[mid] < k) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// the lower bound of k, known to be >= from: probes at from, from + 2, from + 6, from + 14 ... (each 1, 2, 4, 8 ... past the
+// last key found below k) bracket it
+__device__ __forceinline__ int map_gallop_up(const u64* keys, int n, int from, u64 k) {
+  int lo = from, hi = n;
+  for (long long s = 1;; s <<= 1) {
+    const long long p = (long long)lo + (s - 1);
+    if (p >= n) break;
+    if (keys[p] >= k) { hi = (int)p; break; }
+    lo = (int)p + 1;
+  }
+  return map_lower_bound_in(keys, lo, hi, k);
+}
+
+// the lower bound of k, known to be <= from (<= n): probes at from - 1, from - 3, from - 7 ... (each 1, 2, 4 ... below the last
+// key found >= k) bracket it
+__device__ __forceinline__ int map_gallop_down(const u64* keys, int from, u64 k) {
+  int lo = 0, hi = from;
+  for (long long s = 1;; s <<= 1) {
+    const long long p = (long long)hi - s;
+    if (p < 0) break;
+    if (keys[p] < k) { lo = (int)p + 1; break; }
+    hi = (int)p;
+  }
+  return map_lower_bound_in(keys, lo, hi, k);
+}
+
+// the sensor origin as a point of the scan: transformed, keyed; false when it lies beyond the key's range
+__device__ __forceinline__ bool carve_origin(const MapCarveArgs& a, float* ox, float* oy, float* oz, u64* ko) {
+  const double x = a.sx, y = a.sy, z = a.sz;
+  *ox = voxel_xform_row(a.M + 0, x, y, z);
+  *oy = voxel_xform_row(a.M + 4, x, y, z);
+  *oz = voxel_xform_row(a.M + 8, x, y, z);
+  return voxel_key(*ox, *oy, *oz, a.inv_leaf, ko);
+}
+
+// per point of the scan: the row of its voxel, when the map holds it, is hit (plain stores: every writer stores the same 1)
+__global__ __launch_bounds__(256) void map_carve_hit_kernel(MapCarveArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) {
+    float ox, oy, oz;
+    u64 ko;
+    if (!carve_origin(a, &ox, &oy, &oz, &ko)) a.res[kMapRange] = 1;
+  }
+  if (i >= a.n) return;
+  const double x = a.x[i], y = a.y[i], z = a.z[i];
+  const float px = voxel_xform_row(a.M + 0, x, y, z);
+  const float py = voxel_xform_row(a.M + 4, x, y, z);
+  const float pz = voxel_xform_row(a.M + 8, x, y, z);
+  u64 k;
+  if (!voxel_key(px, py, pz, a.inv_leaf, &k)) return;
+  const int r = map_lower_bound(a.key, a.n_map, k);
+  if (r < a.n_map && a.key[r] == k) a.hit[r] = 1;
+}
+
+__device__ __forceinline__ u64 wave_sum(u64 v) {
+  for (int w = 32; w > 0; w >>= 1) v += (u64)__shfl_xor((long long)v, w, 64);
+  return v;
+}
+
+// The walk.  A wave owns the rays [wave * kCarveRaysPerWave, ...) and deals them to its lanes as they fall idle: every turn
+// of the loop the idle lanes take the next rays in lane order, then every lane with a ray visits the voxel it stands in and
+// steps on.  `lb` is the lower bound of the lane's key among the map's and `found` says whether the map holds it; a step
+// along x derives both from the row beside it, a step along y gallops from lb, a step along z searches the side it went to.
+// The counts are integer atomics, so neither the dealing nor the launch shape shows in the result.
+__global__ __launch_bounds__(256) void map_carve_walk_kernel(MapCarveArgs a) {
+  float ox, oy, oz;
+  u64 ko;
+  if (!carve_origin(a, &ox, &oy, &oz, &ko)) return;  // (the same in every lane; the host refuses the call)
+  const int lane = threadIdx.x & 63;
+  const long long first = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * kCarveRaysPerWave;
+  const int end = (int)std::min<long long>(first + kCarveRaysPerWave, a.n);
+  int next = (int)std::min<long long>(first, a.n);
+  const u64* const keys = a.key;
+  const int n_map = a.n_map;
+  const int lb0 = map_lower_bound(keys, n_map, ko);  // every ray starts in the origin's voxel
+  const bool found0 = lb0 < n_map && keys[lb0] == ko;
+  VoxelRay r;
+  int left = 0, lb = 0;
+  bool found = false;
+  u64 rays = 0, steps = 0;
+  for (;;) {
+    const bool idle = left == 0;
+    const u64 idle_mask = __ballot(idle);
+    if (idle_mask == ~0ull && next >= end) break;
+    if (idle) {
+      const int i = next + __popcll(idle_mask & ((1ull << lane) - 1ull));
+      if (i < end) {
+        const double x = a.x[i], y = a.y[i], z = a.z[i];
+        const float px = voxel_xform_row(a.M + 0, x, y, z);
+        const float py = voxel_xform_row(a.M + 4, x, y, z);
+        const float pz = voxel_xform_row(a.M + 8, x, y, z);
+        u64 kp;
+        if (voxel_key(px, py, pz, a.inv_leaf, &kp) && (!a.ranged || voxel_crop_keeps(px, py, pz, ox, oy, oz, a.range_sq))) {
+          rays += 1;
+          voxel_ray_begin(ox, oy, oz, ko, px, py, pz, kp, a.inv_leaf, &r);
+          left = r.n > a.end_margin ? r.n - a.end_margin : 0;
+          steps += (u64)left;
+          if (n_map == 0) left = 0;  // (an empty map: the candidates are counted, there is nothing to look up)
+          lb = lb0;
+          found = found0;
+        }
+      }
+    }
+    next = (int)std::min<long long>((long long)next + __popcll(idle_mask), end);
+    if (left > 0) {
+      if (found) atomicAdd(&a.miss[lb], 1u);
+      left -= 1;
+      if (left > 0) {
+        const int axis = voxel_ray_step(&r);
+        const u64 k = r.key;
+        if (axis == 0 && r.sx < 0) {  // the key went down by 1: it is the row below or it is absent
+          found = lb > 0 && keys[lb - 1] == k;
+          lb -= found ? 1 : 0;
+        } else {
+          if (axis == 0) lb += found ? 1 : 0;  // up by 1: the keys below it are those below the old key, and the old key
+          else if (axis == 1) lb = r.sy > 0 ? map_gallop_up(keys, n_map, lb + (found ? 1 : 0), k) : map_gallop_down(keys, lb, k);
+          else lb = r.sz > 0 ? map_lower_bound_in(keys, lb + (found ? 1 : 0), n_map, k) : map_lower_bound_in(keys, 0, lb, k);
+          found = lb < n_map && keys[lb] == k;
+        }
+      }
+    }
+  }
+  rays = wave_sum(rays);
+  steps = wave_sum(steps);
+  if (lane == 0) {
+    if (rays) atomicAdd(&a.stat[kCarveRays], rays);
+    if (steps) atomicAdd(&a.stat[kCarveSteps], steps);
+  }
+}
+
+// flag[i]: row i stays -- fewer than min_rays rays passed through it, or a return landed in it, or its fullest bin is
+// protected (asked in that order); the counts of sicp_map_carve_info, one integer atomic a wave each
+__global__ __launch_bounds__(256) void map_carve_select_kernel(MapCarveSelectArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  bool touched = false, hit = false, removed = false, spared_hit = false, spared_label = false;
+  if (i < a.n_map) {
+    const uint32_t m = a.miss[i];
+    touched = m > 0u;
+    hit = a.hit[i] != 0;
+    if (m >= (uint32_t)a.min_rays) {
+      if (hit) {
+        spared_hit = true;
+      } else {
+        if (a.n_protect > 0) {
+          const uint32_t l = map_fullest_bin(a.hist + (size_t)i * (size_t)a.stride, a.stride);
+          for (int j = 0; j < a.n_protect; ++j) spared_label = spared_label || a.protect[j] == l;
+        }
+        removed = !spared_label;
+      }
+    }
+    a.flag[i] = removed ? 0 : 1;
+  }
+  const u64 b0 = __ballot(touched), b1 = __ballot(hit), b2 = __ballot(removed), b3 = __ballot(spared_hit), b4 = __ballot(spared_label);
+  if ((threadIdx.x & 63) == 0) {
+    if (b0) atomicAdd(&a.stat[kCarveTouched], (u64)__popcll(b0));
+    if (b1) atomicAdd(&a.stat[kCarveHit], (u64)__popcll(b1));
+    if (b2) atomicAdd(&a.stat[kCarveRemoved], (u64)__popcll(b2));
+    if (b3) atomicAdd(&a.stat[kCarveSparedHit], (u64)__popcll(b3));
+    if (b4) atomicAdd(&a.stat[kCarveSparedLabel], (u64)__popcll(b4));
+  }
 }
 
 // ---- label fusion through the confusion matrix (kernels.h: MapFuseArgs) -------------------------------------------------------
@@ -414,6 +588,26 @@ hipError_t launch_map_prune(const MapSelectArgs& a, hipStream_t st) {
 hipError_t launch_map_extract(const MapSelectArgs& a, hipStream_t st) {
   if (a.n_map <= 0) return hipSuccess;
   hipLaunchKernelGGL(map_extract_kernel, map_grid(a.n_map), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_carve_hits(const MapCarveArgs& a, hipStream_t st) {
+  if (a.n < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(map_carve_hit_kernel, map_grid(std::max(a.n, 1)), dim3(256), 0, st, a);  // (n = 0: the origin's check alone)
+  return hipGetLastError();
+}
+
+hipError_t launch_map_carve_walk(const MapCarveArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  const long long per_block = 4 * kCarveRaysPerWave;  // four waves a workgroup
+  hipLaunchKernelGGL(map_carve_walk_kernel, dim3((unsigned)((a.n + per_block - 1) / per_block)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_carve_select(const MapCarveSelectArgs& a, hipStream_t st) {
+  if (a.n_map <= 0) return hipSuccess;
+  if (a.n_protect < 0 || a.n_protect > kMapMaxProtect || (a.n_protect > 0 && !a.hist)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(map_carve_select_kernel, map_grid(a.n_map), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -871,6 +871,19 @@ int sicp_map_prune(sicp_map m, const double center[3], double range, int64_t* n_
   return abi_guard(m, [&]() -> int { return map_prune(m, center, range, n_removed); });
 }
 
+int sicp_default_map_carve_params(sicp_map_carve_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    map_default_carve_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_map_carve(sicp_map m, sicp_handle h, int which, const double qt[7], const double sensor_origin[3],
+                   const sicp_map_carve_params* p, int32_t capacity, uint32_t* miss, sicp_map_carve_info* info) {
+  return abi_guard(m, [&]() -> int { return map_carve(m, h, which, qt, sensor_origin, p, capacity, miss, info); });
+}
+
 int sicp_map_extract(sicp_map m, const sicp_map_extract_params* p, sicp_handle dst, int dst_which, int32_t capacity, float* x,
                      float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info) {
   return abi_guard(m, [&]() -> int {

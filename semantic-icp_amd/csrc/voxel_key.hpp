@@ -46,5 +46,77 @@ __device__ __forceinline__ bool voxel_key(float px, float py, float pz, float in
   return true;
 }
 
+// the voxel coordinates a key holds
+__device__ __forceinline__ void voxel_key_coords(unsigned long long key, int* vx, int* vy, int* vz) {
+  *vx = (int)(key & 0x1fffffull) - kMergeBias;
+  *vy = (int)((key >> 21) & 0x1fffffull) - kMergeBias;
+  *vz = (int)((key >> 42) & 0x1fffffull) - kMergeBias;
+}
+
+// The voxel walk of sicp_map_carve (include/sicp.h, "free-space carving", rule 4): from the voxel of the origin o to the voxel
+// of the return p in exactly n = |dvx| + |dvy| + |dvz| steps of one voxel along one axis.  Per axis u = (double)o * (double)
+// inv_leaf and w = (double)p * (double)inv_leaf (exact products), du = w - u, and for an axis that has steps to take
+// tmax = ((double)(vo + (step > 0)) - u) / du, tdelta = (double)step / du; a step goes along the axis with steps left whose tmax
+// is the smallest (x before y before z among equals) and adds tdelta to it.  All in double, every operation rounded on its own;
+// the trip count is an integer, so the walk ends in the return's voxel whatever the rounding.
+struct VoxelRay {
+  unsigned long long key;  // the voxel the walk stands in
+  int n;                   // steps from the origin's voxel to the return's
+  int rx, ry, rz;          // steps left per axis
+  int sx, sy, sz;          // +1 / -1 (0: none to take)
+  double mx, my, mz;       // tmax
+  double dx, dy, dz;       // tdelta
+};
+
+__device__ __forceinline__ void voxel_ray_axis(float o, float p, float inv_leaf, int vo, int vp, int* rem, int* step, double* tmax,
+                                               double* tdelta) {
+#pragma clang fp contract(off)
+  const int d = vp - vo;
+  *rem = d < 0 ? -d : d;
+  *step = d > 0 ? 1 : (d < 0 ? -1 : 0);
+  *tmax = 0.0;
+  *tdelta = 0.0;
+  if (d == 0) return;
+  const double u = __dmul_rn((double)o, (double)inv_leaf), w = __dmul_rn((double)p, (double)inv_leaf);
+  const double du = __dsub_rn(w, u);  // (not 0: the two floors differ, so the products do)
+  *tmax = __ddiv_rn(__dsub_rn((double)(vo + (d > 0 ? 1 : 0)), u), du);
+  *tdelta = __ddiv_rn((double)*step, du);
+}
+
+// ko, kp: the keys of o and p (voxel_key)
+__device__ __forceinline__ void voxel_ray_begin(float ox, float oy, float oz, unsigned long long ko, float px, float py, float pz,
+                                                unsigned long long kp, float inv_leaf, VoxelRay* r) {
+  int ax, ay, az, bx, by, bz;
+  voxel_key_coords(ko, &ax, &ay, &az);
+  voxel_key_coords(kp, &bx, &by, &bz);
+  voxel_ray_axis(ox, px, inv_leaf, ax, bx, &r->rx, &r->sx, &r->mx, &r->dx);
+  voxel_ray_axis(oy, py, inv_leaf, ay, by, &r->ry, &r->sy, &r->my, &r->dy);
+  voxel_ray_axis(oz, pz, inv_leaf, az, bz, &r->rz, &r->sz, &r->mz, &r->dz);
+  r->key = ko;
+  r->n = r->rx + r->ry + r->rz;
+}
+
+// one step (the caller counts them: at most n); returns the axis taken, 0 / 1 / 2
+__device__ __forceinline__ int voxel_ray_step(VoxelRay* r) {
+#pragma clang fp contract(off)
+  int axis = -1;
+  double best = 0.0;
+  if (r->rx > 0) { axis = 0; best = r->mx; }
+  if (r->ry > 0 && (axis < 0 || r->my < best)) { axis = 1; best = r->my; }
+  if (r->rz > 0 && (axis < 0 || r->mz < best)) axis = 2;
+  // (selects, not branches: the three axes stay in registers)
+  const bool tx = axis == 0, ty = axis == 1, tz = axis == 2;
+  const long long dk = tx ? (long long)r->sx : (ty ? (long long)r->sy * (1ll << 21) : (tz ? (long long)r->sz * (1ll << 42) : 0ll));
+  r->key += (unsigned long long)dk;
+  r->rx -= tx ? 1 : 0;
+  r->ry -= ty ? 1 : 0;
+  r->rz -= tz ? 1 : 0;
+  const double nx = __dadd_rn(r->mx, r->dx), ny = __dadd_rn(r->my, r->dy), nz = __dadd_rn(r->mz, r->dz);
+  r->mx = tx ? nx : r->mx;
+  r->my = ty ? ny : r->my;
+  r->mz = tz ? nz : r->mz;
+  return axis;
+}
+
 }  // namespace sicp
 #endif
