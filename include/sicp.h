@@ -778,6 +778,108 @@ int sicp_map_fused_labels(sicp_map m, sicp_handle h, int which, const double qt[
                           int32_t include_own_label, int32_t min_count, uint32_t* out_labels,
                           double* out_confidence /* nullable */);
 
+/* ---- a database of scan descriptors: which earlier scan is this one? ---------------
+ * The step of loop closing that comes before sicp_evaluate (accept the pose) and sicp_pose_covariance (weigh the edge): every
+ * keyframe's scan becomes a polar descriptor of R rings x S sectors about the sensor, one uint8 code per cell -- the cell's
+ * dominant label (SICP_PLACE_LABEL) or its highest height level (SICP_PLACE_HEIGHT) -- and the database of them lives on the
+ * device.  A query compares a new scan's descriptor with every entry at every one of the S sector shifts, exactly and in
+ * integers, and returns the best entries with the yaw between the scans.  Contracts as for sicp_map: every call is
+ * synchronous; a database lives on one device and serves one thread at a time; a handle on another device is refused; every
+ * refusal leaves the database byte for byte what it was; buffers come from the arena (sicp_set_memory_limit applies); it has
+ * its own last-error string.  No device floating point beyond rule 3's three operations and rule 4's height level, no float
+ * atomics: every launch shape gives the same bytes, and two databases driven alike are byte-identical.  The rules:
+ *  1. Points.  The finite points the slot holds, whatever the handle's mode and device layout.  No pose is applied: a
+ *     descriptor lives in the sensor's own frame.  d = p - (float)sensor_origin per axis in float; d2 = dx*dx + dy*dy in float,
+ *     each operation rounded.  A point is kept when (double)d2 < edge2[R] and (double)d2 >= min_range * min_range.  Every
+ *     result is a count or a maximum of integers: point order plays no part.
+ *  2. Tables, formed once on the host in double with libm and uploaded (sicp_place_tables hands them back):
+ *     edge2[i] = b*b with b = (double)i * (max_range / (double)R), i = 0..R; cos_half[j] = cos(a), sin_half[j] = sin(a) with
+ *     a = (double)j * (6.283185307179586 / (double)S), j = 0..S/2-1.
+ *  3. Cell.  ring = the number of i in 1..R-1 with (double)d2 >= edge2[i].  lower = !(dy > 0 || (dy == 0 && dx > 0));
+ *     (x', y') = lower ? (-dx, -dy) : (dx, dy), in double; sector = the number of j in 1..S/2-1 with
+ *     cos_half[j]*y' - sin_half[j]*x' >= 0 (two products and a difference, each rounded, no contraction), plus S/2 when lower.
+ *     The counts are the definition: no atan2, no sqrt, no search that assumes the predicate monotone in j.
+ *  4. Code of a cell, one uint8, 0 = empty; the descriptor is desc[ring*S + sector].
+ *     LABEL: a cloud without labels is refused.  A kept point with label 0 or a label in `ignore` takes no part; a kept point
+ *     with a label above num_classes gives SICP_ERR_BAD_LABEL and nothing changes.  The code is the most frequent label of the
+ *     cell's remaining points, ties to the smallest label; the cell is empty when fewer than min_cell_points remain.
+ *     HEIGHT: labels are not read.  t = ((double)dz - z_min) * (1.0 / z_step), the reciprocal formed on the host;
+ *     level = t < 0 ? 0 : t >= 254 ? 254 : (int)floor(t); the code is 1 + the largest level of the cell's kept points; the cell
+ *     is empty when fewer than min_cell_points kept points fall in it.
+ *  5. Score of a query q against an entry e at shift s in 0..S-1: with q_c = q[r*S + c] and e_c = e[r*S + (c + s) % S], match
+ *     counts the cells with q_c == e_c != 0 and either the cells with q_c != 0 || e_c != 0.  a/b beats c/d when a*d > c*b in
+ *     integers; either = 0 scores 0.  An entry's best shift has the largest score, ties to the smallest shift; entries rank by
+ *     best score, largest first, ties to the smallest id.  (either <= 16384: two different scores differ by at least 2^-28, so
+ *     floor(match * 2^30 / either) is an exact integer sort key -- the one the device sorts by.)
+ *  6. Query.  The entries searched are first .. first+count-1 (count = -1: to the end; a loop-closure caller leaves the most
+ *     recent scans out this way).  The output holds the first top_k ranked entries whose host-side score >= min_score, n_found
+ *     says how many; only min(top_k, count) rows per query come back from the device.  An empty range or database: SICP_OK and
+ *     n_found = 0.  sicp_place_query is sicp_place_describe followed by sicp_place_query_descriptors with n_q = 1, bit for bit,
+ *     and every row of a multi-query call equals its lone call.
+ *  7. Meaning of the shift.  When the query's sensor is the entry's sensor turned by psi about z, the best shift is
+ *     round(psi / (2 pi / S)) mod S up to cell-boundary effects, and [0, 0, sin(yaw/2), cos(yaw/2), 0, 0, 0] is the init_qt
+ *     that takes the query (source) onto the entry (target).
+ *  8. Refused with SICP_ERR_INVALID_ARGUMENT, the reason in sicp_place_last_error, nothing written: NULLs; parameters outside
+ *     the ranges below; num_classes = 0 with LABEL; an ignored label outside 1..num_classes; a bad `which`; an origin that is
+ *     not finite; top_k < 1; min_score NaN; first < 0 or a range beyond the size; n < 1 or n_q < 1; a descriptor byte above
+ *     num_classes in a LABEL database (the text names the byte); more than 2^31 - 1 entries; a handle on another device.
+ *     SICP_ERR_NOT_READY: the slot holds no cloud.  SICP_ERR_OUT_OF_MEMORY: the arena refused growth; the entries already held
+ *     stay.  The handle is never modified.
+ * Not built: an approximate pre-filter (the search is exhaustive by design), translation-augmented descriptors, removal of
+ * single entries, a stream entry point, C++ class shims, a pose-graph solver. */
+enum { SICP_PLACE_LABEL = 0, SICP_PLACE_HEIGHT = 1 };
+#define SICP_PLACE_MAX_IGNORE 64
+typedef struct sicp_place_ctx* sicp_place;
+typedef struct sicp_place_params {
+  int32_t n_rings;          /* R, 1..64.  default 20 */
+  int32_t n_sectors;        /* S, a multiple of 4 in 4..256.  default 60 */
+  double max_range;         /* finite, > 0.  default 40 */
+  double min_range;         /* >= 0 and < max_range.  default 0 */
+  int32_t channel;          /* SICP_PLACE_LABEL (default) / SICP_PLACE_HEIGHT */
+  int32_t num_classes;      /* LABEL: 1..255 (labels 1..C; 0 = unlabelled); default 0 = must be set.  HEIGHT: ignored */
+  double z_min, z_step;     /* HEIGHT: level 0 starts at z_min; z_step finite, > 0, 1 / z_step finite.  defaults -2.0, 0.5 */
+  int32_t min_cell_points;  /* a cell with fewer kept points is empty.  default 1, >= 1 */
+  int32_t n_ignore;         /* LABEL: 0..SICP_PLACE_MAX_IGNORE */
+  uint32_t ignore[SICP_PLACE_MAX_IGNORE]; /* labels (each in 1..C) whose points are dropped: moving classes */
+} sicp_place_params;
+typedef struct sicp_place_candidate {
+  int32_t id, shift;        /* entry (0-based, in order of insertion) and its best shift */
+  int32_t match, either;    /* the two integer counts of rule 5 at that shift */
+  double score;             /* (double)match / (double)either on the host; 0 when either = 0 */
+  double yaw;               /* shift * (2 pi / S) wrapped to (-pi, pi]: the rotation about z, query frame -> entry frame */
+} sicp_place_candidate;
+typedef struct sicp_place_describe_info {
+  int64_t n_in;             /* finite points of the slot */
+  int64_t n_kept;           /* ... of which rule 1 keeps */
+  int32_t n_cells;          /* non-empty cells of the descriptor */
+  int32_t reserved_;
+  double t_total_ms;        /* host wall clock */
+} sicp_place_describe_info;
+int sicp_default_place_params(sicp_place_params* p);
+int sicp_place_create(int device_id, const sicp_place_params* p, sicp_place* out);
+int sicp_place_destroy(sicp_place db);
+int sicp_place_clear(sicp_place db);  /* no entries; the buffers stay */
+int sicp_place_size(sicp_place db, int64_t* n_entries);
+const char* sicp_place_last_error(sicp_place db);
+/* The descriptor of slot `which` of h about sensor_origin: desc (R*S bytes) and info are written on success only. */
+int sicp_place_describe(sicp_place db, sicp_handle h, int which, const double sensor_origin[3] /* NULL = 0 0 0 */,
+                        uint8_t* desc /* nullable */, sicp_place_describe_info* info /* nullable */);
+/* describe + append: *id is the new entry's number */
+int sicp_place_add(sicp_place db, sicp_handle h, int which, const double sensor_origin[3] /* NULL = 0 0 0 */, int32_t* id,
+                   uint8_t* desc /* nullable */, sicp_place_describe_info* info /* nullable */);
+/* n descriptors of R*S bytes each appended as they are (reload a saved database); first_id (nullable): the first one's number */
+int sicp_place_add_descriptors(sicp_place db, int32_t n, const uint8_t* desc, int32_t* first_id);
+/* entries first .. first+count-1 (count = -1: to the end) into desc, count*R*S bytes (save the database) */
+int sicp_place_get(sicp_place db, int32_t first, int32_t count, uint8_t* desc);
+/* out: top_k candidates, the first *n_found of which are written */
+int sicp_place_query(sicp_place db, sicp_handle h, int which, const double sensor_origin[3] /* NULL = 0 0 0 */, int32_t first,
+                     int32_t count, int32_t top_k, double min_score, sicp_place_candidate* out, int32_t* n_found);
+/* n_q queries at once: out is n_q*top_k candidates, row q starting at out + q*top_k with its first n_found[q] written */
+int sicp_place_query_descriptors(sicp_place db, int32_t n_q, const uint8_t* desc /* n_q*R*S */, int32_t first, int32_t count,
+                                 int32_t top_k, double min_score, sicp_place_candidate* out, int32_t* n_found /* n_q */);
+/* test hook: the tables of rule 2; cos_half and sin_half hold S/2 doubles, edge2 R+1 (each nullable) */
+int sicp_place_tables(sicp_place db, double* cos_half, double* sin_half, double* edge2);
+
 /* test / bench hook: the keypoints of cloud `which` with their normals, FPFH features and feature-radius
  * neighbour lists (CSR: nbr_offsets[n + 1], nbr_idx sorted by (d^2, index)).  Counts are always written; an output
  * array is written when it is non-NULL and its capacity (points / neighbour entries) suffices, otherwise the call

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import importlib.util
+import math
 import os
 
 import numpy as np
@@ -322,6 +323,56 @@ class SicpMapCarveInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
 
 
+PLACE_LABEL, PLACE_HEIGHT = 0, 1
+PLACE_MAX_IGNORE = 64
+
+
+class SicpPlaceParams(C.Structure):
+    """sicp_place_params (include/sicp.h)"""
+    _fields_ = [
+        ("n_rings", C.c_int32),
+        ("n_sectors", C.c_int32),
+        ("max_range", C.c_double),
+        ("min_range", C.c_double),
+        ("channel", C.c_int32),
+        ("num_classes", C.c_int32),
+        ("z_min", C.c_double),
+        ("z_step", C.c_double),
+        ("min_cell_points", C.c_int32),
+        ("n_ignore", C.c_int32),
+        ("ignore", C.c_uint32 * PLACE_MAX_IGNORE),
+    ]
+
+
+class SicpPlaceCandidate(C.Structure):
+    """sicp_place_candidate (include/sicp.h)"""
+    _fields_ = [
+        ("id", C.c_int32),
+        ("shift", C.c_int32),
+        ("match", C.c_int32),
+        ("either", C.c_int32),
+        ("score", C.c_double),
+        ("yaw", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class SicpPlaceDescribeInfo(C.Structure):
+    """sicp_place_describe_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_in", C.c_int64),
+        ("n_kept", C.c_int64),
+        ("n_cells", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
+
+
 class SicpError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -369,6 +420,8 @@ def lib():
         _lib.sicp_stream_last_error.argtypes = [C.c_void_p]
         _lib.sicp_map_last_error.restype = C.c_char_p
         _lib.sicp_map_last_error.argtypes = [C.c_void_p]
+        _lib.sicp_place_last_error.restype = C.c_char_p
+        _lib.sicp_place_last_error.argtypes = [C.c_void_p]
         for name, args in {
             "sicp_device_count": [C.POINTER(C.c_int)],
             "sicp_create": [C.c_int, C.POINTER(C.c_void_p)],
@@ -453,6 +506,20 @@ def lib():
             "sicp_map_extract_fused": [C.c_void_p, C.POINTER(SicpMapExtractParams), C.c_void_p, C.c_int, C.c_int32, _fp, _fp, _fp, _up, _up,
                                        _dp, C.POINTER(SicpMapExtractInfo)],
             "sicp_map_fused_labels": [C.c_void_p, C.c_void_p, C.c_int, _dp, C.c_int32, C.c_int32, _up, _dp],
+            "sicp_default_place_params": [C.POINTER(SicpPlaceParams)],
+            "sicp_place_create": [C.c_int, C.POINTER(SicpPlaceParams), C.POINTER(C.c_void_p)],
+            "sicp_place_destroy": [C.c_void_p],
+            "sicp_place_clear": [C.c_void_p],
+            "sicp_place_size": [C.c_void_p, C.POINTER(C.c_int64)],
+            "sicp_place_describe": [C.c_void_p, C.c_void_p, C.c_int, _dp, _bp, C.POINTER(SicpPlaceDescribeInfo)],
+            "sicp_place_add": [C.c_void_p, C.c_void_p, C.c_int, _dp, _ip, _bp, C.POINTER(SicpPlaceDescribeInfo)],
+            "sicp_place_add_descriptors": [C.c_void_p, C.c_int32, _bp, _ip],
+            "sicp_place_get": [C.c_void_p, C.c_int32, C.c_int32, _bp],
+            "sicp_place_query": [C.c_void_p, C.c_void_p, C.c_int, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                 C.POINTER(SicpPlaceCandidate), _ip],
+            "sicp_place_query_descriptors": [C.c_void_p, C.c_int32, _bp, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                             C.POINTER(SicpPlaceCandidate), _ip],
+            "sicp_place_tables": [C.c_void_p, _dp, _dp, _dp],
         }.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
@@ -589,6 +656,33 @@ def default_map_carve_params(**overrides) -> SicpMapCarveParams:
         else:
             setattr(p, k, v)
     return p
+
+
+def default_place_params(**overrides) -> SicpPlaceParams:
+    """sicp_default_place_params (20 rings x 60 sectors to 40 m, the label channel, num_classes to be set), with any field
+    overridden by keyword; ignore takes the labels themselves and sets n_ignore with them"""
+    p = SicpPlaceParams()
+    st = lib().sicp_default_place_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_place_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        if k == "ignore":
+            labels = [int(l) for l in v]
+            if len(labels) > PLACE_MAX_IGNORE:
+                raise ValueError(f"at most {PLACE_MAX_IGNORE} ignored labels")
+            p.ignore = (C.c_uint32 * PLACE_MAX_IGNORE)(*labels)
+            if "n_ignore" not in overrides:
+                p.n_ignore = len(labels)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def place_init_qt(yaw: float):
+    """the init_qt of a loop candidate: the rotation by `yaw` about z that takes the query (source) onto the entry (target)"""
+    return np.array([0.0, 0.0, math.sin(0.5 * yaw), math.cos(0.5 * yaw), 0.0, 0.0, 0.0])
 
 
 def _ptr(a, t):
@@ -1190,6 +1284,121 @@ class VoxelMap:
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(lib().sicp_map_size(self._m, C.byref(a), C.byref(b)), "sicp_map_size")
         return a.value, b.value
+
+
+class PlaceDB:
+    """sicp_place_*: a database of scan descriptors that lives on the device -- R rings x S sectors of uint8 cell codes per
+    scan, by label or by height.  add() describes an Engine's cloud and appends it; query() returns the best earlier scans
+    for a new one with the yaw between them (place_init_qt(yaw) is the init_qt of the registration that follows)."""
+
+    def __init__(self, device: int = 0, params: SicpPlaceParams | None = None):
+        self._db = C.c_void_p()
+        p = params if params is not None else default_place_params()
+        self.n_rings, self.n_sectors = int(p.n_rings), int(p.n_sectors)
+        st = lib().sicp_place_create(device, C.byref(p), C.byref(self._db))
+        if st != OK:
+            self._db = C.c_void_p()
+            raise SicpError(st, "sicp_place_create")
+
+    def _check(self, st, where):
+        if st != OK:
+            raise SicpError(st, where, lib().sicp_place_last_error(self._db).decode())
+
+    def close(self):
+        if getattr(self, "_db", None) and self._db.value:
+            lib().sicp_place_destroy(self._db)
+            self._db = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @staticmethod
+    def _origin(sensor_origin):
+        return None if sensor_origin is None else np.ascontiguousarray(sensor_origin, dtype=np.float64).reshape(3)
+
+    def _descs(self, desc):
+        d = np.ascontiguousarray(desc, dtype=np.uint8)
+        if d.ndim == 2:
+            d = d[None]
+        if d.ndim != 3 or d.shape[1:] != (self.n_rings, self.n_sectors):
+            raise ValueError(f"descriptors must be [n, {self.n_rings}, {self.n_sectors}] uint8")
+        return d
+
+    def describe(self, engine: "Engine", which: int = SOURCE, sensor_origin=None):
+        """sicp_place_describe: (desc[R, S] uint8, SicpPlaceDescribeInfo.as_dict()) of engine's slot `which`"""
+        o = self._origin(sensor_origin)
+        desc = np.empty((self.n_rings, self.n_sectors), dtype=np.uint8)
+        info = SicpPlaceDescribeInfo()
+        self._check(lib().sicp_place_describe(self._db, engine._h, which, _ptr(o, _dp), _ptr(desc, _bp), C.byref(info)), "sicp_place_describe")
+        return desc, info.as_dict()
+
+    def add(self, engine: "Engine", which: int = SOURCE, sensor_origin=None) -> int:
+        """sicp_place_add: describe + append; returns the new entry's id"""
+        o = self._origin(sensor_origin)
+        new_id = C.c_int32(-1)
+        self._check(lib().sicp_place_add(self._db, engine._h, which, _ptr(o, _dp), C.byref(new_id), None, None), "sicp_place_add")
+        return new_id.value
+
+    def add_descriptors(self, desc) -> int:
+        """sicp_place_add_descriptors: [n, R, S] (or one [R, S]) descriptors appended as they are; returns the first one's id"""
+        d = self._descs(desc)
+        first = C.c_int32(-1)
+        self._check(lib().sicp_place_add_descriptors(self._db, d.shape[0], _ptr(d, _bp), C.byref(first)), "sicp_place_add_descriptors")
+        return first.value
+
+    def get(self, first: int = 0, count: int = -1):
+        """sicp_place_get: entries first .. first+count-1 (count = -1: to the end) as [count, R, S] uint8"""
+        n = self.size() - first if count < 0 else count
+        out = np.empty((max(n, 0), self.n_rings, self.n_sectors), dtype=np.uint8)
+        self._check(lib().sicp_place_get(self._db, first, count, _ptr(out, _bp) if out.size else None), "sicp_place_get")
+        return out
+
+    def query(self, engine_or_descs, which: int = SOURCE, sensor_origin=None, first: int = 0, count: int = -1, top_k: int = 5,
+              min_score: float = 0.0):
+        """sicp_place_query (an Engine: its slot `which` is described first) or sicp_place_query_descriptors (one [R, S]
+        descriptor or a batch [n, R, S]).  Returns the candidates, best first, as a list of dicts {id, shift, match, either,
+        score, yaw}; for a batch a list of such lists."""
+        cap = max(int(top_k), 1)
+        if isinstance(engine_or_descs, Engine):
+            o = self._origin(sensor_origin)
+            out = (SicpPlaceCandidate * cap)()
+            found = C.c_int32(0)
+            self._check(lib().sicp_place_query(self._db, engine_or_descs._h, which, _ptr(o, _dp), first, count, top_k, min_score, out,
+                                               C.byref(found)), "sicp_place_query")
+            return [out[k].as_dict() for k in range(found.value)]
+        lone = np.asarray(engine_or_descs).ndim == 2
+        d = self._descs(engine_or_descs)
+        n_q = d.shape[0]
+        out = (SicpPlaceCandidate * (cap * max(n_q, 1)))()
+        found = np.zeros(max(n_q, 1), dtype=np.int32)
+        self._check(lib().sicp_place_query_descriptors(self._db, n_q, _ptr(d, _bp), first, count, top_k, min_score, out, _ptr(found, _ip)),
+                    "sicp_place_query_descriptors")
+        rows = [[out[q * cap + k].as_dict() for k in range(int(found[q]))] for q in range(n_q)]
+        return rows[0] if lone else rows
+
+    def tables(self):
+        """sicp_place_tables: {"cos_half": [S/2], "sin_half": [S/2], "edge2": [R+1]} float64, as the device holds them"""
+        c, s = (np.empty(self.n_sectors // 2, dtype=np.float64) for _ in range(2))
+        e = np.empty(self.n_rings + 1, dtype=np.float64)
+        self._check(lib().sicp_place_tables(self._db, _ptr(c, _dp), _ptr(s, _dp), _ptr(e, _dp)), "sicp_place_tables")
+        return {"cos_half": c, "sin_half": s, "edge2": e}
+
+    def size(self) -> int:
+        n = C.c_int64(0)
+        self._check(lib().sicp_place_size(self._db, C.byref(n)), "sicp_place_size")
+        return n.value
+
+    def clear(self):
+        self._check(lib().sicp_place_clear(self._db), "sicp_place_clear")
 
 
 def accumulate_batch(engines, qts, repeat: int = 1):

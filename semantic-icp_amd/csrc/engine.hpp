@@ -609,8 +609,33 @@ struct sicp_map_ctx {
   std::string last_error;
 };
 
+// ---- a database of scan descriptors (sicp_place_*; place.cpp): the entries' R*S bytes one after another in one of two arena
+// buffers -- growth copies into the spare one and swaps last, so a refused call leaves the entries as they were
+struct sicp_place_ctx {
+  int device = 0;
+  sicp_place_params params;
+  int rs = 0;                      // bytes of a descriptor: n_rings * n_sectors
+  OwnedStream stream;
+  std::vector<double> tables;      // edge2[R + 1] | cos_half[S / 2] | sin_half[S / 2] (rule 2: host libm, in double)
+  DevBuf<double> d_tables;
+  DevBuf<uint8_t> store[2];
+  int cur = 0;                     // the buffer that holds the entries
+  long long n_entries = 0, cap_entries = 0;
+  DevBuf<uint8_t> qdesc;           // the descriptors of the running call (describe's result, a query's upload)
+  HostBuf<unsigned char> stage;    // pinned: read-backs and uploads on their way
+  const char* call = "sicp_place";  // the entry point that is running: the head of a HIP failure's text
+  std::string last_error;
+};
+
 namespace sicp {
 namespace host {
+
+template <class Body>
+inline int abi_guard(sicp_place_ctx* db, Body&& body) noexcept {
+  return abi_guard_note(static_cast<Body&&>(body), [db](const char* what) {
+    if (db && what) db->last_error = std::string("internal: ") + what;
+  });
+}
 
 // the barrier of an entry point that has a handle / a stream: the description lands in sicp_last_error /
 // sicp_stream_last_error
@@ -933,6 +958,20 @@ int map_extract_fused(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_co
                       float* y, float* z, uint32_t* label, uint32_t* count, double* confidence, sicp_map_extract_info* info);
 int map_fused_labels(sicp_map_ctx* m, sicp_context* h, int which, const double* qt, int32_t include_own_label, int32_t min_count,
                      uint32_t* out_labels, double* out_confidence);
+// sicp_place_* (place.cpp): the database of scan descriptors
+void place_default_params(sicp_place_params* p);
+int place_create(int device_id, const sicp_place_params* p, sicp_place_ctx** out);
+int place_destroy(sicp_place_ctx* db);
+int place_describe(sicp_place_ctx* db, sicp_context* h, int which, const double* sensor_origin, uint8_t* desc, sicp_place_describe_info* info);
+int place_add(sicp_place_ctx* db, sicp_context* h, int which, const double* sensor_origin, int32_t* id, uint8_t* desc,
+              sicp_place_describe_info* info);
+int place_add_descriptors(sicp_place_ctx* db, int32_t n, const uint8_t* desc, int32_t* first_id);
+int place_get(sicp_place_ctx* db, int32_t first, int32_t count, uint8_t* desc);
+int place_query(sicp_place_ctx* db, sicp_context* h, int which, const double* sensor_origin, int32_t first, int32_t count, int32_t top_k,
+                double min_score, sicp_place_candidate* out, int32_t* n_found);
+int place_query_descriptors(sicp_place_ctx* db, int32_t n_q, const uint8_t* desc, int32_t first, int32_t count, int32_t top_k,
+                            double min_score, sicp_place_candidate* out, int32_t* n_found);
+int place_tables(sicp_place_ctx* db, double* cos_half, double* sin_half, double* edge2);
 
 }  // namespace host
 }  // namespace sicp

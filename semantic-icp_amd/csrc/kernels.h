@@ -715,6 +715,39 @@ hipError_t launch_boot_feature_knn_jobs(const BootPairJob* jobs, const int* blk_
 hipError_t launch_boot_error_jobs(const BootPairJob* jobs, const int* hyp_end, int nj, int hypotheses, double t, bool same_label,
                                   hipStream_t st);
 
+// ---- scan descriptors and the loop-candidate search (place_kernels.hip; driver: place.cpp) ----
+// sicp_place_*: a scan -> R x S cell codes (one pass of integer atomics into a zeroed table, a finalise pass), and the exact
+// search of query descriptors against the stored ones at every sector shift.  Integers only behind the cell arithmetic of
+// include/sicp.h, rules 3 and 4.
+constexpr int kPlaceMaxRings = 64, kPlaceMaxSectors = 256;
+enum { kPlaceKept = 0, kPlaceBadLabel = 1, kPlaceCells = 2, kPlaceRes = 4 };
+struct PlaceDescribeArgs {
+  const float *x, *y, *z;   // the scan's finite points (Cloud::rx ...)
+  const uint32_t* label;    // nullptr for the height channel
+  int n, R, S, C;           // C: num_classes (label channel), 0 for the height channel
+  float ox, oy, oz;         // (float)sensor_origin
+  double min_range_sq, z_min, inv_z_step;
+  const double* tables;     // edge2[R + 1] | cos_half[S / 2] | sin_half[S / 2]
+  uint32_t ignore[8];       // bit l: label l takes no part
+  int min_cell_points;
+  uint32_t* table;          // label: [R*S][C] counts of labels 1..C; height: [R*S][2] count, largest level.  Zeroed before
+  uint8_t* desc;            // [R*S]
+  unsigned long long* res;  // kPlaceRes words, zeroed before
+};
+hipError_t launch_place_cells(const PlaceDescribeArgs& a, hipStream_t st);     // table, res[kept, bad label]
+hipError_t launch_place_finalise(const PlaceDescribeArgs& a, hipStream_t st);  // desc, res[cells]
+struct PlaceSearchArgs {
+  const uint8_t* query;     // [n_q][R*S]
+  const uint8_t* entries;   // [count][R*S]: the searched range's first entry
+  int n_q, count, R, S;
+  unsigned long long* key;  // [n_q][count]: (2^30 - floor(match * 2^30 / either)) << 31 | entry index in the range
+  unsigned long long* hit;  // [n_q][count]: shift | match << 16 | either << 32 of the entry's best shift
+};
+hipError_t launch_place_search(const PlaceSearchArgs& a, hipStream_t st);
+// rows[q][k] = {entry index in the range, shift, match, either} of the k-th sorted key of query q, k < top
+hipError_t launch_place_gather(const unsigned long long* sorted_key, const unsigned long long* hit, int n_q, int count, int top, int4* rows,
+                               hipStream_t st);
+
 // ---- the sorts and scans of the feature calls (prim_kernels.hip: the only rocPRIM instantiations besides build_tree.hip) ----
 // rocPRIM's convention: temp == nullptr asks for the bytes.  Ascending, stable; keys: bits [begin_bit, end_bit).
 hipError_t prim_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long n, int begin_bit,

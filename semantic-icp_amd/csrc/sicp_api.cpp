@@ -909,6 +909,80 @@ int sicp_map_fused_labels(sicp_map m, sicp_handle h, int which, const double qt[
   });
 }
 
+int sicp_default_place_params(sicp_place_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    place_default_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_place_create(int device_id, const sicp_place_params* p, sicp_place* out) {
+  return abi_guard([&]() -> int { return place_create(device_id, p, out); });
+}
+
+int sicp_place_destroy(sicp_place db) {
+  return abi_guard([&]() -> int { return place_destroy(db); });
+}
+
+int sicp_place_clear(sicp_place db) {
+  return abi_guard(db, [&]() -> int {
+    if (!db) return SICP_ERR_INVALID_ARGUMENT;
+    db->n_entries = 0;
+    return SICP_OK;
+  });
+}
+
+int sicp_place_size(sicp_place db, int64_t* n_entries) {
+  return abi_guard(db, [&]() -> int {
+    if (!db) return SICP_ERR_INVALID_ARGUMENT;
+    if (!n_entries) {
+      db->last_error = "sicp_place_size: n_entries is NULL";
+      return SICP_ERR_INVALID_ARGUMENT;
+    }
+    *n_entries = db->n_entries;
+    return SICP_OK;
+  });
+}
+
+const char* sicp_place_last_error(sicp_place db) { return db ? db->last_error.c_str() : ""; }
+
+int sicp_place_describe(sicp_place db, sicp_handle h, int which, const double sensor_origin[3], uint8_t* desc,
+                        sicp_place_describe_info* info) {
+  return abi_guard(db, [&]() -> int { return place_describe(db, h, which, sensor_origin, desc, info); });
+}
+
+int sicp_place_add(sicp_place db, sicp_handle h, int which, const double sensor_origin[3], int32_t* id, uint8_t* desc,
+                   sicp_place_describe_info* info) {
+  return abi_guard(db, [&]() -> int { return place_add(db, h, which, sensor_origin, id, desc, info); });
+}
+
+int sicp_place_add_descriptors(sicp_place db, int32_t n, const uint8_t* desc, int32_t* first_id) {
+  return abi_guard(db, [&]() -> int { return place_add_descriptors(db, n, desc, first_id); });
+}
+
+int sicp_place_get(sicp_place db, int32_t first, int32_t count, uint8_t* desc) {
+  return abi_guard(db, [&]() -> int { return place_get(db, first, count, desc); });
+}
+
+int sicp_place_query(sicp_place db, sicp_handle h, int which, const double sensor_origin[3], int32_t first, int32_t count,
+                     int32_t top_k, double min_score, sicp_place_candidate* out, int32_t* n_found) {
+  return abi_guard(db, [&]() -> int {
+    return place_query(db, h, which, sensor_origin, first, count, top_k, min_score, out, n_found);
+  });
+}
+
+int sicp_place_query_descriptors(sicp_place db, int32_t n_q, const uint8_t* desc, int32_t first, int32_t count, int32_t top_k,
+                                 double min_score, sicp_place_candidate* out, int32_t* n_found) {
+  return abi_guard(db, [&]() -> int {
+    return place_query_descriptors(db, n_q, desc, first, count, top_k, min_score, out, n_found);
+  });
+}
+
+int sicp_place_tables(sicp_place db, double* cos_half, double* sin_half, double* edge2) {
+  return abi_guard(db, [&]() -> int { return place_tables(db, cos_half, sin_half, edge2); });
+}
+
 int sicp_solve(sicp_handle h, const double init_qt[7], double out_qt[7], int32_t* lm_iters, int32_t* evals,
                double* final_cost) {
   return abi_guard(h, [&]() -> int {
