@@ -880,6 +880,101 @@ int sicp_place_query_descriptors(sicp_place db, int32_t n_q, const uint8_t* desc
 /* test hook: the tables of rule 2; cos_half and sin_half hold S/2 doubles, edge2 R+1 (each nullable) */
 int sicp_place_tables(sicp_place db, double* cos_half, double* sin_half, double* edge2);
 
+/* ---- pose graph: the trajectory moved by the loop closures, on the device -------- */
+/* A graph of poses that lives on the device between calls.  Calls are synchronous, on the graph's device, from one thread at
+ * a time; the buffers come from the arena (sicp_set_memory_limit applies).  No float atomics: two graphs driven alike hold
+ * the same bytes.
+ *
+ *  1. Node i is a pose T_i, qt[7] = [qx qy qz qw tx ty tz] (node -> world), with a `fixed` flag.  An edge (i, j, z, Omega)
+ *     measures z ~ T_i^-1 T_j: what sicp_align returns with node j's scan as the source and node i's as the target.  Omega is the
+ *     6x6 information matrix (row-major) in the tangent space of z under the right perturbation z * exp(delta),
+ *     delta = [upsilon; omega]: the inverse of sicp_pose_covariance's `covariance` is Omega, without any conversion.  Either
+ *     order of i and j and duplicate edges are allowed; i == j is refused.
+ *  2. r = log(z^-1 T_i^-1 T_j), s = r^T Omega r, cost = 1/2 sum rho(s): rho(s) = s (SICP_GRAPH_LOSS_NONE) or
+ *     cauchy_a^2 log(1 + s / cauchy_a^2) (SICP_GRAPH_LOSS_CAUCHY).  The robust weight w = rho'(s) multiplies Omega in the normal
+ *     equations (iteratively reweighted least squares, no second-order corrector).  The Jacobians are exact under
+ *     T <- T * exp(delta): dr/d delta_j = Jr^-1(r), dr/d delta_i = -Jr^-1(r) Ad(T_j^-1 T_i).
+ *  3. sicp_graph_optimize: Levenberg-Marquardt with the step control of the registration's inner solve.  Each step solves
+ *     (H + D / radius) delta = -g, D = diag(H) clipped to [min_lm_diagonal, max_lm_diagonal], by conjugate gradients with a
+ *     block-Jacobi preconditioner, to |residual| <= cg_eta |g| or max_cg_iterations; the host reads one record per
+ *     cg_check_every iterations.  A step is accepted when (cost - candidate cost) / model decrease > min_relative_decrease;
+ *     then radius /= max(1/3, 1 - (2 rho - 1)^3), otherwise radius /= decrease_factor, which doubles.  A breakdown of the
+ *     linear solve (a non-finite value, p^T A p <= 0, a diagonal block that is not positive definite) or a non-finite
+ *     candidate cost is an invalid step: handled like a rejection and counted against max_consecutive_invalid_steps.  The run
+ *     ends on: max |g| <= gradient_tolerance; an accepted step whose relative cost decrease <= function_tolerance;
+ *     |delta| <= parameter_tolerance (|x| + parameter_tolerance); max_iterations; radius < min_radius; the invalid steps.
+ *     All of these return SICP_OK with the code in info; the graph holds the last accepted poses.  A fixed node, and a node
+ *     without edges, keep their pose's bytes through every call.
+ *  4. Refused with SICP_ERR_INVALID_ARGUMENT, the reason in sicp_graph_last_error, nothing written and the graph byte for byte
+ *     what it was: NULLs; n < 1 or m < 1; a pose or z that is not finite or whose quaternion's norm differs from 1 by more than
+ *     1e-6 (accepted quaternions are stored normalised); an edge end outside the nodes or i == j; an Omega that is not finite,
+ *     asymmetric by more than 1e-9 of its largest entry (otherwise (Omega + Omega^T) / 2 is stored) or not positive definite
+ *     (Cholesky on the host); a range beyond the size; parameters outside their ranges; more than 2^31 - 1 nodes or edges.
+ *     SICP_ERR_NOT_READY: sicp_graph_optimize without a fixed node or without an edge.  SICP_ERR_OUT_OF_MEMORY: the arena
+ *     refused; the graph holds what it held. */
+enum { SICP_GRAPH_LOSS_NONE = 0, SICP_GRAPH_LOSS_CAUCHY = 1 };
+enum {
+  SICP_GRAPH_GRADIENT_TOLERANCE = 0,
+  SICP_GRAPH_FUNCTION_TOLERANCE = 1,
+  SICP_GRAPH_PARAMETER_TOLERANCE = 2,
+  SICP_GRAPH_MAX_ITERATIONS = 3,
+  SICP_GRAPH_MIN_RADIUS = 4,
+  SICP_GRAPH_INVALID_STEPS = 5
+};
+typedef struct sicp_graph_ctx* sicp_graph;
+typedef struct sicp_graph_params {
+  int32_t loss;                 /* SICP_GRAPH_LOSS_NONE (default) / SICP_GRAPH_LOSS_CAUCHY */
+  int32_t max_iterations;       /* 100; >= 0 */
+  double cauchy_a;              /* 1.0; > 0 */
+  double gradient_tolerance;    /* 1e-10; >= 0 */
+  double function_tolerance;    /* 1e-12; >= 0 */
+  double parameter_tolerance;   /* 1e-12; >= 0 */
+  double initial_radius;        /* 1e4; min_radius <= . <= max_radius */
+  double min_radius;            /* 1e-32; > 0 */
+  double max_radius;            /* 1e16 */
+  double min_relative_decrease; /* 1e-3; in [0, 1) */
+  double min_lm_diagonal;       /* 1e-6; > 0 */
+  double max_lm_diagonal;       /* 1e32; >= min_lm_diagonal */
+  int32_t max_consecutive_invalid_steps; /* 5; >= 1 */
+  int32_t max_cg_iterations;    /* 500; >= 1 */
+  double cg_eta;                /* 0.1; in (0, 1) */
+  int32_t cg_check_every;       /* 8; >= 1 */
+  int32_t reserved_;
+} sicp_graph_params;
+typedef struct sicp_graph_info {
+  int32_t iterations;           /* outer iterations (linear solves) */
+  int32_t accepted_steps;
+  int32_t rejected_steps;
+  int32_t invalid_steps;
+  int32_t cg_iterations;        /* of all linear solves */
+  int32_t termination;          /* SICP_GRAPH_GRADIENT_TOLERANCE ... */
+  double initial_cost;
+  double final_cost;
+  double gradient_max_norm;     /* at the final poses */
+  double radius;                /* the trust region's, at the end */
+} sicp_graph_info;
+int sicp_default_graph_params(sicp_graph_params* p);
+int sicp_graph_create(int device_id, const sicp_graph_params* p, sicp_graph* out);
+int sicp_graph_destroy(sicp_graph g);
+int sicp_graph_clear(sicp_graph g);  /* no nodes, no edges; the buffers stay */
+int sicp_graph_size(sicp_graph g, int64_t* n_nodes, int64_t* n_edges);
+const char* sicp_graph_last_error(sicp_graph g);
+/* n poses qt[7n]; fixed[n] (NULL: none fixed); first_id (nullable): the first new node's id, the rest follow */
+int sicp_graph_add_nodes(sicp_graph g, int32_t n, const double* qt, const uint8_t* fixed, int32_t* first_id);
+/* m edges: ends i[m], j[m], measurements z[7m], information matrices omega[36m]; first_id nullable */
+int sicp_graph_add_edges(sicp_graph g, int32_t m, const int32_t* i, const int32_t* j, const double* z, const double* omega,
+                         int32_t* first_id);
+int sicp_graph_set_poses(sicp_graph g, int32_t first, int32_t count, const double* qt);
+int sicp_graph_get_poses(sicp_graph g, int32_t first, int32_t count, double* qt);
+int sicp_graph_set_fixed(sicp_graph g, int32_t first, int32_t count, const uint8_t* fixed);
+/* per edge at the current poses: chi2[M] = s, residual[6M] = r, weight[M] = w (each nullable), and the cost.  A false loop
+ * closure shows as a large chi2. */
+int sicp_graph_errors(sicp_graph g, double* chi2, double* residual, double* weight, double* cost);
+/* inspection: the gradient[6N] and the diagonal blocks[36N] of the normal equations at the current poses (each nullable),
+ * and the cost.  A fixed node has the identity block and a zero gradient, a node without edges a zero block. */
+int sicp_graph_linearize(sicp_graph g, double* gradient, double* diag_blocks, double* cost);
+int sicp_graph_optimize(sicp_graph g, sicp_graph_info* info);
+
 /* test / bench hook: the keypoints of cloud `which` with their normals, FPFH features and feature-radius
  * neighbour lists (CSR: nbr_offsets[n + 1], nbr_idx sorted by (d^2, index)).  Counts are always written; an output
  * array is written when it is non-NULL and its capacity (points / neighbour entries) suffices, otherwise the call

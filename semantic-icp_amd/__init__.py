@@ -373,6 +373,54 @@ class SicpPlaceDescribeInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
 
 
+GRAPH_LOSS_NONE, GRAPH_LOSS_CAUCHY = 0, 1
+GRAPH_TERMINATIONS = ("gradient", "function", "parameter", "max_iterations", "min_radius", "invalid_steps")
+
+
+class SicpGraphParams(C.Structure):
+    """sicp_graph_params (include/sicp.h)"""
+    _fields_ = [
+        ("loss", C.c_int32),
+        ("max_iterations", C.c_int32),
+        ("cauchy_a", C.c_double),
+        ("gradient_tolerance", C.c_double),
+        ("function_tolerance", C.c_double),
+        ("parameter_tolerance", C.c_double),
+        ("initial_radius", C.c_double),
+        ("min_radius", C.c_double),
+        ("max_radius", C.c_double),
+        ("min_relative_decrease", C.c_double),
+        ("min_lm_diagonal", C.c_double),
+        ("max_lm_diagonal", C.c_double),
+        ("max_consecutive_invalid_steps", C.c_int32),
+        ("max_cg_iterations", C.c_int32),
+        ("cg_eta", C.c_double),
+        ("cg_check_every", C.c_int32),
+        ("reserved_", C.c_int32),
+    ]
+
+
+class SicpGraphInfo(C.Structure):
+    """sicp_graph_info (include/sicp.h)"""
+    _fields_ = [
+        ("iterations", C.c_int32),
+        ("accepted_steps", C.c_int32),
+        ("rejected_steps", C.c_int32),
+        ("invalid_steps", C.c_int32),
+        ("cg_iterations", C.c_int32),
+        ("termination", C.c_int32),
+        ("initial_cost", C.c_double),
+        ("final_cost", C.c_double),
+        ("gradient_max_norm", C.c_double),
+        ("radius", C.c_double),
+    ]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["termination_name"] = GRAPH_TERMINATIONS[self.termination]
+        return d
+
+
 class SicpError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -422,6 +470,8 @@ def lib():
         _lib.sicp_map_last_error.argtypes = [C.c_void_p]
         _lib.sicp_place_last_error.restype = C.c_char_p
         _lib.sicp_place_last_error.argtypes = [C.c_void_p]
+        _lib.sicp_graph_last_error.restype = C.c_char_p
+        _lib.sicp_graph_last_error.argtypes = [C.c_void_p]
         for name, args in {
             "sicp_device_count": [C.POINTER(C.c_int)],
             "sicp_create": [C.c_int, C.POINTER(C.c_void_p)],
@@ -520,6 +570,19 @@ def lib():
             "sicp_place_query_descriptors": [C.c_void_p, C.c_int32, _bp, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                              C.POINTER(SicpPlaceCandidate), _ip],
             "sicp_place_tables": [C.c_void_p, _dp, _dp, _dp],
+            "sicp_default_graph_params": [C.POINTER(SicpGraphParams)],
+            "sicp_graph_create": [C.c_int, C.POINTER(SicpGraphParams), C.POINTER(C.c_void_p)],
+            "sicp_graph_destroy": [C.c_void_p],
+            "sicp_graph_clear": [C.c_void_p],
+            "sicp_graph_size": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+            "sicp_graph_add_nodes": [C.c_void_p, C.c_int32, _dp, _bp, _ip],
+            "sicp_graph_add_edges": [C.c_void_p, C.c_int32, _ip, _ip, _dp, _dp, _ip],
+            "sicp_graph_set_poses": [C.c_void_p, C.c_int32, C.c_int32, _dp],
+            "sicp_graph_get_poses": [C.c_void_p, C.c_int32, C.c_int32, _dp],
+            "sicp_graph_set_fixed": [C.c_void_p, C.c_int32, C.c_int32, _bp],
+            "sicp_graph_errors": [C.c_void_p, _dp, _dp, _dp, _dp],
+            "sicp_graph_linearize": [C.c_void_p, _dp, _dp, _dp],
+            "sicp_graph_optimize": [C.c_void_p, C.POINTER(SicpGraphInfo)],
         }.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
@@ -677,6 +740,20 @@ def default_place_params(**overrides) -> SicpPlaceParams:
                 p.n_ignore = len(labels)
         else:
             setattr(p, k, v)
+    return p
+
+
+def default_graph_params(**overrides) -> SicpGraphParams:
+    """sicp_default_graph_params (no robust loss, the step control of the registration's inner solve, conjugate gradients to
+    0.1 |g|), with any field overridden by keyword"""
+    p = SicpGraphParams()
+    st = lib().sicp_default_graph_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_graph_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
     return p
 
 
@@ -1399,6 +1476,124 @@ class PlaceDB:
 
     def clear(self):
         self._check(lib().sicp_place_clear(self._db), "sicp_place_clear")
+
+
+class PoseGraph:
+    """sicp_graph_*: a pose graph that lives on the device.  Node i is a pose qt[7] (node -> world); an edge (i, j, z, omega)
+    measures z ~ T_i^-1 T_j -- what align() returns with node j's scan as the source and node i's as the target -- with the 6x6
+    information matrix omega = inv(pose_covariance(...)["covariance"]).  optimize() moves the free nodes to the minimum of
+    1/2 sum rho(r^T omega r)."""
+
+    def __init__(self, device: int = 0, params: SicpGraphParams | None = None):
+        self._g = C.c_void_p()
+        p = params if params is not None else default_graph_params()
+        st = lib().sicp_graph_create(device, C.byref(p), C.byref(self._g))
+        if st != OK:
+            self._g = C.c_void_p()
+            raise SicpError(st, "sicp_graph_create")
+
+    def _check(self, st, where):
+        if st != OK:
+            raise SicpError(st, where, lib().sicp_graph_last_error(self._g).decode())
+
+    def close(self):
+        if getattr(self, "_g", None) and self._g.value:
+            lib().sicp_graph_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @staticmethod
+    def _poses(qt):
+        q = np.ascontiguousarray(qt, dtype=np.float64)
+        if q.ndim == 1:
+            q = q[None]
+        if q.ndim != 2 or q.shape[1] != 7:
+            raise ValueError("poses must be [n, 7] float64")
+        return q
+
+    def add_nodes(self, qt, fixed=None) -> int:
+        """sicp_graph_add_nodes: [n, 7] poses (or one), fixed[n] flags or None; returns the first new node's id"""
+        q = self._poses(qt)
+        f = None
+        if fixed is not None:
+            f = np.ascontiguousarray(np.broadcast_to(np.asarray(fixed, dtype=bool), (q.shape[0],)), dtype=np.uint8)
+        first = C.c_int32(-1)
+        self._check(lib().sicp_graph_add_nodes(self._g, q.shape[0], _ptr(q, _dp), _ptr(f, _bp), C.byref(first)), "sicp_graph_add_nodes")
+        return first.value
+
+    def add_edges(self, i, j, z, omega) -> int:
+        """sicp_graph_add_edges: ends i[m], j[m], measurements z[m, 7], information matrices omega[m, 6, 6]; returns the first
+        new edge's id"""
+        zz = self._poses(z)
+        m = zz.shape[0]
+        ii = np.ascontiguousarray(np.atleast_1d(i), dtype=np.int32)
+        jj = np.ascontiguousarray(np.atleast_1d(j), dtype=np.int32)
+        om = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1, 6, 6)
+        if ii.shape != (m,) or jj.shape != (m,) or om.shape[0] != m:
+            raise ValueError("i[m], j[m], z[m, 7] and omega[m, 6, 6] must agree on m")
+        first = C.c_int32(-1)
+        self._check(lib().sicp_graph_add_edges(self._g, m, _ptr(ii, _ip), _ptr(jj, _ip), _ptr(zz, _dp), _ptr(om, _dp), C.byref(first)),
+                    "sicp_graph_add_edges")
+        return first.value
+
+    def set_poses(self, qt, first: int = 0):
+        q = self._poses(qt)
+        self._check(lib().sicp_graph_set_poses(self._g, first, q.shape[0], _ptr(q, _dp)), "sicp_graph_set_poses")
+
+    def poses(self, first: int = 0, count: int | None = None):
+        """sicp_graph_get_poses: [count, 7] float64 (count = None: to the end)"""
+        n = self.size()[0] - first if count is None else count
+        out = np.empty((max(n, 0), 7), dtype=np.float64)
+        if n == 0 and count is None:
+            return out
+        self._check(lib().sicp_graph_get_poses(self._g, first, n, _ptr(out, _dp)), "sicp_graph_get_poses")
+        return out
+
+    def set_fixed(self, fixed, first: int = 0):
+        f = np.ascontiguousarray(np.atleast_1d(np.asarray(fixed, dtype=bool)), dtype=np.uint8)
+        self._check(lib().sicp_graph_set_fixed(self._g, first, f.shape[0], _ptr(f, _bp)), "sicp_graph_set_fixed")
+
+    def errors(self):
+        """sicp_graph_errors at the current poses: {"chi2": [M], "residual": [M, 6], "weight": [M], "cost": float}"""
+        m = self.size()[1]
+        chi2, w, r = np.empty(m), np.empty(m), np.empty((m, 6))
+        cost = C.c_double(0.0)
+        self._check(lib().sicp_graph_errors(self._g, _ptr(chi2, _dp), _ptr(r, _dp), _ptr(w, _dp), C.byref(cost)), "sicp_graph_errors")
+        return {"chi2": chi2, "residual": r, "weight": w, "cost": cost.value}
+
+    def linearize(self):
+        """sicp_graph_linearize at the current poses: {"gradient": [N, 6], "diag_blocks": [N, 6, 6], "cost": float}"""
+        n = self.size()[0]
+        g, H = np.empty((n, 6)), np.empty((n, 6, 6))
+        cost = C.c_double(0.0)
+        self._check(lib().sicp_graph_linearize(self._g, _ptr(g, _dp), _ptr(H, _dp), C.byref(cost)), "sicp_graph_linearize")
+        return {"gradient": g, "diag_blocks": H, "cost": cost.value}
+
+    def optimize(self):
+        """sicp_graph_optimize: SicpGraphInfo.as_dict() (termination_name: one of GRAPH_TERMINATIONS)"""
+        info = SicpGraphInfo()
+        self._check(lib().sicp_graph_optimize(self._g, C.byref(info)), "sicp_graph_optimize")
+        return info.as_dict()
+
+    def size(self):
+        """(nodes, edges)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(lib().sicp_graph_size(self._g, C.byref(a), C.byref(b)), "sicp_graph_size")
+        return a.value, b.value
+
+    def clear(self):
+        self._check(lib().sicp_graph_clear(self._g), "sicp_graph_clear")
 
 
 def accumulate_batch(engines, qts, repeat: int = 1):

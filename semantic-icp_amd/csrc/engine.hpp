@@ -10,6 +10,7 @@
 //   evaluate.cpp  sicp_evaluate: overlap, inlier RMSE and label agreement at a pose
 //   merge.cpp     sicp_merge_clouds: posed clouds into one voxel-grid cloud
 //   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, prune, extract)
+//   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise)
 //   sicp_api.cpp  the remaining C-ABI entry points
 // Every extern "C" entry runs inside abi_guard (abi_barrier.hpp): no exception crosses the boundary.
 #ifndef SICP_ENGINE_HPP_
@@ -627,8 +628,40 @@ struct sicp_place_ctx {
   std::string last_error;
 };
 
+// ---- a pose graph (sicp_graph_*; graph.cpp): nodes and edges one after another in one of two sets of arena buffers -- growth
+// copies into the spare set and swaps last, so a refused call leaves the graph as it was.  The work buffers of linearise and
+// optimise are sized when they are needed and kept.
+struct sicp_graph_ctx {
+  int device = 0;
+  sicp_graph_params params;
+  OwnedStream stream;
+  struct Nodes { DevBuf<double> pose; DevBuf<uint8_t> fixed; } nodes[2];
+  struct Edges { DevBuf<int> i, j; DevBuf<double> z, omega; } edges[2];
+  int ncur = 0, ecur = 0;             // the sets that hold the graph
+  long long n_nodes = 0, n_edges = 0, cap_nodes = 0, cap_edges = 0;
+  long long n_fixed = 0;
+  std::vector<uint8_t> h_fixed;       // the host's copy of the flags (optimize refuses a graph without a fixed node)
+  bool incidence_stale = true;        // edges have been added since the incidence table was built
+  DevBuf<double> C, B, r, s, w, ec, H, g, L, x, rr, zz, p, q, cand, part;
+  DevBuf<unsigned long long> keys, inc;
+  DevBuf<int> deg, off;
+  DevBuf<unsigned char> temp;
+  DevBuf<sicp::GraphScalars> scalars;
+  HostBuf<unsigned char> stage;       // pinned: uploads and read-backs on their way
+  HostBuf<sicp::GraphScalars> rec;    // pinned: the scalars' read-back
+  const char* call = "sicp_graph";    // the entry point that is running: the head of a HIP failure's text
+  std::string last_error;
+};
+
 namespace sicp {
 namespace host {
+
+template <class Body>
+inline int abi_guard(sicp_graph_ctx* g, Body&& body) noexcept {
+  return abi_guard_note(static_cast<Body&&>(body), [g](const char* what) {
+    if (g && what) g->last_error = std::string("internal: ") + what;
+  });
+}
 
 template <class Body>
 inline int abi_guard(sicp_place_ctx* db, Body&& body) noexcept {
@@ -972,6 +1005,20 @@ int place_query(sicp_place_ctx* db, sicp_context* h, int which, const double* se
 int place_query_descriptors(sicp_place_ctx* db, int32_t n_q, const uint8_t* desc, int32_t first, int32_t count, int32_t top_k,
                             double min_score, sicp_place_candidate* out, int32_t* n_found);
 int place_tables(sicp_place_ctx* db, double* cos_half, double* sin_half, double* edge2);
+// sicp_graph_* (graph.cpp): the pose graph
+void graph_default_params(sicp_graph_params* p);
+int graph_create(int device_id, const sicp_graph_params* p, sicp_graph_ctx** out);
+int graph_destroy(sicp_graph_ctx* g);
+int graph_clear(sicp_graph_ctx* g);
+int graph_size(sicp_graph_ctx* g, int64_t* n_nodes, int64_t* n_edges);
+int graph_add_nodes(sicp_graph_ctx* g, int32_t n, const double* qt, const uint8_t* fixed, int32_t* first_id);
+int graph_add_edges(sicp_graph_ctx* g, int32_t m, const int32_t* i, const int32_t* j, const double* z, const double* omega, int32_t* first_id);
+int graph_set_poses(sicp_graph_ctx* g, int32_t first, int32_t count, const double* qt);
+int graph_get_poses(sicp_graph_ctx* g, int32_t first, int32_t count, double* qt);
+int graph_set_fixed(sicp_graph_ctx* g, int32_t first, int32_t count, const uint8_t* fixed);
+int graph_errors(sicp_graph_ctx* g, double* chi2, double* residual, double* weight, double* cost);
+int graph_linearize(sicp_graph_ctx* g, double* gradient, double* diag_blocks, double* cost);
+int graph_optimize(sicp_graph_ctx* g, sicp_graph_info* info);
 
 }  // namespace host
 }  // namespace sicp

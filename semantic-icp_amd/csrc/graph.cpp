@@ -1,0 +1,577 @@
+// graph.cpp -- sicp_graph_* (include/sicp.h): a pose graph that lives on the device between calls.  Nodes and edges lie one
+// after another in one of two sets of arena buffers; growth doubles into the spare set and swaps last, and every check of a
+// call comes before its first write, so a refused call leaves the graph as it was.  The outer Levenberg-Marquardt loop runs
+// here with one read-back per iteration (and one per batch of conjugate-gradient steps); the kernels: graph_kernels.hip, the
+// sort and the scan of prim_kernels.hip.
+#include "engine.hpp"
+
+namespace sicp {
+namespace host {
+namespace {
+
+#define GRAPHCHECK(expr)                                                                       \
+  do {                                                                                         \
+    hipError_t _e = (expr);                                                                    \
+    if (_e != hipSuccess) {                                                                    \
+      G->last_error = std::string(G->call) + ": " #expr ": " + hipGetErrorString(_e) +         \
+                      "; the graph is unchanged";                                              \
+      return _e == hipErrorOutOfMemory ? SICP_ERR_OUT_OF_MEMORY : SICP_ERR_HIP;                \
+    }                                                                                          \
+  } while (0)
+
+bool in_range(double v, double lo, double hi) { return std::isfinite(v) && v >= lo && v <= hi; }
+
+bool params_ok(const sicp_graph_params& p) {
+  if (p.loss != SICP_GRAPH_LOSS_NONE && p.loss != SICP_GRAPH_LOSS_CAUCHY) return false;
+  if (p.max_iterations < 0) return false;
+  if (!std::isfinite(p.cauchy_a) || !(p.cauchy_a > 0.0)) return false;
+  const double big = std::numeric_limits<double>::max();
+  if (!in_range(p.gradient_tolerance, 0, big) || !in_range(p.function_tolerance, 0, big) || !in_range(p.parameter_tolerance, 0, big)) return false;
+  if (!std::isfinite(p.min_radius) || !(p.min_radius > 0.0) || !std::isfinite(p.max_radius)) return false;
+  if (!in_range(p.initial_radius, p.min_radius, p.max_radius)) return false;
+  if (!(p.min_relative_decrease >= 0.0) || !(p.min_relative_decrease < 1.0)) return false;
+  if (!std::isfinite(p.min_lm_diagonal) || !(p.min_lm_diagonal > 0.0) || !in_range(p.max_lm_diagonal, p.min_lm_diagonal, big)) return false;
+  if (p.max_consecutive_invalid_steps < 1 || p.max_cg_iterations < 1 || p.cg_check_every < 1) return false;
+  return p.cg_eta > 0.0 && p.cg_eta < 1.0;
+}
+
+// the first bad pose of qt[7 n] with the reason, or -1
+long long first_bad_pose(const double* qt, long long n, std::string& why) {
+  for (long long k = 0; k < n; ++k) {
+    const double* q = qt + 7 * k;
+    for (int d = 0; d < 7; ++d)
+      if (!std::isfinite(q[d])) { why = "is not finite"; return k; }
+    const double norm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (!(std::fabs(norm - 1.0) <= 1e-6)) { why = "has a quaternion of norm " + std::to_string(norm); return k; }
+  }
+  return -1;
+}
+void store_pose(const double* q, double* o) {
+  const double inv = 1.0 / std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  for (int d = 0; d < 4; ++d) o[d] = q[d] * inv;
+  for (int d = 4; d < 7; ++d) o[d] = q[d];
+}
+
+// (Omega + Omega^T) / 2 into out, or the reason it is refused
+bool take_omega(const double* om, double* out, std::string& why) {
+  double big = 0;
+  for (int k = 0; k < 36; ++k) {
+    if (!std::isfinite(om[k])) { why = "has an information matrix that is not finite"; return false; }
+    big = std::max(big, std::fabs(om[k]));
+  }
+  for (int a = 0; a < 6; ++a)
+    for (int b = 0; b < a; ++b)
+      if (std::fabs(om[6 * a + b] - om[6 * b + a]) > 1e-9 * big) { why = "has an information matrix that is not symmetric"; return false; }
+  for (int a = 0; a < 6; ++a)
+    for (int b = 0; b < 6; ++b) out[6 * a + b] = 0.5 * (om[6 * a + b] + om[6 * b + a]);
+  double A[36], rhs[6] = {0, 0, 0, 0, 0, 0}, y[6];
+  std::memcpy(A, out, sizeof A);
+  if (!sicp::detail::chol6_solve(A, rhs, y)) { why = "has an information matrix that is not positive definite"; return false; }
+  return true;
+}
+
+int resolve_range(const sicp_graph_ctx* G, int32_t first, int32_t count, std::string& why) {
+  if (first < 0 || count < 1) { why = "first must be >= 0 and count >= 1"; return SICP_ERR_INVALID_ARGUMENT; }
+  if ((long long)first + count > G->n_nodes) {
+    why = "the range " + std::to_string(first) + " + " + std::to_string(count) + " reaches beyond the " + std::to_string(G->n_nodes) + " nodes";
+    return SICP_ERR_INVALID_ARGUMENT;
+  }
+  return SICP_OK;
+}
+
+// Room for n more nodes / m more edges in the spare set at twice the capacity, the contents copied, the swap last.
+int grow_nodes(sicp_graph_ctx* G, long long n) {
+  const long long need = G->n_nodes + n;
+  if (need <= G->cap_nodes) return SICP_OK;
+  const long long want = std::max<long long>(std::max<long long>(need, 2 * G->cap_nodes), 64);
+  auto& cur = G->nodes[G->ncur];
+  auto& spare = G->nodes[G->ncur ^ 1];
+  GRAPHCHECK(spare.pose.reserve((size_t)want * 7));
+  GRAPHCHECK(spare.fixed.reserve((size_t)want));
+  if (G->n_nodes > 0) {
+    GRAPHCHECK(hipMemcpyAsync(spare.pose.p, cur.pose.p, sizeof(double) * 7 * (size_t)G->n_nodes, hipMemcpyDeviceToDevice, G->stream));
+    GRAPHCHECK(hipMemcpyAsync(spare.fixed.p, cur.fixed.p, (size_t)G->n_nodes, hipMemcpyDeviceToDevice, G->stream));
+    GRAPHCHECK(hipStreamSynchronize(G->stream));
+  }
+  G->ncur ^= 1;
+  G->cap_nodes = want;
+  DevArena::FreeScope idle(G->device);  // (nothing reads the old set any more)
+  cur.pose.release();
+  cur.fixed.release();
+  return SICP_OK;
+}
+
+int grow_edges(sicp_graph_ctx* G, long long m) {
+  const long long need = G->n_edges + m;
+  if (need <= G->cap_edges) return SICP_OK;
+  const long long want = std::max<long long>(std::max<long long>(need, 2 * G->cap_edges), 64);
+  auto& cur = G->edges[G->ecur];
+  auto& spare = G->edges[G->ecur ^ 1];
+  GRAPHCHECK(spare.i.reserve((size_t)want));
+  GRAPHCHECK(spare.j.reserve((size_t)want));
+  GRAPHCHECK(spare.z.reserve((size_t)want * 7));
+  GRAPHCHECK(spare.omega.reserve((size_t)want * 36));
+  if (G->n_edges > 0) {
+    const size_t M = (size_t)G->n_edges;
+    GRAPHCHECK(hipMemcpyAsync(spare.i.p, cur.i.p, sizeof(int) * M, hipMemcpyDeviceToDevice, G->stream));
+    GRAPHCHECK(hipMemcpyAsync(spare.j.p, cur.j.p, sizeof(int) * M, hipMemcpyDeviceToDevice, G->stream));
+    GRAPHCHECK(hipMemcpyAsync(spare.z.p, cur.z.p, sizeof(double) * 7 * M, hipMemcpyDeviceToDevice, G->stream));
+    GRAPHCHECK(hipMemcpyAsync(spare.omega.p, cur.omega.p, sizeof(double) * 36 * M, hipMemcpyDeviceToDevice, G->stream));
+    GRAPHCHECK(hipStreamSynchronize(G->stream));
+  }
+  G->ecur ^= 1;
+  G->cap_edges = want;
+  DevArena::FreeScope idle(G->device);
+  cur.i.release(); cur.j.release(); cur.z.release(); cur.omega.release();
+  return SICP_OK;
+}
+
+// the work buffers at the graph's size, and the kernels' arguments
+int prepare(sicp_graph_ctx* G, sicp::GraphArgs& A) {
+  const size_t N = (size_t)std::max<long long>(G->n_nodes, 1), M = (size_t)std::max<long long>(G->n_edges, 1);
+  const int stride = sicp::graph_blocks((long long)std::max(6 * N, M));
+  GRAPHCHECK(G->C.reserve(2 * M * sicp::kGraphRec)); GRAPHCHECK(G->B.reserve(36 * M)); GRAPHCHECK(G->r.reserve(6 * M));
+  GRAPHCHECK(G->s.reserve(M)); GRAPHCHECK(G->w.reserve(M)); GRAPHCHECK(G->ec.reserve(M));
+  GRAPHCHECK(G->H.reserve(36 * N)); GRAPHCHECK(G->g.reserve(6 * N)); GRAPHCHECK(G->L.reserve(sicp::kGraphChol * N));
+  GRAPHCHECK(G->x.reserve(6 * N)); GRAPHCHECK(G->rr.reserve(6 * N)); GRAPHCHECK(G->zz.reserve(6 * N));
+  GRAPHCHECK(G->p.reserve(6 * N)); GRAPHCHECK(G->q.reserve(6 * N)); GRAPHCHECK(G->cand.reserve(7 * N));
+  GRAPHCHECK(G->part.reserve(3 * (size_t)stride));
+  GRAPHCHECK(G->inc.reserve(2 * M)); GRAPHCHECK(G->off.reserve(N + 1));
+  GRAPHCHECK(G->scalars.reserve(1));
+  GRAPHCHECK(G->rec.resize(1));
+  std::memset(&A, 0, sizeof A);
+  A.n_nodes = (int)G->n_nodes; A.n_edges = (int)G->n_edges;
+  A.pose = G->nodes[G->ncur].pose.p; A.fixed = G->nodes[G->ncur].fixed.p;
+  const auto& E = G->edges[G->ecur];
+  A.ei = E.i.p; A.ej = E.j.p; A.z = E.z.p; A.omega = E.omega.p;
+  A.loss = G->params.loss; A.cauchy_a = G->params.cauchy_a;
+  A.C = G->C.p; A.B = G->B.p; A.r = G->r.p; A.s = G->s.p; A.w = G->w.p; A.ec = G->ec.p;
+  A.inc = G->inc.p; A.off = G->off.p;
+  A.H = G->H.p; A.g = G->g.p; A.L = G->L.p;
+  A.x = G->x.p; A.rr = G->rr.p; A.zz = G->zz.p; A.p = G->p.p; A.q = G->q.p; A.cand = G->cand.p;
+  A.part = G->part.p; A.part_stride = stride;
+  A.S = G->scalars.p;
+  A.lo = G->params.min_lm_diagonal; A.hi = G->params.max_lm_diagonal; A.radius = G->params.initial_radius; A.eta = G->params.cg_eta;
+  return SICP_OK;
+}
+
+// The incidence table, rebuilt when edges have been added: the slots 2 * edge + side sorted by node (a stable sort of the
+// node bits: within a node the slots ascend), the degrees' scan.
+int build_incidence(sicp_graph_ctx* G, sicp::GraphArgs& A) {
+  if (!G->incidence_stale || G->n_edges == 0) return SICP_OK;
+  const long long slots = 2 * G->n_edges, N = G->n_nodes;
+  hipStream_t st = G->stream;
+  GRAPHCHECK(G->keys.reserve((size_t)slots));
+  GRAPHCHECK(G->deg.reserve((size_t)N + 1));
+  int bits = 1;
+  while (bits < 31 && (1ll << bits) < N) ++bits;
+  size_t sort_bytes = 0, scan_bytes = 0;
+  GRAPHCHECK(sicp::prim_sort_keys(nullptr, sort_bytes, G->keys.p, G->inc.p, slots, 32, 32 + bits, st));
+  GRAPHCHECK(sicp::prim_scan_int(nullptr, scan_bytes, G->deg.p, G->off.p, N + 1, st));
+  GRAPHCHECK(G->temp.reserve(std::max(sort_bytes, scan_bytes) + 256));
+  A.deg = G->deg.p;
+  GRAPHCHECK(hipMemsetAsync(G->deg.p, 0, sizeof(int) * (size_t)(N + 1), st));
+  GRAPHCHECK(sicp::launch_graph_keys(A, G->keys.p, st));
+  GRAPHCHECK(sicp::prim_sort_keys(G->temp.p, sort_bytes, G->keys.p, G->inc.p, slots, 32, 32 + bits, st));
+  GRAPHCHECK(sicp::prim_scan_int(G->temp.p, scan_bytes, G->deg.p, G->off.p, N + 1, st));
+  GRAPHCHECK(hipStreamSynchronize(st));
+  G->incidence_stale = false;
+  return SICP_OK;
+}
+
+int read_scalars(sicp_graph_ctx* G, sicp::GraphScalars& S) {
+  GRAPHCHECK(hipMemcpyAsync(G->rec.data(), G->scalars.p, sizeof(sicp::GraphScalars), hipMemcpyDeviceToHost, G->stream));
+  GRAPHCHECK(hipStreamSynchronize(G->stream));
+  S = G->rec[0];
+  return SICP_OK;
+}
+
+int download(sicp_graph_ctx* G, double* dst, const double* src, size_t count) {
+  if (!dst || count == 0) return SICP_OK;
+  GRAPHCHECK(hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyDeviceToHost, G->stream));
+  GRAPHCHECK(hipStreamSynchronize(G->stream));
+  return SICP_OK;
+}
+
+// full linearisation at the current poses: per-edge records, H, g, S->cost, S->gmax
+int linearise_full(sicp_graph_ctx* G, sicp::GraphArgs& A) {
+  hipStream_t st = G->stream;
+  if (G->n_edges > 0) {
+    GRAPHCHECK(sicp::launch_graph_linearise(A, A.pose, true, st));
+    GRAPHCHECK(sicp::launch_graph_sum(A, sicp::kGraphFinCost, st));
+  }
+  GRAPHCHECK(sicp::launch_graph_gather(A, st));
+  GRAPHCHECK(sicp::launch_graph_sum(A, sicp::kGraphFinGmax, st));
+  return SICP_OK;
+}
+
+}  // namespace
+
+void graph_default_params(sicp_graph_params* p) {
+  std::memset(p, 0, sizeof *p);
+  p->loss = SICP_GRAPH_LOSS_NONE;
+  p->max_iterations = 100;
+  p->cauchy_a = 1.0;
+  p->gradient_tolerance = 1e-10;
+  p->function_tolerance = 1e-12;
+  p->parameter_tolerance = 1e-12;
+  p->initial_radius = 1e4;
+  p->min_radius = 1e-32;
+  p->max_radius = 1e16;
+  p->min_relative_decrease = 1e-3;
+  p->min_lm_diagonal = 1e-6;
+  p->max_lm_diagonal = 1e32;
+  p->max_consecutive_invalid_steps = 5;
+  p->max_cg_iterations = 500;
+  p->cg_eta = 0.1;
+  p->cg_check_every = 8;
+}
+
+int graph_create(int device_id, const sicp_graph_params* p, sicp_graph_ctx** out) {
+  if (!out) return SICP_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  if (!p || !params_ok(*p)) return SICP_ERR_INVALID_ARGUMENT;
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return SICP_ERR_NO_DEVICE;
+  if (device_id < 0 || device_id >= n) return SICP_ERR_INVALID_ARGUMENT;
+  sicp_graph_ctx* G = new (std::nothrow) sicp_graph_ctx();
+  if (!G) return SICP_ERR_OUT_OF_MEMORY;
+  G->device = device_id;
+  G->params = *p;
+  G->params.reserved_ = 0;
+  if (hipSetDevice(device_id) != hipSuccess || G->stream.create() != hipSuccess) {
+    delete G;
+    return SICP_ERR_NO_DEVICE;
+  }
+  *out = G;
+  return SICP_OK;
+}
+
+int graph_destroy(sicp_graph_ctx* G) {
+  if (!G) return SICP_OK;
+  (void)hipSetDevice(G->device);
+  if (G->stream) (void)hipStreamSynchronize(G->stream);
+  {
+    DevArena::FreeScope once(G->device);  // one wait for the device, not one per buffer
+    delete G;
+  }
+  return SICP_OK;
+}
+
+int graph_clear(sicp_graph_ctx* G) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->n_nodes = G->n_edges = G->n_fixed = 0;
+  G->h_fixed.clear();
+  G->incidence_stale = true;
+  G->last_error.clear();
+  return SICP_OK;
+}
+
+int graph_size(sicp_graph_ctx* G, int64_t* n_nodes, int64_t* n_edges) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  if (!n_nodes || !n_edges) {
+    G->last_error = "sicp_graph_size: an output is NULL";
+    return SICP_ERR_INVALID_ARGUMENT;
+  }
+  *n_nodes = G->n_nodes;
+  *n_edges = G->n_edges;
+  return SICP_OK;
+}
+
+int graph_add_nodes(sicp_graph_ctx* G, int32_t n, const double* qt, const uint8_t* fixed, int32_t* first_id) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = "sicp_graph_add_nodes";
+  auto refuse = [&](const std::string& why) {
+    G->last_error = "sicp_graph_add_nodes: " + why + "; the graph is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (n < 1) return refuse("n must be >= 1");
+  if (!qt) return refuse("qt is NULL");
+  if (G->n_nodes + (long long)n > 0x7fffffffll) return refuse("the graph would hold more than 2^31 - 1 nodes");
+  std::string why;
+  const long long bad = first_bad_pose(qt, n, why);
+  if (bad >= 0) return refuse("pose " + std::to_string(bad) + " " + why);
+  GRAPHCHECK(hipSetDevice(G->device));
+  const size_t pose_bytes = sizeof(double) * 7 * (size_t)n;
+  GRAPHCHECK(G->stage.resize(pose_bytes + (size_t)n));
+  double* sp = reinterpret_cast<double*>(G->stage.data());
+  uint8_t* sf = G->stage.data() + pose_bytes;
+  long long add_fixed = 0;
+  for (long long k = 0; k < n; ++k) {
+    store_pose(qt + 7 * k, sp + 7 * k);
+    sf[k] = fixed && fixed[k] ? 1 : 0;
+    add_fixed += sf[k];
+  }
+  G->h_fixed.reserve((size_t)(G->n_nodes + n));  // (may throw: before anything changes)
+  const int rc = grow_nodes(G, n);
+  if (rc != SICP_OK) return rc;
+  auto& cur = G->nodes[G->ncur];
+  GRAPHCHECK(hipMemcpyAsync(cur.pose.p + 7 * (size_t)G->n_nodes, sp, pose_bytes, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipMemcpyAsync(cur.fixed.p + (size_t)G->n_nodes, sf, (size_t)n, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipStreamSynchronize(G->stream));
+  if (first_id) *first_id = (int32_t)G->n_nodes;
+  G->h_fixed.insert(G->h_fixed.end(), sf, sf + n);
+  G->n_nodes += n;
+  G->n_fixed += add_fixed;
+  G->incidence_stale = true;  // (the offsets run over the nodes)
+  return SICP_OK;
+}
+
+int graph_add_edges(sicp_graph_ctx* G, int32_t m, const int32_t* i, const int32_t* j, const double* z, const double* omega, int32_t* first_id) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = "sicp_graph_add_edges";
+  auto refuse = [&](const std::string& why) {
+    G->last_error = "sicp_graph_add_edges: " + why + "; the graph is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (m < 1) return refuse("m must be >= 1");
+  if (!i || !j || !z || !omega) return refuse("an array is NULL");
+  if (G->n_edges + (long long)m > 0x7fffffffll) return refuse("the graph would hold more than 2^31 - 1 edges");
+  for (long long e = 0; e < m; ++e) {
+    if (i[e] < 0 || i[e] >= G->n_nodes || j[e] < 0 || j[e] >= G->n_nodes)
+      return refuse("edge " + std::to_string(e) + " (" + std::to_string(i[e]) + ", " + std::to_string(j[e]) + ") has an end outside the " +
+                    std::to_string(G->n_nodes) + " nodes");
+    if (i[e] == j[e]) return refuse("edge " + std::to_string(e) + " joins node " + std::to_string(i[e]) + " to itself");
+  }
+  std::string why;
+  const long long bad = first_bad_pose(z, m, why);
+  if (bad >= 0) return refuse("the measurement of edge " + std::to_string(bad) + " " + why);
+  GRAPHCHECK(hipSetDevice(G->device));
+  const size_t M = (size_t)m, zb = sizeof(double) * 7 * M, ob = sizeof(double) * 36 * M, ib = sizeof(int) * M;
+  GRAPHCHECK(G->stage.resize(ob + zb + 2 * ib));
+  double* so = reinterpret_cast<double*>(G->stage.data());
+  double* sz = so + 36 * M;
+  int* si = reinterpret_cast<int*>(sz + 7 * M);
+  int* sj = si + M;
+  for (size_t e = 0; e < M; ++e) {
+    if (!take_omega(omega + 36 * e, so + 36 * e, why)) return refuse("edge " + std::to_string(e) + " " + why);
+    store_pose(z + 7 * e, sz + 7 * e);
+    si[e] = i[e];
+    sj[e] = j[e];
+  }
+  const int rc = grow_edges(G, m);
+  if (rc != SICP_OK) return rc;
+  auto& cur = G->edges[G->ecur];
+  const size_t at = (size_t)G->n_edges;
+  GRAPHCHECK(hipMemcpyAsync(cur.omega.p + 36 * at, so, ob, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipMemcpyAsync(cur.z.p + 7 * at, sz, zb, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipMemcpyAsync(cur.i.p + at, si, ib, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipMemcpyAsync(cur.j.p + at, sj, ib, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipStreamSynchronize(G->stream));
+  if (first_id) *first_id = (int32_t)G->n_edges;
+  G->n_edges += m;
+  G->incidence_stale = true;
+  return SICP_OK;
+}
+
+int graph_set_poses(sicp_graph_ctx* G, int32_t first, int32_t count, const double* qt) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = "sicp_graph_set_poses";
+  auto refuse = [&](const std::string& why) {
+    G->last_error = "sicp_graph_set_poses: " + why + "; the graph is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  std::string why;
+  if (resolve_range(G, first, count, why) != SICP_OK) return refuse(why);
+  if (!qt) return refuse("qt is NULL");
+  const long long bad = first_bad_pose(qt, count, why);
+  if (bad >= 0) return refuse("pose " + std::to_string(bad) + " " + why);
+  GRAPHCHECK(hipSetDevice(G->device));
+  const size_t bytes = sizeof(double) * 7 * (size_t)count;
+  GRAPHCHECK(G->stage.resize(bytes));
+  double* sp = reinterpret_cast<double*>(G->stage.data());
+  for (long long k = 0; k < count; ++k) store_pose(qt + 7 * k, sp + 7 * k);
+  GRAPHCHECK(hipMemcpyAsync(G->nodes[G->ncur].pose.p + 7 * (size_t)first, sp, bytes, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipStreamSynchronize(G->stream));
+  return SICP_OK;
+}
+
+int graph_get_poses(sicp_graph_ctx* G, int32_t first, int32_t count, double* qt) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = "sicp_graph_get_poses";
+  auto refuse = [&](const std::string& why) {
+    G->last_error = "sicp_graph_get_poses: " + why + "; nothing was written";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  std::string why;
+  if (resolve_range(G, first, count, why) != SICP_OK) return refuse(why);
+  if (!qt) return refuse("qt is NULL");
+  GRAPHCHECK(hipSetDevice(G->device));
+  return download(G, qt, G->nodes[G->ncur].pose.p + 7 * (size_t)first, 7 * (size_t)count);
+}
+
+int graph_set_fixed(sicp_graph_ctx* G, int32_t first, int32_t count, const uint8_t* fixed) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = "sicp_graph_set_fixed";
+  auto refuse = [&](const std::string& why) {
+    G->last_error = "sicp_graph_set_fixed: " + why + "; the graph is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  std::string why;
+  if (resolve_range(G, first, count, why) != SICP_OK) return refuse(why);
+  if (!fixed) return refuse("fixed is NULL");
+  GRAPHCHECK(hipSetDevice(G->device));
+  GRAPHCHECK(G->stage.resize((size_t)count));
+  for (long long k = 0; k < count; ++k) G->stage[(size_t)k] = fixed[k] ? 1 : 0;
+  GRAPHCHECK(hipMemcpyAsync(G->nodes[G->ncur].fixed.p + (size_t)first, G->stage.data(), (size_t)count, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipStreamSynchronize(G->stream));
+  for (long long k = 0; k < count; ++k) {
+    G->n_fixed += (long long)G->stage[(size_t)k] - (long long)G->h_fixed[(size_t)(first + k)];
+    G->h_fixed[(size_t)(first + k)] = G->stage[(size_t)k];
+  }
+  return SICP_OK;
+}
+
+int graph_errors(sicp_graph_ctx* G, double* chi2, double* residual, double* weight, double* cost) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = "sicp_graph_errors";
+  if (!cost) {
+    G->last_error = "sicp_graph_errors: cost is NULL; nothing was written";
+    return SICP_ERR_INVALID_ARGUMENT;
+  }
+  if (G->n_edges == 0) {
+    *cost = 0.0;
+    return SICP_OK;
+  }
+  GRAPHCHECK(hipSetDevice(G->device));
+  sicp::GraphArgs A;
+  int rc = prepare(G, A);
+  if (rc != SICP_OK) return rc;
+  GRAPHCHECK(sicp::launch_graph_linearise(A, A.pose, true, G->stream));
+  GRAPHCHECK(sicp::launch_graph_sum(A, sicp::kGraphFinCost, G->stream));
+  sicp::GraphScalars S;
+  rc = read_scalars(G, S);
+  if (rc != SICP_OK) return rc;
+  const size_t M = (size_t)G->n_edges;
+  if ((rc = download(G, chi2, A.s, M)) != SICP_OK) return rc;
+  if ((rc = download(G, residual, A.r, 6 * M)) != SICP_OK) return rc;
+  if ((rc = download(G, weight, A.w, M)) != SICP_OK) return rc;
+  *cost = S.cost;
+  return SICP_OK;
+}
+
+int graph_linearize(sicp_graph_ctx* G, double* gradient, double* diag_blocks, double* cost) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = "sicp_graph_linearize";
+  if (!cost) {
+    G->last_error = "sicp_graph_linearize: cost is NULL; nothing was written";
+    return SICP_ERR_INVALID_ARGUMENT;
+  }
+  if (G->n_nodes == 0) {
+    *cost = 0.0;
+    return SICP_OK;
+  }
+  GRAPHCHECK(hipSetDevice(G->device));
+  sicp::GraphArgs A;
+  int rc = prepare(G, A);
+  if (rc != SICP_OK) return rc;
+  if ((rc = build_incidence(G, A)) != SICP_OK) return rc;
+  if (G->n_edges == 0) {  // (every list is empty)
+    GRAPHCHECK(hipMemsetAsync(A.off, 0, sizeof(int) * (size_t)(G->n_nodes + 1), G->stream));
+    GRAPHCHECK(hipMemsetAsync(A.S, 0, sizeof(sicp::GraphScalars), G->stream));
+  }
+  if ((rc = linearise_full(G, A)) != SICP_OK) return rc;
+  sicp::GraphScalars S;
+  if ((rc = read_scalars(G, S)) != SICP_OK) return rc;
+  if ((rc = download(G, gradient, A.g, 6 * (size_t)G->n_nodes)) != SICP_OK) return rc;
+  if ((rc = download(G, diag_blocks, A.H, 36 * (size_t)G->n_nodes)) != SICP_OK) return rc;
+  *cost = G->n_edges > 0 ? S.cost : 0.0;
+  return SICP_OK;
+}
+
+int graph_optimize(sicp_graph_ctx* G, sicp_graph_info* info) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = "sicp_graph_optimize";
+  if (!info) {
+    G->last_error = "sicp_graph_optimize: info is NULL; the graph is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  }
+  if (G->n_edges == 0 || G->n_fixed == 0) {
+    G->last_error = std::string("sicp_graph_optimize: the graph has no ") + (G->n_edges == 0 ? "edge" : "fixed node") + "; the graph is unchanged";
+    return SICP_ERR_NOT_READY;
+  }
+  const sicp_graph_params& P = G->params;
+  GRAPHCHECK(hipSetDevice(G->device));
+  hipStream_t st = G->stream;
+  sicp::GraphArgs A;
+  int rc = prepare(G, A);
+  if (rc != SICP_OK) return rc;
+  if ((rc = build_incidence(G, A)) != SICP_OK) return rc;
+  if ((rc = linearise_full(G, A)) != SICP_OK) return rc;
+  sicp::GraphScalars S;
+  if ((rc = read_scalars(G, S)) != SICP_OK) return rc;
+  sicp_graph_info I;
+  std::memset(&I, 0, sizeof I);
+  double cost = S.cost, gmax = S.gmax, radius = P.initial_radius, decrease_factor = 2.0;
+  I.initial_cost = cost;
+  int invalid = 0;
+  const size_t pose_bytes = sizeof(double) * 7 * (size_t)G->n_nodes;
+  double* pose = G->nodes[G->ncur].pose.p;
+  for (;;) {
+    if (!(gmax > P.gradient_tolerance)) { I.termination = SICP_GRAPH_GRADIENT_TOLERANCE; break; }
+    if (I.iterations >= P.max_iterations) { I.termination = SICP_GRAPH_MAX_ITERATIONS; break; }
+    if (radius < P.min_radius) { I.termination = SICP_GRAPH_MIN_RADIUS; break; }
+    I.iterations++;
+    A.radius = radius;
+    GRAPHCHECK(sicp::launch_graph_cg_begin(A, st));
+    int done = 0;
+    for (;;) {  // batches of conjugate-gradient steps, one small record read per batch
+      const int batch = std::min(P.cg_check_every, P.max_cg_iterations - done);
+      for (int k = 0; k < batch; ++k) GRAPHCHECK(sicp::launch_graph_cg_iteration(A, st));
+      if ((rc = read_scalars(G, S)) != SICP_OK) return rc;
+      done = S.cg_iters;
+      if (S.flag != sicp::kGraphRunning || done >= P.max_cg_iterations || batch <= 0) break;
+    }
+    I.cg_iterations += S.cg_iters;
+    bool valid = S.flag != sicp::kGraphBreakdown;
+    double cand_cost = 0, model = 0;
+    if (valid) {
+      GRAPHCHECK(sicp::launch_graph_candidates(A, st));
+      GRAPHCHECK(sicp::launch_graph_linearise(A, A.cand, false, st));
+      GRAPHCHECK(sicp::launch_graph_sum(A, sicp::kGraphFinCandCost, st));
+      if ((rc = read_scalars(G, S)) != SICP_OK) return rc;
+      cand_cost = S.cand_cost;
+      model = -S.gx - 0.5 * S.xHx;
+      valid = std::isfinite(cand_cost) && std::isfinite(model) && model > 0.0;
+      if (valid && std::sqrt(S.xx) <= P.parameter_tolerance * (std::sqrt(S.pose2) + P.parameter_tolerance)) {
+        I.termination = SICP_GRAPH_PARAMETER_TOLERANCE;
+        break;
+      }
+    }
+    if (!valid) {
+      I.invalid_steps++;
+      if (++invalid >= P.max_consecutive_invalid_steps) { I.termination = SICP_GRAPH_INVALID_STEPS; break; }
+      radius /= decrease_factor;
+      decrease_factor *= 2.0;
+      continue;
+    }
+    invalid = 0;
+    const double change = cost - cand_cost, rho = change / model;
+    if (rho > P.min_relative_decrease) {
+      // the candidates become the poses (a copy inside the set that holds them: nothing can refuse between)
+      GRAPHCHECK(hipMemcpyAsync(pose, A.cand, pose_bytes, hipMemcpyDeviceToDevice, st));
+      if ((rc = linearise_full(G, A)) != SICP_OK) return rc;
+      if ((rc = read_scalars(G, S)) != SICP_OK) return rc;
+      I.accepted_steps++;
+      const double before = cost;
+      cost = S.cost;
+      gmax = S.gmax;
+      const double t = 2.0 * rho - 1.0;
+      radius = std::min(P.max_radius, radius / std::max(1.0 / 3.0, 1.0 - t * t * t));
+      decrease_factor = 2.0;
+      if (std::fabs(change) <= P.function_tolerance * before) { I.termination = SICP_GRAPH_FUNCTION_TOLERANCE; break; }
+    } else {
+      I.rejected_steps++;
+      radius /= decrease_factor;
+      decrease_factor *= 2.0;
+    }
+  }
+  I.final_cost = cost;
+  I.gradient_max_norm = gmax;
+  I.radius = radius;
+  *info = I;
+  return SICP_OK;
+}
+
+}  // namespace host
+}  // namespace sicp

@@ -748,6 +748,53 @@ hipError_t launch_place_search(const PlaceSearchArgs& a, hipStream_t st);
 hipError_t launch_place_gather(const unsigned long long* sorted_key, const unsigned long long* hit, int n_q, int count, int top, int4* rows,
                                hipStream_t st);
 
+// ---- the pose graph (graph_kernels.hip; driver: graph.cpp; the edge's algebra: graph_edge.hpp) ----
+// sicp_graph_*: linearise every edge, gather per node through the incidence table, preconditioned conjugate gradients on the
+// damped normal equations, candidate poses.  No float atomics: every sum has one order (ascending (edge, side) per node;
+// per-workgroup partial sums of 256 lanes added by one workgroup in index order).  The scalars of the iteration stay in
+// GraphScalars on the device: the kernels read the previous step's from memory and return at once when `flag` is set.
+constexpr int kGraphRec = 42;        // a (edge, side) contribution: the 6x6 diagonal block, then the gradient
+constexpr int kGraphChol = 27;       // a node's preconditioner: the 21 entries of L (row-major lower), then 1 / L_kk
+constexpr int kGraphLinLanes = 64;   // lanes of a linearise workgroup (one edge each: the register budget of a whole SIMD)
+enum { kGraphRunning = 0, kGraphConverged = 1, kGraphBreakdown = 2 };
+struct GraphScalars {
+  double rz, pq, alpha, beta, rr, bb;   // conjugate gradients: r.z, p.Ap, the two step scalars, |r|^2, |b|^2
+  double cost, cand_cost, gmax;         // 1/2 sum rho at the poses / at the candidates; max |g|
+  double pose2, xx, gx, xHx;            // |poses|^2, |delta|^2, g.delta, delta^T H delta
+  int cg_iters, flag;                   // kGraph*
+};
+struct GraphArgs {
+  int n_nodes, n_edges;
+  const double* pose;          // [n_nodes][7]
+  const uint8_t* fixed;        // [n_nodes]
+  const int *ei, *ej;          // [n_edges]
+  const double *z, *omega;     // [n_edges][7], [n_edges][36]
+  int loss;
+  double cauchy_a;
+  // per edge
+  double *C, *B, *r, *s, *w, *ec;   // [2 n_edges][kGraphRec], [n_edges][36], [n_edges][6], [n_edges] x 3 (ec: 1/2 rho)
+  // incidence: the slots 2 * edge + side sorted by node (low 32 bits of inc), off[n_nodes + 1]
+  unsigned long long* inc;
+  int *deg, *off;
+  // per node
+  double *H, *g, *L;           // [n_nodes][36], [n_nodes][6], [n_nodes][kGraphChol]
+  double *x, *rr, *zz, *p, *q; // [n_nodes][6]: the step, the residual, M^-1 r, the direction, A p
+  double* cand;                // [n_nodes][7]
+  double* part;                // [3][part_stride] partial sums
+  int part_stride;
+  GraphScalars* S;
+  double lo, hi, radius, eta;  // D = clip(diag H, lo, hi) / radius
+};
+enum { kGraphFinStart, kGraphFinPq, kGraphFinRz, kGraphFinCost, kGraphFinCandCost, kGraphFinGmax, kGraphFinCand, kGraphFinModel };
+hipError_t launch_graph_keys(const GraphArgs& a, unsigned long long* keys, hipStream_t st);  // keys[2 n_edges], deg (zeroed before)
+hipError_t launch_graph_linearise(const GraphArgs& a, const double* pose, bool full, hipStream_t st);  // ec (+ r s w C B when full)
+hipError_t launch_graph_gather(const GraphArgs& a, hipStream_t st);                          // H, g
+hipError_t launch_graph_sum(const GraphArgs& a, int fin, hipStream_t st);                    // ec -> S->cost / cand_cost; g -> S->gmax
+hipError_t launch_graph_cg_begin(const GraphArgs& a, hipStream_t st);                        // L, x = 0, r = -g, z, p, S->rz bb rr
+hipError_t launch_graph_cg_iteration(const GraphArgs& a, hipStream_t st);                    // one step of x, r, z, p
+hipError_t launch_graph_candidates(const GraphArgs& a, hipStream_t st);                      // cand, S->pose2 xx gx xHx
+inline int graph_blocks(long long items) { return (int)((items + 255) / 256); }
+
 // ---- the sorts and scans of the feature calls (prim_kernels.hip: the only rocPRIM instantiations besides build_tree.hip) ----
 // rocPRIM's convention: temp == nullptr asks for the bytes.  Ascending, stable; keys: bits [begin_bit, end_bit).
 hipError_t prim_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long n, int begin_bit,

@@ -983,6 +983,66 @@ int sicp_place_tables(sicp_place db, double* cos_half, double* sin_half, double*
   return abi_guard(db, [&]() -> int { return place_tables(db, cos_half, sin_half, edge2); });
 }
 
+// ---- the pose graph (graph.cpp) ------------------------------------------------------------------------------------------
+int sicp_default_graph_params(sicp_graph_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    graph_default_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_graph_create(int device_id, const sicp_graph_params* p, sicp_graph* out) {
+  return abi_guard([&]() -> int { return graph_create(device_id, p, out); });
+}
+
+int sicp_graph_destroy(sicp_graph g) {
+  return abi_guard([&]() -> int { return graph_destroy(g); });
+}
+
+int sicp_graph_clear(sicp_graph g) {
+  return abi_guard(g, [&]() -> int { return graph_clear(g); });
+}
+
+int sicp_graph_size(sicp_graph g, int64_t* n_nodes, int64_t* n_edges) {
+  return abi_guard(g, [&]() -> int { return graph_size(g, n_nodes, n_edges); });
+}
+
+const char* sicp_graph_last_error(sicp_graph g) { return g ? g->last_error.c_str() : ""; }
+
+int sicp_graph_add_nodes(sicp_graph g, int32_t n, const double* qt, const uint8_t* fixed, int32_t* first_id) {
+  return abi_guard(g, [&]() -> int { return graph_add_nodes(g, n, qt, fixed, first_id); });
+}
+
+int sicp_graph_add_edges(sicp_graph g, int32_t m, const int32_t* i, const int32_t* j, const double* z, const double* omega,
+                         int32_t* first_id) {
+  return abi_guard(g, [&]() -> int { return graph_add_edges(g, m, i, j, z, omega, first_id); });
+}
+
+int sicp_graph_set_poses(sicp_graph g, int32_t first, int32_t count, const double* qt) {
+  return abi_guard(g, [&]() -> int { return graph_set_poses(g, first, count, qt); });
+}
+
+int sicp_graph_get_poses(sicp_graph g, int32_t first, int32_t count, double* qt) {
+  return abi_guard(g, [&]() -> int { return graph_get_poses(g, first, count, qt); });
+}
+
+int sicp_graph_set_fixed(sicp_graph g, int32_t first, int32_t count, const uint8_t* fixed) {
+  return abi_guard(g, [&]() -> int { return graph_set_fixed(g, first, count, fixed); });
+}
+
+int sicp_graph_errors(sicp_graph g, double* chi2, double* residual, double* weight, double* cost) {
+  return abi_guard(g, [&]() -> int { return graph_errors(g, chi2, residual, weight, cost); });
+}
+
+int sicp_graph_linearize(sicp_graph g, double* gradient, double* diag_blocks, double* cost) {
+  return abi_guard(g, [&]() -> int { return graph_linearize(g, gradient, diag_blocks, cost); });
+}
+
+int sicp_graph_optimize(sicp_graph g, sicp_graph_info* info) {
+  return abi_guard(g, [&]() -> int { return graph_optimize(g, info); });
+}
+
 int sicp_solve(sicp_handle h, const double init_qt[7], double out_qt[7], int32_t* lm_iters, int32_t* evals,
                double* final_cost) {
   return abi_guard(h, [&]() -> int {
