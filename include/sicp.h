@@ -975,6 +975,62 @@ int sicp_graph_errors(sicp_graph g, double* chi2, double* residual, double* weig
 int sicp_graph_linearize(sicp_graph g, double* gradient, double* diag_blocks, double* cost);
 int sicp_graph_optimize(sicp_graph g, sicp_graph_info* info);
 
+/* ---- pose-graph covariances: blocks of H^-1 for gating a loop closure before it enters the graph -------- */
+/* What the graph itself knows about a node, or about the relative pose of two nodes, at the current poses: the question to ask
+ * before sicp_graph_add_edges (an edge cannot be taken out again), and the drift that sets a search radius.
+ *
+ *  1. H is the undamped Gauss-Newton matrix at the current poses: exactly what sicp_graph_linearize reports, robust weights
+ *     included; a fixed node's block is the identity and its couplings are dropped.  The call linearises and gathers first.  It
+ *     leaves poses, edges and parameters byte for byte as they were, and a later sicp_graph_optimize returns the bytes it
+ *     returns on a twin graph that never made the call.
+ *  2. sicp_graph_marginals: cov[q] is the 6x6 block (H^-1)[k, k], k = nodes[q], row-major, in the tangent space of
+ *     T_k <- T_k exp(delta), delta = [upsilon; omega].  A fixed node answers exact zeros with status OK.
+ *  3. sicp_graph_relative_covariances: cov[q] is the covariance of z = T_a^-1 T_b under z exp(delta) -- the convention of an
+ *     edge's Omega, so inv(cov[q] + Sigma_measured) gates the residual log(z_graph^-1 z_measured) with no conversion.  To first
+ *     order delta_z = delta_b - Ad(T_b^-1 T_a) delta_a: J has the block -Ad(T_b^-1 T_a) at a and I at b, cov = J H^-1 J^T, found
+ *     from the six columns of H X = J^T as J X.  A fixed end contributes no block; both ends fixed: zeros, status OK.
+ *  4. Every block is written as (S + S^T) / 2.
+ *  5. The call returns SICP_OK when it ran; status[q] says what became of query q:
+ *       SICP_GRAPH_COV_OK             the six columns met |r| <= tolerance |b|
+ *       SICP_GRAPH_COV_NOT_CONVERGED  max_cg_iterations was reached; the block of the last iterate is returned
+ *       SICP_GRAPH_COV_UNANCHORED     the query names a free node without edges, or one whose connected component holds no fixed
+ *                                     node: NaN.  Found on the host before any solve (a singular system is never iterated)
+ *       SICP_GRAPH_COV_BREAKDOWN      a non-finite value or p^T H p <= 0 in the query's columns, or a diagonal block of H that is
+ *                                     not positive definite: NaN
+ *     Inside the solve a free node without edges has an identity block, so it cannot disturb another query's columns.
+ *     The solve: conjugate gradients with the block-Jacobi preconditioner on max_columns right-hand sides in lock step (the
+ *     matrix is read once per iteration for all of them); more queries run as further passes.  max_cg_iterations = 0 means
+ *     20 x the node count, at least 200 (at 1e-10 a ring needs 5-10 x its node count, a short ill-conditioned chain 13 x).  The host reads one record per check_every
+ *     iterations.  max_columns = 0 means 24; either is lowered to what the queries need and, by halving down to 6, to what the
+ *     arena's limit leaves room for.
+ *  6. Refused with SICP_ERR_INVALID_ARGUMENT, the reason in sicp_graph_last_error, nothing written: NULL nodes, a, b or cov;
+ *     n < 1; an index outside the nodes; a == b; parameters outside their ranges (a max_columns that is not a multiple of 6
+ *     among them).  SICP_ERR_OUT_OF_MEMORY: not even a six-column pass fits the arena's limit; nothing written, the graph
+ *     untouched.
+ *  7. A query's 36 doubles and its status are the same bytes asked alone, with any other queries, in any order and at any
+ *     max_columns, and two graphs driven alike return the same bytes: every column has its own scalars and is frozen when it is
+ *     done, and no sum's order depends on the company.  info describes the call as a whole and does depend on it. */
+enum { SICP_GRAPH_COV_OK = 0, SICP_GRAPH_COV_NOT_CONVERGED = 1, SICP_GRAPH_COV_UNANCHORED = 2, SICP_GRAPH_COV_BREAKDOWN = 3 };
+typedef struct sicp_graph_cov_params {
+  double tolerance;           /* 1e-10; in (0, 1): a column is done when |r| <= tolerance |b| */
+  int32_t max_cg_iterations;  /* 0 = automatic (rule 5); otherwise >= 1 */
+  int32_t check_every;        /* 32; >= 1: iterations enqueued between two reads of the device record */
+  int32_t max_columns;        /* 0 = automatic (rule 5); otherwise a multiple of 6: columns solved in one pass */
+  int32_t reserved_;
+} sicp_graph_cov_params;
+typedef struct sicp_graph_cov_info {
+  int32_t passes;
+  int32_t cg_iterations;      /* summed over the passes (a pass counts its longest column) */
+  int32_t n_ok, n_failed;     /* queries with status OK / any other status */
+  double worst_relative_residual; /* max |r| / |b| over the columns that were solved */
+} sicp_graph_cov_info;
+int sicp_default_graph_cov_params(sicp_graph_cov_params* p);
+int sicp_graph_marginals(sicp_graph g, const sicp_graph_cov_params* p /* NULL = defaults */, int32_t n, const int32_t* nodes,
+                         double* cov /* 36 n, row-major */, int32_t* status /* n, nullable */, sicp_graph_cov_info* info /* nullable */);
+int sicp_graph_relative_covariances(sicp_graph g, const sicp_graph_cov_params* p /* NULL = defaults */, int32_t n, const int32_t* a,
+                                    const int32_t* b, double* cov /* 36 n */, int32_t* status /* nullable */,
+                                    sicp_graph_cov_info* info /* nullable */);
+
 /* test / bench hook: the keypoints of cloud `which` with their normals, FPFH features and feature-radius
  * neighbour lists (CSR: nbr_offsets[n + 1], nbr_idx sorted by (d^2, index)).  Counts are always written; an output
  * array is written when it is non-NULL and its capacity (points / neighbour entries) suffices, otherwise the call

@@ -421,6 +421,35 @@ class SicpGraphInfo(C.Structure):
         return d
 
 
+GRAPH_COV_OK, GRAPH_COV_NOT_CONVERGED, GRAPH_COV_UNANCHORED, GRAPH_COV_BREAKDOWN = 0, 1, 2, 3
+GRAPH_COV_STATUSES = ("ok", "not_converged", "unanchored", "breakdown")
+
+
+class SicpGraphCovParams(C.Structure):
+    """sicp_graph_cov_params (include/sicp.h)"""
+    _fields_ = [
+        ("tolerance", C.c_double),
+        ("max_cg_iterations", C.c_int32),
+        ("check_every", C.c_int32),
+        ("max_columns", C.c_int32),
+        ("reserved_", C.c_int32),
+    ]
+
+
+class SicpGraphCovInfo(C.Structure):
+    """sicp_graph_cov_info (include/sicp.h)"""
+    _fields_ = [
+        ("passes", C.c_int32),
+        ("cg_iterations", C.c_int32),
+        ("n_ok", C.c_int32),
+        ("n_failed", C.c_int32),
+        ("worst_relative_residual", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class SicpError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -583,6 +612,10 @@ def lib():
             "sicp_graph_errors": [C.c_void_p, _dp, _dp, _dp, _dp],
             "sicp_graph_linearize": [C.c_void_p, _dp, _dp, _dp],
             "sicp_graph_optimize": [C.c_void_p, C.POINTER(SicpGraphInfo)],
+            "sicp_default_graph_cov_params": [C.POINTER(SicpGraphCovParams)],
+            "sicp_graph_marginals": [C.c_void_p, C.POINTER(SicpGraphCovParams), C.c_int32, _ip, _dp, _ip, C.POINTER(SicpGraphCovInfo)],
+            "sicp_graph_relative_covariances": [C.c_void_p, C.POINTER(SicpGraphCovParams), C.c_int32, _ip, _ip, _dp, _ip,
+                                                C.POINTER(SicpGraphCovInfo)],
         }.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
@@ -755,6 +788,33 @@ def default_graph_params(**overrides) -> SicpGraphParams:
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def default_graph_cov_params(**overrides) -> SicpGraphCovParams:
+    """sicp_default_graph_cov_params (tolerance 1e-10, automatic iteration limit and columns, one read-back per 32 iterations),
+    with any field overridden by keyword.  What needs no device is refused here: a tolerance outside (0, 1), a negative
+    max_cg_iterations, check_every < 1, a max_columns that is negative or no multiple of 6."""
+    p = SicpGraphCovParams()
+    st = lib().sicp_default_graph_cov_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_graph_cov_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    _check_graph_cov_params(p)
+    return p
+
+
+def _check_graph_cov_params(p):
+    if not (0.0 < p.tolerance < 1.0):
+        raise ValueError("tolerance must lie in (0, 1)")
+    if p.max_cg_iterations < 0:
+        raise ValueError("max_cg_iterations must be 0 (automatic) or >= 1")
+    if p.check_every < 1:
+        raise ValueError("check_every must be >= 1")
+    if p.max_columns < 0 or p.max_columns % 6:
+        raise ValueError("max_columns must be 0 (automatic) or a multiple of 6")
 
 
 def place_init_qt(yaw: float):
@@ -1585,6 +1645,35 @@ class PoseGraph:
         info = SicpGraphInfo()
         self._check(lib().sicp_graph_optimize(self._g, C.byref(info)), "sicp_graph_optimize")
         return info.as_dict()
+
+    def _covariances(self, a, b, params):
+        if params is not None:
+            _check_graph_cov_params(params)
+        bb = np.ascontiguousarray(np.atleast_1d(b), dtype=np.int32)
+        n = bb.shape[0]
+        cov, status, info = np.empty((n, 6, 6)), np.empty(n, dtype=np.int32), SicpGraphCovInfo()
+        pp = None if params is None else C.byref(params)
+        if a is None:
+            self._check(lib().sicp_graph_marginals(self._g, pp, n, _ptr(bb, _ip), _ptr(cov, _dp), _ptr(status, _ip), C.byref(info)),
+                        "sicp_graph_marginals")
+        else:
+            aa = np.ascontiguousarray(np.atleast_1d(a), dtype=np.int32)
+            if aa.shape != bb.shape:
+                raise ValueError("a[n] and b[n] must agree on n")
+            self._check(lib().sicp_graph_relative_covariances(self._g, pp, n, _ptr(aa, _ip), _ptr(bb, _ip), _ptr(cov, _dp),
+                                                              _ptr(status, _ip), C.byref(info)), "sicp_graph_relative_covariances")
+        return cov, status, info.as_dict()
+
+    def marginals(self, nodes, params: SicpGraphCovParams | None = None):
+        """sicp_graph_marginals: (cov [n, 6, 6], status [n] of GRAPH_COV_*, info dict).  cov[q] is the block of H^-1 at nodes[q],
+        in the tangent space of T <- T exp(delta); NaN where the status is GRAPH_COV_UNANCHORED or GRAPH_COV_BREAKDOWN."""
+        return self._covariances(None, nodes, params)
+
+    def relative_covariances(self, a, b, params: SicpGraphCovParams | None = None):
+        """sicp_graph_relative_covariances: (cov [n, 6, 6], status [n], info dict).  cov[q] is the covariance of T_a^-1 T_b under
+        z exp(delta), the convention of an edge's omega: inv(cov[q] + pose_covariance(...)["covariance"]) gates
+        log(z_graph^-1 z_measured) before add_edges."""
+        return self._covariances(a, b, params)
 
     def size(self):
         """(nodes, edges)"""

@@ -10,7 +10,7 @@
 //   evaluate.cpp  sicp_evaluate: overlap, inlier RMSE and label agreement at a pose
 //   merge.cpp     sicp_merge_clouds: posed clouds into one voxel-grid cloud
 //   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, prune, extract)
-//   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise)
+//   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
 //   sicp_api.cpp  the remaining C-ABI entry points
 // Every extern "C" entry runs inside abi_guard (abi_barrier.hpp): no exception crosses the boundary.
 #ifndef SICP_ENGINE_HPP_
@@ -641,6 +641,9 @@ struct sicp_graph_ctx {
   long long n_nodes = 0, n_edges = 0, cap_nodes = 0, cap_edges = 0;
   long long n_fixed = 0;
   std::vector<uint8_t> h_fixed;       // the host's copy of the flags (optimize refuses a graph without a fixed node)
+  std::vector<int32_t> h_ei, h_ej;    // the host's copy of the edge ends (the covariance calls' connectivity)
+  std::vector<uint8_t> anchored;      // per node: its connected component holds a fixed node (union-find over h_ei, h_ej)
+  bool anchored_stale = true;         // nodes, edges or flags have changed since
   bool incidence_stale = true;        // edges have been added since the incidence table was built
   DevBuf<double> C, B, r, s, w, ec, H, g, L, x, rr, zz, p, q, cand, part;
   DevBuf<unsigned long long> keys, inc;
@@ -649,6 +652,14 @@ struct sicp_graph_ctx {
   DevBuf<sicp::GraphScalars> scalars;
   HostBuf<unsigned char> stage;       // pinned: uploads and read-backs on their way
   HostBuf<sicp::GraphScalars> rec;    // pinned: the scalars' read-back
+  // the covariance calls' own work buffers (sicp_graph_marginals / _relative_covariances), sized on first use and kept; of the
+  // optimiser's they reuse what every sicp_graph_optimize rewrites before it reads (the linearisation, L)
+  DevBuf<double> cov_x, cov_r, cov_z, cov_p, cov_q, cov_part, cov_J, cov_out;
+  DevBuf<int> cov_query, cov_bad;
+  DevBuf<sicp::GraphCovColumn> cov_cols;
+  HostBuf<sicp::GraphCovColumn> cov_rec;  // pinned: the columns' read-back
+  HostBuf<int> cov_hquery;                // pinned: a pass's query nodes on their way up
+  HostBuf<double> cov_hout;               // pinned: a pass's blocks on their way down
   const char* call = "sicp_graph";    // the entry point that is running: the head of a HIP failure's text
   std::string last_error;
 };
@@ -1019,6 +1030,10 @@ int graph_set_fixed(sicp_graph_ctx* g, int32_t first, int32_t count, const uint8
 int graph_errors(sicp_graph_ctx* g, double* chi2, double* residual, double* weight, double* cost);
 int graph_linearize(sicp_graph_ctx* g, double* gradient, double* diag_blocks, double* cost);
 int graph_optimize(sicp_graph_ctx* g, sicp_graph_info* info);
+void graph_default_cov_params(sicp_graph_cov_params* p);
+// a == NULL with marginals = true: sicp_graph_marginals of the nodes b
+int graph_covariances(sicp_graph_ctx* g, bool marginals, const sicp_graph_cov_params* p, int32_t n, const int32_t* a, const int32_t* b,
+                      double* cov, int32_t* status, sicp_graph_cov_info* info);
 
 }  // namespace host
 }  // namespace sicp

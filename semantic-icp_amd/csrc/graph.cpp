@@ -2,7 +2,8 @@
 // after another in one of two sets of arena buffers; growth doubles into the spare set and swaps last, and every check of a
 // call comes before its first write, so a refused call leaves the graph as it was.  The outer Levenberg-Marquardt loop runs
 // here with one read-back per iteration (and one per batch of conjugate-gradient steps); the kernels: graph_kernels.hip, the
-// sort and the scan of prim_kernels.hip.
+// sort and the scan of prim_kernels.hip.  At the end: sicp_graph_marginals / sicp_graph_relative_covariances, blocks of H^-1 by
+// lock-step conjugate gradients on many right-hand sides (graph_cov_kernels.hip).
 #include "engine.hpp"
 
 namespace sicp {
@@ -262,7 +263,10 @@ int graph_clear(sicp_graph_ctx* G) {
   if (!G) return SICP_ERR_INVALID_ARGUMENT;
   G->n_nodes = G->n_edges = G->n_fixed = 0;
   G->h_fixed.clear();
+  G->h_ei.clear();
+  G->h_ej.clear();
   G->incidence_stale = true;
+  G->anchored_stale = true;
   G->last_error.clear();
   return SICP_OK;
 }
@@ -314,6 +318,7 @@ int graph_add_nodes(sicp_graph_ctx* G, int32_t n, const double* qt, const uint8_
   G->n_nodes += n;
   G->n_fixed += add_fixed;
   G->incidence_stale = true;  // (the offsets run over the nodes)
+  G->anchored_stale = true;
   return SICP_OK;
 }
 
@@ -349,6 +354,8 @@ int graph_add_edges(sicp_graph_ctx* G, int32_t m, const int32_t* i, const int32_
     si[e] = i[e];
     sj[e] = j[e];
   }
+  G->h_ei.reserve((size_t)(G->n_edges + m));  // (may throw: before anything changes)
+  G->h_ej.reserve((size_t)(G->n_edges + m));
   const int rc = grow_edges(G, m);
   if (rc != SICP_OK) return rc;
   auto& cur = G->edges[G->ecur];
@@ -359,8 +366,11 @@ int graph_add_edges(sicp_graph_ctx* G, int32_t m, const int32_t* i, const int32_
   GRAPHCHECK(hipMemcpyAsync(cur.j.p + at, sj, ib, hipMemcpyHostToDevice, G->stream));
   GRAPHCHECK(hipStreamSynchronize(G->stream));
   if (first_id) *first_id = (int32_t)G->n_edges;
+  G->h_ei.insert(G->h_ei.end(), si, si + m);
+  G->h_ej.insert(G->h_ej.end(), sj, sj + m);
   G->n_edges += m;
   G->incidence_stale = true;
+  G->anchored_stale = true;
   return SICP_OK;
 }
 
@@ -419,6 +429,7 @@ int graph_set_fixed(sicp_graph_ctx* G, int32_t first, int32_t count, const uint8
     G->n_fixed += (long long)G->stage[(size_t)k] - (long long)G->h_fixed[(size_t)(first + k)];
     G->h_fixed[(size_t)(first + k)] = G->stage[(size_t)k];
   }
+  G->anchored_stale = true;
   return SICP_OK;
 }
 
@@ -570,6 +581,227 @@ int graph_optimize(sicp_graph_ctx* G, sicp_graph_info* info) {
   I.gradient_max_norm = gmax;
   I.radius = radius;
   *info = I;
+  return SICP_OK;
+}
+
+// ---- blocks of H^-1: sicp_graph_marginals / sicp_graph_relative_covariances ------------------------------------------------------
+namespace {
+
+constexpr int kCovAutoColumns = 24;    // the widest SpMM instantiation: where the time per column stops falling
+constexpr int kCovMaxColumns = 1536;   // what one pass takes at the most, whatever max_columns asks for (grid.y of the launches)
+
+bool cov_params_ok(const sicp_graph_cov_params& p) {
+  if (!std::isfinite(p.tolerance) || !(p.tolerance > 0.0) || !(p.tolerance < 1.0)) return false;
+  if (p.max_cg_iterations < 0 || p.check_every < 1) return false;
+  return p.max_columns >= 0 && p.max_columns % 6 == 0;
+}
+
+// per node: does its connected component hold a fixed node?  Union-find over the edge ends, redone when the graph has changed.
+void refresh_anchored(sicp_graph_ctx* G) {
+  if (!G->anchored_stale) return;
+  const size_t N = (size_t)G->n_nodes;
+  std::vector<int32_t> parent(N);
+  for (size_t k = 0; k < N; ++k) parent[k] = (int32_t)k;
+  auto find = [&](int32_t v) {
+    while (parent[(size_t)v] != v) {
+      parent[(size_t)v] = parent[(size_t)parent[(size_t)v]];
+      v = parent[(size_t)v];
+    }
+    return v;
+  };
+  for (size_t e = 0; e < (size_t)G->n_edges; ++e) {
+    const int32_t a = find(G->h_ei[e]), b = find(G->h_ej[e]);
+    if (a != b) parent[(size_t)std::max(a, b)] = std::min(a, b);
+  }
+  std::vector<uint8_t> root_fixed(N, 0);
+  for (size_t k = 0; k < N; ++k)
+    if (G->h_fixed[k]) root_fixed[(size_t)find((int32_t)k)] = 1;
+  G->anchored.assign(N, 0);
+  for (size_t k = 0; k < N; ++k) G->anchored[k] = root_fixed[(size_t)find((int32_t)k)];
+  G->anchored_stale = false;
+}
+
+// what the arena takes for `count` elements of T (DevBuf::reserve's request)
+template <class T>
+size_t arena_bytes(size_t count) { return DevArena::size_class((count + count / 8 + 64) * sizeof(T)); }
+
+size_t cov_part_stride(long long n_nodes) {
+  return (size_t)std::max(sicp::graph_cov_node_blocks(n_nodes), sicp::graph_blocks(6 * n_nodes));
+}
+
+// the work buffers of a pass of `cols` columns that are not there yet, in bytes of the arena
+size_t cov_bytes_missing(const sicp_graph_ctx* G, int cols) {
+  const size_t N = (size_t)G->n_nodes, vec = 6 * N * (size_t)cols, part = 2 * (size_t)cols * cov_part_stride(G->n_nodes);
+  size_t need = 0;
+  const size_t C = (size_t)cols;
+  for (const DevBuf<double>* b : {&G->cov_x, &G->cov_r, &G->cov_z, &G->cov_p, &G->cov_q})
+    if (b->cap < vec) need += arena_bytes<double>(vec);
+  if (G->cov_part.cap < part) need += arena_bytes<double>(part);
+  if (G->cov_J.cap < 6 * C) need += arena_bytes<double>(6 * C);
+  if (G->cov_out.cap < 6 * C) need += arena_bytes<double>(6 * C);
+  if (G->cov_query.cap < C) need += arena_bytes<int>(C);
+  if (G->cov_bad.cap < 1) need += arena_bytes<int>(1);
+  if (G->cov_cols.cap < C) need += arena_bytes<sicp::GraphCovColumn>(C);
+  return need;
+}
+
+hipError_t cov_reserve(sicp_graph_ctx* G, int cols) {
+  const size_t N = (size_t)G->n_nodes, vec = 6 * N * (size_t)cols, C = (size_t)cols;
+  hipError_t e = hipSuccess;
+  for (DevBuf<double>* b : {&G->cov_x, &G->cov_r, &G->cov_z, &G->cov_p, &G->cov_q})
+    if ((e = b->reserve(vec)) != hipSuccess) return e;
+  if ((e = G->cov_part.reserve(2 * C * cov_part_stride(G->n_nodes))) != hipSuccess) return e;
+  if ((e = G->cov_J.reserve(6 * C)) != hipSuccess) return e;
+  if ((e = G->cov_out.reserve(6 * C)) != hipSuccess) return e;
+  if ((e = G->cov_query.reserve(C)) != hipSuccess) return e;  // (2 per query)
+  if ((e = G->cov_bad.reserve(1)) != hipSuccess) return e;
+  if ((e = G->cov_cols.reserve(C)) != hipSuccess) return e;
+  if ((e = G->cov_rec.resize(C)) != hipSuccess) return e;
+  if ((e = G->cov_hquery.resize(C)) != hipSuccess) return e;
+  return G->cov_hout.resize(6 * C);
+}
+
+}  // namespace
+
+void graph_default_cov_params(sicp_graph_cov_params* p) {
+  std::memset(p, 0, sizeof *p);
+  p->tolerance = 1e-10;
+  p->max_cg_iterations = 0;
+  p->check_every = 32;
+  p->max_columns = 0;
+}
+
+int graph_covariances(sicp_graph_ctx* G, bool marginals, const sicp_graph_cov_params* params, int32_t n, const int32_t* a, const int32_t* b,
+                      double* cov, int32_t* status, sicp_graph_cov_info* info) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = marginals ? "sicp_graph_marginals" : "sicp_graph_relative_covariances";
+  auto refuse = [&](const std::string& why) {
+    G->last_error = std::string(G->call) + ": " + why + "; nothing was written";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  sicp_graph_cov_params P;
+  if (params) P = *params; else graph_default_cov_params(&P);
+  if (!cov_params_ok(P))
+    return refuse("the parameters are outside their ranges (tolerance in (0, 1), max_cg_iterations >= 0, check_every >= 1, max_columns 0 "
+                  "or a multiple of 6)");
+  if (n < 1) return refuse("n must be >= 1");
+  if (!b || (!marginals && !a) || !cov) return refuse("an array is NULL");
+  for (long long q = 0; q < n; ++q) {
+    if (b[q] < 0 || b[q] >= G->n_nodes || (!marginals && (a[q] < 0 || a[q] >= G->n_nodes)))
+      return refuse("query " + std::to_string(q) + " names a node outside the " + std::to_string(G->n_nodes) + " nodes");
+    if (!marginals && a[q] == b[q]) return refuse("query " + std::to_string(q) + " asks for node " + std::to_string(a[q]) + " relative to itself");
+  }
+  // Every answer is formed in host vectors and copied out at the end: a call that fails on the way has written nothing.
+  refresh_anchored(G);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<double> C36(36 * (size_t)n, 0.0);
+  std::vector<int32_t> stat((size_t)n, SICP_GRAPH_COV_OK);
+  std::vector<int32_t> solve;  // the queries that need columns
+  for (int32_t q = 0; q < n; ++q) {
+    const bool afree = !marginals && !G->h_fixed[(size_t)a[q]], bfree = !G->h_fixed[(size_t)b[q]];
+    if ((afree && !G->anchored[(size_t)a[q]]) || (bfree && !G->anchored[(size_t)b[q]])) {
+      stat[(size_t)q] = SICP_GRAPH_COV_UNANCHORED;
+      std::fill(C36.begin() + 36 * (size_t)q, C36.begin() + 36 * (size_t)(q + 1), nan);
+    } else if (afree || bfree) {
+      solve.push_back(q);
+    }  // (otherwise: every end is fixed, the zeros stand)
+  }
+  sicp_graph_cov_info I;
+  std::memset(&I, 0, sizeof I);
+  if (!solve.empty()) {
+    GRAPHCHECK(hipSetDevice(G->device));
+    hipStream_t st = G->stream;
+    sicp::GraphArgs A;
+    int rc = prepare(G, A);
+    if (rc != SICP_OK) return rc;
+    if ((rc = build_incidence(G, A)) != SICP_OK) return rc;
+    if ((rc = linearise_full(G, A)) != SICP_OK) return rc;  // (a query to solve has an anchored free node: there are edges)
+    // the columns of a pass: what is asked for, no more than the queries need, and what the arena's limit leaves room for
+    int cols = (int)std::min<long long>(std::min(P.max_columns > 0 ? P.max_columns : kCovAutoColumns, kCovMaxColumns), 6ll * (long long)solve.size());
+    for (;;) {
+      auto& D = dev_arena().dev[G->device % kArenaDevices];
+      size_t limit, reserved;
+      {
+        std::lock_guard<std::mutex> lock(dev_arena().m);
+        limit = D.limit; reserved = D.reserved;
+      }
+      const bool fits = limit == 0 || reserved + cov_bytes_missing(G, cols) <= limit;
+      if (fits || cols == 6) {  // (the estimate counts no free room inside the slabs: six columns are tried in any case)
+        const hipError_t e = cov_reserve(G, cols);
+        if (e == hipSuccess) break;
+        (void)hipGetLastError();
+        if (e != hipErrorOutOfMemory || cols == 6) {
+          G->last_error = std::string(G->call) + ": the work buffers of a pass of " + std::to_string(cols) + " columns: " + hipGetErrorString(e) +
+                          "; nothing was written and the graph is unchanged";
+          return e == hipErrorOutOfMemory ? SICP_ERR_OUT_OF_MEMORY : SICP_ERR_HIP;
+        }
+      }
+      cols = std::max(6, cols / 12 * 6);  // half, in whole queries
+    }
+    sicp::GraphCovArgs V;
+    std::memset(&V, 0, sizeof V);
+    V.n_nodes = (int)G->n_nodes;
+    V.pose = A.pose; V.fixed = A.fixed; V.ei = A.ei; V.ej = A.ej; V.B = A.B; V.inc = A.inc; V.off = A.off; V.H = A.H; V.L = A.L;
+    V.J = G->cov_J.p; V.x = G->cov_x.p; V.r = G->cov_r.p; V.z = G->cov_z.p; V.p = G->cov_p.p; V.q = G->cov_q.p;
+    V.part = G->cov_part.p; V.part_stride = (int)cov_part_stride(G->n_nodes);
+    V.S = G->cov_cols.p; V.bad = G->cov_bad.p; V.out = G->cov_out.p;
+    V.tolerance = P.tolerance;
+    V.max_iters = P.max_cg_iterations > 0 ? P.max_cg_iterations
+                                          : (int)std::min<long long>(std::max<long long>(20 * G->n_nodes, 200), 0x7fffffffll);
+    GRAPHCHECK(hipMemsetAsync(V.bad, 0, sizeof(int), st));
+    V.cols = 6;
+    GRAPHCHECK(sicp::launch_graph_cov_factor(V, st));
+    const size_t per_pass = (size_t)cols / 6;
+    for (size_t first = 0; first < solve.size(); first += per_pass) {
+      const size_t slots = std::min(per_pass, solve.size() - first);
+      V.cols = 6 * (int)slots;
+      int* hq = G->cov_hquery.data();
+      for (size_t k = 0; k < slots; ++k) {
+        const int32_t q = solve[first + k];
+        hq[k] = marginals ? -1 : a[q];
+        hq[slots + k] = b[q];
+      }
+      GRAPHCHECK(hipMemcpyAsync(G->cov_query.p, hq, sizeof(int) * 2 * slots, hipMemcpyHostToDevice, st));
+      V.qa = G->cov_query.p; V.qb = G->cov_query.p + slots;
+      GRAPHCHECK(sicp::launch_graph_cov_begin(V, st));
+      const sicp::GraphCovColumn* S = G->cov_rec.data();
+      long long enqueued = 0;
+      for (;;) {  // batches of iterations, one read of the columns' records per batch; the device itself stops every column
+        GRAPHCHECK(hipMemcpyAsync(G->cov_rec.data(), V.S, sizeof(sicp::GraphCovColumn) * (size_t)V.cols, hipMemcpyDeviceToHost, st));
+        GRAPHCHECK(hipStreamSynchronize(st));
+        bool running = false;
+        for (int c = 0; c < V.cols; ++c) running = running || S[c].flag == sicp::kGraphCovRunning;
+        if (!running || enqueued >= (long long)V.max_iters) break;
+        const int batch = (int)std::min<long long>(P.check_every, (long long)V.max_iters - enqueued);
+        for (int k = 0; k < batch; ++k) GRAPHCHECK(sicp::launch_graph_cov_iteration(V, st));
+        enqueued += batch;
+      }
+      GRAPHCHECK(sicp::launch_graph_cov_extract(V, st));
+      GRAPHCHECK(hipMemcpyAsync(G->cov_hout.data(), V.out, sizeof(double) * 36 * slots, hipMemcpyDeviceToHost, st));
+      GRAPHCHECK(hipStreamSynchronize(st));
+      int pass_iters = 0;
+      for (size_t k = 0; k < slots; ++k) {
+        const int32_t q = solve[first + k];
+        int32_t s = SICP_GRAPH_COV_OK;
+        for (int c = 6 * (int)k; c < 6 * (int)k + 6; ++c) {
+          pass_iters = std::max(pass_iters, S[c].iters);
+          if (S[c].flag == sicp::kGraphCovBreakdown) s = SICP_GRAPH_COV_BREAKDOWN;
+          else if (S[c].flag != sicp::kGraphCovConverged && s == SICP_GRAPH_COV_OK) s = SICP_GRAPH_COV_NOT_CONVERGED;
+          if (S[c].flag != sicp::kGraphCovBreakdown && S[c].bb > 0.0)
+            I.worst_relative_residual = std::max(I.worst_relative_residual, std::sqrt(S[c].rr) / std::sqrt(S[c].bb));
+        }
+        stat[(size_t)q] = s;
+        const double* got = G->cov_hout.data() + 36 * k;
+        for (int d = 0; d < 36; ++d) C36[36 * (size_t)q + d] = s == SICP_GRAPH_COV_BREAKDOWN ? nan : got[d];
+      }
+      I.passes += 1;
+      I.cg_iterations += pass_iters;
+    }
+  }
+  for (int32_t q = 0; q < n; ++q) (stat[(size_t)q] == SICP_GRAPH_COV_OK ? I.n_ok : I.n_failed) += 1;
+  std::memcpy(cov, C36.data(), sizeof(double) * C36.size());
+  if (status) std::memcpy(status, stat.data(), sizeof(int32_t) * stat.size());
+  if (info) *info = I;
   return SICP_OK;
 }
 

@@ -795,6 +795,48 @@ hipError_t launch_graph_cg_iteration(const GraphArgs& a, hipStream_t st);       
 hipError_t launch_graph_candidates(const GraphArgs& a, hipStream_t st);                      // cand, S->pose2 xx gx xHx
 inline int graph_blocks(long long items) { return (int)((items + 255) / 256); }
 
+// ---- blocks of H^-1 (graph_cov_kernels.hip; driver: graph.cpp; the relative pose's Jacobian: graph_cov.hpp) ----
+// sicp_graph_marginals / sicp_graph_relative_covariances: H X = J^T for `cols` right-hand sides at once (six per query) by
+// conjugate gradients in lock step, on the undamped H of the last linearisation with the block-Jacobi preconditioner.  Every
+// vector is [n_nodes][cols][6]: the six lanes of a node and consecutive columns read contiguous memory.  Each column has its own
+// scalars and its own flag; a column whose flag is set is frozen (x, r, p are no longer written), and no column's arithmetic
+// depends on another's or on how many there are: a query's bytes are the same alone, in any company and at any `cols`.
+// Partial sums go per (column, workgroup) -- the SpMM's workgroup is 256 (node, row) lanes, the others' 64 nodes, whatever
+// `cols` -- and one workgroup per column adds them in graph_finish_kernel's order.
+constexpr int kGraphCovNodes = 64;   // nodes of a workgroup of the begin and update kernels
+enum { kGraphCovRunning = 0, kGraphCovConverged = 1, kGraphCovBreakdown = 2, kGraphCovLimit = 3 };
+struct GraphCovColumn {
+  double rz, pq, alpha, beta, rr, bb;   // as GraphScalars
+  int iters, flag;                      // kGraphCov*
+};
+struct GraphCovArgs {
+  int n_nodes, cols;           // cols = 6 * (queries of this pass)
+  const double* pose;          // [n_nodes][7]
+  const uint8_t* fixed;
+  const int *ei, *ej;
+  const double* B;             // [n_edges][36]
+  const unsigned long long* inc;
+  const int* off;
+  const double* H;             // [n_nodes][36], undamped
+  double* L;                   // [n_nodes][kGraphChol]: the factor of H's blocks (identity for a free node without edges)
+  const int *qa, *qb;          // [cols / 6]: the query's nodes (qa = -1: a marginal); a fixed end has no block
+  double* J;                   // [cols / 6][36]: J_a
+  double *x, *r, *z, *p, *q;   // [n_nodes][cols][6]
+  double* part;                // [2][cols][part_stride]
+  int part_stride;
+  GraphCovColumn* S;           // [cols]
+  int* bad;                    // set when a diagonal block is not positive definite
+  double tolerance;
+  int max_iters;
+  double* out;                 // [cols / 6][36]
+};
+inline int graph_cov_node_blocks(long long n_nodes) { return (int)((n_nodes + kGraphCovNodes - 1) / kGraphCovNodes); }
+inline int graph_cov_spmm_cols(int cols) { return cols % 24 == 0 ? 24 : cols % 12 == 0 ? 12 : 6; }  // the instantiation a pass runs
+hipError_t launch_graph_cov_factor(const GraphCovArgs& a, hipStream_t st);     // L, *bad
+hipError_t launch_graph_cov_begin(const GraphCovArgs& a, hipStream_t st);      // J, x = 0, r = b, z, p, S
+hipError_t launch_graph_cov_iteration(const GraphCovArgs& a, hipStream_t st);  // one step of every running column
+hipError_t launch_graph_cov_extract(const GraphCovArgs& a, hipStream_t st);    // out = sym(J X)
+
 // ---- the sorts and scans of the feature calls (prim_kernels.hip: the only rocPRIM instantiations besides build_tree.hip) ----
 // rocPRIM's convention: temp == nullptr asks for the bytes.  Ascending, stable; keys: bits [begin_bit, end_bit).
 hipError_t prim_sort_keys(void* temp, size_t& bytes, const unsigned long long* in, unsigned long long* out, long long n, int begin_bit,

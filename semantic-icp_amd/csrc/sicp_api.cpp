@@ -1043,6 +1043,24 @@ int sicp_graph_optimize(sicp_graph g, sicp_graph_info* info) {
   return abi_guard(g, [&]() -> int { return graph_optimize(g, info); });
 }
 
+int sicp_default_graph_cov_params(sicp_graph_cov_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    graph_default_cov_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_graph_marginals(sicp_graph g, const sicp_graph_cov_params* p, int32_t n, const int32_t* nodes, double* cov, int32_t* status,
+                         sicp_graph_cov_info* info) {
+  return abi_guard(g, [&]() -> int { return graph_covariances(g, true, p, n, nullptr, nodes, cov, status, info); });
+}
+
+int sicp_graph_relative_covariances(sicp_graph g, const sicp_graph_cov_params* p, int32_t n, const int32_t* a, const int32_t* b,
+                                    double* cov, int32_t* status, sicp_graph_cov_info* info) {
+  return abi_guard(g, [&]() -> int { return graph_covariances(g, false, p, n, a, b, cov, status, info); });
+}
+
 int sicp_solve(sicp_handle h, const double init_qt[7], double out_qt[7], int32_t* lm_iters, int32_t* evals,
                double* final_cost) {
   return abi_guard(h, [&]() -> int {
