@@ -149,7 +149,7 @@ int pose_cov_sweep(sicp_context* h, PoseCovScratch& X, HostBuf<unsigned char>& p
     sicp::PoseCovArgs& a = J.a;
     a.n_s = n_s; a.K = K;
     a.idx = g->idx.p;
-    a.w = g->corr_weighted ? g->w.p : nullptr;
+    a.w = batch[k].a.w;  // the weights of the accumulate launch whose H this covariance is built on (fill_acc)
     a.srec = g->cloud(0).rec.p; a.trec = g->cloud(1).rec.p;
     fill_pose(qt, a.pose);
     a.one_m_eps = 1.0 - P.epsilon;

@@ -441,7 +441,10 @@ void fill_acc(sicp_context* h, sicp::AccArgs& a) {
   Cloud &S = h->cloud(0), &T = h->cloud(1);
   a.n_s = h->corr_n; a.K = h->corr_K;
   a.idx = h->idx.p;
-  a.w = h->corr_weighted ? h->w.p : nullptr;
+  // The weights scale the loss only inside the SQLoss stack (ScaledLoss: em_icp.hpp:115).  Without it the loss is the plain Cauchy
+  // of semantic_icp.hpp:96 and a weight only carries the gate -- which the index already does (-1) -- so the EM probabilities of a
+  // handle in SICP_MODE_EM with use_sqloss = 0 stay out of the sums ("the accumulate kernels at every path").
+  a.w = (h->corr_weighted && P.use_sqloss) ? h->w.p : nullptr;
   a.srec = S.rec.p; a.trec = T.rec.p;
   a.srec_dense = (S.rec_dense_n == S.n && S.n > 0 && S.n == h->corr_n) ? S.rec_dense.p : nullptr;
   // the gathers come from the target's dense arrays whenever they are current: rec_dense_n is set where rec is written (cov_jobs_kernel,
