@@ -53,11 +53,19 @@ def residuals_and_jacobian(T, src, sn, tgt, tn, pairs, eps):
     return r, J
 
 
-def loss(mode, s, w, a):
+def loss(mode, s, w, a, use_sqloss=None):
     """rho(s) and rho'(s) of the reference's loss stacks (em_icp.hpp:109-117, gicp.hpp:98-104,
     semantic_icp.hpp:96), from their definitions: Cauchy(a): a^2 log(1 + s/a^2); SQLoss: sqrt(s + eps);
-    Composed(f, g)(s) = f(g(s)); Scaled(f, w) = w f."""
+    Composed(f, g)(s) = f(g(s)); Scaled(f, w) = w f.
+
+    `use_sqloss` (sicp_params) picks the stack whatever the mode's name: 1 is Scaled(Composed(Cauchy, SQLoss), w) with the
+    weights as given (pass ones where there are none), 0 the bare Cauchy -- no ScaledLoss around it, so w stays out."""
     b = a * a
+    if use_sqloss is not None:
+        if use_sqloss:
+            g = np.sqrt(s + DBL_EPS)
+            return w * (b * np.log1p(g / b)), w * ((1.0 / (1.0 + g / b)) * (0.5 / g))
+        return b * np.log1p(s / b), 1.0 / (1.0 + s / b)
     if mode in ("gicp", "em"):
         g = np.sqrt(s + DBL_EPS)
         rho = b * np.log1p(g / b)
