@@ -595,6 +595,67 @@ int sicp_merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_p
                       int32_t capacity, float* x, float* y, float* z, uint32_t* label, uint32_t* count /* all nullable */,
                       sicp_merge_info* info /* nullable */);
 
+/* ---- objects of a labelled cloud -------------------------------------------------
+ * Label-aware Euclidean clustering of the cloud in a handle's slot (what PCL users know as pcl::EuclideanClusterExtraction /
+ * pcl::LabeledEuclideanClusterExtraction): the connected components of the graph below, numbered, with one table row --
+ * label, count, first index, centroid, box -- per cluster.  The handle may be in any mode.
+ *  1. Vertices.  The finite points the slot's cloud holds (sicp_cloud_size's n_indexed); a point whose label equals one of
+ *     ignore[0 .. n_ignore) is not a vertex.  The result does not depend on the cloud's device layout (a SICP_MODE_SEMANTIC
+ *     handle groups it by label): the same cloud gives the same bytes on a handle of any mode, in either slot.
+ *  2. Edges.  p and q are joined iff d2 < t2, strict (sicp_evaluate's rule), and (same_label = 0 or their labels are equal):
+ *     d = p - q in float, d2 = (dx dx + dy dy) + dz dz in float, every operation rounded on its own, no contraction (the crop
+ *     arithmetic of sicp_merge_clouds, step 3); t2 = (float)tolerance * (float)tolerance in float.  d2 is symmetric in p and
+ *     q: the graph is undirected.
+ *  3. Clusters.  The connected components whose size lies in [min_points, max_points] (max_points = 0: no upper bound),
+ *     numbered 0, 1, ... in ascending order of their smallest caller index, which is first_index[c].  cluster_id[i] is that
+ *     number; -1 for a non-finite point, an ignored label, and a member of a component outside the bounds.
+ *  4. Per cluster.  count[c]: its points.  label[c]: the most frequent label of its points, ties to the smallest value (the
+ *     merge's rule; with same_label = 1 the one label they share).  centroid[3 c ..]: per axis the float64 sum of the members'
+ *     float coordinates in ascending caller index, one add per point, divided by the count in double (the merge's order).
+ *     bbox_min / bbox_max[3 c ..]: the members' float extremes.
+ *  5. Labels.  A cloud set without labels is accepted only with same_label = 0 and n_ignore = 0, and label[] is then written
+ *     as 0; otherwise it is SICP_ERR_INVALID_ARGUMENT.  On a SICP_MODE_SEMANTIC handle a cloud that was never uploaded for want
+ *     of labels gives SICP_ERR_NOT_READY, as it does in sicp_merge_clouds.
+ *  6. Capacity (the merge's rule).  The table arrays hold `capacity` rows (centroid, bbox_min, bbox_max: 3 values per row); each
+ *     is nullable.  A non-NULL table array with capacity < n_clusters: SICP_ERR_INVALID_ARGUMENT with info written and nothing
+ *     else (call once without arrays to size them).  cluster_id (nullable) has no capacity: it is n_points long, caller order.
+ *  7. Nothing on the handle changes: cloud, tree, features, correspondences, statistics and solver state stay, and a later
+ *     sicp_align returns the bytes it returns on a handle that never made the call.  Needs the cloud and nothing else; a cloud
+ *     not yet on the device is prepared as a part of sicp_merge_clouds is.
+ *  8. n_kept = 0 (no finite point, or every label ignored): SICP_OK, no clusters, cluster_id all -1.  The slot holds no cloud:
+ *     SICP_ERR_NOT_READY.
+ *  9. Refused before any device work, with SICP_ERR_INVALID_ARGUMENT, nothing written and the reason in sicp_last_error: a NULL
+ *     handle or params; a `which` outside SICP_SOURCE / SICP_TARGET; a tolerance that is not finite or <= 0; min_points < 1;
+ *     max_points negative, or positive and below min_points; same_label not 0 or 1; n_ignore outside 0 .. SICP_CLUSTER_MAX_IGNORE;
+ *     capacity < 0.  Refused after the first kernel, in the same way: a point whose cell of the internal search grid (edge: a
+ *     hair above the tolerance) has a coordinate of 2^20 - 1 or more in magnitude -- the text names the tolerance.
+ * 10. Bit-reproducible: a function of the points, labels and parameters only, the same bytes for every launch shape and from
+ *     run to run -- integer atomics decide a partition that does not depend on their order, every float sum runs in a fixed
+ *     order, no float atomics.  Permuting the input permutes cluster_id and renumbers the clusters; the partition, counts,
+ *     labels and boxes stay, and centroids may differ in their last bits (the order of the adds changes). */
+#define SICP_CLUSTER_MAX_IGNORE 64
+typedef struct sicp_cluster_params {
+  double tolerance;     /* > 0, finite.  default 0.5 */
+  int32_t min_points;   /* >= 1.  default 10 */
+  int32_t max_points;   /* 0 = no limit (default); otherwise >= min_points */
+  int32_t same_label;   /* 1 (default): only points of equal label are joined; 0: labels play no part in joining */
+  int32_t n_ignore;     /* 0 .. SICP_CLUSTER_MAX_IGNORE.  default 0 */
+  uint32_t ignore[SICP_CLUSTER_MAX_IGNORE];
+} sicp_cluster_params;
+typedef struct sicp_cluster_info {
+  int64_t n_points;            /* what the caller handed over (the size of cluster_id) */
+  int64_t n_kept;              /* vertices: finite points whose label is not ignored */
+  int64_t n_components;        /* connected components of all sizes */
+  int64_t n_clustered;         /* points with cluster_id >= 0 */
+  int32_t n_clusters;          /* components with min_points <= size <= max_points */
+  int32_t max_cluster_points;  /* 0 when n_clusters = 0 */
+  double t_total_ms;           /* host wall clock */
+} sicp_cluster_info;
+int sicp_default_cluster_params(sicp_cluster_params* p);
+int sicp_cluster(sicp_handle h, int which, const sicp_cluster_params* p, int32_t* cluster_id /* n_points, nullable */,
+                 int32_t capacity, uint32_t* label, int32_t* count, int32_t* first_index, double* centroid /* 3 per cluster */,
+                 float* bbox_min, float* bbox_max /* 3 per cluster each; all nullable */, sicp_cluster_info* info /* nullable */);
+
 /* ---- a persistent voxel map ---------------------------------------------------
  * The map of scan-to-map odometry as an object that lives on the device between calls: per occupied voxel of the absolute
  * grid of the merge above (v = floor(p * (1.0f / (float)leaf_size)), |v| < 2^20) its 63-bit key (three biased 21-bit

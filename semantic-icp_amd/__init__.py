@@ -239,6 +239,37 @@ class SicpMergeInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
 
 
+CLUSTER_MAX_IGNORE = 64
+
+
+class SicpClusterParams(C.Structure):
+    """sicp_cluster_params (include/sicp.h)"""
+    _fields_ = [
+        ("tolerance", C.c_double),
+        ("min_points", C.c_int32),
+        ("max_points", C.c_int32),
+        ("same_label", C.c_int32),
+        ("n_ignore", C.c_int32),
+        ("ignore", C.c_uint32 * CLUSTER_MAX_IGNORE),
+    ]
+
+
+class SicpClusterInfo(C.Structure):
+    """sicp_cluster_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_points", C.c_int64),
+        ("n_kept", C.c_int64),
+        ("n_components", C.c_int64),
+        ("n_clustered", C.c_int64),
+        ("n_clusters", C.c_int32),
+        ("max_cluster_points", C.c_int32),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class SicpMapParams(C.Structure):
     """sicp_map_params (include/sicp.h)"""
     _fields_ = [
@@ -568,6 +599,9 @@ def lib():
             "sicp_default_merge_params": [C.POINTER(SicpMergeParams)],
             "sicp_merge_clouds": [C.POINTER(C.c_void_p), _ip, C.c_int32, _dp, C.POINTER(SicpMergeParams), C.c_void_p, C.c_int, C.c_int32,
                                   _fp, _fp, _fp, _up, _up, C.POINTER(SicpMergeInfo)],
+            "sicp_default_cluster_params": [C.POINTER(SicpClusterParams)],
+            "sicp_cluster": [C.c_void_p, C.c_int, C.POINTER(SicpClusterParams), _ip, C.c_int32, _up, _ip, _ip, _dp, _fp, _fp,
+                             C.POINTER(SicpClusterInfo)],
             "sicp_default_map_params": [C.POINTER(SicpMapParams)],
             "sicp_default_map_extract_params": [C.POINTER(SicpMapExtractParams)],
             "sicp_map_create": [C.c_int, C.POINTER(SicpMapParams), C.POINTER(C.c_void_p)],
@@ -703,6 +737,26 @@ def default_merge_params(**overrides) -> SicpMergeParams:
         if not hasattr(p, k):
             raise AttributeError(k)
         setattr(p, k, (C.c_double * 3)(*v) if k == "crop_center" else v)
+    return p
+
+
+def default_cluster_params(ignore=(), **overrides) -> SicpClusterParams:
+    """sicp_default_cluster_params (tolerance 0.5, min_points 10, no upper bound, same_label 1, nothing ignored), with the labels
+    in `ignore` (at most CLUSTER_MAX_IGNORE) and any other field overridden by keyword"""
+    p = SicpClusterParams()
+    st = lib().sicp_default_cluster_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_cluster_params")
+    ignore = [int(v) for v in ignore]
+    if len(ignore) > CLUSTER_MAX_IGNORE:
+        raise ValueError(f"at most {CLUSTER_MAX_IGNORE} labels can be ignored")
+    p.n_ignore = len(ignore)
+    for k, v in enumerate(ignore):
+        p.ignore[k] = v
+    for k, v in overrides.items():
+        if not hasattr(p, k) or k == "ignore":
+            raise AttributeError(k)
+        setattr(p, k, v)
     return p
 
 
@@ -1093,6 +1147,27 @@ class Engine:
         if per_point:
             out["nn_idx"], out["nn_d2"] = idx, d2
         return out
+
+    def cluster(self, which: int = SOURCE, params: SicpClusterParams | None = None):
+        """sicp_cluster: the objects of the cloud in slot `which` -- connected components of the points closer than the tolerance
+        (and, with same_label, of equal label), those within the size bounds numbered by their smallest caller index.  Returns
+        {"cluster_id": [n_points] int32 (-1: in no cluster), "label": uint32, "count": int32, "first_index": int32, "centroid":
+        [n_clusters, 3] float64, "bbox_min" / "bbox_max": [n_clusters, 3] float32, "info": SicpClusterInfo.as_dict()}.  The table
+        is sized by a first call without arrays.  Nothing on the engine changes."""
+        p = params if params is not None else default_cluster_params()
+        info = SicpClusterInfo()
+        fn = lib().sicp_cluster
+        self._check(fn(self._h, which, C.byref(p), None, 0, None, None, None, None, None, None, C.byref(info)), "sicp_cluster")
+        k = info.n_clusters
+        cid = np.empty(max(int(info.n_points), 1), dtype=np.int32)
+        lab = np.empty(max(k, 1), dtype=np.uint32)
+        cnt, first = (np.empty(max(k, 1), dtype=np.int32) for _ in range(2))
+        cen = np.empty((max(k, 1), 3), dtype=np.float64)
+        lo, hi = (np.empty((max(k, 1), 3), dtype=np.float32) for _ in range(2))
+        self._check(fn(self._h, which, C.byref(p), _ptr(cid, _ip), k, _ptr(lab, _up), _ptr(cnt, _ip), _ptr(first, _ip), _ptr(cen, _dp),
+                       _ptr(lo, _fp), _ptr(hi, _fp), C.byref(info)), "sicp_cluster")
+        return {"cluster_id": cid[:int(info.n_points)], "label": lab[:k], "count": cnt[:k], "first_index": first[:k], "centroid": cen[:k],
+                "bbox_min": lo[:k], "bbox_max": hi[:k], "info": info.as_dict()}
 
     def solve(self, init_qt):
         init = np.ascontiguousarray(init_qt, dtype=np.float64)

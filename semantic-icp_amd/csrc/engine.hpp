@@ -9,6 +9,7 @@
 //   pose_cov.cpp  sicp_pose_covariance: the sweep over a group of pairs, the 6x6 algebra
 //   evaluate.cpp  sicp_evaluate: overlap, inlier RMSE and label agreement at a pose
 //   merge.cpp     sicp_merge_clouds: posed clouds into one voxel-grid cloud
+//   cluster.cpp   sicp_cluster: label-aware Euclidean clustering of a cloud
 //   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, prune, extract)
 //   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
 //   sicp_api.cpp  the remaining C-ABI entry points
@@ -504,6 +505,7 @@ struct sicp_context : sicp_use_state {
   // (x | y | z | label | count) on its way to the caller and into dst
   HostBuf<unsigned char> mg_stage;
   HostBuf<uint32_t> mg_out;
+  HostBuf<unsigned char> cl_stage;  // pinned: counts, cluster_id and table of sicp_cluster on their way back (cluster.cpp)
   // lock-step batch (sicp_align_batch), owned by the batch's first handle: one BatchArgs and one LM
   // state per pair, pinned mirrors, and the captured [accumulate_batch, lm_step_batch] x lm_batch graph
   TickSet ts[2];  // two sets: the halves of a batch alternate, one's tick runs while the host turns the other around
@@ -984,6 +986,11 @@ void merge_default_params(sicp_merge_params* p);
 int merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_parts, const double* qt, const sicp_merge_params* p,
                  sicp_context* dst, int dst_which, int32_t capacity, float* x, float* y, float* z, uint32_t* label, uint32_t* count,
                  sicp_merge_info* info);
+// sicp_cluster (cluster.cpp): argument checks, the cell grid / union-find / table kernels on the cloud's device copy, the
+// read-backs
+void cluster_default_params(sicp_cluster_params* p);
+int cluster(sicp_context* h, int which, const sicp_cluster_params* p, int32_t* cluster_id, int32_t capacity, uint32_t* label,
+            int32_t* count, int32_t* first_index, double* centroid, float* bbox_min, float* bbox_max, sicp_cluster_info* info);
 // sicp_map_* (map.cpp): the persistent voxel map
 void map_default_params(sicp_map_params* p);
 void map_default_extract_params(sicp_map_extract_params* p);

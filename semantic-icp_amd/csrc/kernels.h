@@ -500,6 +500,54 @@ hipError_t launch_merge_gather(const MergeReduceArgs& a, hipStream_t st);   // h
 hipError_t launch_merge_centroids(const MergeReduceArgs& a, hipStream_t st);  // ox oy oz, ocount, res[max count]
 hipError_t launch_merge_labels(const MergeReduceArgs& a, hipStream_t st);   // olabel
 
+// ---- label-aware Euclidean clustering (cluster_kernels.hip; driver: cluster.cpp) ----
+// sicp_cluster: the finite points of one cloud in caller order (Cloud::rx ...; index i below is a position in that order).
+// A cell grid finds the close pairs, a union-find over i in HBM joins them, integer atomics size the components, a scan over
+// the roots numbers the clusters, and a sort by (cluster, i) feeds the ordered per-cluster sums.
+constexpr int kClusterCellLimit = (1 << 20) - 1;  // |cell coordinate| < 2^20 - 1: a neighbour's biased coordinate stays in its 21-bit field
+constexpr int kClusterMaxIgnore = 64;             // SICP_CLUSTER_MAX_IGNORE
+enum { kClKept = 0, kClCells = 1, kClRange = 2, kClComponents = 3, kClClusters = 4, kClMaxCount = 5, kClClustered = 6, kClRes = 8 };
+struct ClusterArgs {
+  int n;                           // finite points
+  int same_label, labels;          // params; the cloud has labels
+  int n_ignore;
+  int min_points, max_points;      // max_points: INT_MAX for "no limit"
+  float inv, t2;                   // cells per metre (cluster_kernels.hip: the proof); (float)tol * (float)tol
+  uint32_t ignore[kClusterMaxIgnore];
+  const float *x, *y, *z;
+  const uint32_t* label;           // nullable
+  unsigned long long *key, *skey;  // [n] cell key by i (~0: not a vertex); sorted
+  int *val, *sval;                 // [n] i; i in sorted order
+  int *flag, *pos;                 // [n] scratch of the two scans
+  int* heads;                      // [n + 1] first sorted position of every cell; heads[n_cells] = n_kept
+  unsigned long long* ckey;        // [n] key of every cell, ascending
+  float4* spt;                     // [n] sorted order: x, y, z, label bits
+  int* parent;                     // [n] union-find; after the flatten pass the root (the component's smallest i)
+  int* size;                       // [n] component size at its root
+  int* cid;                        // [n] cluster number by i, -1 outside every cluster
+  unsigned long long *mkey, *msorted;  // [n] cluster << 32 | i (~0 outside every cluster); sorted
+  unsigned long long *lkey, *lsorted;  // [n] cluster << 32 | label; sorted (same_label = 0 with labels only)
+  int* mheads;                     // [n + 1] first position of every cluster in msorted; mheads[n_clusters] = n_clustered
+  uint32_t* olabel;                // [n_clusters] the table
+  int *ocount, *ofirst;
+  double* ocentroid;               // [3 n_clusters]
+  float *obmin, *obmax;            // [3 n_clusters]
+  int* res;                        // kClRes words, zeroed before the first launch
+};
+hipError_t launch_cluster_keys(const ClusterArgs& a, hipStream_t st);       // key, val, parent = i, size = 0, res[range]
+// (prim_sort_pairs key, val -> skey, sval)
+hipError_t launch_cluster_cell_flags(const ClusterArgs& a, hipStream_t st); // flag
+// (prim_scan_int flag -> pos)
+hipError_t launch_cluster_cells(const ClusterArgs& a, hipStream_t st);      // heads, ckey, spt, res[kept, cells]
+hipError_t launch_cluster_pairs(const ClusterArgs& a, hipStream_t st);      // parent: a workgroup per cell and chunk of its points
+hipError_t launch_cluster_sizes(const ClusterArgs& a, hipStream_t st);      // parent flattened, size
+hipError_t launch_cluster_root_flags(const ClusterArgs& a, hipStream_t st); // flag, res[components, max count, clustered]
+// (prim_scan_int flag -> pos)
+hipError_t launch_cluster_ids(const ClusterArgs& a, hipStream_t st);        // cid, mkey, lkey, res[clusters]
+// (prim_sort_keys mkey -> msorted, lkey -> lsorted)
+hipError_t launch_cluster_member_heads(const ClusterArgs& a, hipStream_t st);              // mheads
+hipError_t launch_cluster_table(const ClusterArgs& a, int n_clusters, hipStream_t st);    // the table: one wave per cluster
+
 // ---- the persistent voxel map (map_kernels.hip; driver: map.cpp) ----
 // sicp_map_*: per occupied voxel of merge's grid one row -- key, f64 sums, count, label histogram -- in arrays sorted by key.
 // An integrate keys and sorts the SCAN (the key arithmetic of voxel_key.hpp, merge's heads and gather launches), finds every

@@ -818,6 +818,21 @@ int sicp_merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_p
   });
 }
 
+int sicp_default_cluster_params(sicp_cluster_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    cluster_default_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_cluster(sicp_handle h, int which, const sicp_cluster_params* p, int32_t* cluster_id, int32_t capacity, uint32_t* label,
+                 int32_t* count, int32_t* first_index, double* centroid, float* bbox_min, float* bbox_max, sicp_cluster_info* info) {
+  return abi_guard(h, [&]() -> int {
+    return cluster(h, which, p, cluster_id, capacity, label, count, first_index, centroid, bbox_min, bbox_max, info);
+  });
+}
+
 int sicp_default_map_params(sicp_map_params* p) {
   return abi_guard([&]() -> int {
     if (!p) return SICP_ERR_INVALID_ARGUMENT;
