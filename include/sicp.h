@@ -774,6 +774,73 @@ int sicp_map_carve(sicp_map m, sicp_handle h, int which, const double qt[7] /* N
                    const sicp_map_carve_params* p, int32_t capacity, uint32_t* miss /* nullable */,
                    sicp_map_carve_info* info /* nullable */);
 
+/* ---- ray casting: what a sensor at a pose sees of the map -------------------------
+ * The map read along lines of sight (OctoMap's castRay, Open3D's VoxelBlockGrid.ray_cast).  The caller gives END POINTS, not
+ * directions: ray i is the segment from the sensor origin to (ex, ey, ez)[i], both in the sensor's frame, which is exactly a
+ * carve ray of a virtual return -- so a virtual scan pattern and "the scan's own points" are the same call.  It answers, per
+ * ray, the first opaque voxel on the way, and can make the distinct voxels hit the cloud of a handle's slot: a target without
+ * what is occluded, a rendered scan for sicp_place_query; with `ignore` the rays pass the voxels of moving classes; with the
+ * scan's own points as ends, step < length says that the map holds something in front of that return.  The rules:
+ *  1. Origin and ends.  Carve rule 1 word for word: each end and (float)sensor_origin go through the transform of
+ *     sicp_map_integrate, giving float p and o; both are keyed with the grid's float arithmetic: vp, vo.  An origin with
+ *     |v| >= 2^20 on an axis is refused.  An end that is not finite, or whose voxel is beyond the key's range, casts no ray (it
+ *     is not an error).
+ *  2. Which ends cast.  Carve rule 3: a valid key and either max_range = 0 or step 3's crop test of sicp_merge_clouds for p about
+ *     the centre o with the range max_range.
+ *  3. The walk.  Carve rule 4 unchanged: v_0 = vo, then exactly n = rem_x + rem_y + rem_z steps, so v_n = vp.
+ *  4. Opaque.  A map row is opaque when count >= min_count and, when n_ignore > 0, its fullest histogram bin -- sicp_map_extract's
+ *     label: ties to the smallest label, bin 0 can win -- is not in ignore.
+ *  5. Hit.  The hit is the smallest i in start_margin .. n whose voxel v_i the map holds as an opaque row.  The end's own voxel
+ *     v_n is tested.
+ *  6. A ray with a hit.  row[i]: the row's index in ascending key, the order of sicp_map_extract with default params -- it
+ *     indexes the arrays of sicp_map_extract and sicp_map_extract_fused, so a fused label or a histogram per ray is one gather
+ *     away.  step[i]: the hit's index in the walk.  length[i]: n.  x, y, z: the centroid as extract rounds it, (float)(s /
+ *     count).  label: the fullest bin; 0 on a map with num_classes = 0.  count: the voxel's count.  range_sq: with dx =
+ *     (double)x - (double)o_x and likewise dy, dz, the value (dx dx + dy dy) + dz dz, every operation rounded once, no
+ *     contraction; the caller takes the root, the library takes none.
+ *  7. Without a hit.  A ray that ran to its end gets row = -1, step = -1, length = n, zeros in the other arrays and range_sq =
+ *     -1.0.  An end that cast no ray gets the same with length = -1.
+ *  8. n_steps is the sum over the rays cast of the voxels tested: step - start_margin + 1 for a ray with a hit,
+ *     max(n + 1 - start_margin, 0) for one without.
+ *  9. dst (nullable).  The n_visible distinct rows hit, in ascending key, become slot dst_which of dst: their x, y, z and -- when
+ *     the map has classes -- label, exactly as sicp_set_cloud of those arrays would make it (the path of sicp_map_extract).
+ *     The result is complete before the slot lets go of its old cloud.
+ * 10. n_visible = 0 with a dst gives SICP_ERR_TOO_FEW_POINTS; info is written, dst and every array are untouched.
+ * 11. Contracts.  The map is never modified; dst is the only handle touched; the call is synchronous, on the map's stream.
+ *     SICP_ERR_INVALID_ARGUMENT with nothing written: a NULL map, params or end array; n < 0; a pose or origin that is not
+ *     finite; an origin beyond the key's range; max_range negative or NaN (+inf: every ray); min_count < 1; start_margin < 0;
+ *     n_ignore outside 0..SICP_MAP_RAYCAST_MAX_IGNORE, or > 0 on a map with num_classes = 0; an ignored label above
+ *     num_classes; with a dst, a dst_which outside the two slots or a dst on another device.  SICP_ERR_OUT_OF_MEMORY: the arena
+ *     refused (sicp_set_memory_limit applies); nothing is written.  n = 0, or an empty map, without dst: SICP_OK, the results are
+ *     "no hit", and on an empty map n_steps is still counted.  Every output array is nullable and n long.  No float atomics:
+ *     every per-ray output is a plain store by the lane that owns the ray, the visible marks are plain stores of 1, the counts
+ *     integer atomics -- the bytes depend neither on the launch shape nor on which other rays are in the call.
+ * Cost: as carve's, one lookup among the map's keys per voxel walked, but a walk ends at its hit.  max_range, or the ends
+ * themselves, bound a ray's length.
+ * Not built: an origin per ray; a batch or stream form; the fused label inside the call (gather extract_fused's by row); a hit
+ * position on the voxel's face (the answer is the voxel's centroid). */
+#define SICP_MAP_RAYCAST_MAX_IGNORE 64
+typedef struct sicp_map_raycast_params {
+  double  max_range;     /* 0 (default) = every ray; else only rays whose end passes the crop test about the origin (carve rule 3) */
+  int32_t min_count;     /* a voxel with fewer points is transparent.  default 1, >= 1 */
+  int32_t start_margin;  /* the first start_margin voxels of a walk are not tested.  default 1 (the sensor's own voxel), >= 0 */
+  int32_t n_ignore;      /* 0 (default) .. SICP_MAP_RAYCAST_MAX_IGNORE */
+  int32_t reserved_;
+  uint32_t ignore[SICP_MAP_RAYCAST_MAX_IGNORE]; /* a voxel whose fullest histogram bin (extract's label rule) is one of these is transparent */
+} sicp_map_raycast_params;
+typedef struct sicp_map_raycast_info {
+  int64_t n_in, n_rays, n_steps, n_hits, n_voxels;  /* rays given / cast / voxels tested by all rays / rays with a hit / map rows */
+  int32_t n_visible, reserved_;                     /* distinct rows hit */
+  double t_total_ms;                                /* host wall clock */
+} sicp_map_raycast_info;
+int sicp_default_map_raycast_params(sicp_map_raycast_params* p);
+int sicp_map_raycast(sicp_map m, const double qt[7] /* NULL = identity */, const double sensor_origin[3] /* NULL = 0 0 0 */,
+                     int32_t n, const float* ex, const float* ey, const float* ez,   /* ray i ends at (ex,ey,ez)[i], sensor frame */
+                     const sicp_map_raycast_params* p, sicp_handle dst /* nullable */, int dst_which,
+                     int32_t* row, int32_t* step, int32_t* length, float* x, float* y, float* z, uint32_t* label,
+                     uint32_t* count, double* range_sq,                              /* n each, every one nullable */
+                     sicp_map_raycast_info* info /* nullable */);
+
 typedef struct sicp_map_extract_params {
   int32_t min_count;      /* voxels with fewer points are left out.  default 1 */
   int32_t reserved_;

@@ -354,6 +354,38 @@ class SicpMapCarveInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
 
 
+MAP_RAYCAST_MAX_IGNORE = 64
+
+
+class SicpMapRaycastParams(C.Structure):
+    """sicp_map_raycast_params (include/sicp.h)"""
+    _fields_ = [
+        ("max_range", C.c_double),
+        ("min_count", C.c_int32),
+        ("start_margin", C.c_int32),
+        ("n_ignore", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("ignore", C.c_uint32 * MAP_RAYCAST_MAX_IGNORE),
+    ]
+
+
+class SicpMapRaycastInfo(C.Structure):
+    """sicp_map_raycast_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_in", C.c_int64),
+        ("n_rays", C.c_int64),
+        ("n_steps", C.c_int64),
+        ("n_hits", C.c_int64),
+        ("n_voxels", C.c_int64),
+        ("n_visible", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
+
+
 PLACE_LABEL, PLACE_HEIGHT = 0, 1
 PLACE_MAX_IGNORE = 64
 
@@ -613,6 +645,9 @@ def lib():
             "sicp_default_map_carve_params": [C.POINTER(SicpMapCarveParams)],
             "sicp_map_carve": [C.c_void_p, C.c_void_p, C.c_int, _dp, _dp, C.POINTER(SicpMapCarveParams), C.c_int32, _up,
                                C.POINTER(SicpMapCarveInfo)],
+            "sicp_default_map_raycast_params": [C.POINTER(SicpMapRaycastParams)],
+            "sicp_map_raycast": [C.c_void_p, _dp, _dp, C.c_int32, _fp, _fp, _fp, C.POINTER(SicpMapRaycastParams), C.c_void_p, C.c_int,
+                                 _ip, _ip, _ip, _fp, _fp, _fp, _up, _up, _dp, C.POINTER(SicpMapRaycastInfo)],
             "sicp_map_extract": [C.c_void_p, C.POINTER(SicpMapExtractParams), C.c_void_p, C.c_int, C.c_int32, _fp, _fp, _fp, _up, _up, _up,
                                  C.POINTER(SicpMapExtractInfo)],
             "sicp_map_set_confusion": [C.c_void_p, C.c_int32, _dp],
@@ -806,6 +841,40 @@ def default_map_carve_params(**overrides) -> SicpMapCarveParams:
         else:
             setattr(p, k, v)
     return p
+
+
+def default_map_raycast_params(ignore=(), **overrides) -> SicpMapRaycastParams:
+    """sicp_default_map_raycast_params (every ray, min_count 1, start_margin 1, nothing ignored), with the labels in `ignore`
+    (at most MAP_RAYCAST_MAX_IGNORE; sets n_ignore with them) and any other field overridden by keyword"""
+    p = SicpMapRaycastParams()
+    st = lib().sicp_default_map_raycast_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_map_raycast_params")
+    labels = [int(l) for l in ignore]
+    if len(labels) > MAP_RAYCAST_MAX_IGNORE:
+        raise ValueError(f"at most {MAP_RAYCAST_MAX_IGNORE} ignored labels")
+    p.ignore = (C.c_uint32 * MAP_RAYCAST_MAX_IGNORE)(*labels)
+    p.n_ignore = len(labels)
+    for k, v in overrides.items():
+        if not hasattr(p, k) or k == "ignore":
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def lidar_ray_ends(n_rings: int, n_azimuth: int, elev_min_deg: float, elev_max_deg: float, max_range: float, origin=(0.0, 0.0, 0.0)):
+    """The ends of a spinning lidar's rays for VoxelMap.raycast: n_rings elevations evenly from elev_min_deg to elev_max_deg
+    (both included), n_azimuth azimuths 2 pi k / n_azimuth, each end max_range from `origin` along (cos e cos a, cos e sin a,
+    sin e), sensor frame.  Host numpy (float64, rounded once to float32); returns float32 [n_rings * n_azimuth, 3], ring-major:
+    ray r * n_azimuth + k is ring r, azimuth k.  Neighbouring rays are then neighbours in a wave's share of the rays, and
+    their lookups among the map's keys share cache lines."""
+    if n_rings < 1 or n_azimuth < 1:
+        raise ValueError("n_rings and n_azimuth must be >= 1")
+    e = np.deg2rad(np.linspace(float(elev_min_deg), float(elev_max_deg), int(n_rings)))[:, None]
+    a = (2.0 * np.pi * np.arange(int(n_azimuth)) / int(n_azimuth))[None, :]
+    d = np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e) * np.ones_like(a)], axis=-1)
+    ends = np.asarray(origin, dtype=np.float64).reshape(1, 1, 3) + float(max_range) * d
+    return np.ascontiguousarray(ends.reshape(-1, 3).astype(np.float32))
 
 
 def default_place_params(**overrides) -> SicpPlaceParams:
@@ -1480,6 +1549,35 @@ class VoxelMap:
         self._check(lib().sicp_map_carve(self._m, engine._h, which, _ptr(q, _dp), _ptr(o, _dp), C.byref(p), cap, _ptr(miss, _up),
                                          C.byref(info)), "sicp_map_carve")
         return {"miss": None if miss is None else miss[:cap].copy(), "info": info.as_dict()}
+
+    def raycast(self, ends, qt=None, sensor_origin=None, params: SicpMapRaycastParams | None = None, dst: "Engine | None" = None,
+                dst_which: int = TARGET):
+        """sicp_map_raycast: ray i runs from sensor_origin (None: 0 0 0) to ends[i] ([n, 3], both in the sensor's frame, at pose qt;
+        None: identity) and stops at the first opaque voxel.  Returns {"row": the hit's row in extract()'s default order (-1: none),
+        "step": its index in the walk, "length": the walk's steps (-1: the end cast no ray), "xyz": the hit voxel's centroid,
+        "labels", "count", "range_sq": squared distance from the origin to that centroid (-1.0: none), "info":
+        SicpMapRaycastInfo.as_dict()}.  With dst the distinct voxels hit, ascending key, become that Engine's slot dst_which as if
+        handed to set_cloud."""
+        e = np.ascontiguousarray(ends, dtype=np.float32).reshape(-1, 3)
+        n = len(e)
+        ex, ey, ez = (np.ascontiguousarray(e[:, a]) if n else np.zeros(1, np.float32) for a in range(3))
+        q = None if qt is None else np.ascontiguousarray(qt, dtype=np.float64).reshape(7)
+        o = None if sensor_origin is None else np.ascontiguousarray(sensor_origin, dtype=np.float64).reshape(3)
+        p = params if params is not None else default_map_raycast_params()
+        row, step, length = (np.empty(max(n, 1), dtype=np.int32) for _ in range(3))
+        x, y, z = (np.empty(max(n, 1), dtype=np.float32) for _ in range(3))
+        lab, cnt = (np.empty(max(n, 1), dtype=np.uint32) for _ in range(2))
+        r2 = np.empty(max(n, 1), dtype=np.float64)
+        info = SicpMapRaycastInfo()
+        self._check(lib().sicp_map_raycast(self._m, _ptr(q, _dp), _ptr(o, _dp), n, _ptr(ex, _fp), _ptr(ey, _fp), _ptr(ez, _fp), C.byref(p),
+                                           None if dst is None else dst._h, dst_which, _ptr(row, _ip), _ptr(step, _ip), _ptr(length, _ip),
+                                           _ptr(x, _fp), _ptr(y, _fp), _ptr(z, _fp), _ptr(lab, _up), _ptr(cnt, _up), _ptr(r2, _dp),
+                                           C.byref(info)), "sicp_map_raycast")
+        if dst is not None:
+            dst.n[dst_which] = info.n_visible
+        return {"row": row[:n].copy(), "step": step[:n].copy(), "length": length[:n].copy(),
+                "xyz": np.stack([x[:n], y[:n], z[:n]], axis=1), "labels": lab[:n].copy(), "count": cnt[:n].copy(),
+                "range_sq": r2[:n].copy(), "info": info.as_dict()}
 
     def prune(self, center, range):
         """sicp_map_prune: drops the voxels whose centroid lies further than `range` from `center`; returns their number"""

@@ -10,7 +10,7 @@
 //   evaluate.cpp  sicp_evaluate: overlap, inlier RMSE and label agreement at a pose
 //   merge.cpp     sicp_merge_clouds: posed clouds into one voxel-grid cloud
 //   cluster.cpp   sicp_cluster: label-aware Euclidean clustering of a cloud
-//   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, prune, extract)
+//   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, raycast, prune, extract)
 //   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
 //   sicp_api.cpp  the remaining C-ABI entry points
 // Every extern "C" entry runs inside abi_guard (abi_barrier.hpp): no exception crosses the boundary.
@@ -609,6 +609,7 @@ struct sicp_map_ctx {
   bool has_cm = false;
   HostBuf<unsigned char> stage;  // pinned: the counts' read-back
   HostBuf<uint32_t> out;         // pinned: an extract's result (x | y | z | label | count | hist rows | confidence) on its way out
+  HostBuf<uint32_t> rays;        // pinned: a ray cast's ends on their way up, then its per-ray results on their way out
   std::string last_error;
 };
 
@@ -1002,6 +1003,11 @@ int map_prune(sicp_map_ctx* m, const double* center, double range, int64_t* n_re
 void map_default_carve_params(sicp_map_carve_params* p);
 int map_carve(sicp_map_ctx* m, sicp_context* h, int which, const double* qt, const double* sensor_origin, const sicp_map_carve_params* p,
               int32_t capacity, uint32_t* miss, sicp_map_carve_info* info);
+void map_default_raycast_params(sicp_map_raycast_params* p);
+int map_raycast(sicp_map_ctx* m, const double* qt, const double* sensor_origin, int32_t n, const float* ex, const float* ey,
+                const float* ez, const sicp_map_raycast_params* p, sicp_context* dst, int dst_which, int32_t* row, int32_t* step,
+                int32_t* length, float* x, float* y, float* z, uint32_t* label, uint32_t* count, double* range_sq,
+                sicp_map_raycast_info* info);
 int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
                 float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info);
 int map_set_confusion(sicp_map_ctx* m, int32_t C, const double* cm);

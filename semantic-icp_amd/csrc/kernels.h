@@ -650,6 +650,39 @@ struct MapCarveSelectArgs {
 hipError_t launch_map_carve_hits(const MapCarveArgs& a, hipStream_t st);    // hit, res[kMapRange] (launched for n = 0 too)
 hipError_t launch_map_carve_walk(const MapCarveArgs& a, hipStream_t st);    // miss, stat[rays, steps]
 hipError_t launch_map_carve_select(const MapCarveSelectArgs& a, hipStream_t st);  // flag, stat[touched ... spared]
+// ray casting (sicp_map_raycast): carve's walk, stopped at the first voxel whose row is opaque.  One lane per row first writes
+// an opaque byte (count >= min_count and the fullest bin not ignored), so the walk reads a byte per row it finds and never a
+// histogram; a wave owns kRaycastRaysPerWave consecutive rays and deals them to idle lanes as carve does, the step's lookup is
+// the one device function both walks call.  The lane that owns a ray stores its outputs; a hit stores visible[row] = 1.
+constexpr int kRaycastRaysPerWave = 128;
+constexpr int kMapMaxIgnore = 64;  // SICP_MAP_RAYCAST_MAX_IGNORE
+enum { kRaycastRays = 0, kRaycastSteps, kRaycastHits, kRaycastVisible, kRaycastStats = 4 };
+struct MapRaycastArgs {
+  const float *x, *y, *z;   // [n] the ends, sensor frame (any value: an end that is not finite casts no ray)
+  double M[12];
+  int n;
+  float inv_leaf;
+  float sx, sy, sz;         // (float)sensor_origin, transformed in the kernels as a point is
+  int ranged;               // max_range > 0
+  double range_sq;
+  int start_margin;
+  long long min_count;
+  int n_ignore;
+  uint32_t ignore[kMapMaxIgnore];
+  MapRows rows;             // hist: nullptr when the map keeps no labels
+  int n_map, stride;
+  unsigned char* opaque;    // [n_map]
+  int* visible;             // [n_map] zeroed: 1 where a ray hits
+  int *orow, *ostep, *olength;      // [n] per ray
+  float *ox, *oy, *oz;
+  uint32_t *olabel, *ocount;
+  double* orange_sq;
+  unsigned long long* stat; // kRaycastStats words, zeroed
+  int* res;                 // res[kMapRange]: the origin lies beyond the key's range (zeroed before the launch)
+};
+hipError_t launch_map_raycast_opaque(const MapRaycastArgs& a, hipStream_t st);   // opaque, res[kMapRange] (launched for n_map = 0 too)
+hipError_t launch_map_raycast_walk(const MapRaycastArgs& a, hipStream_t st);     // the per-ray outputs, visible, stat[rays, steps, hits]
+hipError_t launch_map_raycast_visible(const MapRaycastArgs& a, hipStream_t st);  // stat[visible]
 // label fusion through the confusion matrix (sicp_map_extract_fused, sicp_map_fused_labels).  logcm[r * C + s] = log cm[r][s]
 // (observed label r + 1, class s + 1; -inf for a zero entry).  A histogram row's score of class s is the sum over its
 // non-zero bins r = 1..C, ascending, of (double)h[r] * logcm[r - 1][s - 1], each product and each sum rounded once.  An item

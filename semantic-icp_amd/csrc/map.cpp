@@ -528,9 +528,11 @@ int map_carve(sicp_map_ctx* m, sicp_context* h, int which, const double* qt, con
 
 // sicp_map_extract and sicp_map_extract_fused (`confidence_wanted`): the selection, the order, the centroids and counts, the
 // capacity rule, dst and info are one code; the fused call replaces the arg-max label by the posterior's and adds its probability
+// `given_flag` (sicp_map_raycast: the rows its rays hit; [n_map] on the device, written on the map's stream) takes the place of
+// the selection by min_count and crop
 static int extract_rows(sicp_map_ctx* m, const char* call, bool fused, const sicp_map_extract_params* p, sicp_context* dst, int dst_which,
                         int32_t capacity, float* x, float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist,
-                        double* confidence, sicp_map_extract_info* info) {
+                        double* confidence, sicp_map_extract_info* info, int* given_flag = nullptr) {
   if (!m) return SICP_ERR_INVALID_ARGUMENT;
   const std::string name = call;
   auto refuse = [&](const std::string& why) {
@@ -564,26 +566,28 @@ static int extract_rows(sicp_map_ctx* m, const char* call, bool fused, const sic
     X.device = m->device;
     X.idle = false;
     MAPCHECK(m->stage.resize(sizeof res));
-    MAPCHECK(X.flag.reserve(nr)); MAPCHECK(X.pos.reserve(nr)); MAPCHECK(X.src_of.reserve(nr));
+    if (!given_flag) MAPCHECK(X.flag.reserve(nr));
+    MAPCHECK(X.pos.reserve(nr)); MAPCHECK(X.src_of.reserve(nr));
     MAPCHECK(X.ox.reserve(nr)); MAPCHECK(X.oy.reserve(nr)); MAPCHECK(X.oz.reserve(nr)); MAPCHECK(X.oc.reserve(nr));
     if (C > 0) MAPCHECK(X.ol.reserve(nr));
     if (fused) MAPCHECK(X.oconf.reserve(nr));
     MAPCHECK(X.res.reserve(sicp::kMapRes));
     size_t scan_bytes = 0;
-    MAPCHECK(sicp::prim_scan_int(nullptr, scan_bytes, X.flag.p, X.pos.p, n_map, st));
+    int* const flag = given_flag ? given_flag : X.flag.p;
+    MAPCHECK(sicp::prim_scan_int(nullptr, scan_bytes, flag, X.pos.p, n_map, st));
     MAPCHECK(X.temp.reserve(scan_bytes + 256));
     const Crop crop = make_crop(p->crop_center, p->crop_range);
     S.n_map = n_map; S.stride = stride; S.min_count = p->min_count; S.crop = crop.on;
     S.cx = crop.c[0]; S.cy = crop.c[1]; S.cz = crop.c[2]; S.range_sq = crop.range_sq;
     S.rows = rows_of(m->rows[m->cur], stride > 0);
-    S.flag = X.flag.p; S.pos = X.pos.p; S.src_of = X.src_of.p;
+    S.flag = flag; S.pos = X.pos.p; S.src_of = X.src_of.p;
     S.ox = X.ox.p; S.oy = X.oy.p; S.oz = X.oz.p; S.ocount = X.oc.p;
     S.olabel = C > 0 ? X.ol.p : nullptr;
     S.res = X.res.p;
     log.mark("begin");
     MAPCHECK(hipMemsetAsync(X.res.p, 0, sizeof res, st));
-    MAPCHECK(sicp::launch_map_select(S, st));
-    MAPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, X.flag.p, X.pos.p, n_map, st));
+    if (!given_flag) MAPCHECK(sicp::launch_map_select(S, st));
+    MAPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, flag, X.pos.p, n_map, st));
     MAPCHECK(sicp::launch_map_extract(S, st));
     log.mark("select_gather");
     if (fused) {  // (the rows' number is on the device: the kernel reads it there)
@@ -674,6 +678,155 @@ int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context*
 int map_extract_fused(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
                       float* y, float* z, uint32_t* label, uint32_t* count, double* confidence, sicp_map_extract_info* info) {
   return extract_rows(m, "sicp_map_extract_fused", true, p, dst, dst_which, capacity, x, y, z, label, count, nullptr, confidence, info);
+}
+
+void map_default_raycast_params(sicp_map_raycast_params* p) {
+  std::memset(p, 0, sizeof *p);
+  p->min_count = 1;
+  p->start_margin = 1;
+}
+
+// sicp_map_raycast (include/sicp.h, "ray casting"): the ends go up through pinned staging, one lane per row writes its opaque
+// byte, the walk answers every ray and marks the rows hit, and the per-ray results are on the host before dst -- through
+// extract_rows, with the marks as the selection -- or a caller's array is touched.
+int map_raycast(sicp_map_ctx* m, const double* qt, const double* sensor_origin, int32_t n, const float* ex, const float* ey,
+                const float* ez, const sicp_map_raycast_params* p, sicp_context* dst, int dst_which, int32_t* row, int32_t* step,
+                int32_t* length, float* x, float* y, float* z, uint32_t* label, uint32_t* count, double* range_sq,
+                sicp_map_raycast_info* info) {
+  if (!m) return SICP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const std::string& why) {
+    m->last_error = "sicp_map_raycast: " + why + "; nothing was written";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (!p) return refuse("the params are NULL");
+  if (!ex || !ey || !ez) return refuse("an end array is NULL");
+  if (n < 0) return refuse("n is negative");
+  if (dst && !slot_ok(dst_which)) return refuse("dst_which is neither SICP_SOURCE nor SICP_TARGET");
+  if (dst && dst->device != m->device) return refuse("dst is on device " + std::to_string(dst->device) + ", the map on " + std::to_string(m->device));
+  if (!(p->max_range >= 0.0)) return refuse("max_range must be >= 0 (+inf is allowed)");
+  if (p->min_count < 1) return refuse("min_count must be >= 1");
+  if (p->start_margin < 0) return refuse("start_margin must be >= 0");
+  const int C = m->params.num_classes, stride = stride_of(m);
+  if (p->n_ignore < 0 || p->n_ignore > SICP_MAP_RAYCAST_MAX_IGNORE) return refuse("n_ignore must be 0.." + std::to_string(SICP_MAP_RAYCAST_MAX_IGNORE));
+  if (p->n_ignore > 0 && C == 0) return refuse("the map keeps no labels: there is nothing to ignore");
+  for (int j = 0; j < p->n_ignore; ++j)
+    if (p->ignore[j] > (uint32_t)C) return refuse("ignore[" + std::to_string(j) + "] = " + std::to_string(p->ignore[j]) + " is above num_classes = " + std::to_string(C));
+  if (sensor_origin)
+    for (int d = 0; d < 3; ++d)
+      if (!std::isfinite(sensor_origin[d])) return refuse("sensor_origin must be finite");
+  if (qt)
+    for (int k = 0; k < 7; ++k)
+      if (!std::isfinite(qt[k])) return refuse("the pose is not finite");
+  const double t_begin = now_ms();
+  MAPCHECK(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  StageLog log(log_enabled(), st);
+  const int n_map = (int)m->n_voxels;
+  const size_t nr = (size_t)n_map, np = (size_t)n;
+  sicp_map_raycast_info I;
+  std::memset(&I, 0, sizeof I);
+  I.n_in = n;
+  I.n_voxels = m->n_voxels;
+  MapScratch X;
+  X.device = m->device;
+  X.idle = false;
+  unsigned long long stat[sicp::kRaycastStats] = {};
+  const size_t head = sizeof(int) * sicp::kMapRes + sizeof stat;
+  MAPCHECK(m->stage.resize(head));
+  MAPCHECK(m->rays.resize(10 * np));  // the ends on their way up, then: range_sq (doubles first) | row | step | length | x | y | z | label | count
+  MAPCHECK(X.res.reserve(sicp::kMapRes)); MAPCHECK(X.stat.reserve(sicp::kRaycastStats));
+  if (n_map > 0) { MAPCHECK(X.temp.reserve(nr)); MAPCHECK(X.flag.reserve(nr)); }
+  if (n > 0) {
+    MAPCHECK(X.tx.reserve(np)); MAPCHECK(X.ty.reserve(np)); MAPCHECK(X.tz.reserve(np));
+    MAPCHECK(X.val.reserve(np)); MAPCHECK(X.val2.reserve(np)); MAPCHECK(X.rank.reserve(np));
+    MAPCHECK(X.ox.reserve(np)); MAPCHECK(X.oy.reserve(np)); MAPCHECK(X.oz.reserve(np));
+    MAPCHECK(X.ol.reserve(np)); MAPCHECK(X.oc.reserve(np)); MAPCHECK(X.oconf.reserve(np));
+  }
+  const double ident[7] = {0, 0, 0, 1, 0, 0, 0};
+  sicp::MapRaycastArgs A;
+  std::memset(&A, 0, sizeof A);
+  A.x = X.tx.p; A.y = X.ty.p; A.z = X.tz.p;
+  matrix34(qt ? qt : ident, A.M);
+  A.n = n;
+  A.inv_leaf = 1.0f / (float)m->params.leaf_size;
+  A.sx = sensor_origin ? (float)sensor_origin[0] : 0.f;
+  A.sy = sensor_origin ? (float)sensor_origin[1] : 0.f;
+  A.sz = sensor_origin ? (float)sensor_origin[2] : 0.f;
+  A.ranged = p->max_range > 0.0 ? 1 : 0;
+  A.range_sq = p->max_range * p->max_range;
+  A.start_margin = p->start_margin;
+  A.min_count = p->min_count;
+  A.n_ignore = p->n_ignore;
+  for (int j = 0; j < p->n_ignore; ++j) A.ignore[j] = p->ignore[j];
+  A.rows = rows_of(m->rows[m->cur], stride > 0);
+  A.n_map = n_map; A.stride = stride;
+  A.opaque = X.temp.p; A.visible = X.flag.p;
+  A.orow = X.val.p; A.ostep = X.val2.p; A.olength = X.rank.p;
+  A.ox = X.ox.p; A.oy = X.oy.p; A.oz = X.oz.p;
+  A.olabel = X.ol.p; A.ocount = X.oc.p; A.orange_sq = X.oconf.p;
+  A.stat = X.stat.p; A.res = X.res.p;
+  uint32_t* const o = m->rays.data();
+  log.mark("begin");
+  if (n > 0) {
+    std::memcpy(o, ex, 4 * np); std::memcpy(o + np, ey, 4 * np); std::memcpy(o + 2 * np, ez, 4 * np);
+    MAPCHECK(hipMemcpyAsync(X.tx.p, o, 4 * np, hipMemcpyHostToDevice, st));
+    MAPCHECK(hipMemcpyAsync(X.ty.p, o + np, 4 * np, hipMemcpyHostToDevice, st));
+    MAPCHECK(hipMemcpyAsync(X.tz.p, o + 2 * np, 4 * np, hipMemcpyHostToDevice, st));
+  }
+  MAPCHECK(hipMemsetAsync(X.res.p, 0, sizeof(int) * sicp::kMapRes, st));
+  MAPCHECK(hipMemsetAsync(X.stat.p, 0, sizeof stat, st));
+  if (n_map > 0) MAPCHECK(hipMemsetAsync(X.flag.p, 0, sizeof(int) * nr, st));
+  log.mark("ends");
+  MAPCHECK(sicp::launch_map_raycast_opaque(A, st));
+  log.mark("opaque");
+  MAPCHECK(sicp::launch_map_raycast_walk(A, st));
+  log.mark("walk");
+  MAPCHECK(sicp::launch_map_raycast_visible(A, st));
+  int res[sicp::kMapRes];
+  MAPCHECK(hipMemcpyAsync(m->stage.data(), X.res.p, sizeof res, hipMemcpyDeviceToHost, st));
+  MAPCHECK(hipMemcpyAsync(m->stage.data() + sizeof res, X.stat.p, sizeof stat, hipMemcpyDeviceToHost, st));
+  if (n > 0) {  // (the ends have been read by then: the stream keeps the order)
+    MAPCHECK(hipMemcpyAsync(o, X.oconf.p, 8 * np, hipMemcpyDeviceToHost, st));
+    const void* from[8] = {X.val.p, X.val2.p, X.rank.p, X.ox.p, X.oy.p, X.oz.p, X.ol.p, X.oc.p};
+    const void* wanted[8] = {row, step, length, x, y, z, label, count};
+    for (int k = 0; k < 8; ++k)
+      if (wanted[k]) MAPCHECK(hipMemcpyAsync(o + (2 + k) * np, from[k], 4 * np, hipMemcpyDeviceToHost, st));
+  }
+  log.mark("result");
+  MAPCHECK(hipStreamSynchronize(st));
+  std::memcpy(res, m->stage.data(), sizeof res);
+  std::memcpy(stat, m->stage.data() + sizeof res, sizeof stat);
+  X.idle = true;
+  if (res[sicp::kMapRange])
+    return refuse("leaf size " + std::to_string(m->params.leaf_size) + " is too small for the sensor origin: a voxel coordinate reaches 2^20");
+  I.n_rays = (int64_t)stat[sicp::kRaycastRays];
+  I.n_steps = (int64_t)stat[sicp::kRaycastSteps];
+  I.n_hits = (int64_t)stat[sicp::kRaycastHits];
+  I.n_visible = (int32_t)stat[sicp::kRaycastVisible];
+  log.print("sicp_map_raycast: n_in=" + std::to_string(n) + " n_map=" + std::to_string(n_map) + " n_steps=" + std::to_string(I.n_steps) +
+            " n_hits=" + std::to_string(I.n_hits));
+  if (dst && I.n_visible == 0) {
+    I.t_total_ms = now_ms() - t_begin;
+    if (info) *info = I;
+    m->last_error = "sicp_map_raycast: no ray hit the map; dst keeps its cloud";
+    return SICP_ERR_TOO_FEW_POINTS;
+  }
+  if (dst) {  // the rows marked visible are the selection: extract's scan, gather and way into the slot
+    sicp_map_extract_params E;
+    map_default_extract_params(&E);
+    const int rc = extract_rows(m, "sicp_map_raycast (visible rows)", false, &E, dst, dst_which, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                nullptr, nullptr, X.flag.p);
+    if (rc != SICP_OK) return rc;
+  }
+  if (n > 0) {
+    if (range_sq) std::memcpy(range_sq, o, 8 * np);
+    void* to[8] = {row, step, length, x, y, z, label, count};
+    for (int k = 0; k < 8; ++k)
+      if (to[k]) std::memcpy(to[k], o + (2 + k) * np, 4 * np);
+  }
+  I.t_total_ms = now_ms() - t_begin;
+  if (info) *info = I;
+  return SICP_OK;
 }
 
 int map_set_confusion(sicp_map_ctx* m, int32_t C, const double* cm) {

@@ -247,7 +247,8 @@ __device__ __forceinline__ int map_gallop_down(const u64* keys, int from, u64 k)
 }
 
 // the sensor origin as a point of the scan: transformed, keyed; false when it lies beyond the key's range
-__device__ __forceinline__ bool carve_origin(const MapCarveArgs& a, float* ox, float* oy, float* oz, u64* ko) {
+template <class Args>  // (MapCarveArgs, MapRaycastArgs)
+__device__ __forceinline__ bool carve_origin(const Args& a, float* ox, float* oy, float* oz, u64* ko) {
   const double x = a.sx, y = a.sy, z = a.sz;
   *ox = voxel_xform_row(a.M + 0, x, y, z);
   *oy = voxel_xform_row(a.M + 4, x, y, z);
@@ -279,10 +280,31 @@ __device__ __forceinline__ u64 wave_sum(u64 v) {
   return v;
 }
 
+// The lookup of a walk's step (the carve walk and the ray cast share it): the ray has just stepped along `axis` into the voxel
+// r.key; lb and found, which described the voxel it left, become the new key's lower bound among the map's keys and whether
+// the map holds it.  A step along x derives both from the row beside the old one, a step along y gallops from lb, a step
+// along z searches the side it went to.
+__device__ __forceinline__ void map_walk_lookup(const u64* keys, int n_map, const VoxelRay& r, int axis, int* lb_io, bool* found_io) {
+  int lb = *lb_io;
+  bool found = *found_io;
+  const u64 k = r.key;
+  if (axis == 0 && r.sx < 0) {  // the key went down by 1: it is the row below or it is absent
+    found = lb > 0 && keys[lb - 1] == k;
+    lb -= found ? 1 : 0;
+  } else {
+    if (axis == 0) lb += found ? 1 : 0;  // up by 1: the keys below it are those below the old key, and the old key
+    else if (axis == 1) lb = r.sy > 0 ? map_gallop_up(keys, n_map, lb + (found ? 1 : 0), k) : map_gallop_down(keys, lb, k);
+    else lb = r.sz > 0 ? map_lower_bound_in(keys, lb + (found ? 1 : 0), n_map, k) : map_lower_bound_in(keys, 0, lb, k);
+    found = lb < n_map && keys[lb] == k;
+  }
+  *lb_io = lb;
+  *found_io = found;
+}
+
 // The walk.  A wave owns the rays [wave * kCarveRaysPerWave, ...) and deals them to its lanes as they fall idle: every turn
 // of the loop the idle lanes take the next rays in lane order, then every lane with a ray visits the voxel it stands in and
-// steps on.  `lb` is the lower bound of the lane's key among the map's and `found` says whether the map holds it; a step
-// along x derives both from the row beside it, a step along y gallops from lb, a step along z searches the side it went to.
+// steps on.  `lb` is the lower bound of the lane's key among the map's and `found` says whether the map holds it
+// (map_walk_lookup carries them from step to step).
 // The counts are integer atomics, so neither the dealing nor the launch shape shows in the result.
 __global__ __launch_bounds__(256) void map_carve_walk_kernel(MapCarveArgs a) {
   float ox, oy, oz;
@@ -329,16 +351,7 @@ __global__ __launch_bounds__(256) void map_carve_walk_kernel(MapCarveArgs a) {
       left -= 1;
       if (left > 0) {
         const int axis = voxel_ray_step(&r);
-        const u64 k = r.key;
-        if (axis == 0 && r.sx < 0) {  // the key went down by 1: it is the row below or it is absent
-          found = lb > 0 && keys[lb - 1] == k;
-          lb -= found ? 1 : 0;
-        } else {
-          if (axis == 0) lb += found ? 1 : 0;  // up by 1: the keys below it are those below the old key, and the old key
-          else if (axis == 1) lb = r.sy > 0 ? map_gallop_up(keys, n_map, lb + (found ? 1 : 0), k) : map_gallop_down(keys, lb, k);
-          else lb = r.sz > 0 ? map_lower_bound_in(keys, lb + (found ? 1 : 0), n_map, k) : map_lower_bound_in(keys, 0, lb, k);
-          found = lb < n_map && keys[lb] == k;
-        }
+        map_walk_lookup(keys, n_map, r, axis, &lb, &found);
       }
     }
   }
@@ -380,6 +393,136 @@ __global__ __launch_bounds__(256) void map_carve_select_kernel(MapCarveSelectArg
     if (b3) atomicAdd(&a.stat[kCarveSparedHit], (u64)__popcll(b3));
     if (b4) atomicAdd(&a.stat[kCarveSparedLabel], (u64)__popcll(b4));
   }
+}
+
+// ---- ray casting (kernels.h: MapRaycastArgs) -----------------------------------------------------------------------------------
+// opaque[i]: row i stops a ray -- it has min_count points and its fullest bin is not ignored (the histogram is read only when
+// labels are ignored); lane 0 checks the origin as carve's hit kernel does
+__global__ __launch_bounds__(256) void map_raycast_opaque_kernel(MapRaycastArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) {
+    float ox, oy, oz;
+    u64 ko;
+    if (!carve_origin(a, &ox, &oy, &oz, &ko)) a.res[kMapRange] = 1;
+  }
+  if (i >= a.n_map) return;
+  bool opaque = (long long)a.rows.cnt[i] >= a.min_count;
+  if (opaque && a.n_ignore > 0) {
+    const uint32_t l = map_fullest_bin(a.rows.hist + (size_t)i * (size_t)a.stride, a.stride);
+    for (int j = 0; j < a.n_ignore; ++j) opaque = opaque && a.ignore[j] != l;
+  }
+  a.opaque[i] = opaque ? 1 : 0;
+}
+
+// ray i's outputs (plain stores by the lane that owns it): the hit row `row` at walk index `step`, or row < 0 for none
+__device__ __forceinline__ void raycast_store(const MapRaycastArgs& a, int i, int row, int step, int length, float ox, float oy,
+                                              float oz) {
+  float cx = 0.f, cy = 0.f, cz = 0.f;
+  uint32_t label = 0u, count = 0u;
+  double d2 = -1.0;
+  if (row >= 0) {
+    map_centroid(a.rows, row, &cx, &cy, &cz);
+    count = a.rows.cnt[row];
+    if (a.rows.hist) label = map_fullest_bin(a.rows.hist + (size_t)row * (size_t)a.stride, a.stride);
+    const double dx = __dsub_rn((double)cx, (double)ox), dy = __dsub_rn((double)cy, (double)oy), dz = __dsub_rn((double)cz, (double)oz);
+    d2 = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+    a.visible[row] = 1;
+  }
+  a.orow[i] = row; a.ostep[i] = step; a.olength[i] = length;
+  a.ox[i] = cx; a.oy[i] = cy; a.oz[i] = cz;
+  a.olabel[i] = label; a.ocount[i] = count;
+  a.orange_sq[i] = d2;
+}
+
+// The walk, dealt as carve's: a wave owns the rays [wave * kRaycastRaysPerWave, ...) and its idle lanes take the next ones in
+// lane order.  A lane with a ray stands in voxel v_i with `left` = n + 1 - i voxels still to visit (this one included) and
+// `skip` of them not to be tested; it tests the voxel (the map holds it and its row is opaque: the hit, and the lane falls
+// idle), or steps on.  An end that casts no ray is answered by the lane that drew it.
+__global__ __launch_bounds__(256) void map_raycast_walk_kernel(MapRaycastArgs a) {
+  float ox, oy, oz;
+  u64 ko;
+  if (!carve_origin(a, &ox, &oy, &oz, &ko)) return;  // (the same in every lane; the host refuses the call)
+  const int lane = threadIdx.x & 63;
+  const long long first = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * kRaycastRaysPerWave;
+  const int end = (int)std::min<long long>(first + kRaycastRaysPerWave, a.n);
+  int next = (int)std::min<long long>(first, a.n);
+  const u64* const keys = a.rows.key;
+  const unsigned char* const opaque = a.opaque;
+  const int n_map = a.n_map;
+  const int lb0 = map_lower_bound(keys, n_map, ko);  // every ray starts in the origin's voxel
+  const bool found0 = lb0 < n_map && keys[lb0] == ko;
+  VoxelRay r;
+  int left = 0, skip = 0, lb = 0, mine = -1;
+  bool found = false;
+  u64 rays = 0, steps = 0, hits = 0;
+  for (;;) {
+    const bool idle = left == 0;
+    const u64 idle_mask = __ballot(idle);
+    if (idle_mask == ~0ull && next >= end) break;
+    int done = -1, done_row = -1, done_step = -1, done_length = -1;  // the ray this lane answers in this turn (at most one)
+    if (idle) {
+      const int i = next + __popcll(idle_mask & ((1ull << lane) - 1ull));
+      if (i < end) {
+        const double x = a.x[i], y = a.y[i], z = a.z[i];
+        const float px = voxel_xform_row(a.M + 0, x, y, z);
+        const float py = voxel_xform_row(a.M + 4, x, y, z);
+        const float pz = voxel_xform_row(a.M + 8, x, y, z);
+        u64 kp;
+        done = i;  // (an end that casts no ray: length -1)
+        if (voxel_key(px, py, pz, a.inv_leaf, &kp) && (!a.ranged || voxel_crop_keeps(px, py, pz, ox, oy, oz, a.range_sq))) {
+          rays += 1;
+          voxel_ray_begin(ox, oy, oz, ko, px, py, pz, kp, a.inv_leaf, &r);
+          const int tests = r.n + 1 > a.start_margin ? r.n + 1 - a.start_margin : 0;  // the voxels a walk without a hit tests
+          if (n_map == 0 || tests == 0) {  // nothing can stop it
+            steps += (u64)tests;
+            done_length = r.n;
+          } else {
+            done = -1;
+            mine = i;
+            left = r.n + 1;
+            skip = a.start_margin;
+            lb = lb0;
+            found = found0;
+          }
+        }
+      }
+    }
+    next = (int)std::min<long long>((long long)next + __popcll(idle_mask), end);
+    if (left > 0) {
+      const bool tested = skip == 0;
+      steps += tested ? 1 : 0;
+      if (tested && found && opaque[lb] != 0) {
+        hits += 1;
+        done = mine; done_row = lb; done_step = r.n + 1 - left; done_length = r.n;
+        left = 0;
+      } else {
+        skip -= tested ? 0 : 1;
+        left -= 1;
+        if (left > 0) {
+          const int axis = voxel_ray_step(&r);
+          map_walk_lookup(keys, n_map, r, axis, &lb, &found);
+        } else {
+          done = mine; done_length = r.n;
+        }
+      }
+    }
+    if (done >= 0) raycast_store(a, done, done_row, done_step, done_length, ox, oy, oz);
+  }
+  rays = wave_sum(rays);
+  steps = wave_sum(steps);
+  hits = wave_sum(hits);
+  if (lane == 0) {
+    if (rays) atomicAdd(&a.stat[kRaycastRays], rays);
+    if (steps) atomicAdd(&a.stat[kRaycastSteps], steps);
+    if (hits) atomicAdd(&a.stat[kRaycastHits], hits);
+  }
+}
+
+// the distinct rows hit: a ballot and one integer atomic a wave
+__global__ __launch_bounds__(256) void map_raycast_visible_kernel(MapRaycastArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const u64 b = __ballot(i < a.n_map && a.visible[i] != 0);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(&a.stat[kRaycastVisible], (u64)__popcll(b));
 }
 
 // ---- label fusion through the confusion matrix (kernels.h: MapFuseArgs) -------------------------------------------------------
@@ -608,6 +751,25 @@ hipError_t launch_map_carve_select(const MapCarveSelectArgs& a, hipStream_t st) 
   if (a.n_map <= 0) return hipSuccess;
   if (a.n_protect < 0 || a.n_protect > kMapMaxProtect || (a.n_protect > 0 && !a.hist)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(map_carve_select_kernel, map_grid(a.n_map), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_raycast_opaque(const MapRaycastArgs& a, hipStream_t st) {
+  if (a.n_map < 0 || a.n_ignore < 0 || a.n_ignore > kMapMaxIgnore || (a.n_ignore > 0 && !a.rows.hist)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(map_raycast_opaque_kernel, map_grid(std::max(a.n_map, 1)), dim3(256), 0, st, a);  // (n_map = 0: the origin's check alone)
+  return hipGetLastError();
+}
+
+hipError_t launch_map_raycast_walk(const MapRaycastArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  const long long per_block = 4 * kRaycastRaysPerWave;  // four waves a workgroup
+  hipLaunchKernelGGL(map_raycast_walk_kernel, dim3((unsigned)((a.n + per_block - 1) / per_block)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_raycast_visible(const MapRaycastArgs& a, hipStream_t st) {
+  if (a.n_map <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_raycast_visible_kernel, map_grid(a.n_map), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

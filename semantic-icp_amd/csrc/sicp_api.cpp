@@ -899,6 +899,23 @@ int sicp_map_carve(sicp_map m, sicp_handle h, int which, const double qt[7], con
   return abi_guard(m, [&]() -> int { return map_carve(m, h, which, qt, sensor_origin, p, capacity, miss, info); });
 }
 
+int sicp_default_map_raycast_params(sicp_map_raycast_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    map_default_raycast_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_map_raycast(sicp_map m, const double qt[7], const double sensor_origin[3], int32_t n, const float* ex, const float* ey,
+                     const float* ez, const sicp_map_raycast_params* p, sicp_handle dst, int dst_which, int32_t* row, int32_t* step,
+                     int32_t* length, float* x, float* y, float* z, uint32_t* label, uint32_t* count, double* range_sq,
+                     sicp_map_raycast_info* info) {
+  return abi_guard(m, [&]() -> int {
+    return map_raycast(m, qt, sensor_origin, n, ex, ey, ez, p, dst, dst_which, row, step, length, x, y, z, label, count, range_sq, info);
+  });
+}
+
 int sicp_map_extract(sicp_map m, const sicp_map_extract_params* p, sicp_handle dst, int dst_which, int32_t capacity, float* x,
                      float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info) {
   return abi_guard(m, [&]() -> int {
