@@ -1166,6 +1166,14 @@ class Engine:
         self._check(lib().sicp_covariances(self._h, which, _ptr(cov, _dp), _ptr(nrm, _dp), _ptr(hist, _bp), _ptr(nn, _ip)), "sicp_covariances")
         return cov, nrm, hist, nn
 
+    def covariance_matrices(self, which: int):
+        """sicp_covariances with cov9 alone (getSourceCovariances() / getTargetCovariances()): the n 3x3 matrices in the caller's
+        order.  A cloud without dropped points forms them on the device (cov9_caller_order_kernel); the bytes are those of
+        covariances()[0] either way."""
+        cov = np.empty((self.n[which], 3, 3))
+        self._check(lib().sicp_covariances(self._h, which, _ptr(cov, _dp), None, None, None), "sicp_covariances")
+        return cov
+
     def set_covariances(self, which: int, cov9):
         """caller-supplied covariances (n x 3 x 3 or n x 9, the caller's point order); SicpError when one is not I - (1-eps) n n^T"""
         c = np.ascontiguousarray(np.asarray(cov9, dtype=np.float64).reshape(-1, 9))

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 from scipy.spatial.transform import Rotation
 
+import cov_cases as CC
 import oracle_lib as O
 import synth
 from np_ref import mat_to_qt
@@ -236,9 +237,10 @@ def test_any_covariance_k(k, nn_method):
         assert np.array_equal(hist, want_hist)
         ocov, onrm, ohist = O.covariances(src, sl, k, 1e-3, 11, kdtree=True)
         assert np.allclose(hist / float(k), ohist, atol=1e-15)
-        if k >= 5:
-            dots = np.abs(np.einsum("ni,ni->n", nrm, onrm))
-            assert np.median(1 - dots) < 1e-12
+        # every point, at every k: unit length, an eigenvector of smallest |eigenvalue| of the restated moment matrix
+        # within the bar, and the matrix bit for bit from the normal (tests/cov_cases.py)
+        CC.assert_normals(src, nbr, k, 1, nrm, f"any k: k {k} method {nn_method}", onrm)
+        CC.assert_matrices(cov, nrm, 1e-3, f"any k: k {k} method {nn_method}")
     finally:
         e.close()
 
