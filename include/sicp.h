@@ -906,6 +906,78 @@ int sicp_map_fused_labels(sicp_map m, sicp_handle h, int which, const double qt[
                           int32_t include_own_label, int32_t min_count, uint32_t* out_labels,
                           double* out_confidence /* nullable */);
 
+/* ---- fusing maps: a submap into a global map at its pose ---------------------------
+ * After a loop closure the trajectory moves and the map has to follow.  A map does not record which scan gave what, so the
+ * answer is submaps: a few dozen scans integrated into a small map in the submap's own frame, the submap a node of the pose
+ * graph, and after sicp_graph_optimize every submap added into the global map at its corrected pose -- with its counts, the
+ * weight of its centroids and its histograms intact, which sicp_map_extract into a handle followed by sicp_map_integrate
+ * loses (that route counts every voxel as one observation).  sicp_map_merge adds src's rows into dst:
+ *  1. Rows.  src's, in ascending key; row r has the sums s, the count c and the histogram h.  A row with c < min_count takes no
+ *     part.
+ *  2. Moved sums.  M is the matrix of qt exactly as sicp_map_integrate forms it.  Per axis a, in double, every operation
+ *     rounded on its own, no contraction: t_a = ((M[a][0] sx + M[a][1] sy) + M[a][2] sz) + M[a][3] (double)c -- step 2's order
+ *     of sicp_merge_clouds with the translation scaled by the count and no rounding to float.  Under the identity t == s bit for
+ *     bit (a sum of -0.0, which no integrate produces, becomes +0.0).
+ *  3. Where it lands.  p_a = (float)(t_a / (double)c).  When crop_range > 0, p takes step 3's crop test of sicp_merge_clouds
+ *     about crop_center, in dst's frame.  Then p is keyed on DST's grid, v = floor(p * (1.0f / (float)dst.leaf_size)): the two
+ *     maps may differ in leaf size.  |v| >= 2^20 on any axis refuses the call as sicp_map_integrate does (the text names dst's
+ *     leaf size).  Keying the centroid of the moved SUMS, not the moved float centroid, keeps what every integrate-only map
+ *     has: a row's (float)(s / count) lies in the row's own voxel.
+ *  4. Fold.  A dst voxel's sums continue from their stored value (0.0 for a voxel dst did not hold) with the contributions in
+ *     ascending src row, one add per axis and contributing row; count += c; every histogram bin += h[bin].  The order of the
+ *     float adds is the specification; there are no float atomics, so two maps driven alike are byte-identical.  A row moves
+ *     whole: its mass is never spread over several voxels.
+ *  5. Labels.  dst.num_classes == 0: src's histograms are ignored.  Otherwise src.num_classes must equal dst.num_classes.
+ *  6. Limits.  More than 2^31 - 1 voxels or 2^32 - 1 points in dst refuse the call (the second bounds every voxel's count);
+ *     both are checked before a row is written.
+ *  7. Contracts: sicp_map_integrate's.  The call computes into dst's spare set and swaps last: after every refusal dst holds the
+ *     bytes it held and stays usable, and info is not written.  src is never modified.  SICP_ERR_INVALID_ARGUMENT, with the
+ *     reason in sicp_map_last_error(dst): a NULL map; src == dst; maps on different devices; a pose or centre that is not
+ *     finite; crop_range negative or NaN; min_count < 1; a class mismatch; rules 3 and 6.  SICP_ERR_OUT_OF_MEMORY: the arena
+ *     refused.  An empty src, or no kept row: SICP_OK, nothing changes, info is written.  The call is synchronous and runs on
+ *     dst's stream; a map serves one thread at a time, and a merge occupies BOTH maps: no other call may run on src or on dst
+ *     until it returns.
+ * The work is one sort of src's rows plus linear passes over both maps; dst is never sorted. */
+typedef struct sicp_map_merge_params {
+  int32_t min_count;      /* src rows with fewer points take no part.  default 1, >= 1 */
+  int32_t reserved_;
+  double crop_center[3];  /* default 0 0 0, in dst's frame */
+  double crop_range;      /* 0 = no crop (default); +inf allowed */
+} sicp_map_merge_params;
+typedef struct sicp_map_merge_info {
+  int64_t n_src_rows;      /* src's voxels */
+  int64_t n_kept_rows;     /* after min_count and the crop */
+  int64_t n_kept_points;   /* the sum of their counts: what dst's point count rises by */
+  int32_t n_touched;       /* dst voxels that receive something */
+  int32_t n_new_voxels;    /* ... of which dst did not hold */
+  int32_t max_run;         /* most src rows landing in one dst voxel; 0 when nothing was kept */
+  int32_t reserved_;
+  int64_t n_voxels;        /* dst's voxels after the call */
+  double t_total_ms;       /* host wall clock */
+} sicp_map_merge_info;
+int sicp_default_map_merge_params(sicp_map_merge_params* p);
+int sicp_map_merge(sicp_map dst, sicp_map src, const double qt[7] /* src frame -> dst frame; NULL = identity */,
+                   const sicp_map_merge_params* p /* NULL = defaults */, sicp_map_merge_info* info /* nullable */);
+
+/* ---- the map's exact contents: save, reload, inspect ---------------------------------
+ * sicp_map_get_state: the rows in ascending key -- sicp_map_extract's default order, so the `row` outputs of sicp_map_carve and
+ * sicp_map_raycast index them -- as they are stored: key[r], sums[3 r ..] = sx sy sz, count[r], hist[(num_classes + 1) r ..].
+ * n_rows (nullable) is always written.  An array (each nullable, `capacity` rows) is written when it is non-NULL and
+ * capacity >= n_rows; a non-NULL array with a smaller capacity gives SICP_ERR_INVALID_ARGUMENT and nothing else happens (the
+ * merge's capacity rule: call once without arrays to size them).  hist on a map with num_classes = 0 is refused.  The map is
+ * not modified.
+ * sicp_map_set_state: the map's contents become exactly these n rows; n = 0 clears the map.  Every row is checked before the
+ * map changes (the spare set, one swap).  SICP_ERR_INVALID_ARGUMENT with the offending row's index in sicp_map_last_error
+ * and the map unchanged: keys that do not ascend strictly; a key no point can have (the top bit set, or one of the three 21-bit
+ * fields 0); a count of 0; a sum that is not finite; with classes, a histogram row that does not add up to its count (integrate
+ * and merge keep that equality); more than 2^31 - 1 rows or 2^32 - 1 points; a NULL key, sums or count with n > 0; hist NULL
+ * with num_classes > 0 or non-NULL with num_classes = 0.  leaf_size and num_classes are creation parameters and the caller's to
+ * store beside the arrays.  A map filled by set_state(get_state()) gives the same bytes from every later call as the original. */
+int sicp_map_get_state(sicp_map m, int64_t capacity, uint64_t* key, double* sums /* 3 per row: sx sy sz */, uint32_t* count,
+                       uint32_t* hist /* (num_classes+1) per row */, int64_t* n_rows /* every pointer nullable */);
+int sicp_map_set_state(sicp_map m, int64_t n, const uint64_t* key, const double* sums, const uint32_t* count,
+                       const uint32_t* hist /* required iff num_classes > 0 */);
+
 /* ---- a database of scan descriptors: which earlier scan is this one? ---------------
  * The step of loop closing that comes before sicp_evaluate (accept the pose) and sicp_pose_covariance (weigh the edge): every
  * keyframe's scan becomes a polar descriptor of R rings x S sectors about the sensor, one uint8 code per cell -- the cell's

@@ -386,6 +386,34 @@ class SicpMapRaycastInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
 
 
+class SicpMapMergeParams(C.Structure):
+    """sicp_map_merge_params (include/sicp.h)"""
+    _fields_ = [
+        ("min_count", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("crop_center", C.c_double * 3),
+        ("crop_range", C.c_double),
+    ]
+
+
+class SicpMapMergeInfo(C.Structure):
+    """sicp_map_merge_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_src_rows", C.c_int64),
+        ("n_kept_rows", C.c_int64),
+        ("n_kept_points", C.c_int64),
+        ("n_touched", C.c_int32),
+        ("n_new_voxels", C.c_int32),
+        ("max_run", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("n_voxels", C.c_int64),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
+
+
 PLACE_LABEL, PLACE_HEIGHT = 0, 1
 PLACE_MAX_IGNORE = 64
 
@@ -542,6 +570,7 @@ _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
 _up = C.POINTER(C.c_uint32)
 _bp = C.POINTER(C.c_uint8)
+_kp = C.POINTER(C.c_uint64)
 
 
 def lib():
@@ -654,6 +683,10 @@ def lib():
             "sicp_map_extract_fused": [C.c_void_p, C.POINTER(SicpMapExtractParams), C.c_void_p, C.c_int, C.c_int32, _fp, _fp, _fp, _up, _up,
                                        _dp, C.POINTER(SicpMapExtractInfo)],
             "sicp_map_fused_labels": [C.c_void_p, C.c_void_p, C.c_int, _dp, C.c_int32, C.c_int32, _up, _dp],
+            "sicp_default_map_merge_params": [C.POINTER(SicpMapMergeParams)],
+            "sicp_map_merge": [C.c_void_p, C.c_void_p, _dp, C.POINTER(SicpMapMergeParams), C.POINTER(SicpMapMergeInfo)],
+            "sicp_map_get_state": [C.c_void_p, C.c_int64, _kp, _dp, _up, _up, C.POINTER(C.c_int64)],
+            "sicp_map_set_state": [C.c_void_p, C.c_int64, _kp, _dp, _up, _up],
             "sicp_default_place_params": [C.POINTER(SicpPlaceParams)],
             "sicp_place_create": [C.c_int, C.POINTER(SicpPlaceParams), C.POINTER(C.c_void_p)],
             "sicp_place_destroy": [C.c_void_p],
@@ -859,6 +892,19 @@ def default_map_raycast_params(ignore=(), **overrides) -> SicpMapRaycastParams:
         if not hasattr(p, k) or k == "ignore":
             raise AttributeError(k)
         setattr(p, k, v)
+    return p
+
+
+def default_map_merge_params(**overrides) -> SicpMapMergeParams:
+    """sicp_default_map_merge_params (min_count 1, no crop), with any field overridden by keyword (crop_center: 3 values)"""
+    p = SicpMapMergeParams()
+    st = lib().sicp_default_map_merge_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_map_merge_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, (C.c_double * 3)(*v) if k == "crop_center" else v)
     return p
 
 
@@ -1423,6 +1469,7 @@ class VoxelMap:
         self._m = C.c_void_p()
         p = params if params is not None else default_map_params()
         self.num_classes = int(p.num_classes)
+        self.leaf_size = float(p.leaf_size)
         st = lib().sicp_map_create(device, C.byref(p), C.byref(self._m))
         if st != OK:
             self._m = C.c_void_p()
@@ -1586,6 +1633,60 @@ class VoxelMap:
         return {"row": row[:n].copy(), "step": step[:n].copy(), "length": length[:n].copy(),
                 "xyz": np.stack([x[:n], y[:n], z[:n]], axis=1), "labels": lab[:n].copy(), "count": cnt[:n].copy(),
                 "range_sq": r2[:n].copy(), "info": info.as_dict()}
+
+    def merge(self, src: "VoxelMap", qt=None, min_count: int = 1, crop_center=None, crop_range: float = 0.0):
+        """sicp_map_merge: src's voxels with at least min_count points, moved by qt (src's frame -> this map's; None: identity)
+        and cropped about crop_center (None: the origin, this map's frame) with crop_range (0: no crop), added into this map with
+        their sums, counts and histograms; src is not modified.  Returns SicpMapMergeInfo.as_dict()."""
+        q = None if qt is None else np.ascontiguousarray(qt, dtype=np.float64).reshape(7)
+        p = default_map_merge_params(min_count=min_count, crop_range=crop_range,
+                                     crop_center=(0.0, 0.0, 0.0) if crop_center is None else tuple(crop_center))
+        info = SicpMapMergeInfo()
+        self._check(lib().sicp_map_merge(self._m, src._m, _ptr(q, _dp), C.byref(p), C.byref(info)), "sicp_map_merge")
+        return info.as_dict()
+
+    def get_state(self):
+        """sicp_map_get_state: the map's exact contents, rows in ascending key (extract's default order) -- {"key" uint64 [n], "sums"
+        float64 [n, 3], "count" uint32 [n], "hist" uint32 [n, num_classes + 1] (None when the map keeps no labels), "leaf_size",
+        "num_classes"}: what from_state() and set_state() take, and all a caller has to store."""
+        n = self.size()[0]
+        key = np.empty(max(n, 1), dtype=np.uint64)
+        sums = np.empty((max(n, 1), 3), dtype=np.float64)
+        count = np.empty(max(n, 1), dtype=np.uint32)
+        hist = np.empty((max(n, 1), self.num_classes + 1), dtype=np.uint32) if self.num_classes > 0 else None
+        rows = C.c_int64()
+        self._check(lib().sicp_map_get_state(self._m, n, _ptr(key, _kp), _ptr(sums, _dp), _ptr(count, _up), _ptr(hist, _up),
+                                             C.byref(rows)), "sicp_map_get_state")
+        return {"key": key[:n].copy(), "sums": sums[:n].copy(), "count": count[:n].copy(), "hist": None if hist is None else hist[:n].copy(),
+                "leaf_size": self.leaf_size, "num_classes": self.num_classes}
+
+    def set_state(self, state):
+        """sicp_map_set_state: the map's contents become exactly the rows of `state` (a get_state() dict; its leaf_size and
+        num_classes must be this map's).  A refusal names the offending row and leaves the map as it was."""
+        if int(state["num_classes"]) != self.num_classes or float(state["leaf_size"]) != self.leaf_size:
+            raise ValueError("the state's leaf_size / num_classes are not this map's")
+        key = np.ascontiguousarray(state["key"], dtype=np.uint64).reshape(-1)
+        n = len(key)
+        sums = np.ascontiguousarray(state["sums"], dtype=np.float64).reshape(-1, 3)
+        count = np.ascontiguousarray(state["count"], dtype=np.uint32).reshape(-1)
+        hist = None
+        if self.num_classes > 0:
+            hist = np.ascontiguousarray(state["hist"], dtype=np.uint32).reshape(-1, self.num_classes + 1)
+        if len(sums) != n or len(count) != n or (hist is not None and len(hist) != n):
+            raise ValueError("key, sums, count and hist differ in length")
+        self._check(lib().sicp_map_set_state(self._m, n, _ptr(key, _kp), _ptr(sums, _dp), _ptr(count, _up), _ptr(hist, _up)),
+                    "sicp_map_set_state")
+
+    @classmethod
+    def from_state(cls, state, device: int = 0):
+        """a new map with state's leaf_size and num_classes holding exactly its rows"""
+        vm = cls(device, default_map_params(leaf_size=float(state["leaf_size"]), num_classes=int(state["num_classes"])))
+        try:
+            vm.set_state(state)
+        except Exception:
+            vm.close()
+            raise
+        return vm
 
     def prune(self, center, range):
         """sicp_map_prune: drops the voxels whose centroid lies further than `range` from `center`; returns their number"""

@@ -10,7 +10,7 @@
 //   evaluate.cpp  sicp_evaluate: overlap, inlier RMSE and label agreement at a pose
 //   merge.cpp     sicp_merge_clouds: posed clouds into one voxel-grid cloud
 //   cluster.cpp   sicp_cluster: label-aware Euclidean clustering of a cloud
-//   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, raycast, prune, extract)
+//   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, raycast, prune, extract, merge, state)
 //   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
 //   sicp_api.cpp  the remaining C-ABI entry points
 // Every extern "C" entry runs inside abi_guard (abi_barrier.hpp): no exception crosses the boundary.
@@ -1015,6 +1015,10 @@ int map_extract_fused(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_co
                       float* y, float* z, uint32_t* label, uint32_t* count, double* confidence, sicp_map_extract_info* info);
 int map_fused_labels(sicp_map_ctx* m, sicp_context* h, int which, const double* qt, int32_t include_own_label, int32_t min_count,
                      uint32_t* out_labels, double* out_confidence);
+void map_default_merge_params(sicp_map_merge_params* p);
+int map_merge(sicp_map_ctx* dst, sicp_map_ctx* src, const double* qt, const sicp_map_merge_params* p, sicp_map_merge_info* info);
+int map_get_state(sicp_map_ctx* m, int64_t capacity, uint64_t* key, double* sums, uint32_t* count, uint32_t* hist, int64_t* n_rows);
+int map_set_state(sicp_map_ctx* m, int64_t n, const uint64_t* key, const double* sums, const uint32_t* count, const uint32_t* hist);
 // sicp_place_* (place.cpp): the database of scan descriptors
 void place_default_params(sicp_place_params* p);
 int place_create(int device_id, const sicp_place_params* p, sicp_place_ctx** out);

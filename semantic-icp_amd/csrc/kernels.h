@@ -716,6 +716,39 @@ struct MapFuseArgs {
 };
 hipError_t launch_map_posterior(const MapFuseArgs& a, hipStream_t st);  // olabel, oconf of the selected rows
 hipError_t launch_map_relabel(const MapFuseArgs& a, hipStream_t st);    // olabel, oconf of the n points; res[kMapBadLabel]
+// one map into another at a pose (sicp_map_merge; map_merge_kernels.hip).  SRC's rows are the items: one lane per row moves its
+// sums by the pose in double, keys the float centroid of the moved sums on DST's grid, and the (key, row) pairs are sorted -- a
+// stable sort, so rows ascend inside a run of equal keys.  The runs' heads are a sorted list of distinct keys, which is what
+// integrate's rank merge takes (launch_map_lookup / _misses / _scatter / _move_hist, through a MapFoldArgs).  Then one lane per
+// touched dst row continues its sums with the run's moved sums in ascending src row, and a second launch, parallel over
+// (touched row, bin), adds the run's histogram rows: consecutive lanes read consecutive bins of one src row.
+struct MapMergeArgs {
+  int n;                    // src rows
+  int n_map, n_new;         // dst rows before the call; rows it opens (known after the first read-back)
+  int n_runs, n_kept;       // touched dst rows; kept src rows (the sorted pairs before the dropped ones): after the read-back
+  int stride;               // dst's num_classes + 1 (= src's); 0: dst keeps no labels and src's histograms are not read
+  int crop;
+  long long min_count;
+  double M[12];
+  float inv_leaf, cx, cy, cz;  // dst's 1.0f / (float)leaf_size; (float)crop_center
+  double range_sq;
+  MapRows src;
+  double *mx, *my, *mz;     // [n] the moved sums by src row (written for every row with min_count points)
+  unsigned long long* key;  // [n] the dst key of src row r, ~0 for a row that takes no part
+  int* val;                 // [n] r
+  const unsigned long long* skey;  // the pairs sorted
+  const int* sval;
+  const int *flag, *pos;    // launch_merge_heads' flags and their exclusive scan
+  int* heads;               // [n] first sorted position of every run
+  const int *rank, *mpos;   // launch_map_lookup's and the scan of its misses: run k's dst row is rank[k] + mpos[k]
+  unsigned long long* kept_points;  // the sum of the kept rows' counts (zeroed before the launch)
+  int* res;                 // kMapRes words, zeroed: kMapRange (keys), kMapKept / kMapScanVoxels (runs), kMapMaxCount (sums: the longest run)
+  MapRows to;               // dst's spare set, after launch_map_scatter
+};
+hipError_t launch_map_merge_keys(const MapMergeArgs& a, hipStream_t st);       // mx my mz, key, val, kept_points, res[kMapRange]
+hipError_t launch_map_merge_runs(const MapMergeArgs& a, hipStream_t st);       // heads, res[kMapKept, kMapScanVoxels]
+hipError_t launch_map_merge_fold_sums(const MapMergeArgs& a, hipStream_t st);  // to.{sums, cnt} of the touched rows, res[kMapMaxCount]
+hipError_t launch_map_merge_fold_hist(const MapMergeArgs& a, hipStream_t st);  // to.hist of the touched rows
 
 // ---- initial alignment without a pose prior (bootstrap_kernels.hip; driver: bootstrap.cpp) ----
 constexpr int kBootMaxK = 16;  // feature neighbours per source keypoint (k_correspondences)

@@ -1,7 +1,7 @@
 // map.cpp -- sicp_map_* (include/sicp.h): a voxel map that lives on the device between calls.  Its rows (kernels.h: MapRows)
 // lie sorted by key in one of two sets of arena buffers.  A call that changes the map -- integrate, prune -- computes into the
 // spare set and swaps only once the counts and flags have been read back clean, so a refused call leaves the map as it was by
-// construction.  The kernels: map_kernels.hip, merge's heads and gather launches, the rocPRIM wrappers.
+// construction.  The kernels: map_kernels.hip, map_merge_kernels.hip, merge's heads and gather launches, the rocPRIM wrappers.
 #include "engine.hpp"
 
 namespace sicp {
@@ -23,7 +23,7 @@ struct MapScratch {
   DevBuf<unsigned char> temp;
   DevBuf<float> tx, ty, tz, gx, gy, gz, ox, oy, oz;
   DevBuf<uint32_t> ol, oc, ohist;
-  DevBuf<double> oconf;
+  DevBuf<double> oconf, mx, my, mz;
   DevBuf<unsigned long long> key, key2, miss_key, total, stat;
   DevBuf<int> val, val2, flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res, ray_hit;
   DevBuf<uint32_t> ray_miss;
@@ -31,7 +31,7 @@ struct MapScratch {
   bool idle = true;
   ~MapScratch() {
     DevArena::release_scratch(device, idle, temp, tx, ty, tz, gx, gy, gz, ox, oy, oz, ol, oc, ohist, oconf, key, key2, miss_key, total, stat,
-                              val, val2, flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res, ray_hit, ray_miss);
+                              val, val2, flag, pos, heads, rank, miss, mpos, miss_rank, src_of, res, ray_hit, ray_miss, mx, my, mz);
   }
 };
 
@@ -952,6 +952,277 @@ int map_fused_labels(sicp_map_ctx* m, sicp_context* h, int which, const double* 
       if (out_confidence) out_confidence[c.keep[i]] = conf[i];
     }
   }
+  return SICP_OK;
+}
+
+void map_default_merge_params(sicp_map_merge_params* p) {
+  std::memset(p, 0, sizeof *p);
+  p->min_count = 1;
+}
+
+// sicp_map_merge (include/sicp.h, "fusing maps"): src's rows are keyed on dst's grid and sorted, their runs go through
+// integrate's rank merge into dst's spare set, and two fold launches add the runs' sums and histograms.  `m` is dst; src is
+// only read (both maps are idle between calls, so dst's stream may read src's rows).
+int map_merge(sicp_map_ctx* m, sicp_map_ctx* src, const double* qt, const sicp_map_merge_params* p, sicp_map_merge_info* info) {
+  if (!m) return SICP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const std::string& why) {
+    m->last_error = "sicp_map_merge: " + why + "; dst is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (!src) return refuse("src is NULL");
+  if (src == m) return refuse("src and dst are the same map");
+  if (src->device != m->device) return refuse("src is on device " + std::to_string(src->device) + ", dst on " + std::to_string(m->device));
+  sicp_map_merge_params P;
+  if (p) P = *p; else map_default_merge_params(&P);
+  if (P.min_count < 1) return refuse("min_count must be >= 1");
+  if (!(P.crop_range >= 0.0)) return refuse("crop_range must be >= 0 (+inf is allowed)");
+  for (int d = 0; d < 3; ++d)
+    if (!std::isfinite(P.crop_center[d])) return refuse("crop_center must be finite");
+  if (qt)
+    for (int k = 0; k < 7; ++k)
+      if (!std::isfinite(qt[k])) return refuse("the pose is not finite");
+  const int C = m->params.num_classes, stride = stride_of(m);
+  if (C > 0 && src->params.num_classes != C)
+    return refuse("src keeps " + std::to_string(src->params.num_classes) + " classes, dst " + std::to_string(C));
+  const double t_begin = now_ms();
+  const int n = (int)src->n_voxels;
+  const int n_map = (int)m->n_voxels;
+  sicp_map_merge_info I;
+  std::memset(&I, 0, sizeof I);
+  I.n_src_rows = n;
+  I.n_voxels = m->n_voxels;
+  if (n == 0) {
+    I.t_total_ms = now_ms() - t_begin;
+    if (info) *info = I;
+    return SICP_OK;
+  }
+  MAPCHECK(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  StageLog log(log_enabled(), st);
+  MapScratch X;
+  X.device = m->device;
+  X.idle = false;
+  const size_t np = (size_t)n;
+  MAPCHECK(m->stage.resize(sizeof(int) * sicp::kMapRes + sizeof(unsigned long long)));
+  MAPCHECK(X.mx.reserve(np)); MAPCHECK(X.my.reserve(np)); MAPCHECK(X.mz.reserve(np));
+  MAPCHECK(X.key.reserve(np)); MAPCHECK(X.key2.reserve(np));
+  MAPCHECK(X.val.reserve(np)); MAPCHECK(X.val2.reserve(np));
+  MAPCHECK(X.flag.reserve(np)); MAPCHECK(X.pos.reserve(np)); MAPCHECK(X.heads.reserve(np));
+  MAPCHECK(X.rank.reserve(np)); MAPCHECK(X.miss.reserve(np)); MAPCHECK(X.mpos.reserve(np));
+  MAPCHECK(X.miss_key.reserve(np)); MAPCHECK(X.miss_rank.reserve(np));
+  MAPCHECK(X.res.reserve(sicp::kMapRes)); MAPCHECK(X.total.reserve(1));
+  size_t pair_bytes = 0, scan_bytes = 0;
+  MAPCHECK(sicp::prim_sort_pairs(nullptr, pair_bytes, X.key.p, X.key2.p, X.val.p, X.val2.p, n, 0, 64, st));
+  MAPCHECK(sicp::prim_scan_int(nullptr, scan_bytes, X.flag.p, X.pos.p, n, st));
+  MAPCHECK(X.temp.reserve(std::max(pair_bytes, scan_bytes) + 256));
+
+  const Crop crop = make_crop(P.crop_center, P.crop_range);
+  const double ident[7] = {0, 0, 0, 1, 0, 0, 0};
+  sicp_map_ctx::Rows& cur = m->rows[m->cur];
+  sicp_map_ctx::Rows& spare = m->rows[m->cur ^ 1];
+  sicp::MapMergeArgs A;
+  std::memset(&A, 0, sizeof A);
+  A.n = n; A.n_map = n_map; A.stride = stride;
+  A.crop = crop.on; A.min_count = P.min_count;
+  matrix34(qt ? qt : ident, A.M);
+  A.inv_leaf = 1.0f / (float)m->params.leaf_size;
+  A.cx = crop.c[0]; A.cy = crop.c[1]; A.cz = crop.c[2];
+  A.range_sq = crop.range_sq;
+  A.src = rows_of(src->rows[src->cur], stride > 0);
+  A.mx = X.mx.p; A.my = X.my.p; A.mz = X.mz.p;
+  A.key = X.key.p; A.val = X.val.p;
+  A.skey = X.key2.p; A.sval = X.val2.p;
+  A.flag = X.flag.p; A.pos = X.pos.p; A.heads = X.heads.p;
+  A.rank = X.rank.p; A.mpos = X.mpos.p;
+  A.kept_points = X.total.p; A.res = X.res.p;
+  sicp::MergeReduceArgs R;  // (the flags of the runs' first pairs: merge's heads launch)
+  std::memset(&R, 0, sizeof R);
+  R.n = n; R.voxel = 1;
+  R.skey = X.key2.p; R.flag = X.flag.p;
+  sicp::MapFoldArgs F;  // (the runs' keys among dst's: integrate's rank merge)
+  std::memset(&F, 0, sizeof F);
+  F.n = n; F.n_map = n_map; F.n_new = 0; F.stride = stride;
+  F.skey = X.key2.p; F.heads = X.heads.p;
+  F.rank = X.rank.p; F.miss = X.miss.p; F.mpos = X.mpos.p;
+  F.miss_key = X.miss_key.p; F.miss_rank = X.miss_rank.p;
+  F.res = X.res.p;
+  F.from = rows_of(cur, stride > 0);
+
+  log.mark("begin");
+  MAPCHECK(hipMemsetAsync(X.res.p, 0, sizeof(int) * sicp::kMapRes, st));
+  MAPCHECK(hipMemsetAsync(X.total.p, 0, sizeof(unsigned long long), st));
+  MAPCHECK(sicp::launch_map_merge_keys(A, st));
+  log.mark("key");
+  MAPCHECK(sicp::prim_sort_pairs(X.temp.p, pair_bytes, X.key.p, X.key2.p, X.val.p, X.val2.p, n, 0, 64, st));
+  log.mark("sort");
+  MAPCHECK(sicp::launch_merge_heads(R, st));
+  MAPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, X.flag.p, X.pos.p, n, st));
+  MAPCHECK(sicp::launch_map_merge_runs(A, st));
+  log.mark("runs");
+  MAPCHECK(sicp::launch_map_lookup(F, st));
+  MAPCHECK(sicp::prim_scan_int(X.temp.p, scan_bytes, X.miss.p, X.mpos.p, n, st));
+  MAPCHECK(sicp::launch_map_misses(F, st));
+  log.mark("lookup");
+  int res[sicp::kMapRes];
+  unsigned long long kept_points = 0;
+  MAPCHECK(hipMemcpyAsync(m->stage.data(), X.res.p, sizeof res, hipMemcpyDeviceToHost, st));
+  MAPCHECK(hipMemcpyAsync(m->stage.data() + sizeof res, X.total.p, sizeof kept_points, hipMemcpyDeviceToHost, st));
+  MAPCHECK(hipStreamSynchronize(st));
+  std::memcpy(res, m->stage.data(), sizeof res);
+  std::memcpy(&kept_points, m->stage.data() + sizeof res, sizeof kept_points);
+  X.idle = true;
+  // every refusal lies before the first write to a row
+  if (res[sicp::kMapRange])
+    return refuse("dst's leaf size " + std::to_string(m->params.leaf_size) + " is too small for the moved rows: a voxel coordinate reaches 2^20");
+  const int n_kept = res[sicp::kMapKept], n_runs = res[sicp::kMapScanVoxels], n_new = res[sicp::kMapNew];
+  I.n_kept_rows = n_kept;
+  I.n_kept_points = (int64_t)kept_points;
+  I.n_touched = n_runs;
+  I.n_new_voxels = n_new;
+  if (n_kept == 0) {
+    I.t_total_ms = now_ms() - t_begin;
+    if (info) *info = I;
+    return SICP_OK;
+  }
+  if (m->n_voxels + (long long)n_new > 0x7fffffffll) return refuse("dst would hold more than 2^31 - 1 voxels");
+  if (m->n_points + kept_points > 0xffffffffull) return refuse("dst would hold more than 2^32 - 1 points");
+  const size_t rows = (size_t)n_map + (size_t)n_new;
+  X.idle = false;
+  MAPCHECK(reserve_rows(spare, rows, stride));
+  MAPCHECK(X.src_of.reserve(rows));
+  F.n_new = n_new;
+  F.src_of = X.src_of.p;
+  F.to = rows_of(spare, stride > 0);
+  A.n_new = n_new; A.n_runs = n_runs; A.n_kept = n_kept;
+  A.to = F.to;
+  MAPCHECK(sicp::launch_map_scatter(F, st));
+  if (stride > 0) MAPCHECK(sicp::launch_map_move_hist(F.from.hist, F.to.hist, F.src_of, (long long)rows, stride, st));
+  log.mark("scatter");
+  MAPCHECK(sicp::launch_map_merge_fold_sums(A, st));
+  log.mark("fold_sums");
+  if (stride > 0) {
+    MAPCHECK(sicp::launch_map_merge_fold_hist(A, st));
+    log.mark("fold_hist");
+  }
+  MAPCHECK(hipMemcpyAsync(m->stage.data(), X.res.p, sizeof res, hipMemcpyDeviceToHost, st));
+  MAPCHECK(hipStreamSynchronize(st));
+  std::memcpy(res, m->stage.data(), sizeof res);
+  X.idle = true;
+  m->cur ^= 1;
+  m->n_voxels = (long long)rows;
+  m->n_points += kept_points;
+  I.max_run = res[sicp::kMapMaxCount];
+  I.n_voxels = m->n_voxels;
+  log.print("sicp_map_merge: n_src=" + std::to_string(n) + " n_kept=" + std::to_string(n_kept) + " n_map=" + std::to_string(n_map) +
+            " n_touched=" + std::to_string(n_runs) + " n_new=" + std::to_string(n_new));
+  I.t_total_ms = now_ms() - t_begin;
+  if (info) *info = I;
+  return SICP_OK;
+}
+
+// sicp_map_get_state: the stored rows through pinned memory -- key | sx | sy | sz (the 8-byte arrays first) | count | hist
+int map_get_state(sicp_map_ctx* m, int64_t capacity, uint64_t* key, double* sums, uint32_t* count, uint32_t* hist, int64_t* n_rows) {
+  if (!m) return SICP_ERR_INVALID_ARGUMENT;
+  const long long n = m->n_voxels;
+  if (n_rows) *n_rows = n;
+  auto refuse = [&](const std::string& why) {
+    m->last_error = "sicp_map_get_state: " + why + "; no array was written";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  const int stride = stride_of(m);
+  if (hist && stride == 0) return refuse("the map keeps no labels: there are no histograms");
+  const bool want_arrays = key || sums || count || hist;
+  if (want_arrays && capacity < n) return refuse("the map has " + std::to_string(n) + " rows, the arrays hold " + std::to_string(capacity));
+  if (!want_arrays || n == 0) return SICP_OK;
+  MAPCHECK(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  const size_t nr = (size_t)n;
+  const size_t hist_words = hist ? nr * (size_t)stride : 0;
+  MAPCHECK(m->out.resize(9 * nr + hist_words));
+  uint32_t* const o = m->out.data();
+  sicp_map_ctx::Rows& cur = m->rows[m->cur];
+  if (key) MAPCHECK(hipMemcpyAsync(o, cur.key.p, 8 * nr, hipMemcpyDeviceToHost, st));
+  if (sums) {
+    MAPCHECK(hipMemcpyAsync(o + 2 * nr, cur.sx.p, 8 * nr, hipMemcpyDeviceToHost, st));
+    MAPCHECK(hipMemcpyAsync(o + 4 * nr, cur.sy.p, 8 * nr, hipMemcpyDeviceToHost, st));
+    MAPCHECK(hipMemcpyAsync(o + 6 * nr, cur.sz.p, 8 * nr, hipMemcpyDeviceToHost, st));
+  }
+  if (count) MAPCHECK(hipMemcpyAsync(o + 8 * nr, cur.cnt.p, 4 * nr, hipMemcpyDeviceToHost, st));
+  if (hist) MAPCHECK(hipMemcpyAsync(o + 9 * nr, cur.hist.p, 4 * hist_words, hipMemcpyDeviceToHost, st));
+  MAPCHECK(hipStreamSynchronize(st));
+  if (key) std::memcpy(key, o, 8 * nr);
+  if (sums) {
+    const double* s = reinterpret_cast<const double*>(o + 2 * nr);
+    for (size_t r = 0; r < nr; ++r) {
+      sums[3 * r + 0] = s[r]; sums[3 * r + 1] = s[nr + r]; sums[3 * r + 2] = s[2 * nr + r];
+    }
+  }
+  if (count) std::memcpy(count, o + 8 * nr, 4 * nr);
+  if (hist) std::memcpy(hist, o + 9 * nr, 4 * hist_words);
+  return SICP_OK;
+}
+
+// sicp_map_set_state: every row is checked on the host, then the arrays go up through pinned memory into the spare set
+int map_set_state(sicp_map_ctx* m, int64_t n, const uint64_t* key, const double* sums, const uint32_t* count, const uint32_t* hist) {
+  if (!m) return SICP_ERR_INVALID_ARGUMENT;
+  auto refuse = [&](const std::string& why) {
+    m->last_error = "sicp_map_set_state: " + why + "; the map is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  const int stride = stride_of(m);
+  if (n < 0) return refuse("n is negative");
+  if (n > 0x7fffffffll) return refuse("more than 2^31 - 1 rows");
+  if (hist && stride == 0) return refuse("the map keeps no labels: it takes no histograms");
+  if (n > 0 && (!key || !sums || !count)) return refuse("key, sums or count is NULL");
+  if (n > 0 && stride > 0 && !hist) return refuse("hist is NULL and the map keeps " + std::to_string(m->params.num_classes) + " classes");
+  const size_t nr = (size_t)n;
+  unsigned long long points = 0;
+  for (size_t r = 0; r < nr; ++r) {
+    const std::string row = "row " + std::to_string(r);
+    const uint64_t k = key[r];
+    if (r > 0 && !(key[r - 1] < k)) return refuse(row + ": the keys do not ascend strictly");
+    if ((k >> 63) != 0 || (k & 0x1fffffull) == 0 || ((k >> 21) & 0x1fffffull) == 0 || ((k >> 42) & 0x1fffffull) == 0)
+      return refuse(row + ": no point has the key " + std::to_string(k) + " (its top bit is set or a 21-bit field is 0)");
+    if (count[r] == 0u) return refuse(row + ": the count is 0");
+    for (int d = 0; d < 3; ++d)
+      if (!std::isfinite(sums[3 * r + d])) return refuse(row + ": a sum is not finite");
+    if (stride > 0) {
+      unsigned long long h = 0;
+      for (int b = 0; b < stride; ++b) h += hist[r * (size_t)stride + b];
+      if (h != count[r]) return refuse(row + ": the histogram adds up to " + std::to_string(h) + ", the count is " + std::to_string(count[r]));
+    }
+    points += count[r];
+    if (points > 0xffffffffull) return refuse(row + ": more than 2^32 - 1 points up to this row");
+  }
+  if (n == 0) {
+    m->n_voxels = 0;
+    m->n_points = 0;
+    return SICP_OK;
+  }
+  MAPCHECK(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  sicp_map_ctx::Rows& spare = m->rows[m->cur ^ 1];
+  const size_t hist_words = nr * (size_t)stride;
+  MAPCHECK(m->out.resize(9 * nr + hist_words));
+  MAPCHECK(reserve_rows(spare, nr, stride));
+  uint32_t* const o = m->out.data();
+  std::memcpy(o, key, 8 * nr);
+  double* const s = reinterpret_cast<double*>(o + 2 * nr);
+  for (size_t r = 0; r < nr; ++r) {
+    s[r] = sums[3 * r + 0]; s[nr + r] = sums[3 * r + 1]; s[2 * nr + r] = sums[3 * r + 2];
+  }
+  std::memcpy(o + 8 * nr, count, 4 * nr);
+  if (stride > 0) std::memcpy(o + 9 * nr, hist, 4 * hist_words);
+  MAPCHECK(hipMemcpyAsync(spare.key.p, o, 8 * nr, hipMemcpyHostToDevice, st));
+  MAPCHECK(hipMemcpyAsync(spare.sx.p, o + 2 * nr, 8 * nr, hipMemcpyHostToDevice, st));
+  MAPCHECK(hipMemcpyAsync(spare.sy.p, o + 4 * nr, 8 * nr, hipMemcpyHostToDevice, st));
+  MAPCHECK(hipMemcpyAsync(spare.sz.p, o + 6 * nr, 8 * nr, hipMemcpyHostToDevice, st));
+  MAPCHECK(hipMemcpyAsync(spare.cnt.p, o + 8 * nr, 4 * nr, hipMemcpyHostToDevice, st));
+  if (stride > 0) MAPCHECK(hipMemcpyAsync(spare.hist.p, o + 9 * nr, 4 * hist_words, hipMemcpyHostToDevice, st));
+  MAPCHECK(hipStreamSynchronize(st));
+  m->cur ^= 1;
+  m->n_voxels = n;
+  m->n_points = points;
   return SICP_OK;
 }
 

@@ -941,6 +941,26 @@ int sicp_map_fused_labels(sicp_map m, sicp_handle h, int which, const double qt[
   });
 }
 
+int sicp_default_map_merge_params(sicp_map_merge_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    map_default_merge_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_map_merge(sicp_map dst, sicp_map src, const double qt[7], const sicp_map_merge_params* p, sicp_map_merge_info* info) {
+  return abi_guard(dst, [&]() -> int { return map_merge(dst, src, qt, p, info); });
+}
+
+int sicp_map_get_state(sicp_map m, int64_t capacity, uint64_t* key, double* sums, uint32_t* count, uint32_t* hist, int64_t* n_rows) {
+  return abi_guard(m, [&]() -> int { return map_get_state(m, capacity, key, sums, count, hist, n_rows); });
+}
+
+int sicp_map_set_state(sicp_map m, int64_t n, const uint64_t* key, const double* sums, const uint32_t* count, const uint32_t* hist) {
+  return abi_guard(m, [&]() -> int { return map_set_state(m, n, key, sums, count, hist); });
+}
+
 int sicp_default_place_params(sicp_place_params* p) {
   return abi_guard([&]() -> int {
     if (!p) return SICP_ERR_INVALID_ARGUMENT;
