@@ -656,6 +656,79 @@ int sicp_cluster(sicp_handle h, int which, const sicp_cluster_params* p, int32_t
                  int32_t capacity, uint32_t* label, int32_t* count, int32_t* first_index, double* centroid /* 3 per cluster */,
                  float* bbox_min, float* bbox_max /* 3 per cluster each; all nullable */, sicp_cluster_info* info /* nullable */);
 
+/* ---- filtering a cloud -----------------------------------------------------------
+ * Removes points from the cloud in a handle's slot: the statistical outlier test (pcl::StatisticalOutlierRemoval, Open3D's
+ * remove_statistical_outlier), the radius outlier test (pcl::RadiusOutlierRemoval, remove_radius_outlier), a caller's mask and
+ * label lists, in one call; the kept points can become a slot's cloud without leaving the device's side of the library.  The
+ * handle may be in any mode.
+ *  1. Classes.  A point is REMOVED when it is not finite, when mask is given and mask[i] == 0, or when its label is one of
+ *     drop[0 .. n_drop); otherwise it is PROTECTED when its label is one of protect[0 .. n_protect); otherwise it is TESTED.  A
+ *     label in both lists is refused.  A cloud set without labels is accepted only with both lists empty (rule 5 of
+ *     sicp_cluster).
+ *  2. Neighbours are the finite points of the cloud, whatever their class (PCL's filters with indices: the searcher sees the
+ *     whole input, the indices are judged).
+ *  3. Statistical test (mean_k > 0).  For a tested point i take the mean_k + 1 smallest float32 squared distances from p_i to
+ *     the finite points, p_i included -- d2 = (dx dx + dy dy) + dz dz in float, every operation rounded on its own (rule 2 of
+ *     sicp_cluster) -- in ascending order, and leave the first out.  m_i = (sum of (double)sqrtf(d2_j)) / (double)mean_k: the
+ *     float roots correctly rounded, the terms added to a double in ascending order.  Only values enter: ties need no order.
+ *     S1 = sum m_i and S2 = sum m_i m_i over the tested points are sums over the perfect binary tree on the caller's indices
+ *     0 .. 2^ceil(log2 n_points) - 1: absent entries are +0.0, and level by level s[j] = s[2 j] + s[2 j + 1].  mean = S1 /
+ *     n_tested; var = max(0, (S2 - S1 S1 / n_tested) / (n_tested - 1)); threshold = mean + std_mul sqrt(var) -- double
+ *     operations, each rounded on its own, none contracted.  The point passes when m_i <= threshold.  Fewer than mean_k + 1
+ *     finite points, or fewer than 2 tested points: SICP_ERR_TOO_FEW_POINTS.
+ *  4. Radius test (radius > 0).  c_i = the number of finite j != i with d2 < r2, strict, r2 = (float)radius * (float)radius in
+ *     float (the edge rule of sicp_cluster).  The point passes when c_i >= min_neighbors.  neighbors[i] = min(c_i,
+ *     min_neighbors): counting stops at the answer.  A point whose cell of the internal search grid (edge: a hair above the
+ *     radius) has a coordinate of 2^20 - 1 or more in magnitude: SICP_ERR_INVALID_ARGUMENT, the text names the radius (rule 9 of
+ *     sicp_cluster).
+ *  5. Both tests judge the same set: a tested point is kept when it passes every test that is on.  With both off the call is
+ *     a pure selection by mask and labels.
+ *  6. Outputs, all nullable, n_points long, caller order.  keep[i]: 1 for kept and protected points, else 0.  mean_dist[i]:
+ *     m_i; NaN for a point that is not tested, and for every point when the statistical test is off.  neighbors[i]: as in 4;
+ *     -1 for a point that is not tested, and for every point when the radius test is off.
+ *  7. info: the counts -- n_fail_stat and n_fail_radius each on its own, a point may be in both -- and mean, stddev =
+ *     sqrt(var), threshold (NaN when the statistical test is off).
+ *  8. dst (nullable; needs the same device; may be h with dst_which = which: the cloud is filtered in place).  The kept points in
+ *     ascending caller index, with their labels, become the cloud of dst's slot, exactly as sicp_set_cloud of those arrays
+ *     would set it.  An empty result with dst: SICP_ERR_TOO_FEW_POINTS and dst keeps its cloud (the merge's rule).
+ *  9. Every refusal leaves the output arrays, info and dst as they were.  Without dst, or with another handle as dst, nothing h
+ *     holds for sicp_align changes -- correspondences, features, statistics, timers -- and a later sicp_align returns the bytes it
+ *     returns on a handle that never made the call.  The slot holds no cloud: SICP_ERR_NOT_READY.  Refused before any device
+ *     work with SICP_ERR_INVALID_ARGUMENT: a NULL handle or params; a `which` (or, with dst, a dst_which) outside SICP_SOURCE /
+ *     SICP_TARGET; mean_k outside 0 .. 31; std_mul or radius negative or not finite; min_neighbors < 1 with the radius test on;
+ *     n_drop or n_protect outside 0 .. SICP_FILTER_MAX_LABELS; a label in both lists; lists with a cloud without labels; dst on
+ *     another device.
+ * 10. Bit-reproducible: a function of the points, labels, mask and parameters only -- the same bytes on a handle of any mode (a
+ *     SICP_MODE_SEMANTIC handle searches the cloud label by label and merges the lists by value), in either slot, before or
+ *     after a sicp_align has laid the cloud out, for every launch shape.  No float atomics. */
+#define SICP_FILTER_MAX_LABELS 16
+typedef struct sicp_filter_params {
+  int32_t mean_k;         /* 0 = statistical test off; 1 .. 31.  default 20 */
+  int32_t min_neighbors;  /* other points needed inside radius; >= 1 when the radius test is on.  default 2 */
+  double std_mul;         /* threshold = mean + std_mul * stddev; finite, >= 0.  default 2.0 */
+  double radius;          /* 0 = radius test off (default); finite, >= 0 */
+  int32_t n_drop;         /* 0 .. SICP_FILTER_MAX_LABELS.  default 0 */
+  int32_t n_protect;      /* 0 .. SICP_FILTER_MAX_LABELS.  default 0 */
+  uint32_t drop[SICP_FILTER_MAX_LABELS];     /* labels removed outright */
+  uint32_t protect[SICP_FILTER_MAX_LABELS];  /* labels kept without being tested */
+} sicp_filter_params;
+typedef struct sicp_filter_info {
+  int64_t n_points;       /* what the caller handed over (the size of keep, mean_dist, neighbors) */
+  int64_t n_finite;
+  int64_t n_tested;
+  int64_t n_protected;
+  int64_t n_kept;         /* protected points and tested points that passed */
+  int64_t n_fail_stat;    /* tested points with m_i > threshold */
+  int64_t n_fail_radius;  /* tested points with c_i < min_neighbors */
+  double mean, stddev, threshold;  /* NaN when the statistical test is off */
+  double t_total_ms;      /* host wall clock */
+} sicp_filter_info;
+int sicp_default_filter_params(sicp_filter_params* p);
+int sicp_filter(sicp_handle h, int which, const sicp_filter_params* p, const uint8_t* mask /* n_points, nullable */,
+                sicp_handle dst /* nullable */, int dst_which, uint8_t* keep /* n_points, nullable */,
+                double* mean_dist /* n_points, nullable */, int32_t* neighbors /* n_points, nullable */,
+                sicp_filter_info* info /* nullable */);
+
 /* ---- a persistent voxel map ---------------------------------------------------
  * The map of scan-to-map odometry as an object that lives on the device between calls: per occupied voxel of the absolute
  * grid of the merge above (v = floor(p * (1.0f / (float)leaf_size)), |v| < 2^20) its 63-bit key (three biased 21-bit

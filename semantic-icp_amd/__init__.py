@@ -270,6 +270,43 @@ class SicpClusterInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+FILTER_MAX_LABELS = 16
+
+
+class SicpFilterParams(C.Structure):
+    """sicp_filter_params (include/sicp.h)"""
+    _fields_ = [
+        ("mean_k", C.c_int32),
+        ("min_neighbors", C.c_int32),
+        ("std_mul", C.c_double),
+        ("radius", C.c_double),
+        ("n_drop", C.c_int32),
+        ("n_protect", C.c_int32),
+        ("drop", C.c_uint32 * FILTER_MAX_LABELS),
+        ("protect", C.c_uint32 * FILTER_MAX_LABELS),
+    ]
+
+
+class SicpFilterInfo(C.Structure):
+    """sicp_filter_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_points", C.c_int64),
+        ("n_finite", C.c_int64),
+        ("n_tested", C.c_int64),
+        ("n_protected", C.c_int64),
+        ("n_kept", C.c_int64),
+        ("n_fail_stat", C.c_int64),
+        ("n_fail_radius", C.c_int64),
+        ("mean", C.c_double),
+        ("stddev", C.c_double),
+        ("threshold", C.c_double),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class SicpMapParams(C.Structure):
     """sicp_map_params (include/sicp.h)"""
     _fields_ = [
@@ -663,6 +700,9 @@ def lib():
             "sicp_default_cluster_params": [C.POINTER(SicpClusterParams)],
             "sicp_cluster": [C.c_void_p, C.c_int, C.POINTER(SicpClusterParams), _ip, C.c_int32, _up, _ip, _ip, _dp, _fp, _fp,
                              C.POINTER(SicpClusterInfo)],
+            "sicp_default_filter_params": [C.POINTER(SicpFilterParams)],
+            "sicp_filter": [C.c_void_p, C.c_int, C.POINTER(SicpFilterParams), _bp, C.c_void_p, C.c_int, _bp, _dp, _ip,
+                            C.POINTER(SicpFilterInfo)],
             "sicp_default_map_params": [C.POINTER(SicpMapParams)],
             "sicp_default_map_extract_params": [C.POINTER(SicpMapExtractParams)],
             "sicp_map_create": [C.c_int, C.POINTER(SicpMapParams), C.POINTER(C.c_void_p)],
@@ -823,6 +863,27 @@ def default_cluster_params(ignore=(), **overrides) -> SicpClusterParams:
         p.ignore[k] = v
     for k, v in overrides.items():
         if not hasattr(p, k) or k == "ignore":
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_filter_params(drop=(), protect=(), **overrides) -> SicpFilterParams:
+    """sicp_default_filter_params (mean_k 20, std_mul 2.0, radius test off, min_neighbors 2, empty lists), with the labels in
+    `drop` and `protect` (at most FILTER_MAX_LABELS each) and any other field overridden by keyword"""
+    p = SicpFilterParams()
+    st = lib().sicp_default_filter_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_filter_params")
+    for name, values in (("drop", drop), ("protect", protect)):
+        values = [int(v) for v in values]
+        if len(values) > FILTER_MAX_LABELS:
+            raise ValueError(f"at most {FILTER_MAX_LABELS} labels can be in {name}")
+        setattr(p, "n_" + name, len(values))
+        for k, v in enumerate(values):
+            getattr(p, name)[k] = v
+    for k, v in overrides.items():
+        if not hasattr(p, k) or k in ("drop", "protect"):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
@@ -1291,6 +1352,30 @@ class Engine:
                        _ptr(lo, _fp), _ptr(hi, _fp), C.byref(info)), "sicp_cluster")
         return {"cluster_id": cid[:int(info.n_points)], "label": lab[:k], "count": cnt[:k], "first_index": first[:k], "centroid": cen[:k],
                 "bbox_min": lo[:k], "bbox_max": hi[:k], "info": info.as_dict()}
+
+    def filter(self, which: int = SOURCE, params: SicpFilterParams | None = None, mask=None, dst: "Engine | None" = None,
+               dst_which: int | None = None):
+        """sicp_filter: which points of the cloud in slot `which` stay -- the statistical and radius outlier tests of `params` on
+        the points that `mask` ([n_points], 0 removes), the drop labels and the protect labels leave to be tested.  Returns
+        {"keep": [n_points] uint8, "mean_dist": float64 (NaN: not tested), "neighbors": int32 (-1: not tested), "info":
+        SicpFilterInfo.as_dict()}.  With dst the kept points become that Engine's slot dst_which (default: `which`) as if they
+        had been handed to set_cloud; dst may be this engine.  Without dst nothing on the engine changes."""
+        p = params if params is not None else default_filter_params()
+        n = self.n[which] if which in (SOURCE, TARGET) else 0
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.shape != (n,):
+                raise ValueError(f"mask must have one entry per point ({n})")
+        keep = np.empty(max(n, 1), dtype=np.uint8)
+        md = np.empty(max(n, 1), dtype=np.float64)
+        nb = np.empty(max(n, 1), dtype=np.int32)
+        info = SicpFilterInfo()
+        dw = which if dst_which is None else dst_which
+        self._check(lib().sicp_filter(self._h, which, C.byref(p), _ptr(mask, _bp), None if dst is None else dst._h, dw, _ptr(keep, _bp),
+                                      _ptr(md, _dp), _ptr(nb, _ip), C.byref(info)), "sicp_filter")
+        if dst is not None:
+            dst.n[dw] = int(info.n_kept)
+        return {"keep": keep[:n], "mean_dist": md[:n], "neighbors": nb[:n], "info": info.as_dict()}
 
     def solve(self, init_qt):
         init = np.ascontiguousarray(init_qt, dtype=np.float64)

@@ -29,7 +29,9 @@ struct ClusterScratch {
   }
 };
 
-// the largest float inv with inv * t <= 1, decided on the exact double product (cluster_kernels.hip: the proof, step 2); 0 -- one
+}  // namespace
+
+// the largest float inv with inv * t <= 1, decided on the exact double product (cell_grid.hpp: the proof, step 2); 0 -- one
 // cell for everything -- when no finite positive inverse exists
 float cells_per_metre(float t) {
   if (!(t > 0.f) || !std::isfinite(t)) return 0.f;
@@ -38,8 +40,6 @@ float cells_per_metre(float t) {
   while ((double)inv * (double)t > 1.0) inv = std::nextafterf(inv, 0.f);
   return inv;
 }
-
-}  // namespace
 
 void cluster_default_params(sicp_cluster_params* p) {
   std::memset(p, 0, sizeof *p);

@@ -6,31 +6,13 @@
 // order the centroid's float64 sums are specified in.  No floating-point atomics, no grid-wide barrier.
 #include <hip/hip_runtime.h>
 
+#include "cell_grid.hpp"  // the cells, their keys and the proof that neighbouring cells hold every joined pair
 #include "kernels.h"
 
 #pragma clang fp contract(off)
 
 namespace sicp {
 namespace {
-
-typedef unsigned long long u64;
-constexpr u64 kNone = ~0ull;
-constexpr int kCellBias = 1 << 20;
-
-// The grid is an accelerator, not the definition: it must put every joined pair into cells that differ by at most one per axis.
-//  (1) Rounding is monotone, so fl(dx dx) <= d2 (the two adds of non-negative terms never round below their first operand) and
-//      d2 < t2 = fl(t t) gives dx dx < t t, |dx| < t with dx = fl(px - qx); t is a float, so |px - qx| >= t would give
-//      |fl(px - qx)| >= t: hence |px - qx| < t in real numbers, with no rounding allowance left to make.
-//  (2) The host picks the largest float inv with inv t <= 1, tested on the exact product (double)inv (double)t.  u = (double)p
-//      (double)inv is exact too (24 x 24 bits), so |u_p - u_q| = inv |px - qx| < 1 holds in real numbers.
-//  (3) |u_p - u_q| < 1 gives |floor(u_p) - floor(u_q)| <= 1.  The same on y and z.
-// (floor(p * inv) in float, as voxel_key forms it, is off by up to |u| 2^-24 cells and would break (3) at large coordinates.)
-__device__ __forceinline__ bool cluster_cell(float p, float inv, int* c) {
-  const double v = floor(__dmul_rn((double)p, (double)inv));
-  if (!(fabs(v) < (double)kClusterCellLimit)) return false;
-  *c = (int)v;
-  return true;
-}
 
 __device__ __forceinline__ bool cluster_ignored(const ClusterArgs& a, uint32_t l) {
   bool ig = false;
@@ -75,7 +57,7 @@ __global__ __launch_bounds__(256) void cluster_key_kernel(ClusterArgs a) {
   if (vertex) {
     int cx, cy, cz;
     if (cluster_cell(a.x[i], a.inv, &cx) && cluster_cell(a.y[i], a.inv, &cy) && cluster_cell(a.z[i], a.inv, &cz))
-      k = ((u64)(unsigned)(cz + kCellBias) << 42) | ((u64)(unsigned)(cy + kCellBias) << 21) | (u64)(unsigned)(cx + kCellBias);
+      k = cell_key(cx, cy, cz);
     else
       a.res[kClRange] = 1;  // (a plain store: every writer stores the same 1)
   }
@@ -109,14 +91,6 @@ __global__ __launch_bounds__(256) void cluster_cells_kernel(ClusterArgs a) {
       a.heads[p + f] = j + 1;
     }
   }
-}
-
-__device__ __forceinline__ int lower_bound_key(const u64* k, int lo, int hi, u64 v) {  // first position in [lo, hi) with k >= v
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (k[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
 }
 
 // One workgroup per cell and 256 x gridDim.y of its points (blockIdx.y takes every gridDim.y-th chunk of 256, so that a dense

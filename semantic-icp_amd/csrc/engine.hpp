@@ -10,6 +10,7 @@
 //   evaluate.cpp  sicp_evaluate: overlap, inlier RMSE and label agreement at a pose
 //   merge.cpp     sicp_merge_clouds: posed clouds into one voxel-grid cloud
 //   cluster.cpp   sicp_cluster: label-aware Euclidean clustering of a cloud
+//   filter.cpp    sicp_filter: statistical / radius outlier removal and masked selection of a cloud
 //   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, raycast, prune, extract, merge, state)
 //   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
 //   sicp_api.cpp  the remaining C-ABI entry points
@@ -506,6 +507,10 @@ struct sicp_context : sicp_use_state {
   HostBuf<unsigned char> mg_stage;
   HostBuf<uint32_t> mg_out;
   HostBuf<unsigned char> cl_stage;  // pinned: counts, cluster_id and table of sicp_cluster on their way back (cluster.cpp)
+  // sicp_filter (filter.cpp): the pinned mask / caller indices on their way up and counts / per-point outputs on their way
+  // back, and the pinned kept points (x | y | z | label) on their way into dst
+  HostBuf<unsigned char> fl_stage;
+  HostBuf<uint32_t> fl_out;
   // lock-step batch (sicp_align_batch), owned by the batch's first handle: one BatchArgs and one LM
   // state per pair, pinned mirrors, and the captured [accumulate_batch, lm_step_batch] x lm_batch graph
   TickSet ts[2];  // two sets: the halves of a batch alternate, one's tick runs while the host turns the other around
@@ -768,6 +773,15 @@ struct StageLog {
   }
 };
 
+// the searches of a call that must leave the handle as it was (sicp_evaluate, sicp_filter) add to its counters and timers
+// (run_nn): the keeper gives them back as they were
+struct StatsKeeper {
+  sicp_context* h;
+  sicp_stats st;
+  explicit StatsKeeper(sicp_context* ctx) : h(ctx), st(ctx->st) {}
+  ~StatsKeeper() { h->st = st; }
+};
+
 int set_device(sicp_context* h);
 
 // ---- clouds.cpp ------------------------------------------------------------------------------------
@@ -992,6 +1006,12 @@ int merge_clouds(sicp_handle* parts, const int32_t* part_which, int32_t n_parts,
 void cluster_default_params(sicp_cluster_params* p);
 int cluster(sicp_context* h, int which, const sicp_cluster_params* p, int32_t* cluster_id, int32_t capacity, uint32_t* label,
             int32_t* count, int32_t* first_index, double* centroid, float* bbox_min, float* bbox_max, sicp_cluster_info* info);
+float cells_per_metre(float t);  // the grid's cells per metre for a tolerance / radius t (cluster.cpp)
+// sicp_filter (filter.cpp): argument checks, the searches and the mean-distance / tree-sum / radius-count / flag kernels on
+// the cloud's device copy, one read-back, and the kept points' way into dst (set_cloud_common)
+void filter_default_params(sicp_filter_params* p);
+int filter(sicp_context* h, int which, const sicp_filter_params* p, const uint8_t* mask, sicp_context* dst, int dst_which, uint8_t* keep,
+           double* mean_dist, int32_t* neighbors, sicp_filter_info* info);
 // sicp_map_* (map.cpp): the persistent voxel map
 void map_default_params(sicp_map_params* p);
 void map_default_extract_params(sicp_map_extract_params* p);

@@ -29,14 +29,6 @@ struct EvalScratch {
   ~EvalScratch() { DevArena::release_scratch(device, idle, args, res, part_sum, part_cnt, nn_idx, nn_d2); }
 };
 
-// the searches add to the handle's counters and timers (run_nn): an evaluation gives them back as they were
-struct StatsKeeper {
-  sicp_context* h;
-  sicp_stats st;
-  explicit StatsKeeper(sicp_context* ctx) : h(ctx), st(ctx->st) {}
-  ~StatsKeeper() { h->st = st; }
-};
-
 // what a pair must pass before anything is queued for it
 int evaluate_ready(sicp_context* h, bool table) {
   const Cloud &S = h->cloud(0), &T = h->cloud(1);

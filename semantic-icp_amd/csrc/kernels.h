@@ -548,6 +548,62 @@ hipError_t launch_cluster_ids(const ClusterArgs& a, hipStream_t st);        // c
 hipError_t launch_cluster_member_heads(const ClusterArgs& a, hipStream_t st);              // mheads
 hipError_t launch_cluster_table(const ClusterArgs& a, int n_clusters, hipStream_t st);    // the table: one wave per cluster
 
+// ---- outlier removal and masked selection (filter_kernels.hip; driver: filter.cpp) ----
+// sicp_filter: the finite points of one cloud in caller order (Cloud::rx ...; index f below is a position in that order, `caller`
+// maps it to the caller's index when points were dropped).  The cloud's own search trees give every query its distance list,
+// a lane per query turns it into the mean distance, a fixed binary tree over the caller's indices sums them, the cluster's
+// cell grid (launch_cluster_keys ... launch_cluster_cells with the radius as the tolerance) counts the neighbours inside the
+// radius, and a flag per point, its scan and a gather write the kept cloud.
+constexpr int kFilterMaxLabels = 16;  // SICP_FILTER_MAX_LABELS
+constexpr int kFilterTreeRun = 512;   // caller indices one workgroup of the tree sum reduces: a power of two
+enum { kFlTested = 0, kFlProtected = 1, kFlKept = 2, kFlFailStat = 3, kFlFailRadius = 4, kFlRes = 8 };
+enum { kFlRemoved = 0, kFlProtect = 1, kFlTest = 2 };  // a point's class (rule 1)
+struct FilterStats { double s1, s2, mean, stddev, threshold; };
+struct FilterArgs {
+  int n, n_caller;                 // finite points; points the caller handed over
+  int labels;                      // the cloud has labels
+  int mean_k, min_neighbors;       // mean_k = 0: the statistical test is off; min_neighbors = 0: the radius test is off
+  int n_drop, n_protect;
+  uint32_t drop[kFilterMaxLabels], protect[kFilterMaxLabels];
+  double std_mul;
+  float r2;                        // (float)radius * (float)radius
+  const float *x, *y, *z;          // [n] by f
+  const uint32_t* label;           // nullable
+  const int* caller;               // [n] f -> caller index; nullptr: the identity
+  const uint8_t* mask;             // [n_caller] nullable
+  const int* perm;                 // [n] device order -> f (Cloud::d_perm)
+  uint8_t* cls;                    // [n] kFlRemoved / kFlProtect / kFlTest by f
+  float *list, *list2;             // [n][list_k] ascending d2 per query in device order: the merged lists; one segment's
+  int list_k;                      // mean_k + 1
+  // the cell grid (ClusterArgs of the same names)
+  const int* heads;
+  const unsigned long long* ckey;
+  const float4* spt;
+  const int* sval;
+  const int* grid_res;             // the grid's kClRes words
+  int* nb;                         // [n] by f: min(neighbours inside the radius, min_neighbors), zeroed before the count
+  int *flag, *pos;                 // [n] kept flags by f and their exclusive scan
+  // outputs by caller index
+  uint8_t* okeep;                  // [n_caller]
+  double* omd;                     // [n_caller] NaN unless tested with the statistical test on
+  int* onb;                        // [n_caller] -1 unless tested with the radius test on
+  float *ox, *oy, *oz;             // [n] the kept points, ascending caller index
+  uint32_t* ol;
+  FilterStats* stats;
+  int* res;                        // kFlRes words, zeroed before the first launch
+};
+hipError_t launch_filter_classes(const FilterArgs& a, hipStream_t st);     // cls, okeep = 0, omd = NaN, onb = -1, res[tested, protected]
+hipError_t launch_filter_merge_lists(const FilterArgs& a, hipStream_t st); // list <- the list_k smallest of list and list2
+hipError_t launch_filter_mean_dist(const FilterArgs& a, hipStream_t st);   // omd of the tested points
+// one level of the tree sums: count entries -> ceil(count / kFilterTreeRun) partial sums.  first: the entries are omd (NaN is
+// an absent entry: +0.0), the sums are of m and of m m; else the entries are the partials in1 / in2
+hipError_t launch_filter_tree_sum(const double* in1, const double* in2, int count, int first, double* out1, double* out2, hipStream_t st);
+hipError_t launch_filter_threshold(const FilterArgs& a, const double* s1, const double* s2, hipStream_t st);  // stats
+hipError_t launch_filter_radius_count(const FilterArgs& a, hipStream_t st);  // nb: a workgroup per cell and chunk of its points
+hipError_t launch_filter_flags(const FilterArgs& a, hipStream_t st);       // flag, okeep, onb, res[fail stat, fail radius]
+// (prim_scan_int flag -> pos)
+hipError_t launch_filter_gather(const FilterArgs& a, hipStream_t st);      // ox oy oz ol, res[kept]
+
 // ---- the persistent voxel map (map_kernels.hip; driver: map.cpp) ----
 // sicp_map_*: per occupied voxel of merge's grid one row -- key, f64 sums, count, label histogram -- in arrays sorted by key.
 // An integrate keys and sorts the SCAN (the key arithmetic of voxel_key.hpp, merge's heads and gather launches), finds every

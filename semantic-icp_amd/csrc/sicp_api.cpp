@@ -833,6 +833,21 @@ int sicp_cluster(sicp_handle h, int which, const sicp_cluster_params* p, int32_t
   });
 }
 
+int sicp_default_filter_params(sicp_filter_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    filter_default_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_filter(sicp_handle h, int which, const sicp_filter_params* p, const uint8_t* mask, sicp_handle dst, int dst_which, uint8_t* keep,
+                double* mean_dist, int32_t* neighbors, sicp_filter_info* info) {
+  return abi_guard(h, [&]() -> int {
+    return filter(h, which, p, mask, dst, dst_which, keep, mean_dist, neighbors, info);
+  });
+}
+
 int sicp_default_map_params(sicp_map_params* p) {
   return abi_guard([&]() -> int {
     if (!p) return SICP_ERR_INVALID_ARGUMENT;
