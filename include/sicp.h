@@ -729,6 +729,88 @@ int sicp_filter(sicp_handle h, int which, const sicp_filter_params* p, const uin
                 double* mean_dist /* n_points, nullable */, int32_t* neighbors /* n_points, nullable */,
                 sicp_filter_info* info /* nullable */);
 
+/* ---- planes of a cloud -------------------------------------------------------------
+ * RANSAC plane extraction of the cloud in a handle's slot (pcl::SACSegmentation with SACMODEL_PLANE or, with an axis,
+ * SACMODEL_PERPENDICULAR_PLANE; Open3D's segment_plane): up to max_planes planes, one per round, each from a fixed number of
+ * three-point hypotheses scored over every remaining candidate.  plane_id -> a mask -> sicp_filter(mask, dst) -> sicp_cluster
+ * is "remove the ground, then cluster".  The handle may be in any mode.  All arithmetic below is float64 on the points'
+ * float coordinates widened exactly; every operation is rounded on its own, none contracted; (a b + c d) + e f is evaluated
+ * in that order.
+ *  1. Candidates.  A point is a candidate when it is finite, mask is NULL or mask[i] != 0, and its label is not one of
+ *     ignore[0 .. n_ignore).  A cloud set without labels is accepted only with n_ignore = 0 (rule 1 of sicp_filter).  Round
+ *     r = 0, 1, ... works on the candidates no earlier round has taken, in ascending caller index: cand[0 .. m_r).  The result
+ *     does not depend on the handle's mode, slot or device layout.
+ *  2. Hypotheses.  One SplitMix64 stream seeded with `seed`: draw number k (from 0) is the output z of the state
+ *     seed + (k + 1) * 0x9E3779B97F4A7C15 (mod 2^64), z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) *
+ *     0x94D049BB133111EB, z ^ z >> 31.  Draw 3 (r H + h) + s gives sample s of hypothesis h of round r as the index
+ *     min(floor((double)m_r * u), m_r - 1) into cand, u = (double)(z >> 11) * 2^-53.  With a, b, c the three points:
+ *     e1 = b - a, e2 = c - a, n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), nn = (nx nx + ny ny) + nz nz.
+ *     The hypothesis is invalid when two of its sample indices coincide or nn > 0 is false; with an axis also when
+ *     na na >= ((min_cos min_cos) nn) aa is false, na = (nx ax + ny ay) + nz az, aa = (ax ax + ay ay) + az az.  No sqrt, no
+ *     division, no trigonometry.
+ *  3. Score.  Candidate p is an inlier of (a, n) iff e e <= (t t) nn, d = p - a, e = (nx dx + ny dy) + nz dz,
+ *     t = distance_threshold.  A hypothesis' score is its inlier count over cand; the winner is the valid hypothesis with the
+ *     largest score, ties to the smallest h.  The call ends, with SICP_OK and the planes found so far, when m_r < 3 (the round is
+ *     not scored), when no hypothesis is valid or the winner's score is < min_inliers (the round is scored: it counts in
+ *     `rounds` and its invalid hypotheses in n_invalid_hypotheses), or after max_planes planes.
+ *  4. refine = 0.  The plane's members are the winner's inliers.  coeff = (u, D): u = n / sqrt(nn) component by component,
+ *     D = -((ux ax + uy ay) + uz az), then oriented: with an axis all four are negated when s = (ux axis_x + uy axis_y) +
+ *     uz axis_z < 0; without an axis, or when s == 0, when the first non-zero of (D, uz, uy, ux) is negative.
+ *  5. refine = 1.  Over the winner's inliers: S = the sums of x, y, z; g = S / (double)count; Q = the sums of the six products
+ *     dx dx, dy dx, dy dy, dz dx, dz dy, dz dz of d = p - g.  Every sum here and below is the sum over the perfect binary tree on
+ *     the caller's indices (rule 3 of sicp_filter: absent entries are +0.0), and +0.0 is added to the result once (a zero sum
+ *     is +0.0).  Q, undivided, goes through the cyclic Jacobi of the covariance estimation (sweeps over (0,1), (0,2), (1,2), at
+ *     most 30, stopped when off <= 1e-300 or off <= 1e-34 dia, off and dia the sums of the squared off-diagonal and diagonal
+ *     entries); the normal u is the eigenvector column of smallest |eigenvalue|, at ties the last such column.  D = -((ux gx +
+ *     uy gy) + uz gz); coeff = (u, D) oriented as in 4.  Then the members are re-selected once among the round's candidates by
+ *     rule 3's test with a = g, n = u, nn = (ux ux + uy uy) + uz uz (what PCL does after optimizeCoefficients).
+ *  6. Outputs.  plane_id[i] (nullable, n_points long, caller order): the round that took the point, -1 otherwise.  Per plane:
+ *     coeff (4), count = the final members, hyp_index = the winner's h, hyp_count = its score, centroid (3) = the tree sums of
+ *     the final members' x, y, z / (double)count, rms = sqrt(max(0, E / nn) / (double)count), E = the tree sum of e e over the
+ *     final members with a, n, nn the model that selected them (the winner with refine = 0, else (g, u)).  The table arrays are
+ *     nullable and hold `capacity` rows; capacity follows rule 6 of sicp_cluster (a non-NULL table array with capacity < n_planes:
+ *     SICP_ERR_INVALID_ARGUMENT with info written and nothing else).  n_planes <= max_planes: capacity = max_planes always suffices.
+ *  7. Fewer than 3 candidates: SICP_ERR_TOO_FEW_POINTS.  The slot holds no cloud: SICP_ERR_NOT_READY.  Refused before any device
+ *     work with SICP_ERR_INVALID_ARGUMENT (rule 9 of sicp_filter): a NULL handle or params; a `which` outside SICP_SOURCE /
+ *     SICP_TARGET; distance_threshold not finite or <= 0; an axis component that is not finite; an axis with min_cos outside
+ *     (0, 1]; min_cos != 0 without an axis; num_hypotheses outside 1 .. SICP_PLANE_MAX_HYPOTHESES; max_planes outside 1 ..
+ *     SICP_PLANE_MAX_PLANES; min_inliers < 3; refine not 0 or 1; n_ignore outside 0 .. SICP_PLANE_MAX_IGNORE; ignore with a cloud
+ *     without labels; capacity < 0.  Every refusal leaves the outputs and info as they were.  Nothing on the handle changes: a
+ *     later sicp_align returns the bytes it returns on a handle that never made the call.
+ *  8. Bit-reproducible: a function of the points, labels, mask and parameters only -- the same bytes from run to run, on a handle
+ *     of any mode, in either slot, before or after a sicp_align has laid the cloud out, for every launch shape.  Integer counts,
+ *     sums of fixed order, no float atomics. */
+#define SICP_PLANE_MAX_HYPOTHESES 4096
+#define SICP_PLANE_MAX_PLANES 16
+#define SICP_PLANE_MAX_IGNORE 16
+typedef struct sicp_plane_params {
+  double distance_threshold;  /* t > 0, finite.  default 0.2 */
+  double axis[3];             /* all 0 (default): no constraint; otherwise finite, not all 0 */
+  double min_cos;             /* with axis: in (0, 1]; |cos| of the largest angle between normal and axis.  default 0 */
+  uint64_t seed;              /* default 1 */
+  int32_t num_hypotheses;     /* H in 1 .. SICP_PLANE_MAX_HYPOTHESES.  default 1024 */
+  int32_t max_planes;         /* 1 .. SICP_PLANE_MAX_PLANES.  default 1 */
+  int32_t min_inliers;        /* >= 3.  default 100 */
+  int32_t refine;             /* 1 (default): least-squares refit and re-selection; 0: the winning hypothesis as it is */
+  int32_t n_ignore;           /* 0 .. SICP_PLANE_MAX_IGNORE.  default 0 */
+  uint32_t ignore[SICP_PLANE_MAX_IGNORE];
+} sicp_plane_params;
+typedef struct sicp_plane_info {
+  int64_t n_points;              /* what the caller handed over (the size of plane_id) */
+  int64_t n_finite;
+  int64_t n_candidates;          /* rule 1 */
+  int64_t n_assigned;            /* points with plane_id >= 0 */
+  int32_t n_planes;
+  int32_t rounds;                /* rounds scored: n_planes, or one more when the last one found no plane */
+  int64_t n_invalid_hypotheses;  /* over the rounds scored */
+  double t_total_ms;             /* host wall clock */
+} sicp_plane_info;
+int sicp_default_plane_params(sicp_plane_params* p);
+int sicp_segment_planes(sicp_handle h, int which, const sicp_plane_params* p, const uint8_t* mask /* n_points, nullable */,
+                        int32_t* plane_id /* n_points, nullable */, int32_t capacity, double* coeff /* 4 per plane */,
+                        int32_t* count, int32_t* hyp_index, int32_t* hyp_count, double* centroid /* 3 per plane */,
+                        double* rms /* all nullable */, sicp_plane_info* info /* nullable */);
+
 /* ---- a persistent voxel map ---------------------------------------------------
  * The map of scan-to-map odometry as an object that lives on the device between calls: per occupied voxel of the absolute
  * grid of the merge above (v = floor(p * (1.0f / (float)leaf_size)), |v| < 2^20) its 63-bit key (three biased 21-bit

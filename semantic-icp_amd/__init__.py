@@ -307,6 +307,44 @@ class SicpFilterInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+PLANE_MAX_HYPOTHESES = 4096
+PLANE_MAX_PLANES = 16
+PLANE_MAX_IGNORE = 16
+
+
+class SicpPlaneParams(C.Structure):
+    """sicp_plane_params (include/sicp.h)"""
+    _fields_ = [
+        ("distance_threshold", C.c_double),
+        ("axis", C.c_double * 3),
+        ("min_cos", C.c_double),
+        ("seed", C.c_uint64),
+        ("num_hypotheses", C.c_int32),
+        ("max_planes", C.c_int32),
+        ("min_inliers", C.c_int32),
+        ("refine", C.c_int32),
+        ("n_ignore", C.c_int32),
+        ("ignore", C.c_uint32 * PLANE_MAX_IGNORE),
+    ]
+
+
+class SicpPlaneInfo(C.Structure):
+    """sicp_plane_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_points", C.c_int64),
+        ("n_finite", C.c_int64),
+        ("n_candidates", C.c_int64),
+        ("n_assigned", C.c_int64),
+        ("n_planes", C.c_int32),
+        ("rounds", C.c_int32),
+        ("n_invalid_hypotheses", C.c_int64),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class SicpMapParams(C.Structure):
     """sicp_map_params (include/sicp.h)"""
     _fields_ = [
@@ -703,6 +741,9 @@ def lib():
             "sicp_default_filter_params": [C.POINTER(SicpFilterParams)],
             "sicp_filter": [C.c_void_p, C.c_int, C.POINTER(SicpFilterParams), _bp, C.c_void_p, C.c_int, _bp, _dp, _ip,
                             C.POINTER(SicpFilterInfo)],
+            "sicp_default_plane_params": [C.POINTER(SicpPlaneParams)],
+            "sicp_segment_planes": [C.c_void_p, C.c_int, C.POINTER(SicpPlaneParams), _bp, _ip, C.c_int32, _dp, _ip, _ip, _ip, _dp, _dp,
+                                    C.POINTER(SicpPlaneInfo)],
             "sicp_default_map_params": [C.POINTER(SicpMapParams)],
             "sicp_default_map_extract_params": [C.POINTER(SicpMapExtractParams)],
             "sicp_map_create": [C.c_int, C.POINTER(SicpMapParams), C.POINTER(C.c_void_p)],
@@ -884,6 +925,32 @@ def default_filter_params(drop=(), protect=(), **overrides) -> SicpFilterParams:
             getattr(p, name)[k] = v
     for k, v in overrides.items():
         if not hasattr(p, k) or k in ("drop", "protect"):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_plane_params(ignore=(), axis=None, **overrides) -> SicpPlaneParams:
+    """sicp_default_plane_params (distance_threshold 0.2, no axis, seed 1, 1024 hypotheses, one plane, min_inliers 100, refine 1,
+    nothing ignored), with the labels in `ignore` (at most PLANE_MAX_IGNORE), the three components of `axis` and any other field
+    overridden by keyword"""
+    p = SicpPlaneParams()
+    st = lib().sicp_default_plane_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_plane_params")
+    ignore = [int(v) for v in ignore]
+    if len(ignore) > PLANE_MAX_IGNORE:
+        raise ValueError(f"at most {PLANE_MAX_IGNORE} labels can be ignored")
+    p.n_ignore = len(ignore)
+    for k, v in enumerate(ignore):
+        p.ignore[k] = v
+    if axis is not None:
+        axis = [float(v) for v in axis]
+        if len(axis) != 3:
+            raise ValueError("axis must have three components")
+        p.axis = (C.c_double * 3)(*axis)
+    for k, v in overrides.items():
+        if not hasattr(p, k) or k in ("ignore", "axis"):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
@@ -1376,6 +1443,33 @@ class Engine:
         if dst is not None:
             dst.n[dw] = int(info.n_kept)
         return {"keep": keep[:n], "mean_dist": md[:n], "neighbors": nb[:n], "info": info.as_dict()}
+
+    def segment_planes(self, which: int = SOURCE, params: SicpPlaneParams | None = None, mask=None):
+        """sicp_segment_planes: the dominant planes of the cloud in slot `which` by RANSAC -- per round num_hypotheses three-point
+        planes scored over the candidates (finite, `mask` ([n_points], 0 leaves a point out) non-zero, label not ignored) no earlier
+        plane took, the winner refitted and its members re-selected with refine.  Returns {"plane_id": [n_points] int32 (-1: in no
+        plane), "coeff": [n_planes, 4] float64 (unit normal, offset), "count", "hyp_index", "hyp_count": int32, "centroid":
+        [n_planes, 3] float64, "rms": float64, "info": SicpPlaneInfo.as_dict()}.  The tables are sized by max_planes: one call.
+        Nothing on the engine changes."""
+        p = params if params is not None else default_plane_params()
+        n = self.n[which] if which in (SOURCE, TARGET) else 0
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.shape != (n,):
+                raise ValueError(f"mask must have one entry per point ({n})")
+        cap = max(int(p.max_planes), 1)
+        pid = np.empty(max(n, 1), dtype=np.int32)
+        coeff = np.empty((cap, 4), dtype=np.float64)
+        cnt, hi, hc = (np.empty(cap, dtype=np.int32) for _ in range(3))
+        cen = np.empty((cap, 3), dtype=np.float64)
+        rms = np.empty(cap, dtype=np.float64)
+        info = SicpPlaneInfo()
+        self._check(lib().sicp_segment_planes(self._h, which, C.byref(p), _ptr(mask, _bp), _ptr(pid, _ip), cap, _ptr(coeff, _dp),
+                                              _ptr(cnt, _ip), _ptr(hi, _ip), _ptr(hc, _ip), _ptr(cen, _dp), _ptr(rms, _dp),
+                                              C.byref(info)), "sicp_segment_planes")
+        k = int(info.n_planes)
+        return {"plane_id": pid[:n], "coeff": coeff[:k], "count": cnt[:k], "hyp_index": hi[:k], "hyp_count": hc[:k], "centroid": cen[:k],
+                "rms": rms[:k], "info": info.as_dict()}
 
     def solve(self, init_qt):
         init = np.ascontiguousarray(init_qt, dtype=np.float64)

@@ -11,6 +11,7 @@
 //   merge.cpp     sicp_merge_clouds: posed clouds into one voxel-grid cloud
 //   cluster.cpp   sicp_cluster: label-aware Euclidean clustering of a cloud
 //   filter.cpp    sicp_filter: statistical / radius outlier removal and masked selection of a cloud
+//   plane.cpp     sicp_segment_planes: RANSAC plane extraction of a cloud
 //   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, raycast, prune, extract, merge, state)
 //   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
 //   sicp_api.cpp  the remaining C-ABI entry points
@@ -511,6 +512,9 @@ struct sicp_context : sicp_use_state {
   // back, and the pinned kept points (x | y | z | label) on their way into dst
   HostBuf<unsigned char> fl_stage;
   HostBuf<uint32_t> fl_out;
+  // sicp_segment_planes (plane.cpp): the pinned finite positions / mask on their way up, the control block, plane records and
+  // per-point states on their way back
+  HostBuf<unsigned char> pl_stage;
   // lock-step batch (sicp_align_batch), owned by the batch's first handle: one BatchArgs and one LM
   // state per pair, pinned mirrors, and the captured [accumulate_batch, lm_step_batch] x lm_batch graph
   TickSet ts[2];  // two sets: the halves of a batch alternate, one's tick runs while the host turns the other around
@@ -1012,6 +1016,12 @@ float cells_per_metre(float t);  // the grid's cells per metre for a tolerance /
 void filter_default_params(sicp_filter_params* p);
 int filter(sicp_context* h, int which, const sicp_filter_params* p, const uint8_t* mask, sicp_context* dst, int dst_which, uint8_t* keep,
            double* mean_dist, int32_t* neighbors, sicp_filter_info* info);
+// sicp_segment_planes (plane.cpp): argument checks, every round of the plane kernels queued on the handle's stream, one
+// read-back
+void plane_default_params(sicp_plane_params* p);
+int segment_planes(sicp_context* h, int which, const sicp_plane_params* p, const uint8_t* mask, int32_t* plane_id, int32_t capacity,
+                   double* coeff, int32_t* count, int32_t* hyp_index, int32_t* hyp_count, double* centroid, double* rms,
+                   sicp_plane_info* info);
 // sicp_map_* (map.cpp): the persistent voxel map
 void map_default_params(sicp_map_params* p);
 void map_default_extract_params(sicp_map_extract_params* p);

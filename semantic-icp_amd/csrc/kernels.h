@@ -604,6 +604,71 @@ hipError_t launch_filter_flags(const FilterArgs& a, hipStream_t st);       // fl
 // (prim_scan_int flag -> pos)
 hipError_t launch_filter_gather(const FilterArgs& a, hipStream_t st);      // ox oy oz ol, res[kept]
 
+// ---- RANSAC plane extraction (plane_kernels.hip; driver: plane.cpp) ----
+// sicp_segment_planes: every array below that is [n_caller] long is indexed by the caller's index i; `finv` maps it to the
+// position f of the point among the finite ones (Cloud::rx ...), -1 for a point that is not finite.  A round compacts the
+// candidates not yet assigned, a lane per hypothesis samples a plane, the score kernel counts every hypothesis' inliers per
+// tile of candidates with plain stores, a sum and an argmax pick the winner, and the membership pass, the tree sums (the
+// filter's scheme: a perfect binary tree over the caller's indices), the one-lane fit and the re-selection make the plane.
+// Every kernel of a round returns at once when ctl->done is set: the rounds are queued without a host synchronisation.
+constexpr int kPlaneMaxIgnore = 16;      // SICP_PLANE_MAX_IGNORE
+constexpr int kPlaneMaxPlanes = 16;      // SICP_PLANE_MAX_PLANES
+constexpr int kPlaneLanePoints = 4;      // candidates a lane of the score kernel keeps in registers
+constexpr int kPlaneTile = 256 * kPlaneLanePoints;  // candidates one workgroup of the score kernel tests
+constexpr int kPlaneHypGroup = 64;       // hypotheses one workgroup of the score kernel loops over
+constexpr int kPlaneTreeRun = 512;       // caller indices one workgroup of a tree sum reduces: a power of two
+struct PlaneHyp { double ax, ay, az, nx, ny, nz, thr, nn; };  // a point, a normal, thr = (t t) nn (-1: invalid), nn = n . n
+struct PlaneRec { double coeff[4], centroid[3], rms; int count, hyp_index, hyp_count, pad_; };
+struct PlaneCtl {
+  int done, m, n_planes, rounds;   // the call has ended; candidates of the round; planes found; rounds scored
+  int cnt, n_candidates, n_assigned, pad_;  // members of the pass under way; candidates of round 0; points in planes
+  long long n_invalid;             // invalid hypotheses over the rounds scored
+  PlaneHyp model;                  // the plane the membership pass tests: the winner, then the fit
+};
+struct PlaneArgs {
+  int n, n_caller, labels;         // finite points; points the caller handed over; the cloud has labels
+  int H, min_inliers, refine, n_ignore, has_axis;
+  uint32_t ignore[kPlaneMaxIgnore];
+  double tt, axis[3], mc2, aa;     // t t; the axis, min_cos min_cos and axis . axis (has_axis only)
+  unsigned long long seed;
+  const float *x, *y, *z;          // [n] by f
+  const uint32_t* label;           // [n] nullable
+  const int* finv;                 // [n_caller] i -> f or -1; nullptr: the identity
+  const uint8_t* mask;             // [n_caller] nullable
+  int* state;                      // [n_caller] -2: no candidate; -1: a candidate not yet assigned; r: the round that took it
+  int *flag, *pos;                 // [n_caller] state == -1 and its exclusive scan
+  float *cx, *cy, *cz;             // [m] the round's candidates in ascending caller index
+  uint8_t* member;                 // [n_caller] the pass' members
+  PlaneHyp* hyp;                   // [H]
+  int* partial;                    // [tiles][H] inliers per tile of candidates
+  int* total;                      // [H]
+  double *sum_f, *sum_c;           // the tree sums' levels, the last one first: x y z e e (4 channels); the six products
+  PlaneCtl* ctl;
+  PlaneRec* rec;                   // [kPlaneMaxPlanes]
+};
+inline int plane_tiles(long long m) { return (int)((m + kPlaneTile - 1) / kPlaneTile); }
+// doubles the levels of a tree sum over n_caller entries take: 6 per workgroup of every level
+inline size_t plane_tree_doubles(long long n_caller) {
+  size_t total = 0;
+  for (long long cnt = n_caller > 0 ? n_caller : 1;;) {
+    cnt = (cnt + kPlaneTreeRun - 1) / kPlaneTreeRun;
+    total += 6 * (size_t)cnt;
+    if (cnt == 1) return total;
+  }
+}
+hipError_t launch_plane_init(const PlaneArgs& a, hipStream_t st);          // state, ctl->n_candidates
+hipError_t launch_plane_flags(const PlaneArgs& a, hipStream_t st);         // flag
+// (prim_scan_int flag -> pos)
+hipError_t launch_plane_compact(const PlaneArgs& a, hipStream_t st);       // cx cy cz, ctl->m
+hipError_t launch_plane_sample(const PlaneArgs& a, int round, hipStream_t st);  // hyp
+hipError_t launch_plane_score(const PlaneArgs& a, hipStream_t st);         // partial: a workgroup per tile and hypothesis group
+hipError_t launch_plane_winner(const PlaneArgs& a, int round, hipStream_t st);  // total; ctl->model, done, rounds, n_invalid; rec hyp_*
+hipError_t launch_plane_members(const PlaneArgs& a, hipStream_t st);       // member, ctl->cnt
+hipError_t launch_plane_tree_sums(const PlaneArgs& a, int products, hipStream_t st);  // sum_f (products = 0) or sum_c, every level
+hipError_t launch_plane_fit(const PlaneArgs& a, int round, hipStream_t st);      // refine = 1: ctl->model and rec coeff from the sums
+hipError_t launch_plane_record(const PlaneArgs& a, int round, hipStream_t st);   // rec, ctl->n_planes, n_assigned
+hipError_t launch_plane_assign(const PlaneArgs& a, int round, hipStream_t st);   // state of the members
+
 // ---- the persistent voxel map (map_kernels.hip; driver: map.cpp) ----
 // sicp_map_*: per occupied voxel of merge's grid one row -- key, f64 sums, count, label histogram -- in arrays sorted by key.
 // An integrate keys and sorts the SCAN (the key arithmetic of voxel_key.hpp, merge's heads and gather launches), finds every

@@ -848,6 +848,22 @@ int sicp_filter(sicp_handle h, int which, const sicp_filter_params* p, const uin
   });
 }
 
+int sicp_default_plane_params(sicp_plane_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    plane_default_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_segment_planes(sicp_handle h, int which, const sicp_plane_params* p, const uint8_t* mask, int32_t* plane_id, int32_t capacity,
+                        double* coeff, int32_t* count, int32_t* hyp_index, int32_t* hyp_count, double* centroid, double* rms,
+                        sicp_plane_info* info) {
+  return abi_guard(h, [&]() -> int {
+    return segment_planes(h, which, p, mask, plane_id, capacity, coeff, count, hyp_index, hyp_count, centroid, rms, info);
+  });
+}
+
 int sicp_default_map_params(sicp_map_params* p) {
   return abi_guard([&]() -> int {
     if (!p) return SICP_ERR_INVALID_ARGUMENT;
