@@ -1265,8 +1265,45 @@ int sicp_place_tables(sicp_place db, double* cos_half, double* sin_half, double*
  *     1e-6 (accepted quaternions are stored normalised); an edge end outside the nodes or i == j; an Omega that is not finite,
  *     asymmetric by more than 1e-9 of its largest entry (otherwise (Omega + Omega^T) / 2 is stored) or not positive definite
  *     (Cholesky on the host); a range beyond the size; parameters outside their ranges; more than 2^31 - 1 nodes or edges.
- *     SICP_ERR_NOT_READY: sicp_graph_optimize without a fixed node or without an edge.  SICP_ERR_OUT_OF_MEMORY: the arena
- *     refused; the graph holds what it held. */
+ *     SICP_ERR_NOT_READY: sicp_graph_optimize without a fixed node or without an edge (with priors and flags: rule 10).
+ *     SICP_ERR_OUT_OF_MEMORY: the arena refused; the graph holds what it held.
+ *  5. A pose prior (k, z, Omega), sicp_graph_add_priors with SICP_GRAPH_PRIOR_POSE: r = log(z^-1 T_k), a 6-vector in the tangent
+ *     of z exp(delta); s = r^T Omega r; rho and w from the graph's loss, 1/2 rho(s) in the cost.  dr / d delta_k = Jr^-1(r) = J:
+ *     the block w J^T Omega J, the gradient w J^T Omega r.  By definition this is node j's half of an ordinary edge
+ *     (i, k, z, Omega) whose node i is fixed at the identity pose, so Omega may be the inverse of a sicp_graph_marginals block of
+ *     an earlier session, with no conversion.  z and Omega are checked as sicp_graph_add_edges checks them (rule 4).
+ *  6. A position prior (k, p, Omega3), SICP_GRAPH_PRIOR_POSITION: r = t_k - p in the world frame, a 3-vector; s = r^T Omega3 r
+ *     under the same loss.  dr / d delta_k = [R_k | 0] (3x6), exact under T exp(delta) because t' = t + R V(omega) upsilon: the
+ *     block is w [[R^T Omega3 R, 0], [0, 0]], the gradient w [R^T Omega3 r; 0].  p must be finite; Omega3 is checked like
+ *     Omega, at size 3.
+ *  7. Enabled flags.  Every edge and every prior is created enabled.  A disabled one contributes nothing to the cost, to any
+ *     node's block or gradient, to the products of the linear solves, or to the anchoring of rule 11; it keeps its id.
+ *     sicp_graph_errors and sicp_graph_prior_errors still report its chi2, residual and weight at the current poses: that is
+ *     how a caller sees that an edge has become consistent and can be switched on again.  `cost` of sicp_graph_errors,
+ *     sicp_graph_prior_errors and sicp_graph_linearize is one number: over the enabled edges and the enabled priors.  Setting a
+ *     flag to the value it has changes nothing.
+ *  8. Order of sums.  A node's 42 sums start from 0, add its enabled edge records in ascending (edge id, side), then its enabled
+ *     prior records in ascending prior id: a disabled entry is left out of the node's list.  The cost's partial sums run over
+ *     the edges in id order, then the priors in id order; there a disabled entry counts as +0.0 at its place.  No float atomics:
+ *     two graphs driven alike hold the same bytes, and with no priors and every edge enabled every call returns the bytes it
+ *     returned before priors and flags existed.
+ *  9. A prior on a fixed node counts in the cost, like an edge between two fixed nodes, and contributes nothing else: the
+ *     block stays the identity, the gradient 0.  A node without enabled edges and without enabled priors is "a node without
+ *     edges" of the rules above in every call: a zero block, a zero gradient, a pose whose bytes survive sicp_graph_optimize.
+ * 10. sicp_graph_optimize is SICP_ERR_NOT_READY unless there is at least one enabled edge or enabled prior, and at least one
+ *     fixed node or one enabled prior of either kind (the damping carries what a position prior leaves undetermined).  A graph
+ *     without priors and with every edge enabled is refused exactly when rule 4 refuses it.
+ * 11. Covariance queries (next section): H includes the priors' blocks; components are taken over the enabled edges only; a
+ *     component is anchored when it holds a fixed node or a node with an enabled POSE prior.  Position priors never anchor a
+ *     query: one or two of them leave a rotation free, and "a singular system is never iterated" must keep holding.  The
+ *     caller fixes a node or adds a weak pose prior.
+ * 12. Further refusals (as rule 4): a kind other than the two; a prior's node outside the graph; m < 1; NULLs (the outputs of
+ *     sicp_graph_counts and of the two error calls, cost apart, are nullable); a range of flags beyond the count; more than
+ *     2^31 - 1 priors.  SICP_ERR_OUT_OF_MEMORY from the arena leaves the graph as it was.  sicp_graph_clear also drops the
+ *     priors; sicp_graph_size keeps its meaning.
+ *     Not built: physical removal or renumbering of edges; per-edge loss parameters; switchable-constraint variables; position
+ *     priors as anchors of covariance queries; gravity or heading-only priors; incremental (iSAM-style) updates. */
+enum { SICP_GRAPH_PRIOR_POSE = 0, SICP_GRAPH_PRIOR_POSITION = 1 };
 enum { SICP_GRAPH_LOSS_NONE = 0, SICP_GRAPH_LOSS_CAUCHY = 1 };
 enum {
   SICP_GRAPH_GRADIENT_TOLERANCE = 0,
@@ -1311,7 +1348,7 @@ typedef struct sicp_graph_info {
 int sicp_default_graph_params(sicp_graph_params* p);
 int sicp_graph_create(int device_id, const sicp_graph_params* p, sicp_graph* out);
 int sicp_graph_destroy(sicp_graph g);
-int sicp_graph_clear(sicp_graph g);  /* no nodes, no edges; the buffers stay */
+int sicp_graph_clear(sicp_graph g);  /* no nodes, no edges, no priors; the buffers stay */
 int sicp_graph_size(sicp_graph g, int64_t* n_nodes, int64_t* n_edges);
 const char* sicp_graph_last_error(sicp_graph g);
 /* n poses qt[7n]; fixed[n] (NULL: none fixed); first_id (nullable): the first new node's id, the rest follow */
@@ -1319,20 +1356,37 @@ int sicp_graph_add_nodes(sicp_graph g, int32_t n, const double* qt, const uint8_
 /* m edges: ends i[m], j[m], measurements z[7m], information matrices omega[36m]; first_id nullable */
 int sicp_graph_add_edges(sicp_graph g, int32_t m, const int32_t* i, const int32_t* j, const double* z, const double* omega,
                          int32_t* first_id);
+/* m priors of one kind on nodes node[m].  POSE: z[7m], omega[36m].  POSITION: z[3m] (a point in the world frame), omega[9m].
+ * first_id (nullable): the first new prior's id, the rest follow; priors have ids of their own, from 0 */
+int sicp_graph_add_priors(sicp_graph g, int32_t kind, int32_t m, const int32_t* node, const double* z, const double* omega,
+                          int32_t* first_id);
+/* the enabled flags of the edges / the priors first .. first + count (rule 7); a nonzero byte is "enabled" */
+int sicp_graph_set_edges_enabled(sicp_graph g, int32_t first, int32_t count, const uint8_t* enabled);
+int sicp_graph_get_edges_enabled(sicp_graph g, int32_t first, int32_t count, uint8_t* enabled);
+int sicp_graph_set_priors_enabled(sicp_graph g, int32_t first, int32_t count, const uint8_t* enabled);
+int sicp_graph_get_priors_enabled(sicp_graph g, int32_t first, int32_t count, uint8_t* enabled);
+/* per prior at the current poses, each nullable: chi2[P], residual[6P] (a POSITION prior writes r in the first 3 and 0.0 in the
+ * other 3), weight[P]; cost = the graph's whole cost */
+int sicp_graph_prior_errors(sicp_graph g, double* chi2, double* residual, double* weight, double* cost);
+int sicp_graph_counts(sicp_graph g, int64_t* n_nodes, int64_t* n_edges, int64_t* n_edges_enabled, int64_t* n_priors,
+                      int64_t* n_priors_enabled); /* each nullable */
 int sicp_graph_set_poses(sicp_graph g, int32_t first, int32_t count, const double* qt);
 int sicp_graph_get_poses(sicp_graph g, int32_t first, int32_t count, double* qt);
 int sicp_graph_set_fixed(sicp_graph g, int32_t first, int32_t count, const uint8_t* fixed);
-/* per edge at the current poses: chi2[M] = s, residual[6M] = r, weight[M] = w (each nullable), and the cost.  A false loop
- * closure shows as a large chi2. */
+/* per edge at the current poses, a disabled one too: chi2[M] = s, residual[6M] = r, weight[M] = w (each nullable), and the
+ * cost (rule 7).  A false loop closure shows as a large chi2; sicp_graph_set_edges_enabled takes it out. */
 int sicp_graph_errors(sicp_graph g, double* chi2, double* residual, double* weight, double* cost);
 /* inspection: the gradient[6N] and the diagonal blocks[36N] of the normal equations at the current poses (each nullable),
- * and the cost.  A fixed node has the identity block and a zero gradient, a node without edges a zero block. */
+ * and the cost.  A fixed node has the identity block and a zero gradient, a node without edges a zero block (rule 9). */
 int sicp_graph_linearize(sicp_graph g, double* gradient, double* diag_blocks, double* cost);
 int sicp_graph_optimize(sicp_graph g, sicp_graph_info* info);
 
 /* ---- pose-graph covariances: blocks of H^-1 for gating a loop closure before it enters the graph -------- */
 /* What the graph itself knows about a node, or about the relative pose of two nodes, at the current poses: the question to ask
- * before sicp_graph_add_edges (an edge cannot be taken out again), and the drift that sets a search radius.
+ * before sicp_graph_add_edges (an edge that passed the gate wrongly can still be switched off: sicp_graph_set_edges_enabled),
+ * and the drift that sets a search radius.  With priors and enabled flags, rule 11 of the section above says what H holds, what
+ * a component is and what anchors it; where the rules below say "edges" they mean enabled edges, and a node with an enabled
+ * pose prior counts as anchored.
  *
  *  1. H is the undamped Gauss-Newton matrix at the current poses: exactly what sicp_graph_linearize reports, robust weights
  *     included; a fixed node's block is the identity and its couplings are dropped.  The call linearises and gathers first.  It

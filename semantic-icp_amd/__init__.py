@@ -540,6 +540,7 @@ class SicpPlaceDescribeInfo(C.Structure):
 
 
 GRAPH_LOSS_NONE, GRAPH_LOSS_CAUCHY = 0, 1
+PRIOR_POSE, PRIOR_POSITION = 0, 1  # SICP_GRAPH_PRIOR_*
 GRAPH_TERMINATIONS = ("gradient", "function", "parameter", "max_iterations", "min_radius", "invalid_steps")
 
 
@@ -789,6 +790,13 @@ def lib():
             "sicp_graph_size": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
             "sicp_graph_add_nodes": [C.c_void_p, C.c_int32, _dp, _bp, _ip],
             "sicp_graph_add_edges": [C.c_void_p, C.c_int32, _ip, _ip, _dp, _dp, _ip],
+            "sicp_graph_add_priors": [C.c_void_p, C.c_int32, C.c_int32, _ip, _dp, _dp, _ip],
+            "sicp_graph_set_edges_enabled": [C.c_void_p, C.c_int32, C.c_int32, _bp],
+            "sicp_graph_get_edges_enabled": [C.c_void_p, C.c_int32, C.c_int32, _bp],
+            "sicp_graph_set_priors_enabled": [C.c_void_p, C.c_int32, C.c_int32, _bp],
+            "sicp_graph_get_priors_enabled": [C.c_void_p, C.c_int32, C.c_int32, _bp],
+            "sicp_graph_prior_errors": [C.c_void_p, _dp, _dp, _dp, _dp],
+            "sicp_graph_counts": [C.c_void_p] + [C.POINTER(C.c_int64)] * 5,
             "sicp_graph_set_poses": [C.c_void_p, C.c_int32, C.c_int32, _dp],
             "sicp_graph_get_poses": [C.c_void_p, C.c_int32, C.c_int32, _dp],
             "sicp_graph_set_fixed": [C.c_void_p, C.c_int32, C.c_int32, _bp],
@@ -2067,6 +2075,67 @@ class PoseGraph:
         self._check(lib().sicp_graph_add_edges(self._g, m, _ptr(ii, _ip), _ptr(jj, _ip), _ptr(zz, _dp), _ptr(om, _dp), C.byref(first)),
                     "sicp_graph_add_edges")
         return first.value
+
+    def add_priors(self, nodes, z, omega, kind: int = PRIOR_POSE) -> int:
+        """sicp_graph_add_priors: priors of one kind on nodes[m].  PRIOR_POSE: z[m, 7] ~ T_k, omega[m, 6, 6] in the tangent of
+        z exp(delta) (the inverse of a marginals() block, without conversion).  PRIOR_POSITION: z[m, 3] ~ t_k in the world frame
+        (a GPS fix), omega[m, 3, 3].  Returns the first new prior's id."""
+        nn = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.int32)
+        m = nn.shape[0]
+        dz, do = (7, 6) if kind == PRIOR_POSE else (3, 3)
+        zz = np.ascontiguousarray(z, dtype=np.float64).reshape(-1, dz)
+        om = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1, do, do)
+        if nn.ndim != 1 or zz.shape[0] != m or om.shape[0] != m:
+            raise ValueError("nodes[m], z[m, 7 or 3] and omega[m, 6, 6 or 3, 3] must agree on m")
+        first = C.c_int32(-1)
+        self._check(lib().sicp_graph_add_priors(self._g, kind, m, _ptr(nn, _ip), _ptr(zz, _dp), _ptr(om, _dp), C.byref(first)),
+                    "sicp_graph_add_priors")
+        return first.value
+
+    def _set_enabled(self, fn, where, enabled, first):
+        f = np.ascontiguousarray(np.atleast_1d(np.asarray(enabled, dtype=bool)), dtype=np.uint8)
+        self._check(fn(self._g, first, f.shape[0], _ptr(f, _bp)), where)
+
+    def _get_enabled(self, fn, where, have, first, count):
+        n = have - first if count is None else count
+        out = np.zeros(max(n, 0), dtype=np.uint8)
+        if n == 0 and count is None:
+            return out.astype(bool)
+        self._check(fn(self._g, first, n, _ptr(out, _bp)), where)
+        return out.astype(bool)
+
+    def set_edges_enabled(self, enabled, first: int = 0):
+        """sicp_graph_set_edges_enabled: switch the edges first, first + 1, ... on or off; a disabled edge keeps its id and is still
+        reported by errors(), but contributes to nothing"""
+        self._set_enabled(lib().sicp_graph_set_edges_enabled, "sicp_graph_set_edges_enabled", enabled, first)
+
+    def edges_enabled(self, first: int = 0, count: int | None = None):
+        """sicp_graph_get_edges_enabled: [count] bool (count = None: to the end)"""
+        return self._get_enabled(lib().sicp_graph_get_edges_enabled, "sicp_graph_get_edges_enabled", self.counts()["edges"], first, count)
+
+    def set_priors_enabled(self, enabled, first: int = 0):
+        """sicp_graph_set_priors_enabled"""
+        self._set_enabled(lib().sicp_graph_set_priors_enabled, "sicp_graph_set_priors_enabled", enabled, first)
+
+    def priors_enabled(self, first: int = 0, count: int | None = None):
+        """sicp_graph_get_priors_enabled: [count] bool (count = None: to the end)"""
+        return self._get_enabled(lib().sicp_graph_get_priors_enabled, "sicp_graph_get_priors_enabled", self.counts()["priors"], first, count)
+
+    def prior_errors(self):
+        """sicp_graph_prior_errors at the current poses: {"chi2": [P], "residual": [P, 6] (a position prior: r, then three zeros),
+        "weight": [P], "cost": the graph's whole cost}"""
+        m = self.counts()["priors"]
+        chi2, w, r = np.empty(m), np.empty(m), np.empty((m, 6))
+        cost = C.c_double(0.0)
+        self._check(lib().sicp_graph_prior_errors(self._g, _ptr(chi2, _dp), _ptr(r, _dp), _ptr(w, _dp), C.byref(cost)),
+                    "sicp_graph_prior_errors")
+        return {"chi2": chi2, "residual": r, "weight": w, "cost": cost.value}
+
+    def counts(self):
+        """sicp_graph_counts: {"nodes", "edges", "edges_enabled", "priors", "priors_enabled"}"""
+        v = [C.c_int64(0) for _ in range(5)]
+        self._check(lib().sicp_graph_counts(self._g, *[C.byref(x) for x in v]), "sicp_graph_counts")
+        return dict(zip(("nodes", "edges", "edges_enabled", "priors", "priors_enabled"), (x.value for x in v)))
 
     def set_poses(self, qt, first: int = 0):
         q = self._poses(qt)

@@ -22,7 +22,7 @@ HOST_SOURCES = ["memory.cpp", "clouds.cpp", "stages.cpp", "solve.cpp", "streams.
                 "merge.cpp", "cluster.cpp", "filter.cpp", "plane.cpp", "map.cpp", "place.cpp", "graph.cpp", "sicp_api.cpp"]
 SOURCES = DEVICE_SOURCES + HOST_SOURCES
 HEADERS = ["kernels.h", "device_geometry.hpp", "lm.hpp", "se3.hpp", "bvh.hpp", "build_tree.h", "fast_log.hpp", "log_table.inc",
-           "engine.hpp", "abi_barrier.hpp", "bootstrap.hpp", "job_table.hpp", "voxel_key.hpp", "graph_edge.hpp", "graph_cov.hpp", "cell_grid.hpp"]
+           "engine.hpp", "abi_barrier.hpp", "bootstrap.hpp", "job_table.hpp", "voxel_key.hpp", "graph_edge.hpp", "graph_prior.hpp", "graph_cov.hpp", "cell_grid.hpp"]
 EXPORTS = os.path.join(CSRC, "exports.map")
 ARCH = "gfx950"
 

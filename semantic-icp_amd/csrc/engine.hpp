@@ -648,18 +648,24 @@ struct sicp_graph_ctx {
   sicp_graph_params params;
   OwnedStream stream;
   struct Nodes { DevBuf<double> pose; DevBuf<uint8_t> fixed; } nodes[2];
-  struct Edges { DevBuf<int> i, j; DevBuf<double> z, omega; } edges[2];
-  int ncur = 0, ecur = 0;             // the sets that hold the graph
-  long long n_nodes = 0, n_edges = 0, cap_nodes = 0, cap_edges = 0;
-  long long n_fixed = 0;
+  struct Edges { DevBuf<int> i, j; DevBuf<double> z, omega; DevBuf<uint8_t> enabled; } edges[2];
+  struct Priors { DevBuf<int> node, kind; DevBuf<double> z, omega; DevBuf<uint8_t> enabled; } priors[2];  // z[7], omega[36] per prior
+  int ncur = 0, ecur = 0, pcur = 0;   // the sets that hold the graph
+  long long n_nodes = 0, n_edges = 0, n_priors = 0, cap_nodes = 0, cap_edges = 0, cap_priors = 0;
+  long long n_fixed = 0, n_edges_enabled = 0, n_priors_enabled = 0;
   std::vector<uint8_t> h_fixed;       // the host's copy of the flags (optimize refuses a graph without a fixed node)
   std::vector<int32_t> h_ei, h_ej;    // the host's copy of the edge ends (the covariance calls' connectivity)
-  std::vector<uint8_t> anchored;      // per node: its connected component holds a fixed node (union-find over h_ei, h_ej)
-  bool anchored_stale = true;         // nodes, edges or flags have changed since
-  bool incidence_stale = true;        // edges have been added since the incidence table was built
+  std::vector<uint8_t> h_een;         // the host's copies of the enabled flags and of the priors' nodes and kinds
+  std::vector<uint8_t> h_pen;
+  std::vector<int32_t> h_pnode, h_pkind;
+  std::vector<uint8_t> anchored;      // per node: its component over the enabled edges holds a fixed node or an enabled pose prior
+  bool anchored_stale = true;         // nodes, edges, priors or flags have changed since
+  bool incidence_stale = true;        // nodes, edges or priors have been added, or an enabled flag flipped, since the tables were built
   DevBuf<double> C, B, r, s, w, ec, H, g, L, x, rr, zz, p, q, cand, part;
+  DevBuf<double> PC, pr, ps, pw;      // per prior: the record, the residual, chi2, the weight
   DevBuf<unsigned long long> keys, inc;
-  DevBuf<int> deg, off;
+  DevBuf<int> deg, off, pinc, poff;   // pinc, poff: the enabled priors by node, built on the host
+  DevBuf<uint8_t> pheld;              // per node: it has an enabled pose prior
   DevBuf<unsigned char> temp;
   DevBuf<sicp::GraphScalars> scalars;
   HostBuf<unsigned char> stage;       // pinned: uploads and read-backs on their way
@@ -1074,6 +1080,12 @@ int graph_add_edges(sicp_graph_ctx* g, int32_t m, const int32_t* i, const int32_
 int graph_set_poses(sicp_graph_ctx* g, int32_t first, int32_t count, const double* qt);
 int graph_get_poses(sicp_graph_ctx* g, int32_t first, int32_t count, double* qt);
 int graph_set_fixed(sicp_graph_ctx* g, int32_t first, int32_t count, const uint8_t* fixed);
+int graph_add_priors(sicp_graph_ctx* g, int32_t kind, int32_t m, const int32_t* node, const double* z, const double* omega, int32_t* first_id);
+// priors = false: the edges' flags
+int graph_set_enabled(sicp_graph_ctx* g, bool priors, int32_t first, int32_t count, const uint8_t* enabled);
+int graph_get_enabled(sicp_graph_ctx* g, bool priors, int32_t first, int32_t count, uint8_t* enabled);
+int graph_prior_errors(sicp_graph_ctx* g, double* chi2, double* residual, double* weight, double* cost);
+int graph_counts(sicp_graph_ctx* g, int64_t* n_nodes, int64_t* n_edges, int64_t* n_edges_enabled, int64_t* n_priors, int64_t* n_priors_enabled);
 int graph_errors(sicp_graph_ctx* g, double* chi2, double* residual, double* weight, double* cost);
 int graph_linearize(sicp_graph_ctx* g, double* gradient, double* diag_blocks, double* cost);
 int graph_optimize(sicp_graph_ctx* g, sicp_graph_info* info);

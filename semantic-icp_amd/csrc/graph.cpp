@@ -1,5 +1,5 @@
-// graph.cpp -- sicp_graph_* (include/sicp.h): a pose graph that lives on the device between calls.  Nodes and edges lie one
-// after another in one of two sets of arena buffers; growth doubles into the spare set and swaps last, and every check of a
+// graph.cpp -- sicp_graph_* (include/sicp.h): a pose graph that lives on the device between calls.  Nodes, edges and priors lie
+// one after another in one of two sets of arena buffers each; growth doubles into the spare set and swaps last, and every check of a
 // call comes before its first write, so a refused call leaves the graph as it was.  The outer Levenberg-Marquardt loop runs
 // here with one read-back per iteration (and one per batch of conjugate-gradient steps); the kernels: graph_kernels.hip, the
 // sort and the scan of prim_kernels.hip.  At the end: sicp_graph_marginals / sicp_graph_relative_covariances, blocks of H^-1 by
@@ -53,22 +53,39 @@ void store_pose(const double* q, double* o) {
   for (int d = 4; d < 7; ++d) o[d] = q[d];
 }
 
-// (Omega + Omega^T) / 2 into out, or the reason it is refused
-bool take_omega(const double* om, double* out, std::string& why) {
+// (Omega + Omega^T) / 2 of an n x n information matrix (6; 3: a position prior's) into out, or the reason it is refused
+bool take_omega(const double* om, int n, double* out, std::string& why) {
   double big = 0;
-  for (int k = 0; k < 36; ++k) {
+  for (int k = 0; k < n * n; ++k) {
     if (!std::isfinite(om[k])) { why = "has an information matrix that is not finite"; return false; }
     big = std::max(big, std::fabs(om[k]));
   }
-  for (int a = 0; a < 6; ++a)
+  for (int a = 0; a < n; ++a)
     for (int b = 0; b < a; ++b)
-      if (std::fabs(om[6 * a + b] - om[6 * b + a]) > 1e-9 * big) { why = "has an information matrix that is not symmetric"; return false; }
-  for (int a = 0; a < 6; ++a)
-    for (int b = 0; b < 6; ++b) out[6 * a + b] = 0.5 * (om[6 * a + b] + om[6 * b + a]);
-  double A[36], rhs[6] = {0, 0, 0, 0, 0, 0}, y[6];
-  std::memcpy(A, out, sizeof A);
-  if (!sicp::detail::chol6_solve(A, rhs, y)) { why = "has an information matrix that is not positive definite"; return false; }
-  return true;
+      if (std::fabs(om[n * a + b] - om[n * b + a]) > 1e-9 * big) { why = "has an information matrix that is not symmetric"; return false; }
+  for (int a = 0; a < n; ++a)
+    for (int b = 0; b < n; ++b) out[n * a + b] = 0.5 * (om[n * a + b] + om[n * b + a]);
+  bool pd = true;
+  if (n == 6) {
+    double A[36], rhs[6] = {0, 0, 0, 0, 0, 0}, y[6];
+    std::memcpy(A, out, sizeof A);
+    pd = sicp::detail::chol6_solve(A, rhs, y);
+  } else {  // 3 x 3 by hand: every pivot must be > 0
+    double L[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 3 && pd; ++i)
+      for (int j = 0; j <= i && pd; ++j) {
+        double t = out[3 * i + j];
+        for (int k = 0; k < j; ++k) t -= L[3 * i + k] * L[3 * j + k];
+        if (i == j) {
+          pd = t > 0.0 && std::isfinite(t);
+          L[3 * i + i] = std::sqrt(t);
+        } else {
+          L[3 * i + j] = t / L[3 * j + j];
+        }
+      }
+  }
+  if (!pd) why = "has an information matrix that is not positive definite";
+  return pd;
 }
 
 int resolve_range(const sicp_graph_ctx* G, int32_t first, int32_t count, std::string& why) {
@@ -112,8 +129,10 @@ int grow_edges(sicp_graph_ctx* G, long long m) {
   GRAPHCHECK(spare.j.reserve((size_t)want));
   GRAPHCHECK(spare.z.reserve((size_t)want * 7));
   GRAPHCHECK(spare.omega.reserve((size_t)want * 36));
+  GRAPHCHECK(spare.enabled.reserve((size_t)want));
   if (G->n_edges > 0) {
     const size_t M = (size_t)G->n_edges;
+    GRAPHCHECK(hipMemcpyAsync(spare.enabled.p, cur.enabled.p, M, hipMemcpyDeviceToDevice, G->stream));
     GRAPHCHECK(hipMemcpyAsync(spare.i.p, cur.i.p, sizeof(int) * M, hipMemcpyDeviceToDevice, G->stream));
     GRAPHCHECK(hipMemcpyAsync(spare.j.p, cur.j.p, sizeof(int) * M, hipMemcpyDeviceToDevice, G->stream));
     GRAPHCHECK(hipMemcpyAsync(spare.z.p, cur.z.p, sizeof(double) * 7 * M, hipMemcpyDeviceToDevice, G->stream));
@@ -123,16 +142,47 @@ int grow_edges(sicp_graph_ctx* G, long long m) {
   G->ecur ^= 1;
   G->cap_edges = want;
   DevArena::FreeScope idle(G->device);
-  cur.i.release(); cur.j.release(); cur.z.release(); cur.omega.release();
+  cur.i.release(); cur.j.release(); cur.z.release(); cur.omega.release(); cur.enabled.release();
+  return SICP_OK;
+}
+
+int grow_priors(sicp_graph_ctx* G, long long m) {
+  const long long need = G->n_priors + m;
+  if (need <= G->cap_priors) return SICP_OK;
+  const long long want = std::max<long long>(std::max<long long>(need, 2 * G->cap_priors), 64);
+  auto& cur = G->priors[G->pcur];
+  auto& spare = G->priors[G->pcur ^ 1];
+  GRAPHCHECK(spare.node.reserve((size_t)want));
+  GRAPHCHECK(spare.kind.reserve((size_t)want));
+  GRAPHCHECK(spare.z.reserve((size_t)want * 7));
+  GRAPHCHECK(spare.omega.reserve((size_t)want * 36));
+  GRAPHCHECK(spare.enabled.reserve((size_t)want));
+  if (G->n_priors > 0) {
+    const size_t P = (size_t)G->n_priors;
+    GRAPHCHECK(hipMemcpyAsync(spare.node.p, cur.node.p, sizeof(int) * P, hipMemcpyDeviceToDevice, G->stream));
+    GRAPHCHECK(hipMemcpyAsync(spare.kind.p, cur.kind.p, sizeof(int) * P, hipMemcpyDeviceToDevice, G->stream));
+    GRAPHCHECK(hipMemcpyAsync(spare.z.p, cur.z.p, sizeof(double) * 7 * P, hipMemcpyDeviceToDevice, G->stream));
+    GRAPHCHECK(hipMemcpyAsync(spare.omega.p, cur.omega.p, sizeof(double) * 36 * P, hipMemcpyDeviceToDevice, G->stream));
+    GRAPHCHECK(hipMemcpyAsync(spare.enabled.p, cur.enabled.p, P, hipMemcpyDeviceToDevice, G->stream));
+    GRAPHCHECK(hipStreamSynchronize(G->stream));
+  }
+  G->pcur ^= 1;
+  G->cap_priors = want;
+  DevArena::FreeScope idle(G->device);
+  cur.node.release(); cur.kind.release(); cur.z.release(); cur.omega.release(); cur.enabled.release();
   return SICP_OK;
 }
 
 // the work buffers at the graph's size, and the kernels' arguments
 int prepare(sicp_graph_ctx* G, sicp::GraphArgs& A) {
-  const size_t N = (size_t)std::max<long long>(G->n_nodes, 1), M = (size_t)std::max<long long>(G->n_edges, 1);
-  const int stride = sicp::graph_blocks((long long)std::max(6 * N, M));
+  const size_t N = (size_t)std::max<long long>(G->n_nodes, 1), M = (size_t)std::max<long long>(G->n_edges, 1), P = (size_t)G->n_priors;
+  const int stride = sicp::graph_blocks((long long)std::max(6 * N, M + P));
   GRAPHCHECK(G->C.reserve(2 * M * sicp::kGraphRec)); GRAPHCHECK(G->B.reserve(36 * M)); GRAPHCHECK(G->r.reserve(6 * M));
-  GRAPHCHECK(G->s.reserve(M)); GRAPHCHECK(G->w.reserve(M)); GRAPHCHECK(G->ec.reserve(M));
+  GRAPHCHECK(G->s.reserve(M)); GRAPHCHECK(G->w.reserve(M)); GRAPHCHECK(G->ec.reserve(M + P));
+  if (P > 0) {
+    GRAPHCHECK(G->PC.reserve(P * sicp::kGraphRec)); GRAPHCHECK(G->pr.reserve(6 * P)); GRAPHCHECK(G->ps.reserve(P)); GRAPHCHECK(G->pw.reserve(P));
+    GRAPHCHECK(G->pinc.reserve(P)); GRAPHCHECK(G->poff.reserve(N + 1)); GRAPHCHECK(G->pheld.reserve(N));
+  }
   GRAPHCHECK(G->H.reserve(36 * N)); GRAPHCHECK(G->g.reserve(6 * N)); GRAPHCHECK(G->L.reserve(sicp::kGraphChol * N));
   GRAPHCHECK(G->x.reserve(6 * N)); GRAPHCHECK(G->rr.reserve(6 * N)); GRAPHCHECK(G->zz.reserve(6 * N));
   GRAPHCHECK(G->p.reserve(6 * N)); GRAPHCHECK(G->q.reserve(6 * N)); GRAPHCHECK(G->cand.reserve(7 * N));
@@ -141,10 +191,16 @@ int prepare(sicp_graph_ctx* G, sicp::GraphArgs& A) {
   GRAPHCHECK(G->scalars.reserve(1));
   GRAPHCHECK(G->rec.resize(1));
   std::memset(&A, 0, sizeof A);
-  A.n_nodes = (int)G->n_nodes; A.n_edges = (int)G->n_edges;
+  A.n_nodes = (int)G->n_nodes; A.n_edges = (int)G->n_edges; A.n_priors = (int)G->n_priors;
   A.pose = G->nodes[G->ncur].pose.p; A.fixed = G->nodes[G->ncur].fixed.p;
   const auto& E = G->edges[G->ecur];
   A.ei = E.i.p; A.ej = E.j.p; A.z = E.z.p; A.omega = E.omega.p;
+  A.een = G->n_edges_enabled < G->n_edges ? E.enabled.p : nullptr;
+  if (P > 0) {
+    const auto& Q = G->priors[G->pcur];
+    A.pnode = Q.node.p; A.pkind = Q.kind.p; A.pen = Q.enabled.p; A.pz = Q.z.p; A.pomega = Q.omega.p;
+    A.PC = G->PC.p; A.pr = G->pr.p; A.ps = G->ps.p; A.pw = G->pw.p; A.pinc = G->pinc.p; A.poff = G->poff.p;
+  }
   A.loss = G->params.loss; A.cauchy_a = G->params.cauchy_a;
   A.C = G->C.p; A.B = G->B.p; A.r = G->r.p; A.s = G->s.p; A.w = G->w.p; A.ec = G->ec.p;
   A.inc = G->inc.p; A.off = G->off.p;
@@ -156,25 +212,52 @@ int prepare(sicp_graph_ctx* G, sicp::GraphArgs& A) {
   return SICP_OK;
 }
 
-// The incidence table, rebuilt when edges have been added: the slots 2 * edge + side sorted by node (a stable sort of the
-// node bits: within a node the slots ascend), the degrees' scan.
+// The incidence tables, rebuilt when nodes, edges or priors have been added or an enabled flag has flipped.  Edges: the slots
+// 2 * edge + side sorted by node (a stable sort of the node bits: within a node the slots ascend; a disabled edge's slots carry
+// the key n_nodes and land behind every list), the degrees' scan.  Priors: the enabled ones by node in ascending id, counted and
+// placed on the host from its mirrors, and the per-node flag of an enabled pose prior.
 int build_incidence(sicp_graph_ctx* G, sicp::GraphArgs& A) {
-  if (!G->incidence_stale || G->n_edges == 0) return SICP_OK;
+  if (!G->incidence_stale) return SICP_OK;
   const long long slots = 2 * G->n_edges, N = G->n_nodes;
   hipStream_t st = G->stream;
-  GRAPHCHECK(G->keys.reserve((size_t)slots));
-  GRAPHCHECK(G->deg.reserve((size_t)N + 1));
-  int bits = 1;
-  while (bits < 31 && (1ll << bits) < N) ++bits;
-  size_t sort_bytes = 0, scan_bytes = 0;
-  GRAPHCHECK(sicp::prim_sort_keys(nullptr, sort_bytes, G->keys.p, G->inc.p, slots, 32, 32 + bits, st));
-  GRAPHCHECK(sicp::prim_scan_int(nullptr, scan_bytes, G->deg.p, G->off.p, N + 1, st));
-  GRAPHCHECK(G->temp.reserve(std::max(sort_bytes, scan_bytes) + 256));
-  A.deg = G->deg.p;
-  GRAPHCHECK(hipMemsetAsync(G->deg.p, 0, sizeof(int) * (size_t)(N + 1), st));
-  GRAPHCHECK(sicp::launch_graph_keys(A, G->keys.p, st));
-  GRAPHCHECK(sicp::prim_sort_keys(G->temp.p, sort_bytes, G->keys.p, G->inc.p, slots, 32, 32 + bits, st));
-  GRAPHCHECK(sicp::prim_scan_int(G->temp.p, scan_bytes, G->deg.p, G->off.p, N + 1, st));
+  if (G->n_edges_enabled == 0) {  // (every list is empty)
+    GRAPHCHECK(hipMemsetAsync(A.off, 0, sizeof(int) * (size_t)(N + 1), st));
+  } else {
+    GRAPHCHECK(G->keys.reserve((size_t)slots));
+    GRAPHCHECK(G->deg.reserve((size_t)N + 1));
+    const long long top = A.een ? N + 1 : N;  // the keys' values: the nodes, and n_nodes itself where an edge is disabled
+    int bits = 1;
+    while (bits < 31 && (1ll << bits) < top) ++bits;
+    size_t sort_bytes = 0, scan_bytes = 0;
+    GRAPHCHECK(sicp::prim_sort_keys(nullptr, sort_bytes, G->keys.p, G->inc.p, slots, 32, 32 + bits, st));
+    GRAPHCHECK(sicp::prim_scan_int(nullptr, scan_bytes, G->deg.p, G->off.p, N + 1, st));
+    GRAPHCHECK(G->temp.reserve(std::max(sort_bytes, scan_bytes) + 256));
+    A.deg = G->deg.p;
+    GRAPHCHECK(hipMemsetAsync(G->deg.p, 0, sizeof(int) * (size_t)(N + 1), st));
+    GRAPHCHECK(sicp::launch_graph_keys(A, G->keys.p, st));
+    GRAPHCHECK(sicp::prim_sort_keys(G->temp.p, sort_bytes, G->keys.p, G->inc.p, slots, 32, 32 + bits, st));
+    GRAPHCHECK(sicp::prim_scan_int(G->temp.p, scan_bytes, G->deg.p, G->off.p, N + 1, st));
+  }
+  if (G->n_priors > 0) {
+    const size_t P = (size_t)G->n_priors, off_bytes = sizeof(int) * (size_t)(N + 1), inc_bytes = sizeof(int) * P;
+    GRAPHCHECK(G->stage.resize(off_bytes + inc_bytes + (size_t)N));
+    int* off = reinterpret_cast<int*>(G->stage.data());
+    int* inc = off + (N + 1);
+    uint8_t* held = G->stage.data() + off_bytes + inc_bytes;
+    std::memset(G->stage.data(), 0, off_bytes + inc_bytes + (size_t)N);
+    for (size_t p = 0; p < P; ++p)
+      if (G->h_pen[p]) {
+        off[G->h_pnode[p] + 1] += 1;
+        if (G->h_pkind[p] == SICP_GRAPH_PRIOR_POSE) held[G->h_pnode[p]] = 1;
+      }
+    for (long long k = 0; k < N; ++k) off[k + 1] += off[k];
+    std::vector<int> at(off, off + N);
+    for (size_t p = 0; p < P; ++p)
+      if (G->h_pen[p]) inc[at[(size_t)G->h_pnode[p]]++] = (int)p;
+    GRAPHCHECK(hipMemcpyAsync(G->poff.p, off, off_bytes, hipMemcpyHostToDevice, st));
+    GRAPHCHECK(hipMemcpyAsync(G->pinc.p, inc, inc_bytes, hipMemcpyHostToDevice, st));
+    GRAPHCHECK(hipMemcpyAsync(G->pheld.p, held, (size_t)N, hipMemcpyHostToDevice, st));
+  }
   GRAPHCHECK(hipStreamSynchronize(st));
   G->incidence_stale = false;
   return SICP_OK;
@@ -194,15 +277,45 @@ int download(sicp_graph_ctx* G, double* dst, const double* src, size_t count) {
   return SICP_OK;
 }
 
-// full linearisation at the current poses: per-edge records, H, g, S->cost, S->gmax
+// every edge and every prior at `pose`: ec, and the records when full; then the sum of ec into S->cost / S->cand_cost
+int linearise_entries(sicp_graph_ctx* G, sicp::GraphArgs& A, const double* pose, bool full, int fin) {
+  hipStream_t st = G->stream;
+  if (G->n_edges > 0) GRAPHCHECK(sicp::launch_graph_linearise(A, pose, full, st));
+  if (G->n_priors > 0) GRAPHCHECK(sicp::launch_graph_prior_linearise(A, pose, full, st));
+  if (G->n_edges + G->n_priors > 0) GRAPHCHECK(sicp::launch_graph_sum(A, fin, st));
+  return SICP_OK;
+}
+
+// full linearisation at the current poses: per-edge and per-prior records, H, g, S->cost, S->gmax
 int linearise_full(sicp_graph_ctx* G, sicp::GraphArgs& A) {
   hipStream_t st = G->stream;
-  if (G->n_edges > 0) {
-    GRAPHCHECK(sicp::launch_graph_linearise(A, A.pose, true, st));
-    GRAPHCHECK(sicp::launch_graph_sum(A, sicp::kGraphFinCost, st));
-  }
+  const int rc = linearise_entries(G, A, A.pose, true, sicp::kGraphFinCost);
+  if (rc != SICP_OK) return rc;
   GRAPHCHECK(sicp::launch_graph_gather(A, st));
   GRAPHCHECK(sicp::launch_graph_sum(A, sicp::kGraphFinGmax, st));
+  return SICP_OK;
+}
+
+// sicp_graph_errors / sicp_graph_prior_errors: every edge and every prior at the current poses (a disabled one too), the
+// graph's whole cost, and the edges' or the priors' chi2, residuals and weights
+int entry_errors(sicp_graph_ctx* G, bool priors, double* chi2, double* residual, double* weight, double* cost) {
+  if (G->n_edges + G->n_priors == 0) {
+    *cost = 0.0;
+    return SICP_OK;
+  }
+  GRAPHCHECK(hipSetDevice(G->device));
+  sicp::GraphArgs A;
+  int rc = prepare(G, A);
+  if (rc != SICP_OK) return rc;
+  if ((rc = linearise_entries(G, A, A.pose, true, sicp::kGraphFinCost)) != SICP_OK) return rc;
+  sicp::GraphScalars S;
+  rc = read_scalars(G, S);
+  if (rc != SICP_OK) return rc;
+  const size_t M = (size_t)(priors ? G->n_priors : G->n_edges);
+  if ((rc = download(G, chi2, priors ? A.ps : A.s, M)) != SICP_OK) return rc;
+  if ((rc = download(G, residual, priors ? A.pr : A.r, 6 * M)) != SICP_OK) return rc;
+  if ((rc = download(G, weight, priors ? A.pw : A.w, M)) != SICP_OK) return rc;
+  *cost = S.cost;
   return SICP_OK;
 }
 
@@ -262,9 +375,14 @@ int graph_destroy(sicp_graph_ctx* G) {
 int graph_clear(sicp_graph_ctx* G) {
   if (!G) return SICP_ERR_INVALID_ARGUMENT;
   G->n_nodes = G->n_edges = G->n_fixed = 0;
+  G->n_priors = G->n_edges_enabled = G->n_priors_enabled = 0;
   G->h_fixed.clear();
   G->h_ei.clear();
   G->h_ej.clear();
+  G->h_een.clear();
+  G->h_pen.clear();
+  G->h_pnode.clear();
+  G->h_pkind.clear();
   G->incidence_stale = true;
   G->anchored_stale = true;
   G->last_error.clear();
@@ -349,13 +467,14 @@ int graph_add_edges(sicp_graph_ctx* G, int32_t m, const int32_t* i, const int32_
   int* si = reinterpret_cast<int*>(sz + 7 * M);
   int* sj = si + M;
   for (size_t e = 0; e < M; ++e) {
-    if (!take_omega(omega + 36 * e, so + 36 * e, why)) return refuse("edge " + std::to_string(e) + " " + why);
+    if (!take_omega(omega + 36 * e, 6, so + 36 * e, why)) return refuse("edge " + std::to_string(e) + " " + why);
     store_pose(z + 7 * e, sz + 7 * e);
     si[e] = i[e];
     sj[e] = j[e];
   }
   G->h_ei.reserve((size_t)(G->n_edges + m));  // (may throw: before anything changes)
   G->h_ej.reserve((size_t)(G->n_edges + m));
+  G->h_een.reserve((size_t)(G->n_edges + m));
   const int rc = grow_edges(G, m);
   if (rc != SICP_OK) return rc;
   auto& cur = G->edges[G->ecur];
@@ -364,13 +483,145 @@ int graph_add_edges(sicp_graph_ctx* G, int32_t m, const int32_t* i, const int32_
   GRAPHCHECK(hipMemcpyAsync(cur.z.p + 7 * at, sz, zb, hipMemcpyHostToDevice, G->stream));
   GRAPHCHECK(hipMemcpyAsync(cur.i.p + at, si, ib, hipMemcpyHostToDevice, G->stream));
   GRAPHCHECK(hipMemcpyAsync(cur.j.p + at, sj, ib, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipMemsetAsync(cur.enabled.p + at, 1, M, G->stream));  // (every edge is created enabled)
   GRAPHCHECK(hipStreamSynchronize(G->stream));
   if (first_id) *first_id = (int32_t)G->n_edges;
   G->h_ei.insert(G->h_ei.end(), si, si + m);
   G->h_ej.insert(G->h_ej.end(), sj, sj + m);
+  G->h_een.insert(G->h_een.end(), M, (uint8_t)1);
   G->n_edges += m;
+  G->n_edges_enabled += m;
   G->incidence_stale = true;
   G->anchored_stale = true;
+  return SICP_OK;
+}
+
+int graph_add_priors(sicp_graph_ctx* G, int32_t kind, int32_t m, const int32_t* node, const double* z, const double* omega, int32_t* first_id) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = "sicp_graph_add_priors";
+  auto refuse = [&](const std::string& why) {
+    G->last_error = "sicp_graph_add_priors: " + why + "; the graph is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  if (kind != SICP_GRAPH_PRIOR_POSE && kind != SICP_GRAPH_PRIOR_POSITION) return refuse("kind " + std::to_string(kind) + " is not a kind of prior");
+  if (m < 1) return refuse("m must be >= 1");
+  if (!node || !z || !omega) return refuse("an array is NULL");
+  if (G->n_priors + (long long)m > 0x7fffffffll) return refuse("the graph would hold more than 2^31 - 1 priors");
+  for (long long p = 0; p < m; ++p)
+    if (node[p] < 0 || node[p] >= G->n_nodes)
+      return refuse("prior " + std::to_string(p) + " names node " + std::to_string(node[p]) + " outside the " + std::to_string(G->n_nodes) + " nodes");
+  const bool is_pose = kind == SICP_GRAPH_PRIOR_POSE;
+  std::string why;
+  if (is_pose) {
+    const long long bad = first_bad_pose(z, m, why);
+    if (bad >= 0) return refuse("the measurement of prior " + std::to_string(bad) + " " + why);
+  } else {
+    for (long long k = 0; k < 3ll * m; ++k)
+      if (!std::isfinite(z[k])) return refuse("the measurement of prior " + std::to_string(k / 3) + " is not finite");
+  }
+  GRAPHCHECK(hipSetDevice(G->device));
+  const size_t M = (size_t)m, zb = sizeof(double) * 7 * M, ob = sizeof(double) * 36 * M, ib = sizeof(int) * M;
+  GRAPHCHECK(G->stage.resize(ob + zb + 2 * ib));
+  double* so = reinterpret_cast<double*>(G->stage.data());
+  double* sz = so + 36 * M;
+  int* sn = reinterpret_cast<int*>(sz + 7 * M);
+  int* sk = sn + M;
+  std::memset(G->stage.data(), 0, ob + zb);  // (a position prior fills 3 of its 7 and 9 of its 36)
+  for (size_t p = 0; p < M; ++p) {
+    if (is_pose) {
+      if (!take_omega(omega + 36 * p, 6, so + 36 * p, why)) return refuse("prior " + std::to_string(p) + " " + why);
+      store_pose(z + 7 * p, sz + 7 * p);
+    } else {
+      if (!take_omega(omega + 9 * p, 3, so + 36 * p, why)) return refuse("prior " + std::to_string(p) + " " + why);
+      for (int d = 0; d < 3; ++d) sz[7 * p + d] = z[3 * p + d];
+    }
+    sn[p] = node[p];
+    sk[p] = kind;
+  }
+  G->h_pnode.reserve((size_t)(G->n_priors + m));  // (may throw: before anything changes)
+  G->h_pkind.reserve((size_t)(G->n_priors + m));
+  G->h_pen.reserve((size_t)(G->n_priors + m));
+  const int rc = grow_priors(G, m);
+  if (rc != SICP_OK) return rc;
+  auto& cur = G->priors[G->pcur];
+  const size_t at = (size_t)G->n_priors;
+  GRAPHCHECK(hipMemcpyAsync(cur.omega.p + 36 * at, so, ob, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipMemcpyAsync(cur.z.p + 7 * at, sz, zb, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipMemcpyAsync(cur.node.p + at, sn, ib, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipMemcpyAsync(cur.kind.p + at, sk, ib, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipMemsetAsync(cur.enabled.p + at, 1, M, G->stream));  // (every prior is created enabled)
+  GRAPHCHECK(hipStreamSynchronize(G->stream));
+  if (first_id) *first_id = (int32_t)G->n_priors;
+  G->h_pnode.insert(G->h_pnode.end(), sn, sn + m);
+  G->h_pkind.insert(G->h_pkind.end(), sk, sk + m);
+  G->h_pen.insert(G->h_pen.end(), M, (uint8_t)1);
+  G->n_priors += m;
+  G->n_priors_enabled += m;
+  G->incidence_stale = true;
+  G->anchored_stale = true;
+  return SICP_OK;
+}
+
+int graph_set_enabled(sicp_graph_ctx* G, bool priors, int32_t first, int32_t count, const uint8_t* enabled) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = priors ? "sicp_graph_set_priors_enabled" : "sicp_graph_set_edges_enabled";
+  auto refuse = [&](const std::string& why) {
+    G->last_error = std::string(G->call) + ": " + why + "; the graph is unchanged";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  const long long have = priors ? G->n_priors : G->n_edges;
+  if (first < 0 || count < 1) return refuse("first must be >= 0 and count >= 1");
+  if ((long long)first + count > have)
+    return refuse("the range " + std::to_string(first) + " + " + std::to_string(count) + " reaches beyond the " + std::to_string(have) +
+                  (priors ? " priors" : " edges"));
+  if (!enabled) return refuse("enabled is NULL");
+  std::vector<uint8_t>& mirror = priors ? G->h_pen : G->h_een;
+  long long change = 0;
+  bool same = true;
+  for (long long k = 0; k < count; ++k) {
+    const uint8_t v = enabled[k] ? 1 : 0;
+    same = same && v == mirror[(size_t)(first + k)];
+    change += (long long)v - (long long)mirror[(size_t)(first + k)];
+  }
+  if (same) return SICP_OK;  // (the flags have these values: the tables stay)
+  GRAPHCHECK(hipSetDevice(G->device));
+  GRAPHCHECK(G->stage.resize((size_t)count));
+  for (long long k = 0; k < count; ++k) G->stage[(size_t)k] = enabled[k] ? 1 : 0;
+  uint8_t* dev = priors ? G->priors[G->pcur].enabled.p : G->edges[G->ecur].enabled.p;
+  GRAPHCHECK(hipMemcpyAsync(dev + (size_t)first, G->stage.data(), (size_t)count, hipMemcpyHostToDevice, G->stream));
+  GRAPHCHECK(hipStreamSynchronize(G->stream));
+  for (long long k = 0; k < count; ++k) mirror[(size_t)(first + k)] = G->stage[(size_t)k];
+  (priors ? G->n_priors_enabled : G->n_edges_enabled) += change;
+  G->incidence_stale = true;
+  G->anchored_stale = true;
+  return SICP_OK;
+}
+
+int graph_get_enabled(sicp_graph_ctx* G, bool priors, int32_t first, int32_t count, uint8_t* enabled) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = priors ? "sicp_graph_get_priors_enabled" : "sicp_graph_get_edges_enabled";
+  auto refuse = [&](const std::string& why) {
+    G->last_error = std::string(G->call) + ": " + why + "; nothing was written";
+    return SICP_ERR_INVALID_ARGUMENT;
+  };
+  const long long have = priors ? G->n_priors : G->n_edges;
+  if (first < 0 || count < 1) return refuse("first must be >= 0 and count >= 1");
+  if ((long long)first + count > have)
+    return refuse("the range " + std::to_string(first) + " + " + std::to_string(count) + " reaches beyond the " + std::to_string(have) +
+                  (priors ? " priors" : " edges"));
+  if (!enabled) return refuse("enabled is NULL");
+  const std::vector<uint8_t>& mirror = priors ? G->h_pen : G->h_een;  // (the host's copy is the device's, flag for flag)
+  std::memcpy(enabled, mirror.data() + (size_t)first, (size_t)count);
+  return SICP_OK;
+}
+
+int graph_counts(sicp_graph_ctx* G, int64_t* n_nodes, int64_t* n_edges, int64_t* n_edges_enabled, int64_t* n_priors, int64_t* n_priors_enabled) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  if (n_nodes) *n_nodes = G->n_nodes;
+  if (n_edges) *n_edges = G->n_edges;
+  if (n_edges_enabled) *n_edges_enabled = G->n_edges_enabled;
+  if (n_priors) *n_priors = G->n_priors;
+  if (n_priors_enabled) *n_priors_enabled = G->n_priors_enabled;
   return SICP_OK;
 }
 
@@ -440,25 +691,17 @@ int graph_errors(sicp_graph_ctx* G, double* chi2, double* residual, double* weig
     G->last_error = "sicp_graph_errors: cost is NULL; nothing was written";
     return SICP_ERR_INVALID_ARGUMENT;
   }
-  if (G->n_edges == 0) {
-    *cost = 0.0;
-    return SICP_OK;
+  return entry_errors(G, false, chi2, residual, weight, cost);
+}
+
+int graph_prior_errors(sicp_graph_ctx* G, double* chi2, double* residual, double* weight, double* cost) {
+  if (!G) return SICP_ERR_INVALID_ARGUMENT;
+  G->call = "sicp_graph_prior_errors";
+  if (!cost) {
+    G->last_error = "sicp_graph_prior_errors: cost is NULL; nothing was written";
+    return SICP_ERR_INVALID_ARGUMENT;
   }
-  GRAPHCHECK(hipSetDevice(G->device));
-  sicp::GraphArgs A;
-  int rc = prepare(G, A);
-  if (rc != SICP_OK) return rc;
-  GRAPHCHECK(sicp::launch_graph_linearise(A, A.pose, true, G->stream));
-  GRAPHCHECK(sicp::launch_graph_sum(A, sicp::kGraphFinCost, G->stream));
-  sicp::GraphScalars S;
-  rc = read_scalars(G, S);
-  if (rc != SICP_OK) return rc;
-  const size_t M = (size_t)G->n_edges;
-  if ((rc = download(G, chi2, A.s, M)) != SICP_OK) return rc;
-  if ((rc = download(G, residual, A.r, 6 * M)) != SICP_OK) return rc;
-  if ((rc = download(G, weight, A.w, M)) != SICP_OK) return rc;
-  *cost = S.cost;
-  return SICP_OK;
+  return entry_errors(G, true, chi2, residual, weight, cost);
 }
 
 int graph_linearize(sicp_graph_ctx* G, double* gradient, double* diag_blocks, double* cost) {
@@ -477,16 +720,14 @@ int graph_linearize(sicp_graph_ctx* G, double* gradient, double* diag_blocks, do
   int rc = prepare(G, A);
   if (rc != SICP_OK) return rc;
   if ((rc = build_incidence(G, A)) != SICP_OK) return rc;
-  if (G->n_edges == 0) {  // (every list is empty)
-    GRAPHCHECK(hipMemsetAsync(A.off, 0, sizeof(int) * (size_t)(G->n_nodes + 1), G->stream));
-    GRAPHCHECK(hipMemsetAsync(A.S, 0, sizeof(sicp::GraphScalars), G->stream));
-  }
+  const bool entries = G->n_edges + G->n_priors > 0;
+  if (!entries) GRAPHCHECK(hipMemsetAsync(A.S, 0, sizeof(sicp::GraphScalars), G->stream));  // (no cost is summed)
   if ((rc = linearise_full(G, A)) != SICP_OK) return rc;
   sicp::GraphScalars S;
   if ((rc = read_scalars(G, S)) != SICP_OK) return rc;
   if ((rc = download(G, gradient, A.g, 6 * (size_t)G->n_nodes)) != SICP_OK) return rc;
   if ((rc = download(G, diag_blocks, A.H, 36 * (size_t)G->n_nodes)) != SICP_OK) return rc;
-  *cost = G->n_edges > 0 ? S.cost : 0.0;
+  *cost = entries ? S.cost : 0.0;
   return SICP_OK;
 }
 
@@ -497,8 +738,10 @@ int graph_optimize(sicp_graph_ctx* G, sicp_graph_info* info) {
     G->last_error = "sicp_graph_optimize: info is NULL; the graph is unchanged";
     return SICP_ERR_INVALID_ARGUMENT;
   }
-  if (G->n_edges == 0 || G->n_fixed == 0) {
-    G->last_error = std::string("sicp_graph_optimize: the graph has no ") + (G->n_edges == 0 ? "edge" : "fixed node") + "; the graph is unchanged";
+  const bool nothing = G->n_edges_enabled + G->n_priors_enabled == 0;
+  if (nothing || (G->n_fixed == 0 && G->n_priors_enabled == 0)) {
+    G->last_error = std::string("sicp_graph_optimize: the graph has no ") +
+                    (nothing ? "edge or prior that is enabled" : "fixed node and no enabled prior") + "; the graph is unchanged";
     return SICP_ERR_NOT_READY;
   }
   const sicp_graph_params& P = G->params;
@@ -538,8 +781,7 @@ int graph_optimize(sicp_graph_ctx* G, sicp_graph_info* info) {
     double cand_cost = 0, model = 0;
     if (valid) {
       GRAPHCHECK(sicp::launch_graph_candidates(A, st));
-      GRAPHCHECK(sicp::launch_graph_linearise(A, A.cand, false, st));
-      GRAPHCHECK(sicp::launch_graph_sum(A, sicp::kGraphFinCandCost, st));
+      if ((rc = linearise_entries(G, A, A.cand, false, sicp::kGraphFinCandCost)) != SICP_OK) return rc;
       if ((rc = read_scalars(G, S)) != SICP_OK) return rc;
       cand_cost = S.cand_cost;
       model = -S.gx - 0.5 * S.xHx;
@@ -596,7 +838,8 @@ bool cov_params_ok(const sicp_graph_cov_params& p) {
   return p.max_columns >= 0 && p.max_columns % 6 == 0;
 }
 
-// per node: does its connected component hold a fixed node?  Union-find over the edge ends, redone when the graph has changed.
+// per node: does its connected component hold a fixed node or a node with an enabled pose prior?  Union-find over the ends of
+// the enabled edges, redone when the graph has changed.  (A position prior anchors nothing: one or two leave a rotation free.)
 void refresh_anchored(sicp_graph_ctx* G) {
   if (!G->anchored_stale) return;
   const size_t N = (size_t)G->n_nodes;
@@ -610,12 +853,15 @@ void refresh_anchored(sicp_graph_ctx* G) {
     return v;
   };
   for (size_t e = 0; e < (size_t)G->n_edges; ++e) {
+    if (!G->h_een[e]) continue;
     const int32_t a = find(G->h_ei[e]), b = find(G->h_ej[e]);
     if (a != b) parent[(size_t)std::max(a, b)] = std::min(a, b);
   }
   std::vector<uint8_t> root_fixed(N, 0);
   for (size_t k = 0; k < N; ++k)
     if (G->h_fixed[k]) root_fixed[(size_t)find((int32_t)k)] = 1;
+  for (size_t p = 0; p < (size_t)G->n_priors; ++p)
+    if (G->h_pen[p] && G->h_pkind[p] == SICP_GRAPH_PRIOR_POSE) root_fixed[(size_t)find(G->h_pnode[p])] = 1;
   G->anchored.assign(N, 0);
   for (size_t k = 0; k < N; ++k) G->anchored[k] = root_fixed[(size_t)find((int32_t)k)];
   G->anchored_stale = false;
@@ -715,7 +961,7 @@ int graph_covariances(sicp_graph_ctx* G, bool marginals, const sicp_graph_cov_pa
     int rc = prepare(G, A);
     if (rc != SICP_OK) return rc;
     if ((rc = build_incidence(G, A)) != SICP_OK) return rc;
-    if ((rc = linearise_full(G, A)) != SICP_OK) return rc;  // (a query to solve has an anchored free node: there are edges)
+    if ((rc = linearise_full(G, A)) != SICP_OK) return rc;  // (a query to solve has an anchored free node: there are edges or pose priors)
     // the columns of a pass: what is asked for, no more than the queries need, and what the arena's limit leaves room for
     int cols = (int)std::min<long long>(std::min(P.max_columns > 0 ? P.max_columns : kCovAutoColumns, kCovMaxColumns), 6ll * (long long)solve.size());
     for (;;) {
@@ -742,6 +988,7 @@ int graph_covariances(sicp_graph_ctx* G, bool marginals, const sicp_graph_cov_pa
     std::memset(&V, 0, sizeof V);
     V.n_nodes = (int)G->n_nodes;
     V.pose = A.pose; V.fixed = A.fixed; V.ei = A.ei; V.ej = A.ej; V.B = A.B; V.inc = A.inc; V.off = A.off; V.H = A.H; V.L = A.L;
+    V.held = G->n_priors > 0 ? G->pheld.p : nullptr;
     V.J = G->cov_J.p; V.x = G->cov_x.p; V.r = G->cov_r.p; V.z = G->cov_z.p; V.p = G->cov_p.p; V.q = G->cov_q.p;
     V.part = G->cov_part.p; V.part_stride = (int)cov_part_stride(G->n_nodes);
     V.S = G->cov_cols.p; V.bad = G->cov_bad.p; V.out = G->cov_out.p;

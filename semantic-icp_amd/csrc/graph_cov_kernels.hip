@@ -58,7 +58,11 @@ __device__ __forceinline__ void chol_apply(const double* L, const double* r, dou
   }
 }
 
-__device__ __forceinline__ bool lone(const GraphCovArgs& a, int n) { return !a.fixed[n] && a.off[n + 1] == a.off[n]; }
+// a free node without enabled edges and without an enabled pose prior: the identity block.  (A node that only position
+// priors hold has a block of rank 3; it is never asked for -- UNANCHORED -- and couples to nothing.)
+__device__ __forceinline__ bool lone(const GraphCovArgs& a, int n) {
+  return !a.fixed[n] && a.off[n + 1] == a.off[n] && !(a.held && a.held[n]);
+}
 
 __global__ __launch_bounds__(256) void graph_cov_factor_kernel(GraphCovArgs a) {
   const int n = blockIdx.x * 256 + threadIdx.x;

@@ -2,7 +2,10 @@
 // include/sicp.h and INTEGRATION.md, "Pose graph").
 //   linearise   one edge per lane, 64 lanes a workgroup: residual, chi2, weight, the two (diagonal block, gradient) records and
 //               the off-diagonal block; the cost-only form stops after the loss
-//   gather      one lane per (node, entry of the 42-entry record): the sum of the node's records in incidence order
+//   prior       one prior per lane, 64 lanes a workgroup, both kinds in one launch: residual, chi2, weight and the prior's one
+//               (diagonal block, gradient) record; the cost-only form stops after the loss
+//   gather      one lane per (node, entry of the 42-entry record): the sum of the node's edge records in incidence order, then
+//               of its prior records in prior order
 //   CG          A = H + D on the free nodes, block-Jacobi preconditioner (6x6 Cholesky per node).  The SpMV takes one lane per
 //               (node, row) and walks the node's incidence list; dots are per-workgroup partial sums that one workgroup adds;
 //               alpha, beta and the norms live in GraphScalars and every kernel returns when its flag is set
@@ -11,7 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #define SICP_HD __host__ __device__
-#include "graph_edge.hpp"
+#include "graph_prior.hpp"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -39,6 +42,10 @@ __global__ __launch_bounds__(256) void graph_keys_kernel(GraphArgs a, u64* __res
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   if (t >= 2ll * a.n_edges) return;
   const int e = (int)(t >> 1);
+  if (a.een && !a.een[e]) {  // a disabled edge: behind every node's list, in no node's degree
+    keys[t] = ((u64)(unsigned)a.n_nodes << 32) | (u64)(unsigned)t;
+    return;
+  }
   const int node = (t & 1) ? a.ej[e] : a.ei[e];
   keys[t] = ((u64)(unsigned)node << 32) | (u64)(unsigned)t;
   atomicAdd(&a.deg[node], 1);
@@ -57,13 +64,51 @@ __global__ __launch_bounds__(kGraphLinLanes) void graph_linearise_kernel(GraphAr
   for (int k = 0; k < 36; ++k) Om[k] = a.omega[36 * e + k];
   double r[6], Or[6], Tji[7], s, w, rho;
   graph::edge_error(Ti, Tj, z, Om, a.loss, a.cauchy_a, r, Or, &s, &w, &rho, Tji);
-  a.ec[e] = 0.5 * rho;
+  a.ec[e] = (a.een && !a.een[e]) ? 0.0 : 0.5 * rho;
   if (!FULL) return;
   a.s[e] = s;
   a.w[e] = w;
   SICP_UNROLL
   for (int k = 0; k < 6; ++k) a.r[6 * e + k] = r[k];
   graph::edge_blocks(r, Or, Om, w, Tji, a.C + (2 * e) * kGraphRec, a.C + (2 * e + 1) * kGraphRec, a.B + 36 * e);
+}
+
+// One prior per lane.  A pose prior holds two 6x6 arrays beside Omega (an edge: five), a position prior two 3x3.
+template <bool FULL>
+__global__ __launch_bounds__(kGraphLinLanes) void graph_prior_linearise_kernel(GraphArgs a, const double* __restrict__ pose) {
+  const long long p = (long long)blockIdx.x * kGraphLinLanes + threadIdx.x;
+  if (p >= a.n_priors) return;
+  double T[7], r[6], s, w, rho;
+  const double* pk = pose + 7ll * a.pnode[p];
+  SICP_UNROLL
+  for (int k = 0; k < 7; ++k) T[k] = pk[k];
+  double* ec = a.ec + a.n_edges;
+  const bool on = a.pen[p] != 0;
+  if (a.pkind[p] == graph::kPriorPosition) {
+    double pt[3], Om[9], Or[3];
+    SICP_UNROLL
+    for (int k = 0; k < 3; ++k) pt[k] = a.pz[7 * p + k];
+    SICP_UNROLL
+    for (int k = 0; k < 9; ++k) Om[k] = a.pomega[36 * p + k];
+    graph::prior_position_error(T, pt, Om, a.loss, a.cauchy_a, r, Or, &s, &w, &rho);
+    ec[p] = on ? 0.5 * rho : 0.0;
+    if (!FULL) return;
+    graph::prior_position_blocks(T, Or, Om, w, a.PC + p * kGraphRec);
+  } else {
+    double z[7], Om[36], Or[6];
+    SICP_UNROLL
+    for (int k = 0; k < 7; ++k) z[k] = a.pz[7 * p + k];
+    SICP_UNROLL
+    for (int k = 0; k < 36; ++k) Om[k] = a.pomega[36 * p + k];
+    graph::prior_pose_error(T, z, Om, a.loss, a.cauchy_a, r, Or, &s, &w, &rho);
+    ec[p] = on ? 0.5 * rho : 0.0;
+    if (!FULL) return;
+    graph::prior_pose_blocks(r, Or, Om, w, a.PC + p * kGraphRec);
+  }
+  a.ps[p] = s;
+  a.pw[p] = w;
+  SICP_UNROLL
+  for (int k = 0; k < 6; ++k) a.pr[6 * p + k] = r[k];
 }
 
 __global__ __launch_bounds__(256) void graph_gather_kernel(GraphArgs a) {
@@ -76,6 +121,10 @@ __global__ __launch_bounds__(256) void graph_gather_kernel(GraphArgs a) {
   } else {
     const int end = a.off[n + 1];
     for (int q = a.off[n]; q < end; ++q) v += a.C[(long long)(unsigned)a.inc[q] * kGraphRec + k];
+    if (a.n_priors > 0) {
+      const int pend = a.poff[n + 1];
+      for (int q = a.poff[n]; q < pend; ++q) v += a.PC[(long long)a.pinc[q] * kGraphRec + k];
+    }
   }
   if (k < 36) a.H[36ll * n + k] = v; else a.g[6ll * n + (k - 36)] = v;
 }
@@ -355,6 +404,13 @@ hipError_t launch_graph_linearise(const GraphArgs& a, const double* pose, bool f
   return hipGetLastError();
 }
 
+hipError_t launch_graph_prior_linearise(const GraphArgs& a, const double* pose, bool full, hipStream_t st) {
+  const int blocks = (a.n_priors + kGraphLinLanes - 1) / kGraphLinLanes;
+  if (full) graph_prior_linearise_kernel<true><<<blocks, kGraphLinLanes, 0, st>>>(a, pose);
+  else graph_prior_linearise_kernel<false><<<blocks, kGraphLinLanes, 0, st>>>(a, pose);
+  return hipGetLastError();
+}
+
 hipError_t launch_graph_gather(const GraphArgs& a, hipStream_t st) {
   graph_gather_kernel<<<graph_blocks((long long)a.n_nodes * kGraphRec), 256, 0, st>>>(a);
   return hipGetLastError();
@@ -366,8 +422,9 @@ hipError_t launch_graph_sum(const GraphArgs& a, int fin, hipStream_t st) {
     graph_sum_kernel<true><<<b, 256, 0, st>>>(a, a.g, 6ll * a.n_nodes);
     graph_finish_kernel<kGraphFinGmax><<<1, 256, 0, st>>>(a, b);
   } else {
-    const int b = graph_blocks(a.n_edges);
-    graph_sum_kernel<false><<<b, 256, 0, st>>>(a, a.ec, a.n_edges);
+    const long long entries = (long long)a.n_edges + a.n_priors;  // the edges' 1/2 rho, then the priors'
+    const int b = graph_blocks(entries);
+    graph_sum_kernel<false><<<b, 256, 0, st>>>(a, a.ec, entries);
     if (fin == kGraphFinCost) graph_finish_kernel<kGraphFinCost><<<1, 256, 0, st>>>(a, b);
     else graph_finish_kernel<kGraphFinCandCost><<<1, 256, 0, st>>>(a, b);
   }

@@ -985,8 +985,10 @@ hipError_t launch_place_gather(const unsigned long long* sorted_key, const unsig
 
 // ---- the pose graph (graph_kernels.hip; driver: graph.cpp; the edge's algebra: graph_edge.hpp) ----
 // sicp_graph_*: linearise every edge, gather per node through the incidence table, preconditioned conjugate gradients on the
-// damped normal equations, candidate poses.  No float atomics: every sum has one order (ascending (edge, side) per node;
-// per-workgroup partial sums of 256 lanes added by one workgroup in index order).  The scalars of the iteration stay in
+// damped normal equations, candidate poses.  No float atomics: every sum has one order (per node its enabled edge records in
+// ascending (edge, side), then its enabled prior records in ascending prior id; per-workgroup partial sums of 256 lanes added by
+// one workgroup in index order).  A disabled edge is left out of the incidence lists, a disabled prior out of the prior lists,
+// and either counts as +0.0 at its place in the cost's sum (ec: the edges in id order, then the priors in id order).  The scalars of the iteration stay in
 // GraphScalars on the device: the kernels read the previous step's from memory and return at once when `flag` is set.
 constexpr int kGraphRec = 42;        // a (edge, side) contribution: the 6x6 diagonal block, then the gradient
 constexpr int kGraphChol = 27;       // a node's preconditioner: the 21 entries of L (row-major lower), then 1 / L_kk
@@ -999,18 +1001,27 @@ struct GraphScalars {
   int cg_iters, flag;                   // kGraph*
 };
 struct GraphArgs {
-  int n_nodes, n_edges;
+  int n_nodes, n_edges, n_priors;
   const double* pose;          // [n_nodes][7]
   const uint8_t* fixed;        // [n_nodes]
   const int *ei, *ej;          // [n_edges]
   const double *z, *omega;     // [n_edges][7], [n_edges][36]
+  const uint8_t* een;          // [n_edges] enabled flags; NULL: every edge is enabled
+  // priors (graph_prior.hpp): a POSITION prior uses the first 3 of its z and the first 9 of its omega
+  const int *pnode, *pkind;    // [n_priors]
+  const uint8_t* pen;          // [n_priors] enabled flags
+  const double *pz, *pomega;   // [n_priors][7], [n_priors][36]
   int loss;
   double cauchy_a;
   // per edge
-  double *C, *B, *r, *s, *w, *ec;   // [2 n_edges][kGraphRec], [n_edges][36], [n_edges][6], [n_edges] x 3 (ec: 1/2 rho)
-  // incidence: the slots 2 * edge + side sorted by node (low 32 bits of inc), off[n_nodes + 1]
+  double *C, *B, *r, *s, *w, *ec;   // [2 n_edges][kGraphRec], [n_edges][36], [n_edges][6], [n_edges] x 2, ec [n_edges + n_priors]: 1/2 rho
+  // per prior; its 1/2 rho is ec[n_edges + prior]
+  double *PC, *pr, *ps, *pw;        // [n_priors][kGraphRec], [n_priors][6], [n_priors] x 2
+  // incidence: the slots 2 * edge + side of the enabled edges sorted by node (low 32 bits of inc; the disabled ones follow
+  // under the key n_nodes), off[n_nodes + 1]; the enabled priors sorted by node in pinc, poff[n_nodes + 1] (n_priors > 0 only)
   unsigned long long* inc;
   int *deg, *off;
+  const int *pinc, *poff;
   // per node
   double *H, *g, *L;           // [n_nodes][36], [n_nodes][6], [n_nodes][kGraphChol]
   double *x, *rr, *zz, *p, *q; // [n_nodes][6]: the step, the residual, M^-1 r, the direction, A p
@@ -1023,6 +1034,7 @@ struct GraphArgs {
 enum { kGraphFinStart, kGraphFinPq, kGraphFinRz, kGraphFinCost, kGraphFinCandCost, kGraphFinGmax, kGraphFinCand, kGraphFinModel };
 hipError_t launch_graph_keys(const GraphArgs& a, unsigned long long* keys, hipStream_t st);  // keys[2 n_edges], deg (zeroed before)
 hipError_t launch_graph_linearise(const GraphArgs& a, const double* pose, bool full, hipStream_t st);  // ec (+ r s w C B when full)
+hipError_t launch_graph_prior_linearise(const GraphArgs& a, const double* pose, bool full, hipStream_t st);  // ec (+ pr ps pw PC when full)
 hipError_t launch_graph_gather(const GraphArgs& a, hipStream_t st);                          // H, g
 hipError_t launch_graph_sum(const GraphArgs& a, int fin, hipStream_t st);                    // ec -> S->cost / cand_cost; g -> S->gmax
 hipError_t launch_graph_cg_begin(const GraphArgs& a, hipStream_t st);                        // L, x = 0, r = -g, z, p, S->rz bb rr
@@ -1052,8 +1064,10 @@ struct GraphCovArgs {
   const double* B;             // [n_edges][36]
   const unsigned long long* inc;
   const int* off;
+  const uint8_t* held;         // [n_nodes]: the node has an enabled pose prior; NULL: the graph has no priors
   const double* H;             // [n_nodes][36], undamped
-  double* L;                   // [n_nodes][kGraphChol]: the factor of H's blocks (identity for a free node without edges)
+  double* L;                   // [n_nodes][kGraphChol]: the factor of H's blocks (identity for a free node without enabled edges
+                               // or pose prior)
   const int *qa, *qb;          // [cols / 6]: the query's nodes (qa = -1: a marginal); a fixed end has no block
   double* J;                   // [cols / 6][36]: J_a
   double *x, *r, *z, *p, *q;   // [n_nodes][cols][6]

@@ -1102,6 +1102,36 @@ int sicp_graph_add_edges(sicp_graph g, int32_t m, const int32_t* i, const int32_
   return abi_guard(g, [&]() -> int { return graph_add_edges(g, m, i, j, z, omega, first_id); });
 }
 
+int sicp_graph_add_priors(sicp_graph g, int32_t kind, int32_t m, const int32_t* node, const double* z, const double* omega,
+                          int32_t* first_id) {
+  return abi_guard(g, [&]() -> int { return graph_add_priors(g, kind, m, node, z, omega, first_id); });
+}
+
+int sicp_graph_set_edges_enabled(sicp_graph g, int32_t first, int32_t count, const uint8_t* enabled) {
+  return abi_guard(g, [&]() -> int { return graph_set_enabled(g, false, first, count, enabled); });
+}
+
+int sicp_graph_get_edges_enabled(sicp_graph g, int32_t first, int32_t count, uint8_t* enabled) {
+  return abi_guard(g, [&]() -> int { return graph_get_enabled(g, false, first, count, enabled); });
+}
+
+int sicp_graph_set_priors_enabled(sicp_graph g, int32_t first, int32_t count, const uint8_t* enabled) {
+  return abi_guard(g, [&]() -> int { return graph_set_enabled(g, true, first, count, enabled); });
+}
+
+int sicp_graph_get_priors_enabled(sicp_graph g, int32_t first, int32_t count, uint8_t* enabled) {
+  return abi_guard(g, [&]() -> int { return graph_get_enabled(g, true, first, count, enabled); });
+}
+
+int sicp_graph_prior_errors(sicp_graph g, double* chi2, double* residual, double* weight, double* cost) {
+  return abi_guard(g, [&]() -> int { return graph_prior_errors(g, chi2, residual, weight, cost); });
+}
+
+int sicp_graph_counts(sicp_graph g, int64_t* n_nodes, int64_t* n_edges, int64_t* n_edges_enabled, int64_t* n_priors,
+                      int64_t* n_priors_enabled) {
+  return abi_guard(g, [&]() -> int { return graph_counts(g, n_nodes, n_edges, n_edges_enabled, n_priors, n_priors_enabled); });
+}
+
 int sicp_graph_set_poses(sicp_graph g, int32_t first, int32_t count, const double* qt) {
   return abi_guard(g, [&]() -> int { return graph_set_poses(g, first, count, qt); });
 }
