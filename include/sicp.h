@@ -729,6 +729,76 @@ int sicp_filter(sicp_handle h, int which, const sicp_filter_params* p, const uin
                 double* mean_dist /* n_points, nullable */, int32_t* neighbors /* n_points, nullable */,
                 sicp_filter_info* info /* nullable */);
 
+/* ---- deskewing a scan ---------------------------------------------------------------
+ * A spinning lidar takes the points of one revolution over about 0.1 s while the sensor moves; every other entry point of this
+ * header treats a scan as one rigid snapshot.  sicp_deskew moves every point of the cloud in a handle's slot to one common
+ * instant, from a time stamp per point and a trajectory of pose knots (the first step of LOAM, KISS-ICP, CT-ICP); the result
+ * can become a slot's cloud without the caller touching the points.  The handle may be in any mode.
+ *  1. Trajectory.  Knot k says the sensor had pose knot_qt[7 k .. 7 k + 6] = [qx qy qz qw tx ty tz] (sensor -> some fixed frame) at
+ *     knot_time[k].  Times are finite and strictly ascending, 2 <= n_knots <= SICP_DESKEW_MAX_KNOTS; poses are finite with
+ *     | |q| - 1 | <= 1e-6 (the pose graph's rule) and are used normalised.  Point i was measured at times[i]; its output is the
+ *     same physical point in the sensor frame of ref_qt (NULL: the last knot's pose): p' = ref^-1 T(times[i]) p.
+ *  2. Relative knots, on the host.  K_k = ref^-1 T_k is formed once per call in double (quaternions scaled by 1 / |q|, the
+ *     inverse and the product of the engine's SE(3)); then, k ascending from 1, the quaternion of K_k is negated where its dot
+ *     product with that of K_(k-1) -- as stored -- is negative, so consecutive knots lie in one hemisphere.  knots_out returns
+ *     exactly the table the kernel reads (the scheme of sicp_place_tables: the host's libm and composition order are not part of
+ *     the bit-exact rule).
+ *  3. Per point, on the device, in double; only + - * /, each rounded on its own, none contracted, no sin, cos or sqrt.  With
+ *     t = times[i], kt = knot_time and K the table of rule 2:
+ *       a = the largest index with kt[a] <= t, limited to 0 .. n_knots - 2;
+ *       u = (t - kt[a]) / (kt[a+1] - kt[a]);  t < kt[0]: u = 0 (a = 0), counted in n_clamped_lo;  t > kt[n_knots-1]: u = 1
+ *       (a = n_knots - 2), counted in n_clamped_hi;  w = 1 - u;
+ *       c[j] = (w * K[a][j]) + (u * K[a+1][j]) for the seven numbers; (qx qy qz qw) = c[0..3] is not normalised;
+ *       xx = qx qx, yy = qy qy, zz = qz qz, ww = qw qw;  s = ((xx + yy) + zz) + ww;  k = 2 / s;
+ *       xy = qx qy, xz = qx qz, yz = qy qz, wx = qw qx, wy = qw qy, wz = qw qz;
+ *       row 0 = [1 - k (yy + zz),  k (xy - wz),  k (xz + wy),  c[4]]
+ *       row 1 = [k (xy + wz),  1 - k (xx + zz),  k (yz - wx),  c[5]]
+ *       row 2 = [k (xz - wy),  k (yz + wx),  1 - k (xx + yy),  c[6]]
+ *       p'[r] = (float)(((m0 (double)x + m1 (double)y) + m2 (double)z) + m3) of row r: the row rule of sicp_merge_clouds, one
+ *       rounding to float.
+ *     Why knots and not an exponential per point: device sin and cos are not the host libm's to the bit.  The price: between two
+ *     knots whose rotations differ by an angle Theta the blend is off the geodesic by at most (sqrt(3) / 432) Theta^3 ~
+ *     0.00401 Theta^3 rad (to leading order: times 1 + Theta^2 / 80), and the blended translation is off a screw motion's arc by
+ *     the arc's sagitta at most, (L / 2) tan(Theta / 4) ~ L Theta / 8, L the chord length of the interval.  A car at 30 m/s turning at 1 rad/s over a 0.1 s scan with 33 knots: about 1e-10 rad and 4e-5 m.
+ *     Choose n_knots by these two bounds.  (The hemisphere rule keeps s >= 1/2.)
+ *  4. Classes of points.  A point with a coordinate that is not finite keeps its three floats bit for bit and is counted in
+ *     neither n_finite nor n_moved.  A finite point whose time is not finite becomes three quiet NaNs (0x7fc00000) -- it leaves
+ *     the index instead of staying skewed -- and is counted in n_bad_time.  Every other finite point is moved and counted in
+ *     n_moved; the two clamp counts are among the moved points.  Labels are never touched.
+ *  5. Outputs.  ox / oy / oz (nullable, n_points each) in caller order.  With dst (nullable; needs the same device; may be h
+ *     with dst_which = which: the cloud is deskewed in place) all n_points output points with the cloud's labels, or without
+ *     labels when the cloud has none, become the cloud of dst's slot exactly as sicp_set_cloud of those arrays would set it.  No
+ *     moved point and dst: SICP_ERR_TOO_FEW_POINTS, nothing is written and dst keeps its cloud.
+ *  6. Refused before any device work with SICP_ERR_INVALID_ARGUMENT, the outputs, info, knots_out and dst left as they were: a
+ *     NULL handle, times, knot_time or knot_qt; a `which` (or, with dst, a dst_which) outside SICP_SOURCE / SICP_TARGET; n_knots
+ *     out of range; knot times that are not finite or not strictly ascending; a knot pose or ref_qt that is not finite or not
+ *     unit within 1e-6; dst on another device.  The slot holds no cloud: SICP_ERR_NOT_READY.  Without dst, or with another handle
+ *     as dst, nothing h holds for sicp_align changes (rule 9 of sicp_filter).
+ *  7. Bit-reproducible: a function of the points, times and knot table only -- the same bytes on a handle of any mode, in either
+ *     slot, before or after a sicp_align has laid the cloud out, for every launch shape.  No float atomics; the four counters are
+ *     integers from wave ballots and integer atomics.
+ *  8. sicp_deskew_twist_knots (host only, no device): the constant-velocity model of KISS-ICP.  delta_qt is the sensor's motion
+ *     over [t0, t1], T(t0)^-1 T(t1); knot k is exp(s_k log(delta)) at time t0 + s_k (t1 - t0), s_k = k / (n_knots - 1), with the
+ *     engine's SE(3) exp and log (Sophus' formulas) -- held to a tolerance, not to the bit.  With these knots and ref_qt NULL the
+ *     scan is expressed in the sensor frame at t1.  SICP_ERR_INVALID_ARGUMENT: a NULL pointer, a pose that is not finite or not
+ *     unit within 1e-6, times that are not finite, t1 <= t0, n_knots out of range. */
+#define SICP_DESKEW_MAX_KNOTS 1024
+typedef struct sicp_deskew_info {
+  int64_t n_points;       /* what the caller handed over (the size of times, ox, oy, oz) */
+  int64_t n_finite;
+  int64_t n_moved;        /* finite points with a finite time */
+  int64_t n_bad_time;     /* finite points with a time that is not finite: written as NaN */
+  int64_t n_clamped_lo;   /* moved points with a time below the first knot's */
+  int64_t n_clamped_hi;   /* moved points with a time above the last knot's */
+  double t_total_ms;      /* host wall clock */
+} sicp_deskew_info;
+int sicp_deskew(sicp_handle h, int which, const double* times /* n_points */, int32_t n_knots, const double* knot_time /* n_knots */,
+                const double* knot_qt /* n_knots*7 */, const double ref_qt[7] /* NULL = the last knot's pose */,
+                sicp_handle dst /* nullable */, int dst_which, float* ox, float* oy, float* oz /* n_points each, nullable */,
+                double* knots_out /* n_knots*7, nullable */, sicp_deskew_info* info /* nullable */);
+int sicp_deskew_twist_knots(const double delta_qt[7], double t0, double t1, int32_t n_knots, double* knot_time /* n_knots */,
+                            double* knot_qt /* n_knots*7 */);
+
 /* ---- planes of a cloud -------------------------------------------------------------
  * RANSAC plane extraction of the cloud in a handle's slot (pcl::SACSegmentation with SACMODEL_PLANE or, with an axis,
  * SACMODEL_PERPENDICULAR_PLANE; Open3D's segment_plane): up to max_planes planes, one per round, each from a fixed number of

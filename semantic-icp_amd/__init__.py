@@ -307,6 +307,25 @@ class SicpFilterInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+DESKEW_MAX_KNOTS = 1024
+
+
+class SicpDeskewInfo(C.Structure):
+    """sicp_deskew_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_points", C.c_int64),
+        ("n_finite", C.c_int64),
+        ("n_moved", C.c_int64),
+        ("n_bad_time", C.c_int64),
+        ("n_clamped_lo", C.c_int64),
+        ("n_clamped_hi", C.c_int64),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 PLANE_MAX_HYPOTHESES = 4096
 PLANE_MAX_PLANES = 16
 PLANE_MAX_IGNORE = 16
@@ -742,6 +761,9 @@ def lib():
             "sicp_default_filter_params": [C.POINTER(SicpFilterParams)],
             "sicp_filter": [C.c_void_p, C.c_int, C.POINTER(SicpFilterParams), _bp, C.c_void_p, C.c_int, _bp, _dp, _ip,
                             C.POINTER(SicpFilterInfo)],
+            "sicp_deskew": [C.c_void_p, C.c_int, _dp, C.c_int32, _dp, _dp, _dp, C.c_void_p, C.c_int, _fp, _fp, _fp, _dp,
+                            C.POINTER(SicpDeskewInfo)],
+            "sicp_deskew_twist_knots": [_dp, C.c_double, C.c_double, C.c_int32, _dp, _dp],
             "sicp_default_plane_params": [C.POINTER(SicpPlaneParams)],
             "sicp_segment_planes": [C.c_void_p, C.c_int, C.POINTER(SicpPlaneParams), _bp, _ip, C.c_int32, _dp, _ip, _ip, _ip, _dp, _dp,
                                     C.POINTER(SicpPlaneInfo)],
@@ -936,6 +958,22 @@ def default_filter_params(drop=(), protect=(), **overrides) -> SicpFilterParams:
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def deskew_twist_knots(delta_qt, t0: float, t1: float, n_knots: int = 33):
+    """sicp_deskew_twist_knots (host only): the knots of the constant-velocity model -- delta_qt = T(t0)^-1 T(t1) is the sensor's
+    motion over [t0, t1], knot k is exp(s_k log(delta)) at t0 + s_k (t1 - t0), s_k = k / (n_knots - 1).  Returns (knot_times
+    [n_knots] float64, knot_qts [n_knots, 7] float64) for Engine.deskew."""
+    d = np.ascontiguousarray(delta_qt, dtype=np.float64)
+    if d.shape != (7,):
+        raise ValueError("delta_qt must hold 7 numbers")
+    m = max(int(n_knots), 1)
+    kt = np.empty(m, dtype=np.float64)
+    kq = np.empty((m, 7), dtype=np.float64)
+    st = lib().sicp_deskew_twist_knots(_ptr(d, _dp), float(t0), float(t1), int(n_knots), _ptr(kt, _dp), _ptr(kq, _dp))
+    if st != OK:
+        raise SicpError(st, "sicp_deskew_twist_knots")
+    return kt, kq
 
 
 def default_plane_params(ignore=(), axis=None, **overrides) -> SicpPlaneParams:
@@ -1451,6 +1489,39 @@ class Engine:
         if dst is not None:
             dst.n[dw] = int(info.n_kept)
         return {"keep": keep[:n], "mean_dist": md[:n], "neighbors": nb[:n], "info": info.as_dict()}
+
+    def deskew(self, which: int, times, knot_times, knot_qts, ref_qt=None, dst: "Engine | None" = None, dst_which: int | None = None,
+               want_points: bool = True):
+        """sicp_deskew: every point of the cloud in slot `which` moved to one instant -- times [n_points] float64 is when each
+        point was measured, knot_times [n_knots] (ascending) and knot_qts [n_knots, 7] the sensor's trajectory, ref_qt the pose
+        whose sensor frame the result is in (None: the last knot's).  Returns {"points": [n_points, 3] float32 (None without
+        want_points), "knots": [n_knots, 7] float64, the relative knots the kernel read, "info": SicpDeskewInfo.as_dict()}.  With
+        dst the moved points and the cloud's labels become that Engine's slot dst_which (default: `which`) as if they had been
+        handed to set_cloud; dst may be this engine.  Without dst nothing on the engine changes."""
+        n = self.n[which] if which in (SOURCE, TARGET) else 0
+        times = np.ascontiguousarray(times, dtype=np.float64)
+        if times.shape != (n,):
+            raise ValueError(f"times must have one entry per point ({n})")
+        kt = np.ascontiguousarray(knot_times, dtype=np.float64)
+        kq = np.ascontiguousarray(knot_qts, dtype=np.float64)
+        if kt.ndim != 1 or kq.shape != (kt.shape[0], 7):
+            raise ValueError("knot_times must be [n_knots] and knot_qts [n_knots, 7]")
+        if ref_qt is not None:
+            ref_qt = np.ascontiguousarray(ref_qt, dtype=np.float64)
+            if ref_qt.shape != (7,):
+                raise ValueError("ref_qt must hold 7 numbers")
+        nk = int(kt.shape[0])
+        out = np.empty((3, max(n, 1)), dtype=np.float32) if want_points else None
+        knots = np.empty((max(nk, 1), 7), dtype=np.float64)
+        info = SicpDeskewInfo()
+        dw = which if dst_which is None else dst_which
+        ox, oy, oz = (None, None, None) if out is None else (out[0], out[1], out[2])
+        self._check(lib().sicp_deskew(self._h, which, _ptr(times, _dp), nk, _ptr(kt, _dp), _ptr(kq, _dp), _ptr(ref_qt, _dp),
+                                      None if dst is None else dst._h, dw, _ptr(ox, _fp), _ptr(oy, _fp), _ptr(oz, _fp),
+                                      _ptr(knots, _dp), C.byref(info)), "sicp_deskew")
+        if dst is not None:
+            dst.n[dw] = int(info.n_points)
+        return {"points": None if out is None else np.ascontiguousarray(out[:, :n].T), "knots": knots[:nk], "info": info.as_dict()}
 
     def segment_planes(self, which: int = SOURCE, params: SicpPlaneParams | None = None, mask=None):
         """sicp_segment_planes: the dominant planes of the cloud in slot `which` by RANSAC -- per round num_hypotheses three-point

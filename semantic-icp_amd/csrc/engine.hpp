@@ -11,6 +11,7 @@
 //   merge.cpp     sicp_merge_clouds: posed clouds into one voxel-grid cloud
 //   cluster.cpp   sicp_cluster: label-aware Euclidean clustering of a cloud
 //   filter.cpp    sicp_filter: statistical / radius outlier removal and masked selection of a cloud
+//   deskew.cpp    sicp_deskew: a scan's points moved to one instant from per-point times and a knot trajectory
 //   plane.cpp     sicp_segment_planes: RANSAC plane extraction of a cloud
 //   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, raycast, prune, extract, merge, state)
 //   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
@@ -512,6 +513,10 @@ struct sicp_context : sicp_use_state {
   // back, and the pinned kept points (x | y | z | label) on their way into dst
   HostBuf<unsigned char> fl_stage;
   HostBuf<uint32_t> fl_out;
+  // sicp_deskew (deskew.cpp): the pinned times / knots / caller indices on their way up and the counts on their way back, and the
+  // pinned moved points (x | y | z | label, the caller's indices) on their way to the caller and into dst
+  HostBuf<unsigned char> dk_stage;
+  HostBuf<uint32_t> dk_out;
   // sicp_segment_planes (plane.cpp): the pinned finite positions / mask on their way up, the control block, plane records and
   // per-point states on their way back
   HostBuf<unsigned char> pl_stage;
@@ -1022,6 +1027,12 @@ float cells_per_metre(float t);  // the grid's cells per metre for a tolerance /
 void filter_default_params(sicp_filter_params* p);
 int filter(sicp_context* h, int which, const sicp_filter_params* p, const uint8_t* mask, sicp_context* dst, int dst_which, uint8_t* keep,
            double* mean_dist, int32_t* neighbors, sicp_filter_info* info);
+// sicp_deskew (deskew.cpp): argument checks, the relative knots composed on the host, the one kernel on the cloud's device copy,
+// one read-back, and the moved cloud's way into dst (set_cloud_common); sicp_deskew_twist_knots: host only
+int deskew(sicp_context* h, int which, const double* times, int32_t n_knots, const double* knot_time, const double* knot_qt,
+           const double* ref_qt, sicp_context* dst, int dst_which, float* ox, float* oy, float* oz, double* knots_out,
+           sicp_deskew_info* info);
+int deskew_twist_knots(const double* delta_qt, double t0, double t1, int32_t n_knots, double* knot_time, double* knot_qt);
 // sicp_segment_planes (plane.cpp): argument checks, every round of the plane kernels queued on the handle's stream, one
 // read-back
 void plane_default_params(sicp_plane_params* p);

@@ -604,6 +604,27 @@ hipError_t launch_filter_flags(const FilterArgs& a, hipStream_t st);       // fl
 // (prim_scan_int flag -> pos)
 hipError_t launch_filter_gather(const FilterArgs& a, hipStream_t st);      // ox oy oz ol, res[kept]
 
+// ---- deskewing a scan (deskew_kernels.hip; driver: deskew.cpp) ----
+// sicp_deskew: the finite points of one cloud in caller order (Cloud::rx ...; index f is a position in that order, `caller` maps
+// it to the caller's index when points were dropped), every point's time at its caller index, and the relative knots the host
+// composed (rule 2).  One launch: the table goes to LDS, a lane finds its interval by binary search, blends the two knots,
+// forms the rotation and moves its point; the outputs sit at the caller's index.
+constexpr int kDeskewMaxKnots = 1024;  // SICP_DESKEW_MAX_KNOTS
+constexpr int kDeskewMaxGroups = 512;  // the launch is at most this many workgroups of 256: more points stride over them
+enum { kDkMoved = 0, kDkBadTime = 1, kDkClampedLo = 2, kDkClampedHi = 3, kDkRes = 4 };
+struct DeskewArgs {
+  int n;                    // finite points
+  int n_knots;
+  const float *x, *y, *z;   // [n] by f
+  const int* caller;        // [n] f -> caller index; nullptr: the identity
+  const double* times;      // [n_caller]
+  const double* knot_time;  // [n_knots]
+  const double* knot_qt;    // [n_knots][7]
+  float *ox, *oy, *oz;      // [n_caller]; only the entries of finite points are written
+  int* res;                 // kDkRes words, zeroed before the launch
+};
+hipError_t launch_deskew(const DeskewArgs& a, hipStream_t st);
+
 // ---- RANSAC plane extraction (plane_kernels.hip; driver: plane.cpp) ----
 // sicp_segment_planes: every array below that is [n_caller] long is indexed by the caller's index i; `finv` maps it to the
 // position f of the point among the finite ones (Cloud::rx ...), -1 for a point that is not finite.  A round compacts the

@@ -848,6 +848,18 @@ int sicp_filter(sicp_handle h, int which, const sicp_filter_params* p, const uin
   });
 }
 
+int sicp_deskew(sicp_handle h, int which, const double* times, int32_t n_knots, const double* knot_time, const double* knot_qt,
+                const double ref_qt[7], sicp_handle dst, int dst_which, float* ox, float* oy, float* oz, double* knots_out,
+                sicp_deskew_info* info) {
+  return abi_guard(h, [&]() -> int {
+    return deskew(h, which, times, n_knots, knot_time, knot_qt, ref_qt, dst, dst_which, ox, oy, oz, knots_out, info);
+  });
+}
+
+int sicp_deskew_twist_knots(const double delta_qt[7], double t0, double t1, int32_t n_knots, double* knot_time, double* knot_qt) {
+  return abi_guard([&]() -> int { return deskew_twist_knots(delta_qt, t0, t1, n_knots, knot_time, knot_qt); });
+}
+
 int sicp_default_plane_params(sicp_plane_params* p) {
   return abi_guard([&]() -> int {
     if (!p) return SICP_ERR_INVALID_ARGUMENT;
