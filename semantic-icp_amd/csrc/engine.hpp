@@ -394,10 +394,17 @@ struct JobSlice {
 constexpr int kParts = 4;  // slices of a batch whose stage sequences run on their own streams
 
 struct JobCollector {
-  // EM weights written by the search's own epilogue (stages.cpp: run_correspondences) instead of a weight kernel behind it:
-  // set by a batch of at most 4 pairs, where every launch is on the critical path of an align() (one pair alone: -46 us of
-  // 1.98 ms).  Not by larger batches and streams: there the separate weight kernel runs hidden beside the accumulate launches
-  // and the longer search does not (measured, profiles/r05/weights_in_search_epilogue.json: 256-pair step 184.4 against 185.3 ms).
+  // EM weights written by the search's own epilogue (stages.cpp: run_correspondences) instead of a weight kernel behind it.
+  // In a 16-job launch the epilogue adds 4.8 us to a 100K-point search (24.3 -> 29.1 us), the kernel it replaces takes 13.4 us
+  // alone.  Set by:
+  //   a batch of at most 4 pairs  every launch is on the critical path of an align() (one pair alone: -46 us of 1.98 ms);
+  //   an open stream              256 pairs in flight: 167.9 against 170.6 ms per step, every run faster than every run without
+  //                               in each of four alternated blocks (2.4 - 3.5 ms; twice the parent's spread in two of them);
+  //   a batch of 16 pairs or more closed 256-pair batch 184.8 against 187.4 ms, 16 full-size pairs 42.3 against 43.6 ms.
+  // (profiles/weights_dense/ab.json.  Since the accumulate launches hand their chunks out dynamically a search workgroup that
+  // stays longer on a CU no longer delays a launch.  What a step saves is under a third of the 9.5 ms the sum of unit costs
+  // predicts: most of the weight kernel ran hidden beside the accumulate launches.  Round 5's static ranges gave 0.5 %.)
+  // Batches of 5 to 15 pairs were not measured and keep the kernel.
   bool fold_weights = false;
   int slice = 0;  // slice of the batch the pair whose stage is running belongs to (set by the driver)
   JobSlice part[kParts];

@@ -316,7 +316,7 @@ int run_correspondences(sicp_context* h, const double* qt, int K, bool weights) 
   h->counted_in_search = false;
   // EM-ICP, K = 4, at most 16 classes, packet search: the weights are written by the search's own epilogue
   // (knn_kernels.hip: KnnArgs::w_*; the same operations as em_weight_rows4_jobs_kernel, which then does not run) -- for a handle
-  // on its own and in batches of at most 4 pairs (JobCollector::fold_weights says why not in larger ones).  Only when
+  // on its own, in streams and in the batches JobCollector::fold_weights names (it says which and why).  Only when
   // the projections it reads are already there -- computed by an EARLIER flush, not waiting in this one (a flush launches
   // its searches first).
   WeightFold fold_args;

@@ -44,6 +44,9 @@ static void stream_worker_loop(sicp_stream_ctx* S) {
   TickGroup G;
   G.lo = 0; G.hi = S->cap; G.M = L->own_stream; G.S = &L->ts[0]; G.side_done = L->side_done;
   JobCollector jc;
+  // (a new pair's features are flushed below, in a flush of their own ahead of its first search: every search of a
+  // registration, the first included, finds its projections computed and writes its weights itself)
+  jc.fold_weights = true;
   for (sicp_context* g : S->slots) g->collect = &jc;
   std::vector<int> free_slots;
   for (int p = S->cap - 1; p >= 0; --p) free_slots.push_back(p);
