@@ -799,6 +799,118 @@ int sicp_deskew(sicp_handle h, int which, const double* times /* n_points */, in
 int sicp_deskew_twist_knots(const double delta_qt[7], double t0, double t1, int32_t n_knots, double* knot_time /* n_knots */,
                             double* knot_qt /* n_knots*7 */);
 
+/* ---- range image and labels from it ---------------------------------------------------
+ * The labels of a lidar scan come from a network that reads a range image (RangeNet++, SalsaNext, the SemanticKITTI tools).
+ * sicp_range_image is the step before the network: the spherical projection of the cloud in a handle's slot, about
+ * sensor_origin in the cloud's own frame, into height x width pixels.  sicp_range_labels is the step after it: the per-pixel
+ * classes carried back onto every point by a vote among the nearest pixels of a window, the points that lost their pixel to a
+ * nearer one included; the relabelled cloud can become a slot's cloud without leaving the library.  The image is also what depth
+ * clustering, visibility tests and organised down-sampling work on.  The handle may be in any mode.
+ *  Tables, on the host, once per call, in double with libm; sicp_range_tables returns exactly what the kernels read (the scheme
+ *  of sicp_place_tables: the host's libm is not part of the bit-exact rule).  With W = width, H = height:
+ *     cos_half[j], sin_half[j] = cos, sin of 2 pi j / W for j < W / 2;
+ *     row_edge[r] = tan(a_r) |tan(a_r)| for r = 0 .. H, strictly descending: the signed squared tangent of the elevation a_r of
+ *     the edge between rows r - 1 and r.  Without a beam table a_r = fov_up + (fov_down - fov_up) (r / H) (a_H = fov_down).  With
+ *     beam_elevation[H] (radians, strictly descending, row 0 the top beam) the inner edges are the midpoints (b[r-1] + b[r]) / 2,
+ *     a_0 = b[0] + (b[0] - b[1]) / 2 and a_H = b[H-1] - (b[H-2] - b[H-1]) / 2; for H = 1 the edges are fov_up and fov_down.
+ *     A table entry that is not finite, or edges that do not strictly descend, are refused.
+ *  The projection (fp contraction off, every operation rounded on its own; restated in numpy by tests/range_ref.py):
+ *  1. Offset.  dx, dy, dz = the point minus sensor_origin in float (NULL: 0 0 0), as sicp_place_describe forms them.
+ *  2. Range.  r2 = (dx dx + dy dy) + dz dz in float.  The point is KEPT iff (double)r2 >= min_range^2 and (double)r2 <
+ *     max_range^2, the bounds squared on the host in double.
+ *  3. Doubles.  X, Y, Z = (double)dx, dy, dz;  D = X X + Y Y (both products exact, one rounded sum);  Zs = Z |Z| (exact).
+ *  4. Column.  The half plane of sicp_place_describe: lower = !(dy > 0 || (dy == 0 && dx > 0)), (xp, yp) = lower ? (-X, -Y) :
+ *     (X, Y).  The sector inside it by one fixed bisection:
+ *       lo = 0, hi = W / 2;  while (hi - lo > 1) { mid = (lo + hi) >> 1;  if (cos_half[mid] yp - sin_half[mid] xp >= 0.0) lo = mid;
+ *       else hi = mid; }
+ *     each product and the difference rounded on their own.  s = lo (+ W / 2 when lower); c = clockwise ? W - 1 - s : s;
+ *     col = (c + col_shift) mod W.  The bisection, not monotonicity of the rounded predicate, is the definition.  Sector s holds
+ *     the azimuths atan2(dy, dx) in [2 pi s / W, 2 pi (s + 1) / W) counted from +x through +y; clockwise = 1 with col_shift =
+ *     W / 2 is the RangeNet++ column floor(0.5 (1 - yaw / pi) W) for every point away from a sector edge.
+ *  5. Row.  The point is inside the field of view iff !(Zs > row_edge[0] D) and Zs >= row_edge[H] D, one rounded product each.
+ *     Its row by the same kind of bisection over the inner edges:
+ *       lo = 0, hi = H;  while (hi - lo > 1) { mid = (lo + hi) >> 1;  if (Zs < row_edge[mid] D) lo = mid; else hi = mid; }
+ *     row = lo: a point exactly on an inner edge belongs to the row above it, both outer edges are inside.  A kept point
+ *     outside the field of view is counted in n_outside_fov and has pixel -1.  A point on the sensor's vertical axis has D = 0
+ *     and needs no special case: the comparisons put it outside (above or below), or, at the origin itself, inside.
+ *  6. Winner.  A pixel's winner is its kept, in-view point with the smallest 64-bit key (bits(r2) << 32) | index, the index
+ *     ascending with the caller's: the nearest point, equal ranges to the smaller caller index.  One unsigned 64-bit atomic
+ *     minimum per point: an integer atomic, so the bytes depend neither on the launch shape nor on the other points' order.
+ *  7. Outputs, every one nullable.  Per pixel, H W long, row-major: index (the winner's caller index, -1: empty), range_sq
+ *     (r2, 0: empty; no root is taken on the device), x, y, z (the winner's coordinates as the caller gave them, 0: empty), label
+ *     (the winner's label; 0 when empty or when the cloud has no labels), count (the kept, in-view points that fell into the
+ *     pixel).  Per point, n_points long, caller order: pixel = row W + col or -1; visible = 1 iff the point won its pixel.  A
+ *     point that is not finite has pixel -1, visible 0 and is counted in neither n_finite nor anything after it (rule 4 of
+ *     sicp_deskew).  info: n_kept (rule 2), n_out_of_range = n_finite - n_kept, n_outside_fov, n_pixels_hit.
+ *  The vote (sicp_range_labels): the call projects as above; pixel_label[H W] is the network's class per pixel, 0 = no class.
+ *  Every kept, in-view point i with pixel (r, c) then:
+ *  8. Candidates.  The occupied pixels of the window x window block centred on (r, c); columns wrap modulo W, rows outside
+ *     0 .. H - 1 are absent; visited in ascending (window row, window column).
+ *  9. Distance.  d2 = (ex ex + ey ey) + ez ez in float, e = the point minus the pixel's winner in float.  A candidate takes
+ *     part iff (double)d2 < max_dist_sq, strictly (the comparison of sicp_evaluate).  This true 3-D distance deliberately
+ *     replaces RangeNet++'s range difference under a Gaussian window weight: it needs no root and no exponential, and two
+ *     points of equal range in neighbouring pixels can be metres apart only in range-image terms, never in d2.
+ * 10. Neighbours.  The k participants with the smallest (bits(d2), visiting order).
+ * 11. Vote.  Each neighbour whose pixel_label is not 0 gives one vote to that class; the class with the most votes wins, ties
+ *     to the smallest label (the rule of sicp_merge_clouds).  out_label[i] = the winner, votes[i] = its vote count.
+ * 12. No vote.  A point without any vote -- no neighbour of a class, not kept, outside the view -- keeps its own label (0 when
+ *     the cloud has none) with votes = 0; a point that is not finite has out_label 0 (sicp_set_cloud dropped it with its
+ *     label).  info: n_voted = the points with votes > 0, n_unvoted = n_points - n_voted.
+ * 13. dst (nullable; needs the same device; may be h with dst_which = which: the cloud is relabelled in place).  All n_points
+ *     points with out_label become the cloud of dst's slot exactly as sicp_set_cloud of those arrays would set it; a cloud that
+ *     had no labels becomes a labelled one.  Everything is on the host before the slot lets go of its old cloud.  No finite
+ *     point and dst: SICP_ERR_TOO_FEW_POINTS, dst keeps its cloud.
+ * 14. Refused before any device work with SICP_ERR_INVALID_ARGUMENT, the outputs, info and dst left as they were, the reason in
+ *     sicp_last_error: a NULL handle or params; a `which` (or, with dst, a dst_which) outside SICP_SOURCE / SICP_TARGET; width odd
+ *     or outside 16 .. SICP_RANGE_MAX_WIDTH; height outside 1 .. SICP_RANGE_MAX_HEIGHT; fov_up <= fov_down, or either not
+ *     strictly inside +-pi/2; min_range negative or not finite, max_range not finite or <= min_range; clockwise not 0 or 1;
+ *     col_shift outside 0 .. W - 1; window even or outside 1 .. SICP_RANGE_MAX_WINDOW; k outside 1 .. SICP_RANGE_MAX_K;
+ *     max_dist_sq negative or NaN; a beam table that is not finite or not strictly descending, or whose edges are not; a
+ *     sensor_origin that is not finite; a NULL pixel_label (the vote); dst on another device.  The slot holds no cloud:
+ *     SICP_ERR_NOT_READY.  Without dst, or with another handle as dst, nothing h holds for sicp_align changes (rule 9 of
+ *     sicp_filter).  sicp_range_tables (host only, no handle) returns the status alone.
+ * 15. Bit-reproducible: a function of the points, labels, parameters and tables only -- the same bytes on a handle of any mode,
+ *     in either slot, before or after a sicp_align has laid the cloud out, for every launch shape.  No float atomics. */
+#define SICP_RANGE_MAX_WIDTH 4096
+#define SICP_RANGE_MAX_HEIGHT 256
+#define SICP_RANGE_MAX_WINDOW 7
+#define SICP_RANGE_MAX_K 16
+typedef struct sicp_range_params {
+  int32_t width;       /* W: even, 16 .. SICP_RANGE_MAX_WIDTH.  default 2048 */
+  int32_t height;      /* H: 1 .. SICP_RANGE_MAX_HEIGHT.  default 64 */
+  double fov_up;       /* radians, strictly inside +-pi/2, > fov_down.  default +3 degrees */
+  double fov_down;     /* default -25 degrees */
+  double min_range;    /* metres, finite, >= 0.  default 0.5 */
+  double max_range;    /* finite, > min_range.  default 120 */
+  int32_t clockwise;   /* 0: columns ascend with the azimuth; 1 (default): they descend */
+  int32_t col_shift;   /* 0 .. W - 1.  default W / 2 = 1024 (with clockwise: the RangeNet++ column) */
+  int32_t window;      /* the vote: S odd, 1 .. SICP_RANGE_MAX_WINDOW.  default 5 */
+  int32_t k;           /* the vote: 1 .. SICP_RANGE_MAX_K.  default 5 */
+  double max_dist_sq;  /* the vote: >= 0 (infinity allowed).  default 1.0 */
+} sicp_range_params;
+typedef struct sicp_range_info {
+  int64_t n_points;        /* what the caller handed over (the size of pixel, visible, out_label, votes) */
+  int64_t n_finite;
+  int64_t n_kept;          /* finite points inside [min_range, max_range) */
+  int64_t n_out_of_range;  /* n_finite - n_kept */
+  int64_t n_outside_fov;   /* kept points outside the field of view */
+  int64_t n_pixels_hit;    /* pixels with a winner */
+  int64_t n_voted;         /* sicp_range_labels: points with votes > 0; sicp_range_image: 0 */
+  int64_t n_unvoted;       /* sicp_range_labels: n_points - n_voted; sicp_range_image: 0 */
+  double t_total_ms;       /* host wall clock */
+} sicp_range_info;
+int sicp_default_range_params(sicp_range_params* p);
+int sicp_range_tables(const sicp_range_params* p, const double* beam_elevation /* height, nullable */,
+                      double* cos_half /* width/2 */, double* sin_half /* width/2 */, double* row_edge /* height+1; all nullable */);
+int sicp_range_image(sicp_handle h, int which, const sicp_range_params* p, const double* beam_elevation /* height, nullable */,
+                     const float sensor_origin[3] /* NULL = 0 0 0 */, int32_t* index, float* range_sq, float* x, float* y, float* z,
+                     uint32_t* label, uint32_t* count /* height*width each, nullable */, int32_t* pixel, uint8_t* visible
+                     /* n_points each, nullable */, sicp_range_info* info /* nullable */);
+int sicp_range_labels(sicp_handle h, int which, const sicp_range_params* p, const double* beam_elevation /* height, nullable */,
+                      const float sensor_origin[3] /* NULL = 0 0 0 */, const uint32_t* pixel_label /* height*width */,
+                      sicp_handle dst /* nullable */, int dst_which, uint32_t* out_label, uint8_t* votes
+                      /* n_points each, nullable */, sicp_range_info* info /* nullable */);
+
 /* ---- planes of a cloud -------------------------------------------------------------
  * RANSAC plane extraction of the cloud in a handle's slot (pcl::SACSegmentation with SACMODEL_PLANE or, with an axis,
  * SACMODEL_PERPENDICULAR_PLANE; Open3D's segment_plane): up to max_planes planes, one per round, each from a fixed number of

@@ -326,6 +326,47 @@ class SicpDeskewInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+RANGE_MAX_WIDTH = 4096
+RANGE_MAX_HEIGHT = 256
+RANGE_MAX_WINDOW = 7
+RANGE_MAX_K = 16
+
+
+class SicpRangeParams(C.Structure):
+    """sicp_range_params (include/sicp.h)"""
+    _fields_ = [
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("fov_up", C.c_double),
+        ("fov_down", C.c_double),
+        ("min_range", C.c_double),
+        ("max_range", C.c_double),
+        ("clockwise", C.c_int32),
+        ("col_shift", C.c_int32),
+        ("window", C.c_int32),
+        ("k", C.c_int32),
+        ("max_dist_sq", C.c_double),
+    ]
+
+
+class SicpRangeInfo(C.Structure):
+    """sicp_range_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_points", C.c_int64),
+        ("n_finite", C.c_int64),
+        ("n_kept", C.c_int64),
+        ("n_out_of_range", C.c_int64),
+        ("n_outside_fov", C.c_int64),
+        ("n_pixels_hit", C.c_int64),
+        ("n_voted", C.c_int64),
+        ("n_unvoted", C.c_int64),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 PLANE_MAX_HYPOTHESES = 4096
 PLANE_MAX_PLANES = 16
 PLANE_MAX_IGNORE = 16
@@ -764,6 +805,12 @@ def lib():
             "sicp_deskew": [C.c_void_p, C.c_int, _dp, C.c_int32, _dp, _dp, _dp, C.c_void_p, C.c_int, _fp, _fp, _fp, _dp,
                             C.POINTER(SicpDeskewInfo)],
             "sicp_deskew_twist_knots": [_dp, C.c_double, C.c_double, C.c_int32, _dp, _dp],
+            "sicp_default_range_params": [C.POINTER(SicpRangeParams)],
+            "sicp_range_tables": [C.POINTER(SicpRangeParams), _dp, _dp, _dp, _dp],
+            "sicp_range_image": [C.c_void_p, C.c_int, C.POINTER(SicpRangeParams), _dp, _fp, _ip, _fp, _fp, _fp, _fp, _up, _up, _ip, _bp,
+                                 C.POINTER(SicpRangeInfo)],
+            "sicp_range_labels": [C.c_void_p, C.c_int, C.POINTER(SicpRangeParams), _dp, _fp, _up, C.c_void_p, C.c_int, _up, _bp,
+                                  C.POINTER(SicpRangeInfo)],
             "sicp_default_plane_params": [C.POINTER(SicpPlaneParams)],
             "sicp_segment_planes": [C.c_void_p, C.c_int, C.POINTER(SicpPlaneParams), _bp, _ip, C.c_int32, _dp, _ip, _ip, _ip, _dp, _dp,
                                     C.POINTER(SicpPlaneInfo)],
@@ -974,6 +1021,45 @@ def deskew_twist_knots(delta_qt, t0: float, t1: float, n_knots: int = 33):
     if st != OK:
         raise SicpError(st, "sicp_deskew_twist_knots")
     return kt, kq
+
+
+def default_range_params(**overrides) -> SicpRangeParams:
+    """sicp_default_range_params (2048 x 64, +3 / -25 degrees, 0.5 .. 120 m, clockwise with col_shift = width / 2: the RangeNet++
+    layout; the vote: window 5, k 5, max_dist_sq 1.0) with any field overridden by keyword.  A width given without a col_shift
+    moves the shift to the new width / 2."""
+    p = SicpRangeParams()
+    st = lib().sicp_default_range_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_range_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    if "width" in overrides and "col_shift" not in overrides:
+        p.col_shift = int(p.width) // 2
+    return p
+
+
+def _beam_table(params: SicpRangeParams, beam_elevation):
+    if beam_elevation is None:
+        return None
+    b = np.ascontiguousarray(beam_elevation, dtype=np.float64)
+    if b.shape != (max(int(params.height), 0),):
+        raise ValueError(f"beam_elevation must have one entry per row ({params.height})")
+    return b
+
+
+def range_tables(params: SicpRangeParams, beam_elevation=None):
+    """sicp_range_tables (host only): {"cos_half": [W/2], "sin_half": [W/2], "row_edge": [H+1]} float64, exactly what the kernels
+    of Engine.range_image / range_labels read for these parameters and this beam table"""
+    b = _beam_table(params, beam_elevation)
+    half, rows = max(int(params.width) // 2, 1), max(int(params.height) + 1, 1)
+    c, s = np.empty(half, dtype=np.float64), np.empty(half, dtype=np.float64)
+    e = np.empty(rows, dtype=np.float64)
+    st = lib().sicp_range_tables(C.byref(params), _ptr(b, _dp), _ptr(c, _dp), _ptr(s, _dp), _ptr(e, _dp))
+    if st != OK:
+        raise SicpError(st, "sicp_range_tables")
+    return {"cos_half": c, "sin_half": s, "row_edge": e}
 
 
 def default_plane_params(ignore=(), axis=None, **overrides) -> SicpPlaneParams:
@@ -1522,6 +1608,65 @@ class Engine:
         if dst is not None:
             dst.n[dw] = int(info.n_points)
         return {"points": None if out is None else np.ascontiguousarray(out[:, :n].T), "knots": knots[:nk], "info": info.as_dict()}
+
+    @staticmethod
+    def _origin(sensor_origin):
+        if sensor_origin is None:
+            return None
+        o = np.ascontiguousarray(sensor_origin, dtype=np.float32)
+        if o.shape != (3,):
+            raise ValueError("sensor_origin must hold 3 numbers")
+        return o
+
+    def range_image(self, which: int = SOURCE, params: SicpRangeParams | None = None, sensor_origin=None, beam_elevation=None,
+                    per_point: bool = True):
+        """sicp_range_image: the spherical projection of the cloud in slot `which` about sensor_origin (None: 0 0 0) into
+        height x width pixels, each won by its nearest point.  Returns {"index": int32 (-1: empty), "range_sq", "range" (its root,
+        taken here), "x", "y", "z": float32, "label", "count": uint32, all [H, W]; with per_point "pixel": [n_points] int32
+        (row * W + col or -1) and "visible": [n_points] uint8; "info": SicpRangeInfo.as_dict()}.  Nothing on the engine changes."""
+        p = params if params is not None else default_range_params()
+        b, o = _beam_table(p, beam_elevation), self._origin(sensor_origin)
+        n = self.n[which] if which in (SOURCE, TARGET) else 0
+        H, W = max(int(p.height), 1), max(int(p.width), 1)
+        index = np.empty((H, W), dtype=np.int32)
+        r2, x, y, z = (np.empty((H, W), dtype=np.float32) for _ in range(4))
+        label, count = (np.empty((H, W), dtype=np.uint32) for _ in range(2))
+        pixel = np.empty(max(n, 1), dtype=np.int32) if per_point else None
+        visible = np.empty(max(n, 1), dtype=np.uint8) if per_point else None
+        info = SicpRangeInfo()
+        self._check(lib().sicp_range_image(self._h, which, C.byref(p), _ptr(b, _dp), _ptr(o, _fp), _ptr(index, _ip), _ptr(r2, _fp),
+                                           _ptr(x, _fp), _ptr(y, _fp), _ptr(z, _fp), _ptr(label, _up), _ptr(count, _up),
+                                           _ptr(pixel, _ip), _ptr(visible, _bp), C.byref(info)), "sicp_range_image")
+        out = {"index": index, "range_sq": r2, "range": np.sqrt(r2), "x": x, "y": y, "z": z, "label": label, "count": count,
+               "info": info.as_dict()}
+        if per_point:
+            out["pixel"], out["visible"] = pixel[:n], visible[:n]
+        return out
+
+    def range_labels(self, which: int, pixel_label, params: SicpRangeParams | None = None, sensor_origin=None, beam_elevation=None,
+                     dst: "Engine | None" = None, dst_which: int | None = None):
+        """sicp_range_labels: pixel_label [H, W] uint32 (a network's class per pixel of range_image's picture, 0: none) carried
+        back onto the points of the cloud in slot `which` by the vote of the k nearest occupied pixels of the window.  Returns
+        {"labels": [n_points] uint32, "votes": [n_points] uint8, "info": SicpRangeInfo.as_dict()}.  With dst the points with
+        their new labels become that Engine's slot dst_which (default: `which`) as if they had been handed to set_cloud; dst may
+        be this engine.  Without dst nothing on the engine changes."""
+        p = params if params is not None else default_range_params()
+        b, o = _beam_table(p, beam_elevation), self._origin(sensor_origin)
+        n = self.n[which] if which in (SOURCE, TARGET) else 0
+        if pixel_label is not None:
+            pixel_label = np.ascontiguousarray(pixel_label, dtype=np.uint32)
+            if pixel_label.size != max(int(p.height), 0) * max(int(p.width), 0):
+                raise ValueError(f"pixel_label must have one entry per pixel ({p.height} x {p.width})")
+        labels = np.empty(max(n, 1), dtype=np.uint32)
+        votes = np.empty(max(n, 1), dtype=np.uint8)
+        info = SicpRangeInfo()
+        dw = which if dst_which is None else dst_which
+        self._check(lib().sicp_range_labels(self._h, which, C.byref(p), _ptr(b, _dp), _ptr(o, _fp), _ptr(pixel_label, _up),
+                                            None if dst is None else dst._h, dw, _ptr(labels, _up), _ptr(votes, _bp),
+                                            C.byref(info)), "sicp_range_labels")
+        if dst is not None:
+            dst.n[dw] = int(info.n_points)
+        return {"labels": labels[:n], "votes": votes[:n], "info": info.as_dict()}
 
     def segment_planes(self, which: int = SOURCE, params: SicpPlaneParams | None = None, mask=None):
         """sicp_segment_planes: the dominant planes of the cloud in slot `which` by RANSAC -- per round num_hypotheses three-point

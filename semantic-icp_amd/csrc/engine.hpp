@@ -12,6 +12,7 @@
 //   cluster.cpp   sicp_cluster: label-aware Euclidean clustering of a cloud
 //   filter.cpp    sicp_filter: statistical / radius outlier removal and masked selection of a cloud
 //   deskew.cpp    sicp_deskew: a scan's points moved to one instant from per-point times and a knot trajectory
+//   range.cpp     sicp_range_image / sicp_range_labels: a scan's spherical projection and the vote back from per-pixel classes
 //   plane.cpp     sicp_segment_planes: RANSAC plane extraction of a cloud
 //   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, raycast, prune, extract, merge, state)
 //   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
@@ -524,6 +525,9 @@ struct sicp_context : sicp_use_state {
   // pinned moved points (x | y | z | label, the caller's indices) on their way to the caller and into dst
   HostBuf<unsigned char> dk_stage;
   HostBuf<uint32_t> dk_out;
+  // sicp_range_image / sicp_range_labels (range.cpp): the pinned tables / caller indices / pixel classes on their way up, the
+  // counts, images and per-point outputs on their way back, and the points (x | y | z) on their way into dst
+  HostBuf<unsigned char> rg_stage;
   // sicp_segment_planes (plane.cpp): the pinned finite positions / mask on their way up, the control block, plane records and
   // per-point states on their way back
   HostBuf<unsigned char> pl_stage;
@@ -1040,6 +1044,16 @@ int deskew(sicp_context* h, int which, const double* times, int32_t n_knots, con
            const double* ref_qt, sicp_context* dst, int dst_which, float* ox, float* oy, float* oz, double* knots_out,
            sicp_deskew_info* info);
 int deskew_twist_knots(const double* delta_qt, double t0, double t1, int32_t n_knots, double* knot_time, double* knot_qt);
+// sicp_range_image / sicp_range_labels (range.cpp): argument checks, the tables formed on the host, the projection / resolve /
+// visible or vote kernels on the cloud's device copy, one read-back, and the relabelled cloud's way into dst (set_cloud_common);
+// sicp_range_tables: host only
+void range_default_params(sicp_range_params* p);
+int range_tables(const sicp_range_params* p, const double* beam, double* cos_half, double* sin_half, double* row_edge);
+int range_image(sicp_context* h, int which, const sicp_range_params* p, const double* beam, const float* origin, int32_t* index,
+                float* range_sq, float* x, float* y, float* z, uint32_t* label, uint32_t* count, int32_t* pixel, uint8_t* visible,
+                sicp_range_info* info);
+int range_labels(sicp_context* h, int which, const sicp_range_params* p, const double* beam, const float* origin,
+                 const uint32_t* pixel_label, sicp_context* dst, int dst_which, uint32_t* out_label, uint8_t* votes, sicp_range_info* info);
 // sicp_segment_planes (plane.cpp): argument checks, every round of the plane kernels queued on the handle's stream, one
 // read-back
 void plane_default_params(sicp_plane_params* p);

@@ -625,6 +625,52 @@ struct DeskewArgs {
 };
 hipError_t launch_deskew(const DeskewArgs& a, hipStream_t st);
 
+// ---- range image and labels from it (range_kernels.hip; driver: range.cpp) ----
+// sicp_range_image / sicp_range_labels: the finite points of one cloud in caller order (Cloud::rx ...; index f, `caller` as in
+// DeskewArgs) projected into H x W pixels.  Project: the tables in LDS, a lane per point, two bisections, one 64-bit atomicMin
+// on the pixel's key (bits(r2) << 32 | f: f ascends with the caller's index) and one atomicAdd on its count.  Resolve: a lane per
+// pixel decodes the key, gathers the winner into a 16-byte record (x, y, z, word) and writes the dense outputs.  Then a lane
+// per point either marks the winners (visible) or votes over the records of its window.
+constexpr int kRangeMaxWidth = 4096;   // SICP_RANGE_MAX_WIDTH
+constexpr int kRangeMaxHeight = 256;   // SICP_RANGE_MAX_HEIGHT
+constexpr int kRangeMaxWindow = 7;     // SICP_RANGE_MAX_WINDOW
+constexpr int kRangeMaxK = 16;         // SICP_RANGE_MAX_K
+constexpr int kRangeMaxGroups = 1024;  // a per-point launch is at most this many workgroups of 256: more points stride over them
+constexpr unsigned long long kRangeEmptyKey = ~0ull;  // no point holds it: the bits of r2 are those of a finite float
+enum { kRgKept = 0, kRgOutsideFov = 1, kRgPixelsHit = 2, kRgVoted = 3, kRgRes = 4 };
+struct RangeArgs {
+  int n, n_caller;             // finite points; points the caller handed over
+  int W, H;
+  int clockwise, col_shift;
+  int window, k;               // the vote
+  float ox, oy, oz;            // the sensor's origin
+  double min_sq, max_sq;       // the range bounds, squared on the host
+  double max_dist_sq;          // the vote
+  const float *x, *y, *z;      // [n] by f
+  const uint32_t* label;       // [n] by f, nullable
+  const int* caller;           // [n] f -> caller index; nullptr: the identity
+  const double* tables;        // row_edge [H + 1] | cos_half [W / 2] | sin_half [W / 2]
+  const uint32_t* pixel_label; // [H W] the vote; nullptr: the records' word is the cloud's label
+  unsigned long long* key;     // [H W] set to kRangeEmptyKey before the projection
+  uint32_t* count;             // [H W] zeroed before the projection
+  int* pix;                    // [n] by f: row W + col or -1
+  float4* rec;                 // [H W] the winner's x, y, z and a word; x = NaN in an empty pixel
+  // dense outputs, [H W], every one nullable
+  int* o_index;
+  float *o_range_sq, *o_x, *o_y, *o_z;
+  uint32_t* o_label;
+  // per-point outputs by caller index, [n_caller], preset for the points that are not finite; every one nullable
+  int* o_pixel;                // preset -1
+  uint8_t* o_visible;          // preset 0
+  uint32_t* o_out_label;       // preset 0
+  uint8_t* o_votes;            // preset 0
+  int* res;                    // kRgRes words, zeroed before the first launch
+};
+hipError_t launch_range_project(const RangeArgs& a, hipStream_t st);  // key, count, pix, o_pixel, res[kept, outside fov]
+hipError_t launch_range_resolve(const RangeArgs& a, hipStream_t st);  // rec, the dense outputs, res[pixels hit]
+hipError_t launch_range_visible(const RangeArgs& a, hipStream_t st);  // o_visible
+hipError_t launch_range_vote(const RangeArgs& a, hipStream_t st);     // o_out_label, o_votes, res[voted]
+
 // ---- RANSAC plane extraction (plane_kernels.hip; driver: plane.cpp) ----
 // sicp_segment_planes: every array below that is [n_caller] long is indexed by the caller's index i; `finv` maps it to the
 // position f of the point among the finite ones (Cloud::rx ...), -1 for a point that is not finite.  A round compacts the

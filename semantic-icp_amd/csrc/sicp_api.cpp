@@ -860,6 +860,34 @@ int sicp_deskew_twist_knots(const double delta_qt[7], double t0, double t1, int3
   return abi_guard([&]() -> int { return deskew_twist_knots(delta_qt, t0, t1, n_knots, knot_time, knot_qt); });
 }
 
+int sicp_default_range_params(sicp_range_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    range_default_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_range_tables(const sicp_range_params* p, const double* beam_elevation, double* cos_half, double* sin_half, double* row_edge) {
+  return abi_guard([&]() -> int { return range_tables(p, beam_elevation, cos_half, sin_half, row_edge); });
+}
+
+int sicp_range_image(sicp_handle h, int which, const sicp_range_params* p, const double* beam_elevation, const float sensor_origin[3],
+                     int32_t* index, float* range_sq, float* x, float* y, float* z, uint32_t* label, uint32_t* count, int32_t* pixel,
+                     uint8_t* visible, sicp_range_info* info) {
+  return abi_guard(h, [&]() -> int {
+    return range_image(h, which, p, beam_elevation, sensor_origin, index, range_sq, x, y, z, label, count, pixel, visible, info);
+  });
+}
+
+int sicp_range_labels(sicp_handle h, int which, const sicp_range_params* p, const double* beam_elevation, const float sensor_origin[3],
+                      const uint32_t* pixel_label, sicp_handle dst, int dst_which, uint32_t* out_label, uint8_t* votes,
+                      sicp_range_info* info) {
+  return abi_guard(h, [&]() -> int {
+    return range_labels(h, which, p, beam_elevation, sensor_origin, pixel_label, dst, dst_which, out_label, votes, info);
+  });
+}
+
 int sicp_default_plane_params(sicp_plane_params* p) {
   return abi_guard([&]() -> int {
     if (!p) return SICP_ERR_INVALID_ARGUMENT;
