@@ -195,6 +195,12 @@ const char* sicp_version(void);
 
 /* ---- configuration --------------------------------------------------------- */
 int sicp_default_params(int mode, sicp_params* p);
+/* Besides mode, knn, k_cov, epsilon, cauchy_a and nn_method, the trust-region options are checked, because their loop
+ * runs inside kernels: SICP_ERR_INVALID_ARGUMENT, the field named in sicp_last_error and the handle's parameters left as
+ * they were, unless the nine option doubles and outer_tol are finite, gradient_ / function_ / parameter_tolerance >= 0,
+ * 0 <= min_radius <= initial_radius <= max_radius with initial_radius > 0 (denormal radii are legal),
+ * 0 <= min_relative_decrease < 1, 0 <= min_lm_diagonal <= max_lm_diagonal, max_lm_iterations >= 0 and
+ * max_consecutive_invalid_steps >= 1.  sicp_stream_create applies the same rule to its params. */
 int sicp_set_params(sicp_handle h, const sicp_params* p);
 int sicp_get_params(sicp_handle h, sicp_params* p);
 
@@ -248,8 +254,11 @@ int sicp_set_confusion(sicp_handle h, int32_t C, const double* cm_rowmajor);
  * stats may be NULL. */
 int sicp_align(sicp_handle h, const double init_qt[7], double out_qt[7],
                int32_t* outer_iters, sicp_stats* stats);
-/* n independent align() calls -- one handle per scan pair, all on one device, same mode /
- * knn / solver knobs -- batched continuously: every launch of the inner solve evaluates the
+/* n independent align() calls -- one handle per scan pair, all on one device, equal in the
+ * fields that decide what a launch does: mode, knn, k_cov, use_sqloss, nn_method, lm_on_device,
+ * lm_batch and profile (anything else -- the trust-region options, outer_tol, max_outer, gate_sq,
+ * epsilon, cauchy_a, num_classes and its matrix, min_class_pts, the quirks, reuse_features -- is
+ * each pair's own) -- batched continuously: every launch of the inner solve evaluates the
  * pairs that are inside a solve (up to 256; with more, the others wait with their search done),
  * the searches of the pairs between two solves run between the launches (what
  * exec/kitti_eval.cc:124-249 does pair after pair).  Per pair the result is bit-identical to

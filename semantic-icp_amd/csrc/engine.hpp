@@ -870,6 +870,7 @@ int flush_jobs(sicp_context* h, JobCollector& jc, hipStream_t base = nullptr);
 
 // ---- solve.cpp -------------------------------------------------------------------------------------
 sicp::LmOptions lm_options(const sicp_params& P);
+const char* lm_options_refused(const sicp_params& P);  // nullptr, or what sicp_set_params says about the first bad field
 struct SolveResult {
   int status = 0, iterations = 0, evaluations = 0;
   double cost = 0;

@@ -294,6 +294,13 @@ int sicp_set_params(sicp_handle h, const sicp_params* p) {
       return SICP_ERR_INVALID_ARGUMENT;
     }
     if (!(p->epsilon > 0) || !(p->cauchy_a > 0) || p->nn_method < 0 || p->nn_method > 2) return SICP_ERR_INVALID_ARGUMENT;
+    // The trust-region options reach lm_propose's retry loop inside a kernel (csrc/lm.hpp): a radius that never falls to
+    // min_radius (NaN, Inf) under caps near INT_MAX would keep a wave spinning for minutes.  Inside the rule below the
+    // loop is bounded without the caps: a finite radius is halved to 0 <= min_radius in at most ~2100 retries.
+    if (const char* bad = lm_options_refused(*p)) {
+      h->last_error = std::string("sicp_set_params: ") + bad;
+      return SICP_ERR_INVALID_ARGUMENT;
+    }
     // engine knobs (profiling, batching) do not invalidate the correspondences held on the device
     sicp_params a = h->params, b = *p;
     a.profile = b.profile = 0; a.lm_batch = b.lm_batch = 0; a.lm_on_device = b.lm_on_device = 0;

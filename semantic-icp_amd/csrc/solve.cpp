@@ -24,6 +24,31 @@ sicp::LmOptions lm_options(const sicp_params& P) {
   return o;
 }
 
+// The rule of sicp_set_params for the trust-region options (include/sicp.h): the first field that breaks it, by name.
+const char* lm_options_refused(const sicp_params& P) {
+  const struct { double v; const char* finite; } d[10] = {
+      {P.gradient_tolerance, "gradient_tolerance must be finite"},       {P.function_tolerance, "function_tolerance must be finite"},
+      {P.parameter_tolerance, "parameter_tolerance must be finite"},     {P.initial_radius, "initial_radius must be finite"},
+      {P.max_radius, "max_radius must be finite"},                       {P.min_radius, "min_radius must be finite"},
+      {P.min_relative_decrease, "min_relative_decrease must be finite"}, {P.min_lm_diagonal, "min_lm_diagonal must be finite"},
+      {P.max_lm_diagonal, "max_lm_diagonal must be finite"},             {P.outer_tol, "outer_tol must be finite"}};
+  for (int i = 0; i < 10; ++i)
+    if (!(d[i].v - d[i].v == 0.0)) return d[i].finite;
+  if (P.gradient_tolerance < 0) return "gradient_tolerance must be >= 0";
+  if (P.function_tolerance < 0) return "function_tolerance must be >= 0";
+  if (P.parameter_tolerance < 0) return "parameter_tolerance must be >= 0";
+  if (P.min_radius < 0) return "min_radius must be >= 0";
+  if (!(P.initial_radius > 0)) return "initial_radius must be > 0";
+  if (P.min_radius > P.initial_radius) return "min_radius must not exceed initial_radius";
+  if (P.initial_radius > P.max_radius) return "initial_radius must not exceed max_radius";
+  if (P.min_relative_decrease < 0 || P.min_relative_decrease >= 1) return "min_relative_decrease must be in [0, 1)";
+  if (P.min_lm_diagonal < 0) return "min_lm_diagonal must be >= 0";
+  if (P.min_lm_diagonal > P.max_lm_diagonal) return "min_lm_diagonal must not exceed max_lm_diagonal";
+  if (P.max_lm_iterations < 0) return "max_lm_iterations must be >= 0";
+  if (P.max_consecutive_invalid_steps < 1) return "max_consecutive_invalid_steps must be >= 1";
+  return nullptr;
+}
+
 // may the next launch of this leader be a persistent one?  (after a timed-out launch a number of them are not)
 bool solo_allowed(sicp_context* h) {
   if (h->solo_skip > 0) { --h->solo_skip; return false; }
@@ -338,7 +363,7 @@ int BatchRun::turn(TickGroup& G, JobCollector& jc) {
     }
     for (int p : G.finished) {
       jc.slice = 0;
-      outer_finish(P, o[p]);
+      outer_finish(hs[p]->params, o[p]);  // the pair's own outer_tol / max_outer (same_solver lets them differ from the leader's)
       phase[p] = o[p].converged ? PAIR_DONE : PAIR_NEED_SEARCH;
     }
   }
