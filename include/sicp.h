@@ -920,6 +920,120 @@ int sicp_range_labels(sicp_handle h, int which, const sicp_range_params* p, cons
                       sicp_handle dst /* nullable */, int dst_which, uint32_t* out_label, uint8_t* votes
                       /* n_points each, nullable */, sicp_range_info* info /* nullable */);
 
+/* ---- camera: depth frames and image labels -------------------------------------------
+ * The camera's side of what the range image does for a lidar.  sicp_camera_unproject turns a depth frame (and a label image)
+ * into a slot's cloud -- the organised 640 x 480 clouds of RGB-D datasets, invalid pixels included.  sicp_camera_image projects
+ * the cloud in a handle's slot through a calibrated pinhole camera into height x width pixels, each won by its nearest point.
+ * sicp_camera_labels carries an image network's per-pixel classes onto the points the camera sees: a lidar point behind a
+ * parked car projects into the car's pixels, so a point keeps its own label when a nearer surface covers its window.  The
+ * handle may be in any mode.
+ *  Calibration: OpenCV's convention -- the centre of pixel (row r, column c) is at (u, v) = (c, r); fx fy cx cy in pixels;
+ *  k1 k2 p1 p2 k3 the Brown-Conrady coefficients in OpenCV's order.  camera_qt[7] = [qx qy qz qw tx ty tz] is the camera's pose
+ *  in the cloud's frame (camera -> cloud; x right, y down, z forward); NULL: the identity, through the same arithmetic.
+ *  Matrices, on the host, once per call, in double; sicp_camera_matrices returns exactly what the kernels read (the scheme of
+ *  sicp_range_tables).  cam_to_cloud[12] = the 3 x 4 matrix of camera_qt as the engine forms a pose matrix (rule 2 of
+ *  sicp_merge_clouds: no normalisation), rows of (R | t).  cloud_to_cam[12] = (R^T | t') with t'_i = -((R_0i t_0 + R_1i t_1) +
+ *  R_2i t_2): the inverse for a unit quaternion.
+ *  The projection, shared by sicp_camera_image and sicp_camera_labels, per finite point f of the cloud in the caller's order (fp
+ *  contraction off, everything in double, every operation rounded on its own; restated in numpy by tests/camera_ref.py):
+ *  1. Camera frame.  Xc, Yc, Zc = ((m0 x + m1 y) + m2 z) + m3 per row of cloud_to_cam, x y z widened from float: rule 2 of
+ *     sicp_merge_clouds without the final rounding.
+ *  2. Depth gate.  The point is KEPT iff Zc >= min_depth && Zc < max_depth.
+ *  3. Normalised coordinates.  xn = Xc / Zc, yn = Yc / Zc;  a = xn xn, b = yn yn, c = xn yn;  r2 = a + b.  A kept point with
+ *     !(r2 <= max_tan_sq) is outside the view: far off the axis the distortion polynomial folds back into the image.
+ *  4. Distortion.  rad = 1 + r2 (k1 + r2 (k2 + r2 k3)) by Horner;  xd = xn rad + ((2 p1) c + p2 (r2 + 2 a));
+ *     yd = yn rad + (p1 (r2 + 2 b) + (2 p2) c).
+ *  5. Pixel.  u = fx xd + cx, v = fy yd + cy;  cf = floor(u + 0.5), rf = floor(v + 0.5).  The point is inside the image iff
+ *     cf >= 0 && cf <= W - 1 && rf >= 0 && rf <= H - 1, compared as doubles (a NaN is outside);  pixel = rf W + cf.
+ *  6. Winner.  A pixel's winner is its kept, in-image point with the smallest 64-bit key (bits((float)Zc) << 32) | f: the
+ *     nearest point, equal float depths to the smaller caller index.  One unsigned 64-bit atomic minimum per point.
+ *  Outputs of sicp_camera_image, every one nullable.  Per pixel, H W long, row-major: index (the winner's caller index, -1:
+ *  empty), depth (the winner's (float)Zc, 0: empty), x, y, z (the winner as the caller gave it, 0: empty), label (the winner's;
+ *  0 when empty or when the cloud has no labels), count (the kept, in-image points of the pixel).  Per point, n_points long,
+ *  caller order: pixel (rf W + cf or -1), u, v ((float)u, (float)v; NaN unless the point is kept and inside the view of rule 3),
+ *  visible (1 iff the point won its pixel).  A point that is not finite has -1 / NaN / 0 and is counted in nothing after
+ *  n_finite.  info: n_kept (rule 2), n_outside (kept, no pixel), n_pixels_hit.
+ *  sicp_camera_labels: the call projects as above; pixel_label[H W] is the network's class per pixel, 0 = no class.  Every kept,
+ *  in-image point with zf = (float)Zc and pixel (r, c) then:
+ *  7. Front depth.  zmin = the smallest winner depth over the occupied pixels of the window x window block centred on (r, c),
+ *     truncated at the image's border (no wrap).  The point's own pixel always has a winner.
+ *  8. Occlusion.  The point is occluded iff (double)zf - (double)zmin > occlusion_abs + occlusion_rel (double)zmin, strictly.
+ *  9. Label.  Not occluded and pixel_label[pixel] != 0: out_label = pixel_label[pixel], state = 1.  Occluded: state = 2.  Visible
+ *     with class 0: state = 3.  No pixel, for any reason: state = 0.  In states 0, 2 and 3 the point keeps its own label (0 when
+ *     the cloud has none).  A point that is not finite has out_label 0 and state 0 (rule 12 of sicp_range_labels).  info:
+ *     n_labelled, n_occluded, n_unclassed = the points of states 1, 2, 3.
+ * 10. dst: exactly rule 13 of sicp_range_labels, in place included; a cloud without labels becomes a labelled one.  Because a
+ *     point the camera does not see keeps its label, a rig of N cameras is N calls with dst = h.
+ *  sicp_camera_unproject: exactly one of depth_u16 / depth_f32 [H W]; label (nullable) uint32 [H W].  h gives the device, the
+ *  stream and the scratch; it needs no cloud, and dst may be h.  Per pixel (r, c):
+ * 11. Depth.  Z = (double)d16 * depth_scale, or (double)df.  The pixel is valid iff Z is finite and Z >= min_depth &&
+ *     Z < max_depth (a uint16 of 0 is invalid).
+ * 12. Ray.  xd = ((double)c - cx) / fx, yd = ((double)r - cy) / fy;  x = xd, y = yd;  then exactly undistort_iterations times,
+ *     with rule 4's rad, tx = (2 p1) c + p2 (r2 + 2 a) and ty = p1 (r2 + 2 b) + (2 p2) c formed from the current x, y:
+ *     x = (xd - tx) / rad, y = (yd - ty) / rad.  The fixed count is the definition (OpenCV's undistortPoints runs 5; 20 brings
+ *     wide lenses below 1e-3 px); with zero coefficients every pass is exact.
+ * 13. Point.  Pc = (x Z, y Z, Z); then cam_to_cloud as rule 2 of sicp_merge_clouds applies a pose, one rounding to float per
+ *     coordinate.  An invalid pixel gives NaN NaN NaN; valid[p] = 1 / 0; info: n_valid.
+ * 14. dst (nullable; the same device).  The H W points with `label` become the cloud of dst's slot exactly as sicp_set_cloud of
+ *     those arrays would set it: n_points = H W as in an organised cloud, the NaN pixels left out of the index; without `label`
+ *     the cloud has none.  No valid pixel and dst: SICP_ERR_TOO_FEW_POINTS, dst keeps its cloud.
+ * 15. Refused before any device work with SICP_ERR_INVALID_ARGUMENT, the outputs, info and dst left as they were, the reason in
+ *     sicp_last_error: a NULL handle or params; a `which` (or, with dst, a dst_which) outside SICP_SOURCE / SICP_TARGET; width or
+ *     height outside 8 .. SICP_CAMERA_MAX_WIDTH / _HEIGHT; fx fy cx cy or a coefficient not finite, fx or fy <= 0; min_depth
+ *     <= 0 or NaN, max_depth not finite or <= min_depth; max_tan_sq or depth_scale <= 0 or NaN; undistort_iterations outside
+ *     0 .. 64; window even or outside 1 .. SICP_CAMERA_MAX_WINDOW; occlusion_abs or occlusion_rel negative or NaN; a camera_qt
+ *     that is not finite or whose quaternion is zero; a NULL pixel_label; both or neither depth pointer; dst on another device.
+ *     The slot holds no cloud: SICP_ERR_NOT_READY.  Without dst, or with another handle as dst, nothing h holds for sicp_align
+ *     changes.  sicp_camera_matrices (host only, no handle) returns the status alone.  SICP_ERR_OUT_OF_MEMORY (the arena
+ *     refused, sicp_set_memory_limit applies) is a status: refused for the call's scratch, the outputs, info and dst are left as
+ *     they were; refused for dst's own device buffers, the outputs and info are left as they were and dst's slot is what
+ *     sicp_set_cloud of the same arrays leaves under the same limit.  The handles stay usable.
+ * 16. Bit-reproducible: a function of the points, labels, images, parameters and matrices only -- the same bytes on a handle of
+ *     any mode, in either slot, before or after a sicp_align, for every launch shape.  No float atomics. */
+#define SICP_CAMERA_MAX_WIDTH 4096
+#define SICP_CAMERA_MAX_HEIGHT 4096
+#define SICP_CAMERA_MAX_WINDOW 15
+typedef struct sicp_camera_params {
+  int32_t width;                 /* W: 8 .. SICP_CAMERA_MAX_WIDTH.  default 640 */
+  int32_t height;                /* H: 8 .. SICP_CAMERA_MAX_HEIGHT.  default 480 */
+  double fx, fy, cx, cy;         /* finite, fx fy > 0.  default 525 525 319.5 239.5 */
+  double k1, k2, p1, p2, k3;     /* Brown-Conrady, finite.  default 0 */
+  double min_depth;              /* > 0.  default 0.3 */
+  double max_depth;              /* finite, > min_depth.  default 100 */
+  double max_tan_sq;             /* > 0: the largest xn^2 + yn^2 the distortion is trusted at.  default 4.0 */
+  double depth_scale;            /* > 0: metres per uint16 unit.  default 0.001 */
+  int32_t undistort_iterations;  /* 0 .. 64.  default 20 */
+  int32_t window;                /* odd, 1 .. SICP_CAMERA_MAX_WINDOW.  default 5 */
+  double occlusion_abs;          /* >= 0, metres.  default 0.3 */
+  double occlusion_rel;          /* >= 0, per metre of front depth.  default 0.02 */
+} sicp_camera_params;
+typedef struct sicp_camera_info {
+  int64_t n_points;      /* what the caller handed over; sicp_camera_unproject: H W */
+  int64_t n_finite;
+  int64_t n_kept;        /* finite points inside [min_depth, max_depth) */
+  int64_t n_outside;     /* kept points without a pixel */
+  int64_t n_pixels_hit;  /* pixels with a winner */
+  int64_t n_labelled;    /* sicp_camera_labels: state 1 */
+  int64_t n_occluded;    /* state 2 */
+  int64_t n_unclassed;   /* state 3 */
+  int64_t n_valid;       /* sicp_camera_unproject: valid pixels */
+  double t_total_ms;     /* host wall clock */
+} sicp_camera_info;
+int sicp_default_camera_params(sicp_camera_params* p);
+int sicp_camera_matrices(const double camera_qt[7] /* NULL = identity */, double cam_to_cloud[12], double cloud_to_cam[12] /* nullable */);
+int sicp_camera_image(sicp_handle h, int which, const sicp_camera_params* p, const double camera_qt[7] /* NULL = identity */,
+                      int32_t* index, float* depth, float* x, float* y, float* z, uint32_t* label, uint32_t* count
+                      /* height*width each, nullable */, int32_t* pixel, float* u, float* v, uint8_t* visible
+                      /* n_points each, nullable */, sicp_camera_info* info /* nullable */);
+int sicp_camera_labels(sicp_handle h, int which, const sicp_camera_params* p, const double camera_qt[7] /* NULL = identity */,
+                       const uint32_t* pixel_label /* height*width */, sicp_handle dst /* nullable */, int dst_which,
+                       uint32_t* out_label, uint8_t* state /* n_points each, nullable */, sicp_camera_info* info /* nullable */);
+int sicp_camera_unproject(sicp_handle h, const sicp_camera_params* p, const double camera_qt[7] /* NULL = identity */,
+                          const uint16_t* depth_u16, const float* depth_f32 /* height*width, exactly one */,
+                          const uint32_t* label /* height*width, nullable */, sicp_handle dst /* nullable */, int dst_which,
+                          float* x, float* y, float* z, uint8_t* valid /* height*width each, nullable */,
+                          sicp_camera_info* info /* nullable */);
+
 /* ---- planes of a cloud -------------------------------------------------------------
  * RANSAC plane extraction of the cloud in a handle's slot (pcl::SACSegmentation with SACMODEL_PLANE or, with an axis,
  * SACMODEL_PERPENDICULAR_PLANE; Open3D's segment_plane): up to max_planes planes, one per round, each from a fixed number of

@@ -367,6 +367,55 @@ class SicpRangeInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+CAMERA_MAX_WIDTH = 4096
+CAMERA_MAX_HEIGHT = 4096
+CAMERA_MAX_WINDOW = 15
+
+
+class SicpCameraParams(C.Structure):
+    """sicp_camera_params (include/sicp.h)"""
+    _fields_ = [
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("fx", C.c_double),
+        ("fy", C.c_double),
+        ("cx", C.c_double),
+        ("cy", C.c_double),
+        ("k1", C.c_double),
+        ("k2", C.c_double),
+        ("p1", C.c_double),
+        ("p2", C.c_double),
+        ("k3", C.c_double),
+        ("min_depth", C.c_double),
+        ("max_depth", C.c_double),
+        ("max_tan_sq", C.c_double),
+        ("depth_scale", C.c_double),
+        ("undistort_iterations", C.c_int32),
+        ("window", C.c_int32),
+        ("occlusion_abs", C.c_double),
+        ("occlusion_rel", C.c_double),
+    ]
+
+
+class SicpCameraInfo(C.Structure):
+    """sicp_camera_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_points", C.c_int64),
+        ("n_finite", C.c_int64),
+        ("n_kept", C.c_int64),
+        ("n_outside", C.c_int64),
+        ("n_pixels_hit", C.c_int64),
+        ("n_labelled", C.c_int64),
+        ("n_occluded", C.c_int64),
+        ("n_unclassed", C.c_int64),
+        ("n_valid", C.c_int64),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 PLANE_MAX_HYPOTHESES = 4096
 PLANE_MAX_PLANES = 16
 PLANE_MAX_IGNORE = 16
@@ -707,6 +756,7 @@ _ip = C.POINTER(C.c_int32)
 _up = C.POINTER(C.c_uint32)
 _bp = C.POINTER(C.c_uint8)
 _kp = C.POINTER(C.c_uint64)
+_hp = C.POINTER(C.c_uint16)
 
 
 def lib():
@@ -805,6 +855,14 @@ def lib():
             "sicp_deskew": [C.c_void_p, C.c_int, _dp, C.c_int32, _dp, _dp, _dp, C.c_void_p, C.c_int, _fp, _fp, _fp, _dp,
                             C.POINTER(SicpDeskewInfo)],
             "sicp_deskew_twist_knots": [_dp, C.c_double, C.c_double, C.c_int32, _dp, _dp],
+            "sicp_default_camera_params": [C.POINTER(SicpCameraParams)],
+            "sicp_camera_matrices": [_dp, _dp, _dp],
+            "sicp_camera_image": [C.c_void_p, C.c_int, C.POINTER(SicpCameraParams), _dp, _ip, _fp, _fp, _fp, _fp, _up, _up, _ip, _fp, _fp,
+                                  _bp, C.POINTER(SicpCameraInfo)],
+            "sicp_camera_labels": [C.c_void_p, C.c_int, C.POINTER(SicpCameraParams), _dp, _up, C.c_void_p, C.c_int, _up, _bp,
+                                   C.POINTER(SicpCameraInfo)],
+            "sicp_camera_unproject": [C.c_void_p, C.POINTER(SicpCameraParams), _dp, _hp, _fp, _up, C.c_void_p, C.c_int, _fp, _fp, _fp,
+                                      _bp, C.POINTER(SicpCameraInfo)],
             "sicp_default_range_params": [C.POINTER(SicpRangeParams)],
             "sicp_range_tables": [C.POINTER(SicpRangeParams), _dp, _dp, _dp, _dp],
             "sicp_range_image": [C.c_void_p, C.c_int, C.POINTER(SicpRangeParams), _dp, _fp, _ip, _fp, _fp, _fp, _fp, _up, _up, _ip, _bp,
@@ -1060,6 +1118,40 @@ def range_tables(params: SicpRangeParams, beam_elevation=None):
     if st != OK:
         raise SicpError(st, "sicp_range_tables")
     return {"cos_half": c, "sin_half": s, "row_edge": e}
+
+
+def default_camera_params(**overrides) -> SicpCameraParams:
+    """sicp_default_camera_params (640 x 480, fx = fy = 525, cx, cy = 319.5, 239.5, no distortion, depths 0.3 .. 100 m, max_tan_sq 4,
+    depth_scale 0.001, 20 undistortion passes, window 5, occlusion 0.3 m + 2 %) with any field overridden by keyword"""
+    p = SicpCameraParams()
+    st = lib().sicp_default_camera_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_camera_params")
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _camera_qt(camera_qt):
+    if camera_qt is None:
+        return None
+    q = np.ascontiguousarray(camera_qt, dtype=np.float64)
+    if q.shape != (7,):
+        raise ValueError("camera_qt must hold 7 numbers [qx qy qz qw tx ty tz]")
+    return q
+
+
+def camera_matrices(camera_qt=None):
+    """sicp_camera_matrices (host only): {"cam_to_cloud": [3, 4], "cloud_to_cam": [3, 4]} float64, exactly what the kernels of
+    Engine.camera_image / camera_labels / camera_unproject read for this camera pose (None: the identity)"""
+    q = _camera_qt(camera_qt)
+    a, b = np.empty((3, 4), dtype=np.float64), np.empty((3, 4), dtype=np.float64)
+    st = lib().sicp_camera_matrices(_ptr(q, _dp), _ptr(a, _dp), _ptr(b, _dp))
+    if st != OK:
+        raise SicpError(st, "sicp_camera_matrices")
+    return {"cam_to_cloud": a, "cloud_to_cam": b}
 
 
 def default_plane_params(ignore=(), axis=None, **overrides) -> SicpPlaneParams:
@@ -1667,6 +1759,92 @@ class Engine:
         if dst is not None:
             dst.n[dw] = int(info.n_points)
         return {"labels": labels[:n], "votes": votes[:n], "info": info.as_dict()}
+
+    def camera_image(self, which: int = SOURCE, params: SicpCameraParams | None = None, camera_qt=None, per_point: bool = False):
+        """sicp_camera_image: the cloud in slot `which` through the pinhole camera of `params` at pose camera_qt (camera -> cloud,
+        None: the identity) into height x width pixels, each won by its nearest point.  Returns {"index": int32 (-1: empty),
+        "depth", "x", "y", "z": float32, "label", "count": uint32, all [H, W]; with per_point "pixel": [n_points] int32
+        (row * W + col or -1), "u", "v": float32 (NaN: out of view) and "visible": uint8; "info": SicpCameraInfo.as_dict()}.
+        Nothing on the engine changes."""
+        p = params if params is not None else default_camera_params()
+        q = _camera_qt(camera_qt)
+        n = self.n[which] if which in (SOURCE, TARGET) else 0
+        H, W = max(int(p.height), 1), max(int(p.width), 1)
+        index = np.empty((H, W), dtype=np.int32)
+        depth, x, y, z = (np.empty((H, W), dtype=np.float32) for _ in range(4))
+        label, count = (np.empty((H, W), dtype=np.uint32) for _ in range(2))
+        pixel = np.empty(max(n, 1), dtype=np.int32) if per_point else None
+        u, v = ((np.empty(max(n, 1), dtype=np.float32) if per_point else None) for _ in range(2))
+        visible = np.empty(max(n, 1), dtype=np.uint8) if per_point else None
+        info = SicpCameraInfo()
+        self._check(lib().sicp_camera_image(self._h, which, C.byref(p), _ptr(q, _dp), _ptr(index, _ip), _ptr(depth, _fp), _ptr(x, _fp),
+                                            _ptr(y, _fp), _ptr(z, _fp), _ptr(label, _up), _ptr(count, _up), _ptr(pixel, _ip),
+                                            _ptr(u, _fp), _ptr(v, _fp), _ptr(visible, _bp), C.byref(info)), "sicp_camera_image")
+        out = {"index": index, "depth": depth, "x": x, "y": y, "z": z, "label": label, "count": count, "info": info.as_dict()}
+        if per_point:
+            out["pixel"], out["u"], out["v"], out["visible"] = pixel[:n], u[:n], v[:n], visible[:n]
+        return out
+
+    def camera_labels(self, which: int, pixel_label, params: SicpCameraParams | None = None, camera_qt=None,
+                      dst: "Engine | None" = None, dst_which: int | None = None):
+        """sicp_camera_labels: pixel_label [H, W] uint32 (an image network's class per pixel, 0: none) carried onto the points of
+        the cloud in slot `which` that the camera sees; a point behind a nearer surface, outside the image or in a pixel of class 0
+        keeps its label.  Returns {"labels": [n_points] uint32, "state": [n_points] uint8 (0: no pixel, 1: labelled, 2: occluded,
+        3: class 0), "info": SicpCameraInfo.as_dict()}.  With dst the points with their new labels become that Engine's slot
+        dst_which (default: `which`) as if they had been handed to set_cloud; dst may be this engine (a rig of cameras: one call
+        each).  Without dst nothing on the engine changes."""
+        p = params if params is not None else default_camera_params()
+        q = _camera_qt(camera_qt)
+        n = self.n[which] if which in (SOURCE, TARGET) else 0
+        if pixel_label is not None:
+            pixel_label = np.ascontiguousarray(pixel_label, dtype=np.uint32)
+            if pixel_label.size != max(int(p.height), 0) * max(int(p.width), 0):
+                raise ValueError(f"pixel_label must have one entry per pixel ({p.height} x {p.width})")
+        labels = np.empty(max(n, 1), dtype=np.uint32)
+        state = np.empty(max(n, 1), dtype=np.uint8)
+        info = SicpCameraInfo()
+        dw = which if dst_which is None else dst_which
+        self._check(lib().sicp_camera_labels(self._h, which, C.byref(p), _ptr(q, _dp), _ptr(pixel_label, _up),
+                                             None if dst is None else dst._h, dw, _ptr(labels, _up), _ptr(state, _bp),
+                                             C.byref(info)), "sicp_camera_labels")
+        if dst is not None:
+            dst.n[dw] = int(info.n_points)
+        return {"labels": labels[:n], "state": state[:n], "info": info.as_dict()}
+
+    def camera_unproject(self, depth, params: SicpCameraParams | None = None, camera_qt=None, label=None,
+                         dst: "Engine | None" = None, dst_which: int = SOURCE, want_points: bool = True):
+        """sicp_camera_unproject: a depth frame [H, W] -- uint16 (times depth_scale) or float32 (metres) -- back-projected through
+        the camera of `params` at pose camera_qt into H W points in the cloud's frame, NaN where the depth is invalid.  With dst
+        the points (and `label` [H, W] uint32, if given) become that Engine's slot dst_which as if they had been handed to
+        set_cloud; dst may be this engine.  Returns {"info": SicpCameraInfo.as_dict()} and, with want_points, "xyz": [H W, 3]
+        float32 and "valid": [H, W] uint8."""
+        p = params if params is not None else default_camera_params()
+        q = _camera_qt(camera_qt)
+        H, W = max(int(p.height), 0), max(int(p.width), 0)
+        d = np.ascontiguousarray(depth)
+        if d.dtype not in (np.uint16, np.float32):
+            raise TypeError("depth must be uint16 or float32")
+        if d.size != H * W:
+            raise ValueError(f"depth must have one entry per pixel ({p.height} x {p.width})")
+        if label is not None:
+            label = np.ascontiguousarray(label, dtype=np.uint32)
+            if label.size != H * W:
+                raise ValueError(f"label must have one entry per pixel ({p.height} x {p.width})")
+        npx = max(H * W, 1)
+        x, y, z = ((np.empty(npx, dtype=np.float32) if want_points else None) for _ in range(3))
+        valid = np.empty(npx, dtype=np.uint8) if want_points else None
+        info = SicpCameraInfo()
+        self._check(lib().sicp_camera_unproject(self._h, C.byref(p), _ptr(q, _dp), _ptr(d if d.dtype == np.uint16 else None, _hp),
+                                                _ptr(d if d.dtype == np.float32 else None, _fp), _ptr(label, _up),
+                                                None if dst is None else dst._h, dst_which, _ptr(x, _fp), _ptr(y, _fp), _ptr(z, _fp),
+                                                _ptr(valid, _bp), C.byref(info)), "sicp_camera_unproject")
+        if dst is not None:
+            dst.n[dst_which] = int(info.n_points)
+        out = {"info": info.as_dict()}
+        if want_points:
+            out["xyz"] = np.stack([x[:H * W], y[:H * W], z[:H * W]], axis=1)
+            out["valid"] = valid[:H * W].reshape(H, W)
+        return out
 
     def segment_planes(self, which: int = SOURCE, params: SicpPlaneParams | None = None, mask=None):
         """sicp_segment_planes: the dominant planes of the cloud in slot `which` by RANSAC -- per round num_hypotheses three-point

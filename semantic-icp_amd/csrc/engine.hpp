@@ -13,6 +13,7 @@
 //   filter.cpp    sicp_filter: statistical / radius outlier removal and masked selection of a cloud
 //   deskew.cpp    sicp_deskew: a scan's points moved to one instant from per-point times and a knot trajectory
 //   range.cpp     sicp_range_image / sicp_range_labels: a scan's spherical projection and the vote back from per-pixel classes
+//   camera.cpp    sicp_camera_image / sicp_camera_labels / sicp_camera_unproject: a scan through a pinhole camera, a depth frame out of one
 //   plane.cpp     sicp_segment_planes: RANSAC plane extraction of a cloud
 //   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, raycast, prune, extract, merge, state)
 //   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
@@ -528,6 +529,10 @@ struct sicp_context : sicp_use_state {
   // sicp_range_image / sicp_range_labels (range.cpp): the pinned tables / caller indices / pixel classes on their way up, the
   // counts, images and per-point outputs on their way back, and the points (x | y | z) on their way into dst
   HostBuf<unsigned char> rg_stage;
+  // sicp_camera_image / sicp_camera_labels / sicp_camera_unproject (camera.cpp): the pinned caller indices / pixel classes / depth
+  // frame on their way up, the counts, images and per-point outputs on their way back, and the points (x | y | z) on their way
+  // into dst
+  HostBuf<unsigned char> cm_stage;
   // sicp_segment_planes (plane.cpp): the pinned finite positions / mask on their way up, the control block, plane records and
   // per-point states on their way back
   HostBuf<unsigned char> pl_stage;
@@ -1055,6 +1060,19 @@ int range_image(sicp_context* h, int which, const sicp_range_params* p, const do
                 sicp_range_info* info);
 int range_labels(sicp_context* h, int which, const sicp_range_params* p, const double* beam, const float* origin,
                  const uint32_t* pixel_label, sicp_context* dst, int dst_which, uint32_t* out_label, uint8_t* votes, sicp_range_info* info);
+// sicp_camera_image / sicp_camera_labels / sicp_camera_unproject (camera.cpp): argument checks, the two matrices formed on the
+// host, the projection / resolve / visible or labels kernels on the cloud's device copy, or the unprojection of a depth frame,
+// one read-back, and the cloud's way into dst (set_cloud_common); sicp_camera_matrices: host only
+void camera_default_params(sicp_camera_params* p);
+int camera_matrices(const double* qt, double* cam_to_cloud, double* cloud_to_cam);
+int camera_image(sicp_context* h, int which, const sicp_camera_params* p, const double* qt, int32_t* index, float* depth, float* x,
+                 float* y, float* z, uint32_t* label, uint32_t* count, int32_t* pixel, float* u, float* v, uint8_t* visible,
+                 sicp_camera_info* info);
+int camera_labels(sicp_context* h, int which, const sicp_camera_params* p, const double* qt, const uint32_t* pixel_label,
+                  sicp_context* dst, int dst_which, uint32_t* out_label, uint8_t* state, sicp_camera_info* info);
+int camera_unproject(sicp_context* h, const sicp_camera_params* p, const double* qt, const uint16_t* depth_u16, const float* depth_f32,
+                     const uint32_t* label, sicp_context* dst, int dst_which, float* x, float* y, float* z, uint8_t* valid,
+                     sicp_camera_info* info);
 // sicp_segment_planes (plane.cpp): argument checks, every round of the plane kernels queued on the handle's stream, one
 // read-back
 void plane_default_params(sicp_plane_params* p);

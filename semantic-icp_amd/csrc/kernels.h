@@ -671,6 +671,62 @@ hipError_t launch_range_resolve(const RangeArgs& a, hipStream_t st);  // rec, th
 hipError_t launch_range_visible(const RangeArgs& a, hipStream_t st);  // o_visible
 hipError_t launch_range_vote(const RangeArgs& a, hipStream_t st);     // o_out_label, o_votes, res[voted]
 
+// ---- camera: depth frames and image labels (camera_kernels.hip; driver: camera.cpp) ----
+// sicp_camera_image / sicp_camera_labels: the finite points of one cloud in caller order (index f, `caller` as in DeskewArgs)
+// through cloud -> camera, the depth gate, the Brown-Conrady distortion and the pinhole into H x W pixels.  Project: a lane per
+// point, everything in double, one 64-bit atomicMin on the pixel's key (bits((float)Zc) << 32 | f) and one atomicAdd on its
+// count.  Resolve: a lane per pixel decodes the key and gathers the winner into a 16-byte record (x, y, z, depth; depth = +inf
+// in an empty pixel).  Then a lane per point either marks the winners (visible) or takes the smallest depth of its window
+// and decides between seen, occluded and unclassed.  sicp_camera_unproject: a lane per pixel of a depth frame, the fixed-count
+// undistortion in registers, the point through camera -> cloud.
+constexpr int kCameraMaxWidth = 4096;   // SICP_CAMERA_MAX_WIDTH
+constexpr int kCameraMaxHeight = 4096;  // SICP_CAMERA_MAX_HEIGHT
+constexpr int kCameraMaxWindow = 15;    // SICP_CAMERA_MAX_WINDOW
+constexpr int kCameraMaxIterations = 64;
+constexpr int kCameraMaxGroups = 1024;  // a per-point launch is at most this many workgroups of 256: more points stride over them
+constexpr unsigned long long kCameraEmptyKey = ~0ull;  // no point holds it: f is below 2^31
+enum { kCmKept = 0, kCmOutside = 1, kCmPixelsHit = 2, kCmLabelled = 3, kCmOccluded = 4, kCmUnclassed = 5, kCmValid = 6, kCmRes = 8 };
+struct CameraArgs {
+  int n, n_caller;             // finite points; points the caller handed over
+  int W, H;
+  int window, iterations;
+  double m[12];                // project: cloud -> camera; unproject: camera -> cloud (rows of 4)
+  double fx, fy, cx, cy;
+  double k1, k2, p1, p2, k3;
+  double min_depth, max_depth, max_tan_sq, depth_scale;
+  double occlusion_abs, occlusion_rel;
+  const float *x, *y, *z;      // [n] by f
+  const uint32_t* label;       // [n] by f, nullable
+  const int* caller;           // [n] f -> caller index; nullptr: the identity
+  const uint32_t* pixel_label; // [H W] sicp_camera_labels
+  unsigned long long* key;     // [H W] set to kCameraEmptyKey before the projection
+  uint32_t* count;             // [H W] zeroed before the projection
+  int* pix;                    // [n] by f: row W + col or -1
+  float* zf;                   // [n] by f: (float)Zc of a point with a pixel
+  float4* rec;                 // [H W] the winner's x, y, z and depth; depth = +inf in an empty pixel
+  // dense outputs, [H W], every one nullable
+  int* o_index;
+  float *o_depth, *o_x, *o_y, *o_z;
+  uint32_t* o_label;
+  // per-point outputs by caller index, [n_caller], preset for the points that are not finite; every one nullable
+  int* o_pixel;                // preset -1
+  float *o_u, *o_v;            // preset NaN
+  uint8_t* o_visible;          // preset 0
+  uint32_t* o_out_label;       // preset 0
+  uint8_t* o_state;            // preset 0
+  // sicp_camera_unproject: exactly one of the two depths; the points and flags per pixel
+  const uint16_t* depth_u16;
+  const float* depth_f32;
+  float *p_x, *p_y, *p_z;      // [H W]
+  uint8_t* p_valid;            // [H W] nullable
+  int* res;                    // kCmRes words, zeroed before the first launch
+};
+hipError_t launch_camera_project(const CameraArgs& a, hipStream_t st);    // key, count, pix, zf, o_pixel, o_u, o_v, res[kept, outside]
+hipError_t launch_camera_resolve(const CameraArgs& a, hipStream_t st);    // rec, the dense outputs, res[pixels hit]
+hipError_t launch_camera_visible(const CameraArgs& a, hipStream_t st);    // o_visible
+hipError_t launch_camera_labels(const CameraArgs& a, hipStream_t st);     // o_out_label, o_state, res[labelled, occluded, unclassed]
+hipError_t launch_camera_unproject(const CameraArgs& a, hipStream_t st);  // p_x p_y p_z, p_valid, res[valid]
+
 // ---- RANSAC plane extraction (plane_kernels.hip; driver: plane.cpp) ----
 // sicp_segment_planes: every array below that is [n_caller] long is indexed by the caller's index i; `finv` maps it to the
 // position f of the point among the finite ones (Cloud::rx ...), -1 for a point that is not finite.  A round compacts the

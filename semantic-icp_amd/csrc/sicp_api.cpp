@@ -895,6 +895,41 @@ int sicp_range_labels(sicp_handle h, int which, const sicp_range_params* p, cons
   });
 }
 
+int sicp_default_camera_params(sicp_camera_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    camera_default_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_camera_matrices(const double camera_qt[7], double cam_to_cloud[12], double cloud_to_cam[12]) {
+  return abi_guard([&]() -> int { return camera_matrices(camera_qt, cam_to_cloud, cloud_to_cam); });
+}
+
+int sicp_camera_image(sicp_handle h, int which, const sicp_camera_params* p, const double camera_qt[7], int32_t* index, float* depth,
+                      float* x, float* y, float* z, uint32_t* label, uint32_t* count, int32_t* pixel, float* u, float* v,
+                      uint8_t* visible, sicp_camera_info* info) {
+  return abi_guard(h, [&]() -> int {
+    return camera_image(h, which, p, camera_qt, index, depth, x, y, z, label, count, pixel, u, v, visible, info);
+  });
+}
+
+int sicp_camera_labels(sicp_handle h, int which, const sicp_camera_params* p, const double camera_qt[7], const uint32_t* pixel_label,
+                       sicp_handle dst, int dst_which, uint32_t* out_label, uint8_t* state, sicp_camera_info* info) {
+  return abi_guard(h, [&]() -> int {
+    return camera_labels(h, which, p, camera_qt, pixel_label, dst, dst_which, out_label, state, info);
+  });
+}
+
+int sicp_camera_unproject(sicp_handle h, const sicp_camera_params* p, const double camera_qt[7], const uint16_t* depth_u16,
+                          const float* depth_f32, const uint32_t* label, sicp_handle dst, int dst_which, float* x, float* y, float* z,
+                          uint8_t* valid, sicp_camera_info* info) {
+  return abi_guard(h, [&]() -> int {
+    return camera_unproject(h, p, camera_qt, depth_u16, depth_f32, label, dst, dst_which, x, y, z, valid, info);
+  });
+}
+
 int sicp_default_plane_params(sicp_plane_params* p) {
   return abi_guard([&]() -> int {
     if (!p) return SICP_ERR_INVALID_ARGUMENT;
