@@ -12,6 +12,8 @@ COUNTS = ("n_points", "n_finite", "n_kept", "n_outside", "n_pixels_hit")
 LABEL_COUNTS = ("n_labelled", "n_occluded", "n_unclassed")
 IMAGES = ("index", "depth", "x", "y", "z", "label", "count")
 PER_POINT = ("pixel", "u", "v", "visible")
+GROUP = 256        # points one workgroup of a per-point launch takes per pass (the shapes the GPU tests straddle; no rule depends on it)
+MAX_GROUPS = 1024  # workgroups a per-point launch has at most: more finite points than GROUP MAX_GROUPS and some take a second pass (likewise)
 
 
 def params(**kw):

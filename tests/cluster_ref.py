@@ -10,6 +10,9 @@ from scipy.spatial import cKDTree
 
 
 CELL_LIMIT = 2 ** 20 - 1  # include/sicp.h, rule 9: a cell coordinate of this magnitude or more is refused
+PAIR_CHUNK = 256          # points of a cell one workgroup of the pair pass (and of the filter's radius count) takes per step
+PAIR_CHUNK_GROUPS = 8     # workgroups a cell's chunks go round: a cell of more than PAIR_CHUNK PAIR_CHUNK_GROUPS points gives one a second
+                          # step (the shapes the GPU tests straddle; no rule depends on either)
 
 
 class GridOverflow(ValueError):

@@ -95,6 +95,26 @@ def tree_sum(values, present, n_points):
     return float(s[0])
 
 
+def tree_levels(values, present, n_points, run=TREE_RUN):
+    """the same tree cut the way the launches cut it: level 0 holds the sums of the aligned runs of `run` caller indices, level l
+    those of the runs of `run` entries of level l - 1, each the perfect binary tree over its run with +0.0 for what is absent;
+    the last level holds one sum -- tree_sum's, a taller tree adding nothing but +0.0"""
+    s = np.zeros(n_points, np.float64)
+    s[np.flatnonzero(present)] = values[present]
+    levels = []
+    while True:
+        blocks = (len(s) + run - 1) // run
+        t = np.zeros(blocks * run, np.float64)
+        t[:len(s)] = s
+        t = t.reshape(blocks, run)
+        while t.shape[1] > 1:
+            t = t[:, 0::2] + t[:, 1::2]
+        s = t[:, 0].copy()
+        levels.append(s)
+        if blocks == 1:
+            return levels
+
+
 def threshold(S1, S2, n_tested, std_mul):
     """rule 3: (mean, raw variance, stddev, threshold): double operations, each rounded on its own"""
     nt = float(n_tested)

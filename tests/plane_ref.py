@@ -15,6 +15,7 @@ MAX_IGNORE = 16
 LANE_POINTS = 4
 TILE = 256 * LANE_POINTS  # candidates one workgroup of the score kernel tests (the shapes the GPU tests straddle; no rule depends on it)
 HYP_GROUP = 64            # hypotheses one workgroup of the score kernel loops over (likewise)
+TREE_RUN = 512            # caller indices one workgroup of a tree sum reduces, level over level (likewise)
 GOLDEN = 0x9E3779B97F4A7C15
 DEFAULTS = dict(distance_threshold=0.2, axis=None, min_cos=0.0, seed=1, num_hypotheses=1024, max_planes=1, min_inliers=100, refine=1,
                 ignore=())

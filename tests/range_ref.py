@@ -12,6 +12,8 @@ F = np.float32
 EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
 COUNTS = ("n_points", "n_finite", "n_kept", "n_out_of_range", "n_outside_fov", "n_pixels_hit")
 IMAGES = ("index", "range_sq", "x", "y", "z", "label", "count")
+GROUP = 256        # points one workgroup of a per-point launch takes per pass (the shapes the GPU tests straddle; no rule depends on it)
+MAX_GROUPS = 1024  # workgroups a per-point launch has at most: more finite points than GROUP MAX_GROUPS and some take a second pass (likewise)
 
 
 def params(**kw):
