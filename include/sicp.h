@@ -1116,6 +1116,136 @@ int sicp_segment_planes(sicp_handle h, int which, const sicp_plane_params* p, co
                         int32_t* count, int32_t* hyp_index, int32_t* hyp_count, double* centroid /* 3 per plane */,
                         double* rms /* all nullable */, sicp_plane_info* info /* nullable */);
 
+/* ---- ground of a cloud -------------------------------------------------------------
+ * Piecewise-planar ground of the cloud in a handle's slot on a polar grid around the sensor (Zermas et al. 2017, "ground plane
+ * fitting"; Patchwork, Patchwork++): R rings x S sectors of cells, one small plane per cell, fitted from the cell's lowest
+ * points upward, and for every point its height above the local ground.  A ramp, a crowned road or a kerb that leave the one
+ * plane of sicp_segment_planes(axis = up) stay ground here.  z is up; the sensor looks along its own axes (no pose).  The handle
+ * may be in any mode; nothing on it changes unless dst is given.  All arithmetic below is float64 on the points' float
+ * coordinates widened exactly; every operation is rounded on its own, none contracted; (a b + c d) + e f is evaluated in that
+ * order; no atan2 and no sqrt but the Jacobi's.
+ *  1. Frame and candidates.  d = p - sensor_origin per axis (NULL: 0 0 0).  r2 = dx dx + dy dy.  A point is `inside` when it
+ *     is finite and edge2[0] <= r2 < edge2[R].  An inside point is a candidate when mask is NULL or mask[i] != 0, its label is
+ *     not one of ignore[0 .. n_ignore) (rule 1 of sicp_segment_planes: a cloud without labels only with n_ignore = 0), and
+ *     dz >= -(sensor_height + max_below), the bound formed once (a sum, a negation).  An inside point that fails only this last
+ *     test -- a multipath return under the road -- is counted in info.n_below.
+ *  2. Cell.  Tables formed once on the host in double with libm (sicp_ground_tables hands back what the kernel reads):
+ *     edge[i] = ring_edge[i] when the caller gives a table of R + 1 entries, else min_range + (double)i * ((max_range -
+ *     min_range) / (double)R), i = 0..R; edge2[i] = edge[i] * edge[i]; cos_half[j] = cos(a), sin_half[j] = sin(a), a = (double)j *
+ *     (6.283185307179586 / (double)S), j = 0..S/2-1 (rule 2 of sicp_place_*).  ring = the number of i in 1..R-1 with r2 >=
+ *     edge2[i].  sector by rule 3 of sicp_place_* on the doubles dx, dy: lower = !(dy > 0 || (dy == 0 && dx > 0)); (x', y') =
+ *     lower ? (-dx, -dy) : (dx, dy); sector = the number of j in 1..S/2-1 with cos_half[j]*y' - sin_half[j]*x' >= 0, plus S/2
+ *     when lower.  cell = ring * S + sector.  R in 1..64, S even in 4..256.
+ *  3. Order inside a cell.  The candidates, taken in ascending caller index, go through one stable sort by the key
+ *     (cell << 32) | ordered_bits(z): z the float32 as stored (not dz), ordered_bits(b) = b ^ 0x80000000 for a clear sign bit
+ *     and ~b otherwise, so -0.0 comes before +0.0.  A cell's members are one segment m_0 .. m_(m-1): lowest z first, ties by
+ *     caller index.
+ *  4. Seeds.  L = min(n_lpr, m); lpr = (((+0.0 + dz(m_0)) + dz(m_1)) + ...) / (double)L over the first L members; the seed
+ *     set is the members with dz < lpr + th_seeds (the sum formed once).
+ *  5. Fit, n_iter times, the first on the seed set.  A sum over a set is formed so: lane l of 64 adds, from +0.0, the terms of
+ *     the members m_j of the set with j mod 64 == l, in ascending j; then T_0[l] = the lane's sum, T_(k+1)[l] = T_k[l] +
+ *     T_k[l xor 2^k] for k = 0..5, and the sum is T_6[0] (pairs at distance 1, 2, 4, .. 32: the tree of sicp_map_extract_fused's
+ *     confidence).  A set with count < min_points ends the cell with status TOO_FEW.  S = the sums of dx, dy, dz; g = S /
+ *     (double)count; Q = the sums of the six products ex ex, ey ex, ey ey, ez ex, ez ey, ez ez of e = d - g.  Q, undivided, goes
+ *     through the cyclic Jacobi of rule 5 of sicp_segment_planes; u is the eigenvector column of smallest |eigenvalue| (at ties
+ *     the last such column), lambda_min that column's diagonal entry as the Jacobi left it; u is negated, all three components,
+ *     when uz < 0.  The next set is ALL members of the cell with (ux ex + uy ey) + uz ez < th_dist, e = d - g: signed, points
+ *     under the plane are ground.  The set selected by the last fit is the cell's ground; the model reported is the last fit:
+ *     u, g, lambda_min and n_fit = the count of the set it was fitted to.
+ *  6. Cell tests on the last fit, in this order: `uz >= min_cos` false: NOT_UPRIGHT; ring < elevation_rings and gz >=
+ *     -sensor_height + max_elevation (the bound formed once): TOO_HIGH (a hood, a roof, a loading ramp beside the sensor);
+ *     max_thickness > 0 and lambda_min > (max_thickness max_thickness) (double)n_fit: TOO_THICK; otherwise GROUND.  A cell
+ *     without candidates is EMPTY.  Only GROUND cells have ground points and a model.
+ *  7. Height, for every inside point, candidate or not: with the model of its own cell if that is GROUND, otherwise of the
+ *     first GROUND cell of the same sector at ring - 1, ring - 2, .. 0: height = (ux ex + uy ey) + uz ez, e = d - g.  No such
+ *     cell, or a point that is not inside: NaN.
+ *  8. Outputs (sicp_ground_out; every array nullable).  Per point, caller order: ground (1: a ground point), cell (the cell
+ *     of an inside point, candidate or not; -1 otherwise), height.  Per cell, R*S rows: status, n_members (candidates), n_ground,
+ *     n_fit, normal = u, centroid = g + sensor_origin, lambda_min, lpr; a row that is not GROUND has n_ground = n_fit = 0 and NaN
+ *     in normal, centroid and lambda_min; lpr is NaN only in an EMPTY row.  Capacity follows rule 6 of sicp_segment_planes with
+ *     R*S for n_planes (a non-NULL cell array with capacity < R*S: SICP_ERR_INVALID_ARGUMENT with info written and nothing
+ *     else, dst included).  select: 0 nothing, 1 the finite points that are not ground (non-candidates and points outside the
+ *     rings among them), 2 the ground points; with dst they become dst's slot dst_which exactly as sicp_set_cloud of them, in
+ *     caller order and with their labels, would make it (the route of sicp_filter(mask, dst)); dst may be h itself.  An empty
+ *     selection: SICP_ERR_TOO_FEW_POINTS, dst keeps its cloud, outputs and info untouched.
+ *  9. No candidate at all: SICP_OK, every cell EMPTY.  The slot holds no cloud: SICP_ERR_NOT_READY.  Refused before any device
+ *     work with SICP_ERR_INVALID_ARGUMENT, outputs and info left as they were: a NULL handle or params; a `which` (or, with
+ *     dst, dst_which) outside SICP_SOURCE / SICP_TARGET; a sensor_origin component or a double of params that is not finite;
+ *     min_range < 0; max_range <= min_range; a ring_edge table with a non-finite entry, ring_edge[0] < 0 or ring_edge[i + 1] <=
+ *     ring_edge[i]; n_rings outside 1..64; n_sectors outside 4..256 or odd; n_lpr outside 1..64; n_iter outside 1..8;
+ *     min_points < 3; min_cos outside (0, 1]; th_dist or th_seeds not > 0; max_thickness < 0; elevation_rings outside
+ *     0..n_rings; n_ignore outside 0..SICP_GROUND_MAX_IGNORE; ignore with a cloud without labels; select outside 0..2;
+ *     select != 0 without dst (dst with select = 0 is left alone); dst on another device; capacity < 0.  An out-of-memory answer
+ *     (sicp_set_memory_limit applies to the call's scratch) leaves both handles as they were.
+ * 10. Bit-reproducible: a function of the points, labels, mask, origin and parameters only, on a handle of any mode, in either
+ *     slot, before or after a sicp_align has laid the cloud out, for every launch shape: one wave owns a cell, integer counts,
+ *     sums of fixed order, no float atomics.
+ * The defaults are Patchwork's published KITTI values where it has them; nobody has tuned them on this engine. */
+#define SICP_GROUND_MAX_RINGS 64
+#define SICP_GROUND_MAX_SECTORS 256
+#define SICP_GROUND_MAX_IGNORE 16
+#define SICP_GROUND_EMPTY 0
+#define SICP_GROUND_GROUND 1
+#define SICP_GROUND_TOO_FEW 2
+#define SICP_GROUND_NOT_UPRIGHT 3
+#define SICP_GROUND_TOO_HIGH 4
+#define SICP_GROUND_TOO_THICK 5
+typedef struct sicp_ground_params {
+  double min_range;        /* >= 0.  default 2.7 */
+  double max_range;        /* > min_range.  default 80 */
+  double sensor_height;    /* of the sensor above the road.  default 1.73 */
+  double max_below;        /* candidates reach this far under the road.  default 1.0 */
+  double th_seeds;         /* > 0.  default 0.5 */
+  double th_dist;          /* > 0.  default 0.2 */
+  double min_cos;          /* in (0, 1].  default 0.707 */
+  double max_elevation;    /* default 0.5 */
+  double max_thickness;    /* >= 0; 0 (default): the test is off */
+  int32_t n_rings;         /* R in 1 .. SICP_GROUND_MAX_RINGS.  default 16 */
+  int32_t n_sectors;       /* S even in 4 .. SICP_GROUND_MAX_SECTORS.  default 32 */
+  int32_t n_lpr;           /* 1 .. 64.  default 20 */
+  int32_t n_iter;          /* 1 .. 8.  default 3 */
+  int32_t min_points;      /* >= 3.  default 10 */
+  int32_t elevation_rings; /* 0 .. R.  default 4 */
+  int32_t select;          /* what goes to dst: 0 (default) nothing, 1 the non-ground points, 2 the ground points */
+  int32_t n_ignore;        /* 0 .. SICP_GROUND_MAX_IGNORE.  default 0 */
+  uint32_t ignore[SICP_GROUND_MAX_IGNORE];
+} sicp_ground_params;
+typedef struct sicp_ground_out {
+  uint8_t* ground;         /* n_points */
+  int32_t* cell;           /* n_points */
+  double* height;          /* n_points */
+  int32_t capacity;        /* rows the cell arrays below hold */
+  int32_t pad_;
+  uint8_t* status;
+  int32_t* n_members;
+  int32_t* n_ground;
+  int32_t* n_fit;
+  double* normal;          /* 3 per cell */
+  double* centroid;        /* 3 per cell */
+  double* lambda_min;
+  double* lpr;
+} sicp_ground_out;
+typedef struct sicp_ground_info {
+  int64_t n_points;        /* what the caller handed over */
+  int64_t n_finite;
+  int64_t n_candidates;    /* rule 1 */
+  int64_t n_below;         /* rule 1 */
+  int64_t n_ground;
+  int64_t n_selected;      /* points handed to dst; 0 with select = 0 */
+  int32_t n_cells;         /* R*S */
+  int32_t cells[6];        /* cells per status, indexed by SICP_GROUND_EMPTY .. SICP_GROUND_TOO_THICK */
+  int32_t pad_;
+  double t_total_ms;       /* host wall clock */
+} sicp_ground_info;
+int sicp_default_ground_params(sicp_ground_params* p);
+/* rule 2's tables as the kernel reads them: cos_half, sin_half [S/2], edge2 [R+1], all nullable; host only */
+int sicp_ground_tables(const sicp_ground_params* p, const double* ring_edge /* R+1, nullable */, double* cos_half, double* sin_half,
+                       double* edge2);
+int sicp_segment_ground(sicp_handle h, int which, const sicp_ground_params* p, const uint8_t* mask /* n_points, nullable */,
+                        const double sensor_origin[3] /* nullable */, const double* ring_edge /* R+1, nullable */,
+                        sicp_handle dst /* nullable */, int dst_which, const sicp_ground_out* out /* nullable */,
+                        sicp_ground_info* info /* nullable */);
+
 /* ---- a persistent voxel map ---------------------------------------------------
  * The map of scan-to-map odometry as an object that lives on the device between calls: per occupied voxel of the absolute
  * grid of the merge above (v = floor(p * (1.0f / (float)leaf_size)), |v| < 2^20) its 63-bit key (three biased 21-bit

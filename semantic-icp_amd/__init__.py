@@ -454,6 +454,76 @@ class SicpPlaneInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+GROUND_MAX_RINGS = 64
+GROUND_MAX_SECTORS = 256
+GROUND_MAX_IGNORE = 16
+GROUND_EMPTY, GROUND_GROUND, GROUND_TOO_FEW, GROUND_NOT_UPRIGHT, GROUND_TOO_HIGH, GROUND_TOO_THICK = range(6)
+
+
+class SicpGroundParams(C.Structure):
+    """sicp_ground_params (include/sicp.h)"""
+    _fields_ = [
+        ("min_range", C.c_double),
+        ("max_range", C.c_double),
+        ("sensor_height", C.c_double),
+        ("max_below", C.c_double),
+        ("th_seeds", C.c_double),
+        ("th_dist", C.c_double),
+        ("min_cos", C.c_double),
+        ("max_elevation", C.c_double),
+        ("max_thickness", C.c_double),
+        ("n_rings", C.c_int32),
+        ("n_sectors", C.c_int32),
+        ("n_lpr", C.c_int32),
+        ("n_iter", C.c_int32),
+        ("min_points", C.c_int32),
+        ("elevation_rings", C.c_int32),
+        ("select", C.c_int32),
+        ("n_ignore", C.c_int32),
+        ("ignore", C.c_uint32 * GROUND_MAX_IGNORE),
+    ]
+
+
+class SicpGroundOut(C.Structure):
+    """sicp_ground_out (include/sicp.h)"""
+    _fields_ = [
+        ("ground", C.POINTER(C.c_uint8)),
+        ("cell", C.POINTER(C.c_int32)),
+        ("height", C.POINTER(C.c_double)),
+        ("capacity", C.c_int32),
+        ("pad_", C.c_int32),
+        ("status", C.POINTER(C.c_uint8)),
+        ("n_members", C.POINTER(C.c_int32)),
+        ("n_ground", C.POINTER(C.c_int32)),
+        ("n_fit", C.POINTER(C.c_int32)),
+        ("normal", C.POINTER(C.c_double)),
+        ("centroid", C.POINTER(C.c_double)),
+        ("lambda_min", C.POINTER(C.c_double)),
+        ("lpr", C.POINTER(C.c_double)),
+    ]
+
+
+class SicpGroundInfo(C.Structure):
+    """sicp_ground_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_points", C.c_int64),
+        ("n_finite", C.c_int64),
+        ("n_candidates", C.c_int64),
+        ("n_below", C.c_int64),
+        ("n_ground", C.c_int64),
+        ("n_selected", C.c_int64),
+        ("n_cells", C.c_int32),
+        ("cells", C.c_int32 * 6),
+        ("pad_", C.c_int32),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_ if name not in ("cells", "pad_")}
+        d["cells"] = [int(v) for v in self.cells]
+        return d
+
+
 class SicpMapParams(C.Structure):
     """sicp_map_params (include/sicp.h)"""
     _fields_ = [
@@ -872,6 +942,10 @@ def lib():
             "sicp_default_plane_params": [C.POINTER(SicpPlaneParams)],
             "sicp_segment_planes": [C.c_void_p, C.c_int, C.POINTER(SicpPlaneParams), _bp, _ip, C.c_int32, _dp, _ip, _ip, _ip, _dp, _dp,
                                     C.POINTER(SicpPlaneInfo)],
+            "sicp_default_ground_params": [C.POINTER(SicpGroundParams)],
+            "sicp_ground_tables": [C.POINTER(SicpGroundParams), _dp, _dp, _dp, _dp],
+            "sicp_segment_ground": [C.c_void_p, C.c_int, C.POINTER(SicpGroundParams), _bp, _dp, _dp, C.c_void_p, C.c_int,
+                                    C.POINTER(SicpGroundOut), C.POINTER(SicpGroundInfo)],
             "sicp_default_map_params": [C.POINTER(SicpMapParams)],
             "sicp_default_map_extract_params": [C.POINTER(SicpMapExtractParams)],
             "sicp_map_create": [C.c_int, C.POINTER(SicpMapParams), C.POINTER(C.c_void_p)],
@@ -1178,6 +1252,51 @@ def default_plane_params(ignore=(), axis=None, **overrides) -> SicpPlaneParams:
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def default_ground_params(ignore=(), **overrides) -> SicpGroundParams:
+    """sicp_default_ground_params (16 rings x 32 sectors from 2.7 m to 80 m, sensor 1.73 m above the road, n_lpr 20, th_seeds
+    0.5, th_dist 0.2, 3 iterations, min_points 10, min_cos 0.707, 4 elevation rings at 0.5 m, no thickness test, select 0: Patchwork's
+    KITTI values where it has them, untuned on this engine), with the labels in `ignore` (at most GROUND_MAX_IGNORE) and any other
+    field overridden by keyword"""
+    p = SicpGroundParams()
+    st = lib().sicp_default_ground_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_ground_params")
+    ignore = [int(v) for v in ignore]
+    if len(ignore) > GROUND_MAX_IGNORE:
+        raise ValueError(f"at most {GROUND_MAX_IGNORE} labels can be ignored")
+    p.n_ignore = len(ignore)
+    for k, v in enumerate(ignore):
+        p.ignore[k] = v
+    for k, v in overrides.items():
+        if not hasattr(p, k) or k == "ignore":
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _ring_edge(params, ring_edge):
+    if ring_edge is None:
+        return None
+    ring_edge = np.ascontiguousarray(ring_edge, dtype=np.float64)
+    if ring_edge.shape != (int(params.n_rings) + 1,):
+        raise ValueError(f"ring_edge must hold n_rings + 1 = {int(params.n_rings) + 1} numbers")
+    return ring_edge
+
+
+def ground_tables(params: SicpGroundParams, ring_edge=None):
+    """sicp_ground_tables (host only): {"edge2": [R+1], "cos_half": [S/2], "sin_half": [S/2]} float64, exactly what the kernels of
+    Engine.segment_ground read for these parameters and this ring table (None: uniform rings from min_range to max_range)"""
+    R, S = int(params.n_rings), int(params.n_sectors)
+    if not (1 <= R <= GROUND_MAX_RINGS and 4 <= S <= GROUND_MAX_SECTORS):
+        raise SicpError(ERR_INVALID_ARGUMENT, "sicp_ground_tables")
+    ring_edge = _ring_edge(params, ring_edge)
+    e2, ch, sh = np.empty(R + 1, dtype=np.float64), np.empty(S // 2, dtype=np.float64), np.empty(S // 2, dtype=np.float64)
+    st = lib().sicp_ground_tables(C.byref(params), _ptr(ring_edge, _dp), _ptr(ch, _dp), _ptr(sh, _dp), _ptr(e2, _dp))
+    if st != OK:
+        raise SicpError(st, "sicp_ground_tables")
+    return {"edge2": e2, "cos_half": ch, "sin_half": sh}
 
 
 def default_map_params(**overrides) -> SicpMapParams:
@@ -1872,6 +1991,48 @@ class Engine:
         k = int(info.n_planes)
         return {"plane_id": pid[:n], "coeff": coeff[:k], "count": cnt[:k], "hyp_index": hi[:k], "hyp_count": hc[:k], "centroid": cen[:k],
                 "rms": rms[:k], "info": info.as_dict()}
+
+    def segment_ground(self, which: int = SOURCE, params: SicpGroundParams | None = None, mask=None, sensor_origin=None, ring_edge=None,
+                       dst: "Engine | None" = None, dst_which: int | None = None):
+        """sicp_segment_ground: the piecewise-planar ground of the cloud in slot `which` on a polar grid of n_rings x n_sectors
+        cells around sensor_origin (None: 0 0 0; z is up), one plane per cell fitted from the cell's lowest candidates (finite,
+        `mask` ([n_points], 0 leaves a point out) non-zero, label not ignored, not under the road) upward, and every point's height
+        above the local ground.  ring_edge ([n_rings + 1], ascending) replaces the uniform rings.  Returns {"ground": [n_points]
+        uint8, "cell": int32 (-1: outside the rings), "height": float64 (NaN: no ground model), per cell [n_rings n_sectors]
+        "status": uint8 (GROUND_*), "n_members", "n_ground", "n_fit": int32, "normal", "centroid": [.., 3] float64, "lambda_min",
+        "lpr": float64, "info": SicpGroundInfo.as_dict()}.  With dst and params.select = 1 (the points that are not ground) or 2
+        (the ground points) the selection becomes that Engine's slot dst_which (default: `which`) as if it had been handed to
+        set_cloud; dst may be this engine.  Without dst nothing on the engine changes."""
+        p = params if params is not None else default_ground_params()
+        n = self.n[which] if which in (SOURCE, TARGET) else 0
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.shape != (n,):
+                raise ValueError(f"mask must have one entry per point ({n})")
+        if sensor_origin is not None:
+            sensor_origin = np.ascontiguousarray(sensor_origin, dtype=np.float64)
+            if sensor_origin.shape != (3,):
+                raise ValueError("sensor_origin must hold 3 numbers")
+        ring_edge = _ring_edge(p, ring_edge)
+        cap = max(int(p.n_rings), 1) * max(int(p.n_sectors), 1)
+        m = max(n, 1)
+        arr = {"ground": np.empty(m, np.uint8), "cell": np.empty(m, np.int32), "height": np.empty(m, np.float64),
+               "status": np.empty(cap, np.uint8), "n_members": np.empty(cap, np.int32), "n_ground": np.empty(cap, np.int32),
+               "n_fit": np.empty(cap, np.int32), "normal": np.empty((cap, 3), np.float64), "centroid": np.empty((cap, 3), np.float64),
+               "lambda_min": np.empty(cap, np.float64), "lpr": np.empty(cap, np.float64)}
+        out = SicpGroundOut()
+        out.capacity = cap
+        for k, a in arr.items():
+            setattr(out, k, a.ctypes.data_as(dict(SicpGroundOut._fields_)[k]))
+        info = SicpGroundInfo()
+        dw = which if dst_which is None else dst_which
+        self._check(lib().sicp_segment_ground(self._h, which, C.byref(p), _ptr(mask, _bp), _ptr(sensor_origin, _dp), _ptr(ring_edge, _dp),
+                                              None if dst is None else dst._h, dw, C.byref(out), C.byref(info)), "sicp_segment_ground")
+        if dst is not None and int(p.select) != 0:
+            dst.n[dw] = int(info.n_selected)
+        res = {k: (a[:n] if k in ("ground", "cell", "height") else a) for k, a in arr.items()}
+        res["info"] = info.as_dict()
+        return res
 
     def solve(self, init_qt):
         init = np.ascontiguousarray(init_qt, dtype=np.float64)

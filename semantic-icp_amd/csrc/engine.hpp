@@ -15,6 +15,7 @@
 //   range.cpp     sicp_range_image / sicp_range_labels: a scan's spherical projection and the vote back from per-pixel classes
 //   camera.cpp    sicp_camera_image / sicp_camera_labels / sicp_camera_unproject: a scan through a pinhole camera, a depth frame out of one
 //   plane.cpp     sicp_segment_planes: RANSAC plane extraction of a cloud
+//   ground.cpp    sicp_segment_ground: piecewise-planar ground on a polar grid, height above it
 //   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, raycast, prune, extract, merge, state)
 //   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
 //   sicp_api.cpp  the remaining C-ABI entry points
@@ -536,6 +537,10 @@ struct sicp_context : sicp_use_state {
   // sicp_segment_planes (plane.cpp): the pinned finite positions / mask on their way up, the control block, plane records and
   // per-point states on their way back
   HostBuf<unsigned char> pl_stage;
+  // sicp_segment_ground (ground.cpp): the pinned tables / finite positions / mask on their way up, the control block, cell rows
+  // and per-point outputs on their way back, and the pinned selected points (x | y | z | label) on their way into dst
+  HostBuf<unsigned char> gr_stage;
+  HostBuf<uint32_t> gr_out;
   // lock-step batch (sicp_align_batch), owned by the batch's first handle: one BatchArgs and one LM
   // state per pair, pinned mirrors, and the captured [accumulate_batch, lm_step_batch] x lm_batch graph
   TickSet ts[2];  // two sets: the halves of a batch alternate, one's tick runs while the host turns the other around
@@ -1079,6 +1084,12 @@ void plane_default_params(sicp_plane_params* p);
 int segment_planes(sicp_context* h, int which, const sicp_plane_params* p, const uint8_t* mask, int32_t* plane_id, int32_t capacity,
                    double* coeff, int32_t* count, int32_t* hyp_index, int32_t* hyp_count, double* centroid, double* rms,
                    sicp_plane_info* info);
+// sicp_segment_ground (ground.cpp): argument checks, the tables, the key / sort / segment / fit / point kernels queued on the
+// handle's stream, one read-back, and the selection's way into dst (set_cloud_common); sicp_ground_tables: host only
+void ground_default_params(sicp_ground_params* p);
+int ground_tables(const sicp_ground_params* p, const double* ring_edge, double* cos_half, double* sin_half, double* edge2);
+int segment_ground(sicp_context* h, int which, const sicp_ground_params* p, const uint8_t* mask, const double* sensor_origin,
+                   const double* ring_edge, sicp_context* dst, int dst_which, const sicp_ground_out* out, sicp_ground_info* info);
 // sicp_map_* (map.cpp): the persistent voxel map
 void map_default_params(sicp_map_params* p);
 void map_default_extract_params(sicp_map_extract_params* p);

@@ -792,6 +792,51 @@ hipError_t launch_plane_fit(const PlaneArgs& a, int round, hipStream_t st);     
 hipError_t launch_plane_record(const PlaneArgs& a, int round, hipStream_t st);   // rec, ctl->n_planes, n_assigned
 hipError_t launch_plane_assign(const PlaneArgs& a, int round, hipStream_t st);   // state of the members
 
+// ---- piecewise-planar ground on a polar grid (ground_kernels.hip; driver: ground.cpp) ----
+// sicp_segment_ground: arrays [n_caller] long are indexed by the caller's index i, `finv` as in PlaneArgs.  The key kernel gives
+// every point its cell and sort key (a point that is no candidate sorts behind every cell, under cell R*S), one stable sort of
+// the pairs, a pass that finds every cell's segment and writes the sorted coordinates densely, the fit kernel -- one wave per
+// cell -- and the per-point flag / height pass.  Nothing waits for the host.
+constexpr int kGroundMaxRings = 64, kGroundMaxSectors = 256;  // SICP_GROUND_MAX_RINGS, SICP_GROUND_MAX_SECTORS
+constexpr int kGroundMaxIgnore = 16;                          // SICP_GROUND_MAX_IGNORE
+constexpr int kGroundSortBits = 32 + 15;                      // cell <= R*S = 2^14 above the 32 bits of z
+enum { kGroundEmpty = 0, kGroundOk = 1, kGroundTooFew = 2, kGroundNotUpright = 3, kGroundTooHigh = 4, kGroundTooThick = 5 };
+struct GroundCell { double normal[3], centroid[3], lambda_min, lpr; int status, n_members, n_ground, n_fit; };  // centroid: g of rule 5
+struct GroundCtl { int n_candidates, n_below, n_selected, pad_; };
+struct GroundArgs {
+  int n, n_caller, labels;         // finite points; points the caller handed over; the cloud has labels
+  int R, S, n_lpr, n_iter, min_points, elevation_rings, select, n_ignore;
+  uint32_t ignore[kGroundMaxIgnore];
+  double org[3];                   // sensor_origin
+  double below, elev;              // -(sensor_height + max_below); -sensor_height + max_elevation
+  double th_seeds, th_dist, min_cos, thick2;  // thick2: max_thickness max_thickness, 0: the test is off
+  const double* tables;            // edge2 [R+1] | cos_half [S/2] | sin_half [S/2]
+  const float *x, *y, *z;          // [n] by f
+  const uint32_t* label;           // [n] nullable
+  const int* finv;                 // [n_caller] i -> f or -1; nullptr: the identity
+  const uint8_t* mask;             // [n_caller] nullable
+  unsigned long long *key, *skey;  // [n_caller] rule 3's key, before and after the sort
+  int *val, *sval;                 // [n_caller] the caller's index, likewise
+  int* cellv;                      // [n_caller] the cell of an inside point, -1 otherwise
+  uint8_t* cand;                   // [n_caller]
+  float *sx, *sy, *sz;             // [n_caller] the candidates' coordinates in sorted order
+  int *seg_begin, *seg_end;        // [R*S + 1] a cell's segment of the sorted arrays; zeroed before
+  GroundCell* cells;               // [R*S]
+  uint8_t* oground;                // [n_caller]
+  double* oheight;                 // [n_caller]
+  int *flag, *pos;                 // [n_caller] selected for dst and its exclusive scan (select != 0)
+  float *gx, *gy, *gz;             // [n_selected] the selection in ascending caller index
+  uint32_t* gl;                    // nullable
+  GroundCtl* ctl;                  // zeroed before
+};
+hipError_t launch_ground_keys(const GroundArgs& a, hipStream_t st);      // key, val, cellv, cand, ctl->n_candidates, n_below
+// (prim_sort_pairs key, val -> skey, sval over bits [0, kGroundSortBits))
+hipError_t launch_ground_segments(const GroundArgs& a, hipStream_t st);  // seg_begin, seg_end, sx sy sz
+hipError_t launch_ground_fit(const GroundArgs& a, hipStream_t st);       // cells
+hipError_t launch_ground_points(const GroundArgs& a, hipStream_t st);    // oground, oheight, flag
+// (prim_scan_int flag -> pos)
+hipError_t launch_ground_select(const GroundArgs& a, hipStream_t st);    // gx gy gz gl, ctl->n_selected
+
 // ---- the persistent voxel map (map_kernels.hip; driver: map.cpp) ----
 // sicp_map_*: per occupied voxel of merge's grid one row -- key, f64 sums, count, label histogram -- in arrays sorted by key.
 // An integrate keys and sorts the SCAN (the key arithmetic of voxel_key.hpp, merge's heads and gather launches), finds every

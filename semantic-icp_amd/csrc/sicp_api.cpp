@@ -946,6 +946,25 @@ int sicp_segment_planes(sicp_handle h, int which, const sicp_plane_params* p, co
   });
 }
 
+int sicp_default_ground_params(sicp_ground_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    ground_default_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_ground_tables(const sicp_ground_params* p, const double* ring_edge, double* cos_half, double* sin_half, double* edge2) {
+  return abi_guard([&]() -> int { return ground_tables(p, ring_edge, cos_half, sin_half, edge2); });
+}
+
+int sicp_segment_ground(sicp_handle h, int which, const sicp_ground_params* p, const uint8_t* mask, const double sensor_origin[3],
+                        const double* ring_edge, sicp_handle dst, int dst_which, const sicp_ground_out* out, sicp_ground_info* info) {
+  return abi_guard(h, [&]() -> int {
+    return segment_ground(h, which, p, mask, sensor_origin, ring_edge, dst, dst_which, out, info);
+  });
+}
+
 int sicp_default_map_params(sicp_map_params* p) {
   return abi_guard([&]() -> int {
     if (!p) return SICP_ERR_INVALID_ARGUMENT;
