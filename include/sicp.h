@@ -1431,6 +1431,123 @@ int sicp_map_raycast(sicp_map m, const double qt[7] /* NULL = identity */, const
                      uint32_t* count, double* range_sq,                              /* n each, every one nullable */
                      sicp_map_raycast_info* info /* nullable */);
 
+/* ---- elevation: the map as a semantic 2.5-D height grid ---------------------------
+ * What a planner reads (grid_map, elevation_mapping, OctoMap's projected map, multi-level surface maps): per ground cell of a
+ * window the height of the surface one can stand on, what it is, what hangs over it, how much it steps to its neighbours and
+ * whether it is free -- and, for the points of a handle's slot, their height above that MAPPED ground, which is there where a
+ * single scan sees no ground at all.  The map is read and never modified.  Every floating-point operation is rounded on its
+ * own, no contraction.  leaf and inv_leaf = 1.0f / (float)leaf_size are the map's; B = cell_voxels; fdiv(a, B) is the
+ * mathematical floor of a / B (not C's division for a negative a).  The host forms once: lo = floorf((float)z_min * inv_leaf)
+ * and hi = floorf((float)z_max * inv_leaf), both clamped to the key's range -(2^20 - 1) .. 2^20 - 1 (so -inf and +inf give its
+ * ends), and vref = floorf((float)ref_z * inv_leaf) clamped to -2^20 .. 2^20.  The rules:
+ *  1. Window.  center (x, y; finite) is keyed with the grid's float arithmetic, vc = floorf((float)center * inv_leaf) per axis;
+ *     a centre with |vc| >= 2^20 is refused.  x0 = fdiv(vc_x, B) - width / 2 and y0 = fdiv(vc_y, B) - height / 2 (integer
+ *     halves).  Cell (i, j), output index c = j * width + i, holds the voxel columns with fdiv(vx, B) = x0 + i and fdiv(vy, B) =
+ *     y0 + j.  info returns x0, y0 and cell_size = B * leaf_size.
+ *  2. Rows that count.  A map row counts when count >= min_count; when n_ignore > 0, its fullest histogram bin --
+ *     sicp_map_extract's label: ties to the smallest label, bin 0 can win -- is not in ignore (sicp_map_raycast's rule 4);
+ *     lo <= vz <= hi; and its column lies in the window.
+ *  3. Levels and runs.  A cell's levels are the distinct vz of its counting rows, ascending: l_0 < l_1 < ...  Level l_k starts a
+ *     new run when k = 0 or l_k - l_(k-1) > clearance_voxels.  A cell without a level is EMPTY.
+ *  4. The chosen run.  use_ref_z = 0: the first run.  use_ref_z = 1: the last run whose bottom level is <= vref; when there is
+ *     none, the first run (a level of a multi-level place: a bridge deck over a road).
+ *  5. Per SURFACE cell, the chosen run having top level t and bottom level b.  The mean at a level: S = 0.0, N = 0, then over
+ *     the cell's counting rows at that level in ascending map row (= ascending key) S = S + sz[row], N += count[row]; the mean
+ *     is (float)(S / (double)N) -- for B = 1 sicp_map_extract's z of that voxel, byte for byte.  elevation: the mean at t.
+ *     bottom: the mean at b.  ceiling: the mean at the bottom level of the run that follows the chosen one, +inf when there is
+ *     none.  count: N at t.  label: the fullest bin of the level-t rows' histograms added bin by bin (ties to the smallest
+ *     label, bin 0 can win); 0 on a map without classes.  level_top = t, level_bottom = b; n_levels: the levels of the run;
+ *     state = 1.  An EMPTY cell: state = 0; elevation, bottom and ceiling the quiet NaN 0x7fc00000; zeros elsewhere.
+ *  6. Neighbourhood.  neighbors of a SURFACE cell: the SURFACE cells among the up to 8 adjacent cells inside the window.  step:
+ *     the maximum over those of fabsf(e_n - e_c), one float subtraction each (the maximum is exact: the order does not matter);
+ *     0.0f when there are none.  An EMPTY cell: step that NaN, neighbors 0.
+ *  7. Class; the first test that holds decides:
+ *       SICP_ELEVATION_UNKNOWN 0        the cell is EMPTY
+ *       SICP_ELEVATION_BLOCKED_LABEL 2  n_blocked > 0 and the label is in blocked, or n_drivable > 0 and it is not in drivable
+ *       SICP_ELEVATION_OBSTACLE 3       level_top - level_bottom > max_extent_voxels (a wall, a trunk, a parked car not ignored)
+ *       SICP_ELEVATION_LOW_CLEARANCE 4  min_clearance > 0, ceiling finite, (double)(ceiling - elevation) < min_clearance (the
+ *                                       difference in float)
+ *       SICP_ELEVATION_STEP 5           (double)step > max_step
+ *       SICP_ELEVATION_SPARSE 6         neighbors < min_neighbors
+ *       SICP_ELEVATION_FREE 1           none of the above
+ *     info.n_class[8]: the cells per class, counted on the device with integer atomics, so valid without any array.
+ *  8. Points (h non-NULL).  Every one of the slot's n_points in caller order, whatever the handle's mode and device layout: a
+ *     point that is not finite gets point_cell = -1 and point_height = that NaN; a finite one goes through
+ *     sicp_map_integrate's transform and the grid's key arithmetic, without a crop; beyond the key's range or outside the window
+ *     it gets -1 and NaN; in an EMPTY cell c and NaN; otherwise c and pz - elevation[c], one float subtraction.  The handle is
+ *     not modified; a cloud that is not yet on the device is prepared as a merge part is.
+ *  9. Contracts.  Every output array is nullable; the cell arrays are width * height long, the point arrays n_points.  The call
+ *     is synchronous, on the map's stream.  No float atomics: every cell's bytes are plain stores by the lane that owns the
+ *     cell and do not depend on the launch shape; those of state, elevation, bottom, ceiling, label, count and the levels do
+ *     not depend on the window the cell is seen through.  An empty map: SICP_OK, every cell EMPTY.
+ *     SICP_ERR_INVALID_ARGUMENT with nothing written (info included): a NULL map, params or centre; width or height outside
+ *     1..2048; cell_voxels outside 1..8; min_count < 1; n_ignore, n_blocked or n_drivable outside
+ *     0..SICP_MAP_ELEVATION_MAX_LABELS, or > 0 on a map with num_classes = 0; a listed label above num_classes; z_min or z_max
+ *     NaN, or z_min > z_max; clearance_voxels < 1; use_ref_z neither 0 nor 1, or 1 with a ref_z that is not finite;
+ *     max_extent_voxels < 0; min_clearance or max_step negative or NaN; min_neighbors outside 0..8; a centre that is not finite
+ *     or beyond the key's range; a pose that is not finite; with a handle, `which` outside the two slots or a handle on another
+ *     device; point outputs without a handle.  SICP_ERR_NOT_READY: the slot holds no cloud.  SICP_ERR_OUT_OF_MEMORY: the arena
+ *     refused (sicp_set_memory_limit applies); nothing is written.  sicp_map_last_error names the cause.
+ * Cost: one sort of the map's rows by (cell, level) -- the rows outside the window sort behind -- and linear passes; a cell's
+ * column is walked by one lane, so a facade at cell_voxels = 8 costs its lane a few hundred rows.
+ * Memory: device scratch of about 45 bytes a cell and 28 a map row for the call's duration (the arena keeps it for later
+ * calls), and a pinned read-back buffer sized by the arrays asked for -- up to 39 bytes a cell, 160 MB at 2048 x 2048 -- which
+ * stays with the map for the next call up to 64 MB and is given back at the call's end above that.
+ * Not built: a dst cloud of the surface cells; slope or roughness (they need roots and quotients); fused (confusion-matrix)
+ * labels per cell; a persistent grid updated per scan; batch and stream forms; the C++ class shims. */
+#define SICP_MAP_ELEVATION_MAX_LABELS 64
+enum {
+  SICP_ELEVATION_UNKNOWN = 0, SICP_ELEVATION_FREE = 1, SICP_ELEVATION_BLOCKED_LABEL = 2, SICP_ELEVATION_OBSTACLE = 3,
+  SICP_ELEVATION_LOW_CLEARANCE = 4, SICP_ELEVATION_STEP = 5, SICP_ELEVATION_SPARSE = 6
+};
+typedef struct sicp_map_elevation_params {
+  double  z_min, z_max;        /* rows outside are not seen.  default -inf, +inf; not NaN, z_min <= z_max */
+  double  ref_z;               /* read with use_ref_z = 1; finite then.  default 0 */
+  double  min_clearance;       /* >= 0; 0 (default) = the LOW_CLEARANCE test is off */
+  double  max_step;            /* >= 0; +inf (default) = the STEP test is off */
+  int32_t width, height;       /* cells, 1..2048 each; no default: the caller sets them */
+  int32_t cell_voxels;         /* a cell is B x B voxel columns.  1..8, default 1 */
+  int32_t min_count;           /* a voxel with fewer points is not seen.  default 1, >= 1 */
+  int32_t clearance_voxels;    /* the free height that separates one surface from the one above it.  default 10, >= 1 */
+  int32_t use_ref_z;           /* 0 (default): the lowest surface; 1: rule 4's run at ref_z */
+  int32_t max_extent_voxels;   /* a run taller than this is an OBSTACLE.  default 2, >= 0 */
+  int32_t min_neighbors;       /* 0 (default, off) .. 8 */
+  int32_t n_ignore, n_blocked, n_drivable;  /* 0 (default) .. SICP_MAP_ELEVATION_MAX_LABELS each */
+  int32_t reserved_;
+  uint32_t ignore[SICP_MAP_ELEVATION_MAX_LABELS];   /* a voxel whose fullest histogram bin is one of these does not exist here */
+  uint32_t blocked[SICP_MAP_ELEVATION_MAX_LABELS];  /* a surface with one of these labels is BLOCKED_LABEL */
+  uint32_t drivable[SICP_MAP_ELEVATION_MAX_LABELS]; /* when given, a surface with any other label is BLOCKED_LABEL */
+} sicp_map_elevation_params;
+typedef struct sicp_map_elevation_out {
+  uint8_t* state;              /* width * height each, c = j * width + i */
+  float* elevation;
+  float* bottom;
+  float* ceiling;
+  uint32_t* label;
+  uint32_t* count;
+  int32_t* level_top;
+  int32_t* level_bottom;
+  int32_t* n_levels;
+  float* step;
+  uint8_t* neighbors;
+  uint8_t* cell_class;
+  int32_t* point_cell;         /* n_points each; they need a handle */
+  float* point_height;
+} sicp_map_elevation_out;
+typedef struct sicp_map_elevation_info {
+  int64_t n_voxels;            /* map rows */
+  int64_t n_points;            /* what the slot's caller handed over; 0 without a handle */
+  int32_t x0, y0;              /* rule 1: the cell coordinates of output cell (0, 0) */
+  int32_t width, height;
+  int32_t n_class[8];          /* cells per class, indexed by SICP_ELEVATION_UNKNOWN .. SICP_ELEVATION_SPARSE (7: unused, 0) */
+  double cell_size;            /* cell_voxels * leaf_size */
+  double t_total_ms;           /* host wall clock */
+} sicp_map_elevation_info;
+int sicp_default_map_elevation_params(sicp_map_elevation_params* p);
+int sicp_map_elevation(sicp_map m, const double center[2], const sicp_map_elevation_params* p,
+                       const sicp_map_elevation_out* out /* nullable */, sicp_handle h /* nullable */, int which,
+                       const double qt[7] /* NULL = identity */, sicp_map_elevation_info* info /* nullable */);
+
 typedef struct sicp_map_extract_params {
   int32_t min_count;      /* voxels with fewer points are left out.  default 1 */
   int32_t reserved_;

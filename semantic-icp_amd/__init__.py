@@ -640,6 +640,85 @@ class SicpMapRaycastInfo(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
 
 
+MAP_ELEVATION_MAX_LABELS = 64
+ELEVATION_CLASSES = ("unknown", "free", "blocked_label", "obstacle", "low_clearance", "step", "sparse")
+ELEVATION_UNKNOWN, ELEVATION_FREE, ELEVATION_BLOCKED_LABEL, ELEVATION_OBSTACLE, ELEVATION_LOW_CLEARANCE, ELEVATION_STEP, \
+    ELEVATION_SPARSE = range(7)
+
+
+class SicpMapElevationParams(C.Structure):
+    """sicp_map_elevation_params (include/sicp.h)"""
+    _fields_ = [
+        ("z_min", C.c_double),
+        ("z_max", C.c_double),
+        ("ref_z", C.c_double),
+        ("min_clearance", C.c_double),
+        ("max_step", C.c_double),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("cell_voxels", C.c_int32),
+        ("min_count", C.c_int32),
+        ("clearance_voxels", C.c_int32),
+        ("use_ref_z", C.c_int32),
+        ("max_extent_voxels", C.c_int32),
+        ("min_neighbors", C.c_int32),
+        ("n_ignore", C.c_int32),
+        ("n_blocked", C.c_int32),
+        ("n_drivable", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("ignore", C.c_uint32 * MAP_ELEVATION_MAX_LABELS),
+        ("blocked", C.c_uint32 * MAP_ELEVATION_MAX_LABELS),
+        ("drivable", C.c_uint32 * MAP_ELEVATION_MAX_LABELS),
+    ]
+
+
+class SicpMapElevationOut(C.Structure):
+    """sicp_map_elevation_out (include/sicp.h)"""
+    _fields_ = [
+        ("state", C.POINTER(C.c_uint8)),
+        ("elevation", C.POINTER(C.c_float)),
+        ("bottom", C.POINTER(C.c_float)),
+        ("ceiling", C.POINTER(C.c_float)),
+        ("label", C.POINTER(C.c_uint32)),
+        ("count", C.POINTER(C.c_uint32)),
+        ("level_top", C.POINTER(C.c_int32)),
+        ("level_bottom", C.POINTER(C.c_int32)),
+        ("n_levels", C.POINTER(C.c_int32)),
+        ("step", C.POINTER(C.c_float)),
+        ("neighbors", C.POINTER(C.c_uint8)),
+        ("cell_class", C.POINTER(C.c_uint8)),
+        ("point_cell", C.POINTER(C.c_int32)),
+        ("point_height", C.POINTER(C.c_float)),
+    ]
+
+
+class SicpMapElevationInfo(C.Structure):
+    """sicp_map_elevation_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_voxels", C.c_int64),
+        ("n_points", C.c_int64),
+        ("x0", C.c_int32),
+        ("y0", C.c_int32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("n_class", C.c_int32 * 8),
+        ("cell_size", C.c_double),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_ if name != "n_class"}
+        d["n_class"] = [int(v) for v in self.n_class]
+        return d
+
+
+# the cell arrays of VoxelMap.elevation, in sicp_map_elevation_out's order, with their dtypes
+ELEVATION_CELL_ARRAYS = (("state", np.uint8), ("elevation", np.float32), ("bottom", np.float32), ("ceiling", np.float32),
+                         ("label", np.uint32), ("count", np.uint32), ("level_top", np.int32), ("level_bottom", np.int32),
+                         ("n_levels", np.int32), ("step", np.float32), ("neighbors", np.uint8), ("cell_class", np.uint8))
+ELEVATION_POINT_ARRAYS = (("point_cell", np.int32), ("point_height", np.float32))
+
+
 class SicpMapMergeParams(C.Structure):
     """sicp_map_merge_params (include/sicp.h)"""
     _fields_ = [
@@ -960,6 +1039,9 @@ def lib():
             "sicp_default_map_raycast_params": [C.POINTER(SicpMapRaycastParams)],
             "sicp_map_raycast": [C.c_void_p, _dp, _dp, C.c_int32, _fp, _fp, _fp, C.POINTER(SicpMapRaycastParams), C.c_void_p, C.c_int,
                                  _ip, _ip, _ip, _fp, _fp, _fp, _up, _up, _dp, C.POINTER(SicpMapRaycastInfo)],
+            "sicp_default_map_elevation_params": [C.POINTER(SicpMapElevationParams)],
+            "sicp_map_elevation": [C.c_void_p, _dp, C.POINTER(SicpMapElevationParams), C.POINTER(SicpMapElevationOut), C.c_void_p, C.c_int,
+                                   _dp, C.POINTER(SicpMapElevationInfo)],
             "sicp_map_extract": [C.c_void_p, C.POINTER(SicpMapExtractParams), C.c_void_p, C.c_int, C.c_int32, _fp, _fp, _fp, _up, _up, _up,
                                  C.POINTER(SicpMapExtractInfo)],
             "sicp_map_set_confusion": [C.c_void_p, C.c_int32, _dp],
@@ -1361,6 +1443,28 @@ def default_map_raycast_params(ignore=(), **overrides) -> SicpMapRaycastParams:
     p.n_ignore = len(labels)
     for k, v in overrides.items():
         if not hasattr(p, k) or k == "ignore":
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_map_elevation_params(ignore=(), blocked=(), drivable=(), **overrides) -> SicpMapElevationParams:
+    """sicp_default_map_elevation_params (cell_voxels 1, min_count 1, every level, clearance_voxels 10, the lowest surface,
+    max_extent_voxels 2, the clearance, step and neighbour tests off, no label lists; width and height are the caller's), with
+    the labels in `ignore`, `blocked` and `drivable` (at most MAP_ELEVATION_MAX_LABELS each; they set their counts) and any
+    other field overridden by keyword"""
+    p = SicpMapElevationParams()
+    st = lib().sicp_default_map_elevation_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_map_elevation_params")
+    for name, given in (("ignore", ignore), ("blocked", blocked), ("drivable", drivable)):
+        labels = [int(l) for l in given]
+        if len(labels) > MAP_ELEVATION_MAX_LABELS:
+            raise ValueError(f"at most {MAP_ELEVATION_MAX_LABELS} {name} labels")
+        setattr(p, name, (C.c_uint32 * MAP_ELEVATION_MAX_LABELS)(*labels))
+        setattr(p, "n_" + name, len(labels))
+    for k, v in overrides.items():
+        if not hasattr(p, k) or k in ("ignore", "blocked", "drivable"):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
@@ -2375,6 +2479,52 @@ class VoxelMap:
         return {"row": row[:n].copy(), "step": step[:n].copy(), "length": length[:n].copy(),
                 "xyz": np.stack([x[:n], y[:n], z[:n]], axis=1), "labels": lab[:n].copy(), "count": cnt[:n].copy(),
                 "range_sq": r2[:n].copy(), "info": info.as_dict()}
+
+    def elevation(self, center, width: int, height: int, params: SicpMapElevationParams | None = None, engine: "Engine | None" = None,
+                  which: int = SOURCE, qt=None, want=None):
+        """sicp_map_elevation: the map as a 2.5-D grid of height x width cells about center (x, y) -- per cell the surface one can
+        stand on.  Returns a dict of [height, width] arrays "state", "elevation", "bottom", "ceiling", "label", "count",
+        "level_top", "level_bottom", "n_levels", "step", "neighbors", "cell_class" (ELEVATION_*), and "info"
+        (SicpMapElevationInfo.as_dict(): x0, y0, cell_size, n_class ...).  With an engine also "point_cell" and "point_height":
+        for every point of its slot `which` (caller order), at pose qt (None: identity), its cell (-1: none) and its height above
+        that cell's elevation (NaN: none).  `want` (None: everything) names the arrays to ask for; the others are not returned.
+        params (None: the defaults) is not modified; width and height are set from the arguments."""
+        p = SicpMapElevationParams()
+        C.memmove(C.byref(p), C.byref(params if params is not None else default_map_elevation_params()), C.sizeof(p))
+        p.width, p.height = int(width), int(height)
+        c = np.ascontiguousarray(center, dtype=np.float64).reshape(2)
+        q = None if qt is None else np.ascontiguousarray(qt, dtype=np.float64).reshape(7)
+        names = [n for n, _ in ELEVATION_CELL_ARRAYS] + ([n for n, _ in ELEVATION_POINT_ARRAYS] if engine is not None else [])
+        if want is not None:
+            unknown = [n for n in want if n not in [a for a, _ in ELEVATION_CELL_ARRAYS + ELEVATION_POINT_ARRAYS]]
+            if unknown:
+                raise KeyError(unknown[0])
+            names = list(want)
+        n_cells = max(p.width, 0) * max(p.height, 0)
+        n_points = 0
+        if engine is not None and any(n in names for n, _ in ELEVATION_POINT_ARRAYS):
+            try:
+                n_points = engine.cloud_size(which)[0]
+            except SicpError:
+                pass  # (no cloud, a bad slot: the call below refuses and names the cause)
+        out = SicpMapElevationOut()
+        arrays = {}
+        for name, dt in ELEVATION_CELL_ARRAYS + ELEVATION_POINT_ARRAYS:
+            if name not in names:
+                continue
+            cells = (name, dt) in ELEVATION_CELL_ARRAYS
+            a = np.zeros(max(n_cells if cells else n_points, 1), dtype=dt)
+            arrays[name] = a
+            setattr(out, name, a.ctypes.data_as(dict(SicpMapElevationOut._fields_)[name]))
+        info = SicpMapElevationInfo()
+        self._check(lib().sicp_map_elevation(self._m, _ptr(c, _dp), C.byref(p), C.byref(out), None if engine is None else engine._h, which,
+                                             _ptr(q, _dp), C.byref(info)), "sicp_map_elevation")
+        res = {}
+        for name, a in arrays.items():
+            cells = name in [n for n, _ in ELEVATION_CELL_ARRAYS]
+            res[name] = a[:n_cells].reshape(p.height, p.width).copy() if cells else a[:n_points].copy()
+        res["info"] = info.as_dict()
+        return res
 
     def merge(self, src: "VoxelMap", qt=None, min_count: int = 1, crop_center=None, crop_range: float = 0.0):
         """sicp_map_merge: src's voxels with at least min_count points, moved by qt (src's frame -> this map's; None: identity)

@@ -17,6 +17,7 @@
 //   plane.cpp     sicp_segment_planes: RANSAC plane extraction of a cloud
 //   ground.cpp    sicp_segment_ground: piecewise-planar ground on a polar grid, height above it
 //   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, raycast, prune, extract, merge, state)
+//   elevation.cpp sicp_map_elevation: the map as a 2.5-D height grid
 //   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
 //   sicp_api.cpp  the remaining C-ABI entry points
 // Every extern "C" entry runs inside abi_guard (abi_barrier.hpp): no exception crosses the boundary.
@@ -643,7 +644,8 @@ struct sicp_map_ctx {
   DevBuf<double> logcm;      // sicp_map_set_confusion: log cm[r][s], num_classes^2 doubles (the host takes the logarithms)
   bool has_cm = false;
   HostBuf<unsigned char> stage;  // pinned: the counts' read-back
-  HostBuf<uint32_t> out;         // pinned: an extract's result (x | y | z | label | count | hist rows | confidence) on its way out
+  HostBuf<uint32_t> out;         // pinned: an extract's result (x | y | z | label | count | hist rows | confidence) on its way out; an
+                                 // elevation's control words and arrays
   HostBuf<uint32_t> rays;        // pinned: a ray cast's ends on their way up, then its per-ray results on their way out
   std::string last_error;
 };
@@ -1106,6 +1108,11 @@ int map_raycast(sicp_map_ctx* m, const double* qt, const double* sensor_origin, 
                 const float* ez, const sicp_map_raycast_params* p, sicp_context* dst, int dst_which, int32_t* row, int32_t* step,
                 int32_t* length, float* x, float* y, float* z, uint32_t* label, uint32_t* count, double* range_sq,
                 sicp_map_raycast_info* info);
+// sicp_map_elevation (elevation.cpp): argument checks, the window, the key / sort / segment / cell / stencil / point kernels
+// queued on the map's stream, one read-back through the map's pinned buffer
+void map_default_elevation_params(sicp_map_elevation_params* p);
+int map_elevation(sicp_map_ctx* m, const double* center, const sicp_map_elevation_params* p, const sicp_map_elevation_out* out,
+                  sicp_context* h, int which, const double* qt, sicp_map_elevation_info* info);
 int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
                 float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info);
 int map_set_confusion(sicp_map_ctx* m, int32_t C, const double* cm);

@@ -972,6 +972,58 @@ struct MapRaycastArgs {
 hipError_t launch_map_raycast_opaque(const MapRaycastArgs& a, hipStream_t st);   // opaque, res[kMapRange] (launched for n_map = 0 too)
 hipError_t launch_map_raycast_walk(const MapRaycastArgs& a, hipStream_t st);     // the per-ray outputs, visible, stat[rays, steps, hits]
 hipError_t launch_map_raycast_visible(const MapRaycastArgs& a, hipStream_t st);  // stat[visible]
+// the 2.5-D height grid (sicp_map_elevation; elevation_kernels.hip, driver: elevation.cpp).  One lane per map row writes
+// (cell << 21) | (vz + bias) for a row that counts and all ones for one that does not; one stable sort over the cell's and the
+// level's bits puts a cell's rows together, its levels ascending and equal levels in ascending map row -- the order in which
+// the rule adds a level's sums -- and the rows that do not count behind (the cell field is wide enough that all ones is no
+// cell).  Heads, their scan and a gather list the occupied cells with where their rows begin; one lane per occupied cell walks
+// its rows, finds the runs and writes the cell; one lane per cell of the window then looks at its eight neighbours and
+// classifies it.  A cell's index is a function of the lane id everywhere: nothing is dealt through a counter.
+constexpr int kElevMaxLabels = 64;  // SICP_MAP_ELEVATION_MAX_LABELS
+constexpr int kElevLevelBits = 21;
+// the control words: rows that count, occupied cells, the cells per class
+enum { kElevValid = 0, kElevOccupied = 1, kElevClass = 2, kElevCtl = 10 };
+inline int elevation_cell_bits(long long cells) {  // the smallest k with 2^k > cells
+  int k = 0;
+  while ((1ll << k) <= cells) ++k;
+  return k;
+}
+struct MapElevationArgs {
+  MapRows rows;                    // hist: nullptr when the map keeps no labels
+  int n_map, stride;
+  int W, H, B, x0, y0;             // the window (rule 1)
+  int lo, hi;                      // the levels seen
+  long long min_count;
+  int clearance, use_ref, vref, max_extent, min_neighbors;
+  double min_clearance, max_step;
+  int n_ignore, n_blocked, n_drivable;
+  uint32_t ignore[kElevMaxLabels], blocked[kElevMaxLabels], drivable[kElevMaxLabels];
+  unsigned long long *key, *skey;  // [n_map]
+  int *val, *sval;                 // [n_map] the map row
+  int *flag, *pos;                 // [n_map] a cell's first sorted row and its exclusive scan
+  int *occ_cell, *occ_begin;       // [min(n_map, W*H)] the occupied cells, ascending, and their first sorted row
+  int* ctl;                        // kElevCtl words, zeroed
+  uint8_t *state, *neighbors, *cls;  // [W*H] each
+  float *elevation, *bottom, *ceiling, *step;
+  uint32_t *label, *count;
+  int *level_top, *level_bottom, *n_levels;
+  const float *px, *py, *pz;       // the slot's finite points in caller order (Cloud::rx ...)
+  const int* keep;                 // [n] their caller indices; nullptr when nothing was dropped
+  double M[12];
+  int n, n_caller;
+  float inv_leaf;
+  int* point_cell;                 // [n_caller]
+  float* point_height;
+};
+hipError_t launch_elevation_init(const MapElevationArgs& a, hipStream_t st);      // every cell EMPTY; every point -1 / NaN
+hipError_t launch_elevation_keys(const MapElevationArgs& a, hipStream_t st);      // key, val
+// (prim_sort_pairs key, val -> skey, sval over bits [0, kElevLevelBits + elevation_cell_bits(W * H)))
+hipError_t launch_elevation_heads(const MapElevationArgs& a, hipStream_t st);     // flag, ctl[kElevValid]
+// (prim_scan_int flag -> pos)
+hipError_t launch_elevation_segments(const MapElevationArgs& a, hipStream_t st);  // occ_cell, occ_begin, ctl[kElevOccupied]
+hipError_t launch_elevation_cells(const MapElevationArgs& a, hipStream_t st);     // rule 5's arrays of the occupied cells
+hipError_t launch_elevation_stencil(const MapElevationArgs& a, hipStream_t st);   // step, neighbors, cls, ctl[kElevClass ..]
+hipError_t launch_elevation_points(const MapElevationArgs& a, hipStream_t st);    // point_cell, point_height of the finite points
 // label fusion through the confusion matrix (sicp_map_extract_fused, sicp_map_fused_labels).  logcm[r * C + s] = log cm[r][s]
 // (observed label r + 1, class s + 1; -inf for a zero entry).  A histogram row's score of class s is the sum over its
 // non-zero bins r = 1..C, ascending, of (double)h[r] * logcm[r - 1][s - 1], each product and each sum rounded once.  An item

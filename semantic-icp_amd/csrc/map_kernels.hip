@@ -176,16 +176,6 @@ __global__ __launch_bounds__(256) void map_prune_kernel(MapSelectArgs a) {
   if ((threadIdx.x & 63) == 0 && sum) atomicAdd(a.kept_points, sum);
 }
 
-// a histogram row's fullest bin: ties to the smallest label, bin 0 can win
-__device__ __forceinline__ uint32_t map_fullest_bin(const uint32_t* h, int stride) {
-  uint32_t best = 0, best_n = h[0];
-  for (int l = 1; l < stride; ++l) {
-    const uint32_t m = h[l];
-    if (m > best_n) { best_n = m; best = (uint32_t)l; }
-  }
-  return best;
-}
-
 // the selected rows as points, ascending key: centroid, count, the arg-max bin (ties to the smallest label); their number and
 // the largest count
 __global__ __launch_bounds__(256) void map_extract_kernel(MapSelectArgs a) {

@@ -1048,6 +1048,19 @@ int sicp_map_raycast(sicp_map m, const double qt[7], const double sensor_origin[
   });
 }
 
+int sicp_default_map_elevation_params(sicp_map_elevation_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    map_default_elevation_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_map_elevation(sicp_map m, const double center[2], const sicp_map_elevation_params* p, const sicp_map_elevation_out* out,
+                       sicp_handle h, int which, const double qt[7], sicp_map_elevation_info* info) {
+  return abi_guard(m, [&]() -> int { return map_elevation(m, center, p, out, h, which, qt, info); });
+}
+
 int sicp_map_extract(sicp_map m, const sicp_map_extract_params* p, sicp_handle dst, int dst_which, int32_t capacity, float* x,
                      float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info) {
   return abi_guard(m, [&]() -> int {

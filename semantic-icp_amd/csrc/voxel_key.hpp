@@ -53,6 +53,17 @@ __device__ __forceinline__ void voxel_key_coords(unsigned long long key, int* vx
   *vz = (int)((key >> 42) & 0x1fffffull) - kMergeBias;
 }
 
+// a histogram row's fullest bin, the label of a map row wherever one is asked for (extract, carve, raycast, elevation): ties to
+// the smallest label, bin 0 can win
+__device__ __forceinline__ uint32_t map_fullest_bin(const uint32_t* h, int stride) {
+  uint32_t best = 0, best_n = h[0];
+  for (int l = 1; l < stride; ++l) {
+    const uint32_t m = h[l];
+    if (m > best_n) { best_n = m; best = (uint32_t)l; }
+  }
+  return best;
+}
+
 // The voxel walk of sicp_map_carve (include/sicp.h, "free-space carving", rule 4): from the voxel of the origin o to the voxel
 // of the return p in exactly n = |dvx| + |dvy| + |dvz| steps of one voxel along one axis.  Per axis u = (double)o * (double)
 // inv_leaf and w = (double)p * (double)inv_leaf (exact products), du = w - u, and for an axis that has steps to take
