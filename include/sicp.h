@@ -1548,6 +1548,101 @@ int sicp_map_elevation(sicp_map m, const double center[2], const sicp_map_elevat
                        const sicp_map_elevation_out* out /* nullable */, sicp_handle h /* nullable */, int which,
                        const double qt[7] /* NULL = identity */, sicp_map_elevation_info* info /* nullable */);
 
+/* ---- distance: a truncated Euclidean distance field of the map ------------------------
+ * What Voxblox, FIESTA and nvblox keep for a planner: per voxel of a dense window, how far the nearest occupied voxel is and
+ * which map row that is -- for collision checks of a body with height, for obstacle inflation of a 2-D grid (planar mode), for
+ * "which points of this scan are far from everything the map holds" (the points of a handle's slot), and, through `only`, for
+ * "how far is this place from the nearest voxel of class X".  The map is read and never modified.  leaf and inv_leaf = 1.0f /
+ * (float)leaf_size are the map's; everything after the keying is integer arithmetic, in units of one voxel.  The rules:
+ *  1. Window.  center[3] (finite) is keyed with the grid's float arithmetic, vc = floorf((float)center * inv_leaf) per axis; a
+ *     centre with |vc| >= 2^20 is refused.  nx, ny in 1..1024, nz in 1..256, nx * ny * nz <= 2^24.  x0 = vc_x - nx / 2, y0 =
+ *     vc_y - ny / 2, z0 = vc_z - nz / 2 (integer halves).  Cell (i, j, k), output index c = (k * ny + j) * nx + i, is the voxel
+ *     (x0 + i, y0 + j, z0 + k).  Voxels beyond the key's range are simply never occupied.  info returns x0, y0, z0.
+ *  2. Obstacles.  A map row counts when count >= min_count; when n_ignore > 0, its fullest histogram bin -- sicp_map_extract's
+ *     label: ties to the smallest label, bin 0 can win -- is not in ignore; when n_only > 0, that label is in only; and its
+ *     voxel lies in the window.  An obstacle outside the window does not exist for the call.
+ *  3. Planar mode (planar = 1; nz must be 1).  An obstacle is a column (vx, vy) of the window that holds a counting row with
+ *     lo <= vz <= hi, where lo = floorf((float)z_min * inv_leaf) and hi = floorf((float)z_max * inv_leaf), both clamped to the
+ *     key's range -(2^20 - 1) .. 2^20 - 1 as sicp_map_elevation's are.  The column's row is the smallest such row.  Distances
+ *     are taken in the plane, center[2] is ignored apart from being finite, and z0 = 0.  This is obstacle inflation for a body
+ *     that occupies a height band.  With planar = 0, z_min and z_max are checked and otherwise not read.
+ *  4. The field.  R = max_dist_voxels, 1..64.  For cell c, D = the minimum over the obstacles o of di^2 + dj^2 + dk^2
+ *     (integers; dk = 0 in planar mode).  D <= R^2: dist_sq[c] = D, nearest[c] = the smallest map row among the obstacles at
+ *     exactly D -- a row is its index in sicp_map_get_state's order, ascending key -- and label[c] = that row's fullest bin (0
+ *     on a map without classes).  Otherwise dist_sq[c] = -1, nearest[c] = -1, label[c] = 0.  The truncation is a ball, not a
+ *     cube: with R = 5 an obstacle at offset (3, 4, 0) is found, one at (5, 1, 0) is not.  The metric distance is leaf_size *
+ *     sqrt(dist_sq); the call takes no root.
+ *  5. Points (h non-NULL).  Every one of the slot's n_points in caller order, whatever the handle's mode and device layout.  A
+ *     point that is not finite gets point_cell = -1, point_dist_sq = -1, point_nearest = -1 and point_range_sq the quiet NaN
+ *     0x7fc00000.  A finite one goes through sicp_map_integrate's transform and the grid's key arithmetic, v = floorf(p *
+ *     inv_leaf) per axis in float, without a crop; with a |v| >= 2^20 or outside the window it gets the same values; inside,
+ *     point_cell = c, point_dist_sq = dist_sq[c], point_nearest = nearest[c].  In planar mode only x and y decide (z is not
+ *     looked at).  point_range_sq (3-D mode only): with nearest[c] >= 0 the float squared distance from the moved point to that
+ *     row's centroid (float)(s / count) -- d = p - centroid, (dx dx + dy dy) + dz dz, each operation rounded on its own --
+ *     otherwise that NaN.  The handle is not modified; a cloud that is not yet on the device is prepared as a merge part is.
+ *  6. Contracts.  Every output array is nullable; the cell arrays are nx * ny * nz long, the point arrays n_points.  The call is
+ *     synchronous, on the map's stream.  Integer arithmetic and plain stores, plus one integer atomicMin per row when seeding
+ *     in planar mode: the bytes do not depend on the launch shape.  A cell at least R cells from every face of the window has
+ *     bytes that do not depend on the window (nearest: between calls on equal map state).  An empty map: SICP_OK, every cell
+ *     -1.  info: n_voxels, n_points, n_points_inside (points with point_cell >= 0), x0, y0, z0, nx, ny, nz, n_obstacles
+ *     (obstacle cells of the window), n_reached (cells with dist_sq >= 0), max_dist_sq (the largest reached value, -1 when
+ *     there is none), voxel_size = leaf_size and t_total_ms; the counts come from the device with integer atomics, so they
+ *     are valid without any array.
+ *     SICP_ERR_INVALID_ARGUMENT with nothing written (info included): a NULL map, params or centre; nx or ny outside 1..1024,
+ *     nz outside 1..256, or nx * ny * nz above 2^24; max_dist_voxels outside 1..64; min_count < 1; planar neither 0 nor 1, or
+ *     1 with nz != 1; z_min or z_max NaN, or z_min > z_max; n_ignore or n_only outside 0..SICP_MAP_DISTANCE_MAX_LABELS, or > 0
+ *     on a map with num_classes = 0; a listed label above num_classes; a centre that is not finite or beyond the key's range; a
+ *     pose that is not finite; with a handle, `which` outside the two slots or a handle on another device; point outputs
+ *     without a handle; point_range_sq with planar = 1.  SICP_ERR_NOT_READY: the slot holds no cloud.
+ *     SICP_ERR_OUT_OF_MEMORY: the arena refused (sicp_set_memory_limit applies); nothing is written.  sicp_map_last_error
+ *     names the cause.
+ * Cost: one lane per map row to seed, then one windowed-minimum sweep per axis longer than one cell -- 2 R + 1 integer
+ * min-adds and 16 bytes of traffic a cell each -- and one pass that unpacks.  The field is the lexicographic minimum of
+ * (d^2, row), which is separable: see DESIGN.md 3.20.
+ * Memory: device scratch of 28 bytes a cell (two 8-byte key buffers and the three outputs; 0.47 GB at 2^24 cells), 4 a map
+ * row and 16 a point for the call's duration (the arena keeps it for later calls), and a pinned read-back buffer of 4 bytes a
+ * cell and a point per array asked for -- up to 12 bytes a cell, 201 MB at 2^24 cells -- which stays with the map for the next
+ * call up to 64 MB and is given back at the call's end above that.
+ * Not built: a field kept on the device between calls or updated per scan; a signed field (distance inside obstacles);
+ * gradients; batch and stream forms; the C++ class shims. */
+#define SICP_MAP_DISTANCE_MAX_LABELS 64
+typedef struct sicp_map_distance_params {
+  double  z_min, z_max;        /* planar mode: the height band.  default -inf, +inf; not NaN, z_min <= z_max */
+  int32_t nx, ny, nz;          /* cells: 1..1024, 1..1024, 1..256, product <= 2^24; no default: the caller sets them */
+  int32_t max_dist_voxels;     /* R: the field is truncated at this many voxels.  1..64, default 10 */
+  int32_t min_count;           /* a voxel with fewer points is not seen.  default 1, >= 1 */
+  int32_t planar;              /* 0 (default): the 3-D field; 1: rule 3's field in the plane, nz = 1 */
+  int32_t n_ignore, n_only;    /* 0 (default) .. SICP_MAP_DISTANCE_MAX_LABELS each */
+  uint32_t ignore[SICP_MAP_DISTANCE_MAX_LABELS];  /* a voxel whose fullest histogram bin is one of these does not exist here */
+  uint32_t only[SICP_MAP_DISTANCE_MAX_LABELS];    /* when given, a voxel with any other label does not exist here */
+} sicp_map_distance_params;
+typedef struct sicp_map_distance_out {
+  int32_t* dist_sq;            /* nx * ny * nz each, c = (k * ny + j) * nx + i */
+  int32_t* nearest;
+  uint32_t* label;
+  int32_t* point_cell;         /* n_points each; they need a handle */
+  int32_t* point_dist_sq;
+  int32_t* point_nearest;
+  float* point_range_sq;       /* 3-D mode only */
+} sicp_map_distance_out;
+typedef struct sicp_map_distance_info {
+  int64_t n_voxels;            /* map rows */
+  int64_t n_points;            /* what the slot's caller handed over; 0 without a handle */
+  int64_t n_points_inside;     /* points with point_cell >= 0 */
+  int32_t x0, y0, z0;          /* rule 1: the voxel of output cell (0, 0, 0) */
+  int32_t nx, ny, nz;
+  int32_t n_obstacles;         /* obstacle cells of the window */
+  int32_t n_reached;           /* cells with dist_sq >= 0 */
+  int32_t max_dist_sq;         /* the largest dist_sq; -1 when no cell is reached */
+  int32_t reserved_;
+  double voxel_size;           /* leaf_size: the metric distance is voxel_size * sqrt(dist_sq) */
+  double t_total_ms;           /* host wall clock */
+} sicp_map_distance_info;
+int sicp_default_map_distance_params(sicp_map_distance_params* p);
+int sicp_map_distance(sicp_map m, const double center[3], const sicp_map_distance_params* p,
+                      const sicp_map_distance_out* out /* nullable */, sicp_handle h /* nullable */, int which,
+                      const double qt[7] /* NULL = identity */, sicp_map_distance_info* info /* nullable */);
+
 typedef struct sicp_map_extract_params {
   int32_t min_count;      /* voxels with fewer points are left out.  default 1 */
   int32_t reserved_;

@@ -718,6 +718,69 @@ ELEVATION_CELL_ARRAYS = (("state", np.uint8), ("elevation", np.float32), ("botto
                          ("n_levels", np.int32), ("step", np.float32), ("neighbors", np.uint8), ("cell_class", np.uint8))
 ELEVATION_POINT_ARRAYS = (("point_cell", np.int32), ("point_height", np.float32))
 
+MAP_DISTANCE_MAX_LABELS = 64
+
+
+class SicpMapDistanceParams(C.Structure):
+    """sicp_map_distance_params (include/sicp.h)"""
+    _fields_ = [
+        ("z_min", C.c_double),
+        ("z_max", C.c_double),
+        ("nx", C.c_int32),
+        ("ny", C.c_int32),
+        ("nz", C.c_int32),
+        ("max_dist_voxels", C.c_int32),
+        ("min_count", C.c_int32),
+        ("planar", C.c_int32),
+        ("n_ignore", C.c_int32),
+        ("n_only", C.c_int32),
+        ("ignore", C.c_uint32 * MAP_DISTANCE_MAX_LABELS),
+        ("only", C.c_uint32 * MAP_DISTANCE_MAX_LABELS),
+    ]
+
+
+class SicpMapDistanceOut(C.Structure):
+    """sicp_map_distance_out (include/sicp.h)"""
+    _fields_ = [
+        ("dist_sq", C.POINTER(C.c_int32)),
+        ("nearest", C.POINTER(C.c_int32)),
+        ("label", C.POINTER(C.c_uint32)),
+        ("point_cell", C.POINTER(C.c_int32)),
+        ("point_dist_sq", C.POINTER(C.c_int32)),
+        ("point_nearest", C.POINTER(C.c_int32)),
+        ("point_range_sq", C.POINTER(C.c_float)),
+    ]
+
+
+class SicpMapDistanceInfo(C.Structure):
+    """sicp_map_distance_info (include/sicp.h)"""
+    _fields_ = [
+        ("n_voxels", C.c_int64),
+        ("n_points", C.c_int64),
+        ("n_points_inside", C.c_int64),
+        ("x0", C.c_int32),
+        ("y0", C.c_int32),
+        ("z0", C.c_int32),
+        ("nx", C.c_int32),
+        ("ny", C.c_int32),
+        ("nz", C.c_int32),
+        ("n_obstacles", C.c_int32),
+        ("n_reached", C.c_int32),
+        ("max_dist_sq", C.c_int32),
+        ("reserved_", C.c_int32),
+        ("voxel_size", C.c_double),
+        ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
+
+
+# the cell and point arrays of VoxelMap.distance, in sicp_map_distance_out's order, with their dtypes
+DISTANCE_CELL_ARRAYS = (("dist_sq", np.int32), ("nearest", np.int32), ("label", np.uint32))
+DISTANCE_POINT_ARRAYS = (("point_cell", np.int32), ("point_dist_sq", np.int32), ("point_nearest", np.int32),
+                         ("point_range_sq", np.float32))
+
 
 class SicpMapMergeParams(C.Structure):
     """sicp_map_merge_params (include/sicp.h)"""
@@ -1042,6 +1105,9 @@ def lib():
             "sicp_default_map_elevation_params": [C.POINTER(SicpMapElevationParams)],
             "sicp_map_elevation": [C.c_void_p, _dp, C.POINTER(SicpMapElevationParams), C.POINTER(SicpMapElevationOut), C.c_void_p, C.c_int,
                                    _dp, C.POINTER(SicpMapElevationInfo)],
+            "sicp_default_map_distance_params": [C.POINTER(SicpMapDistanceParams)],
+            "sicp_map_distance": [C.c_void_p, _dp, C.POINTER(SicpMapDistanceParams), C.POINTER(SicpMapDistanceOut), C.c_void_p, C.c_int,
+                                  _dp, C.POINTER(SicpMapDistanceInfo)],
             "sicp_map_extract": [C.c_void_p, C.POINTER(SicpMapExtractParams), C.c_void_p, C.c_int, C.c_int32, _fp, _fp, _fp, _up, _up, _up,
                                  C.POINTER(SicpMapExtractInfo)],
             "sicp_map_set_confusion": [C.c_void_p, C.c_int32, _dp],
@@ -1465,6 +1531,27 @@ def default_map_elevation_params(ignore=(), blocked=(), drivable=(), **overrides
         setattr(p, "n_" + name, len(labels))
     for k, v in overrides.items():
         if not hasattr(p, k) or k in ("ignore", "blocked", "drivable"):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_map_distance_params(ignore=(), only=(), **overrides) -> SicpMapDistanceParams:
+    """sicp_default_map_distance_params (max_dist_voxels 10, min_count 1, the 3-D field, every level in planar mode, no label
+    lists; nx, ny and nz are the caller's), with the labels in `ignore` and `only` (at most MAP_DISTANCE_MAX_LABELS each; they set
+    their counts) and any other field overridden by keyword"""
+    p = SicpMapDistanceParams()
+    st = lib().sicp_default_map_distance_params(C.byref(p))
+    if st != OK:
+        raise SicpError(st, "sicp_default_map_distance_params")
+    for name, given in (("ignore", ignore), ("only", only)):
+        labels = [int(l) for l in given]
+        if len(labels) > MAP_DISTANCE_MAX_LABELS:
+            raise ValueError(f"at most {MAP_DISTANCE_MAX_LABELS} {name} labels")
+        setattr(p, name, (C.c_uint32 * MAP_DISTANCE_MAX_LABELS)(*labels))
+        setattr(p, "n_" + name, len(labels))
+    for k, v in overrides.items():
+        if not hasattr(p, k) or k in ("ignore", "only"):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
@@ -2523,6 +2610,55 @@ class VoxelMap:
         for name, a in arrays.items():
             cells = name in [n for n, _ in ELEVATION_CELL_ARRAYS]
             res[name] = a[:n_cells].reshape(p.height, p.width).copy() if cells else a[:n_points].copy()
+        res["info"] = info.as_dict()
+        return res
+
+    def distance(self, center, shape, params: SicpMapDistanceParams | None = None, engine: "Engine | None" = None, which: int = SOURCE,
+                 qt=None, want=None):
+        """sicp_map_distance: the truncated Euclidean distance field of the map on a window of shape = (nx, ny, nz) voxels about
+        center (x, y, z).  Returns a dict of [nz, ny, nx] arrays "dist_sq" (squared distance to the nearest obstacle voxel in
+        voxels, -1 beyond params.max_dist_voxels), "nearest" (that voxel's row in get_state()'s order, -1) and "label" (its
+        label), and "info" (SicpMapDistanceInfo.as_dict(): x0, y0, z0, n_obstacles, n_reached, max_dist_sq, voxel_size ...).  With
+        an engine also "point_cell", "point_dist_sq", "point_nearest" and, in 3-D mode, "point_range_sq": for every point of its
+        slot `which` (caller order) at pose qt (None: identity) its cell (-1: none), that cell's values, and its squared metric
+        distance to the nearest voxel's centroid (NaN: none).  `want` (None: everything) names the arrays to ask for; the others
+        are not returned.  params (None: the defaults) is not modified; nx, ny and nz are set from shape."""
+        p = SicpMapDistanceParams()
+        C.memmove(C.byref(p), C.byref(params if params is not None else default_map_distance_params()), C.sizeof(p))
+        p.nx, p.ny, p.nz = (int(v) for v in shape)
+        c = np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+        q = None if qt is None else np.ascontiguousarray(qt, dtype=np.float64).reshape(7)
+        point_names = [n for n, _ in DISTANCE_POINT_ARRAYS if not (p.planar and n == "point_range_sq")]
+        names = [n for n, _ in DISTANCE_CELL_ARRAYS] + (point_names if engine is not None else [])
+        if want is not None:
+            unknown = [n for n in want if n not in [a for a, _ in DISTANCE_CELL_ARRAYS + DISTANCE_POINT_ARRAYS]]
+            if unknown:
+                raise KeyError(unknown[0])
+            names = list(want)
+        n_cells = max(p.nx, 0) * max(p.ny, 0) * max(p.nz, 0)
+        n_points = 0
+        if engine is not None and any(n in names for n, _ in DISTANCE_POINT_ARRAYS):
+            try:
+                n_points = engine.cloud_size(which)[0]
+            except SicpError:
+                pass  # (no cloud, a bad slot: the call below refuses and names the cause)
+        out = SicpMapDistanceOut()
+        arrays = {}
+        for name, dt in DISTANCE_CELL_ARRAYS + DISTANCE_POINT_ARRAYS:
+            if name not in names:
+                continue
+            cells = (name, dt) in DISTANCE_CELL_ARRAYS
+            a = np.zeros(max(n_cells if cells else n_points, 1), dtype=dt)
+            arrays[name] = a
+            setattr(out, name, a.ctypes.data_as(dict(SicpMapDistanceOut._fields_)[name]))
+        info = SicpMapDistanceInfo()
+        self._check(lib().sicp_map_distance(self._m, _ptr(c, _dp), C.byref(p), C.byref(out), None if engine is None else engine._h, which,
+                                            _ptr(q, _dp), C.byref(info)), "sicp_map_distance")
+        res = {}
+        for name, a in arrays.items():
+            cells = name in [n for n, _ in DISTANCE_CELL_ARRAYS]
+            # (a cell array is handed over as it is: a window can hold 64 MB an array)
+            res[name] = a[:n_cells].reshape(p.nz, p.ny, p.nx) if cells else a[:n_points].copy()
         res["info"] = info.as_dict()
         return res
 

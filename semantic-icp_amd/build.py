@@ -16,10 +16,10 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libsicp.so")
 OBJDIR = os.path.join(PKG, "build")  # git-ignored and gpurun-ignored: the .so is what travels
 DEVICE_SOURCES = ["knn_kernels.hip", "feature_kernels.hip", "solve_kernels.hip", "build_tree.hip", "bootstrap_kernels.hip",
-                  "pose_cov_kernels.hip", "evaluate_kernels.hip", "merge_kernels.hip", "cluster_kernels.hip", "filter_kernels.hip", "deskew_kernels.hip", "range_kernels.hip", "camera_kernels.hip", "plane_kernels.hip", "ground_kernels.hip", "map_kernels.hip", "map_merge_kernels.hip", "elevation_kernels.hip", "place_kernels.hip", "graph_kernels.hip", "graph_cov_kernels.hip",
+                  "pose_cov_kernels.hip", "evaluate_kernels.hip", "merge_kernels.hip", "cluster_kernels.hip", "filter_kernels.hip", "deskew_kernels.hip", "range_kernels.hip", "camera_kernels.hip", "plane_kernels.hip", "ground_kernels.hip", "map_kernels.hip", "map_merge_kernels.hip", "elevation_kernels.hip", "distance_kernels.hip", "place_kernels.hip", "graph_kernels.hip", "graph_cov_kernels.hip",
                   "prim_kernels.hip"]
 HOST_SOURCES = ["memory.cpp", "clouds.cpp", "stages.cpp", "solve.cpp", "streams.cpp", "bootstrap.cpp", "pose_cov.cpp", "evaluate.cpp",
-                "merge.cpp", "cluster.cpp", "filter.cpp", "deskew.cpp", "range.cpp", "camera.cpp", "plane.cpp", "ground.cpp", "map.cpp", "elevation.cpp", "place.cpp", "graph.cpp", "sicp_api.cpp"]
+                "merge.cpp", "cluster.cpp", "filter.cpp", "deskew.cpp", "range.cpp", "camera.cpp", "plane.cpp", "ground.cpp", "map.cpp", "elevation.cpp", "distance.cpp", "place.cpp", "graph.cpp", "sicp_api.cpp"]
 SOURCES = DEVICE_SOURCES + HOST_SOURCES
 HEADERS = ["kernels.h", "device_geometry.hpp", "lm.hpp", "se3.hpp", "bvh.hpp", "build_tree.h", "fast_log.hpp", "log_table.inc",
            "engine.hpp", "abi_barrier.hpp", "bootstrap.hpp", "job_table.hpp", "voxel_key.hpp", "graph_edge.hpp", "graph_prior.hpp", "graph_cov.hpp", "cell_grid.hpp"]

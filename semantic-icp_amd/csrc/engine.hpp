@@ -18,6 +18,7 @@
 //   ground.cpp    sicp_segment_ground: piecewise-planar ground on a polar grid, height above it
 //   map.cpp       sicp_map_*: the persistent voxel map (integrate, carve, raycast, prune, extract, merge, state)
 //   elevation.cpp sicp_map_elevation: the map as a 2.5-D height grid
+//   distance.cpp  sicp_map_distance: a truncated Euclidean distance field of the map
 //   graph.cpp     sicp_graph_*: the pose graph (nodes, edges, linearise, optimise, blocks of H^-1)
 //   sicp_api.cpp  the remaining C-ABI entry points
 // Every extern "C" entry runs inside abi_guard (abi_barrier.hpp): no exception crosses the boundary.
@@ -1113,6 +1114,11 @@ int map_raycast(sicp_map_ctx* m, const double* qt, const double* sensor_origin, 
 void map_default_elevation_params(sicp_map_elevation_params* p);
 int map_elevation(sicp_map_ctx* m, const double* center, const sicp_map_elevation_params* p, const sicp_map_elevation_out* out,
                   sicp_context* h, int which, const double* qt, sicp_map_elevation_info* info);
+// sicp_map_distance (distance.cpp): argument checks, the window, the init / seed / sweep / final / point kernels queued on the
+// map's stream, one read-back through the map's pinned buffer
+void map_default_distance_params(sicp_map_distance_params* p);
+int map_distance(sicp_map_ctx* m, const double* center, const sicp_map_distance_params* p, const sicp_map_distance_out* out,
+                 sicp_context* h, int which, const double* qt, sicp_map_distance_info* info);
 int map_extract(sicp_map_ctx* m, const sicp_map_extract_params* p, sicp_context* dst, int dst_which, int32_t capacity, float* x,
                 float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info);
 int map_set_confusion(sicp_map_ctx* m, int32_t C, const double* cm);

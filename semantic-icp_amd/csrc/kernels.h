@@ -1024,6 +1024,50 @@ hipError_t launch_elevation_segments(const MapElevationArgs& a, hipStream_t st);
 hipError_t launch_elevation_cells(const MapElevationArgs& a, hipStream_t st);     // rule 5's arrays of the occupied cells
 hipError_t launch_elevation_stencil(const MapElevationArgs& a, hipStream_t st);   // step, neighbors, cls, ctl[kElevClass ..]
 hipError_t launch_elevation_points(const MapElevationArgs& a, hipStream_t st);    // point_cell, point_height of the finite points
+// the truncated distance field (sicp_map_distance; distance_kernels.hip, driver: distance.cpp).  A cell's state is one packed
+// 64-bit key (d^2 << 32) | map row: an obstacle cell is seeded with (0, row), every other cell with kDistNone, whose d^2 field
+// is above every reachable sum and survives three additions of up to 64^2.  A sweep along an axis replaces a cell's key by the
+// minimum over s in -R..R of key[cell + s along the axis] + (s^2 << 32), cells outside the window taking no part; an addition
+// to the high field keeps the order of the packed keys, so after the sweeps along x, y and z the key is the lexicographic
+// minimum of (d^2, row) over the cube, and the test d^2 <= R^2 makes it the ball's.  Integer arithmetic, plain stores (one
+// 64-bit atomicMin per row when seeding a column in planar mode): the bytes do not depend on the launch shape.
+constexpr int kDistMaxLabels = 64;  // SICP_MAP_DISTANCE_MAX_LABELS
+constexpr int kDistMaxR = 64;
+constexpr unsigned long long kDistNone = (0x40000000ull << 32) | 0xffffffffull;
+// the control words: obstacle cells, reached cells, the largest d^2 + 1 (0: none), points inside the window
+enum { kDistObstacles = 0, kDistReached = 1, kDistMaxPlus1 = 2, kDistInside = 3, kDistCtl = 4 };
+constexpr int kDistLineTile = 256;  // the x sweep: cells of a line per workgroup, R of halo on either side in LDS
+constexpr int kDistTileX = 32;      // the y and z sweeps: a workgroup's tile is kDistTileX lanes along x (256 contiguous bytes a
+constexpr int kDistTileA = 64;      // row) by kDistTileA cells along the axis plus 2 R of halo: (64 + 2 R) * 256 bytes of LDS,
+                                    // 48 KiB at R = 64 (three workgroups a CU), 21 KiB at R = 10
+struct MapDistanceArgs {
+  MapRows rows;                    // hist: nullptr when the map keeps no labels
+  int n_map, stride;
+  int nx, ny, nz, x0, y0, z0;      // the window (rule 1)
+  int planar, lo, hi;              // rule 3's band
+  int R;
+  long long min_count;
+  int n_ignore, n_only;
+  uint32_t ignore[kDistMaxLabels], only[kDistMaxLabels];
+  unsigned long long* key;         // [cells] the buffer the seeds go to
+  uint32_t* row_label;             // [n_map] the fullest bin of the obstacle rows (nullptr without labels)
+  int* ctl;                        // kDistCtl words, zeroed
+  int *dist_sq, *nearest;          // [cells]
+  uint32_t* label;
+  const float *px, *py, *pz;       // the slot's finite points in caller order (Cloud::rx ...)
+  const int* keep;                 // [n] their caller indices; nullptr when nothing was dropped
+  double M[12];
+  int n, n_caller;
+  float inv_leaf;
+  int *point_cell, *point_dist_sq, *point_nearest;  // [n_caller]
+  float* point_range_sq;
+};
+hipError_t launch_distance_init(const MapDistanceArgs& a, hipStream_t st);    // every key kDistNone; every point -1 / NaN
+hipError_t launch_distance_seed(const MapDistanceArgs& a, hipStream_t st);    // the obstacle cells' keys, row_label, ctl[kDistObstacles]
+// one sweep, src -> dst: axis 0 along x, 1 along y, 2 along z
+hipError_t launch_distance_sweep(const MapDistanceArgs& a, int axis, const unsigned long long* src, unsigned long long* dst, hipStream_t st);
+hipError_t launch_distance_final(const MapDistanceArgs& a, const unsigned long long* src, hipStream_t st);  // dist_sq, nearest, label, ctl
+hipError_t launch_distance_points(const MapDistanceArgs& a, hipStream_t st);  // the point arrays of the finite points, ctl[kDistInside]
 // label fusion through the confusion matrix (sicp_map_extract_fused, sicp_map_fused_labels).  logcm[r * C + s] = log cm[r][s]
 // (observed label r + 1, class s + 1; -inf for a zero entry).  A histogram row's score of class s is the sum over its
 // non-zero bins r = 1..C, ascending, of (double)h[r] * logcm[r - 1][s - 1], each product and each sum rounded once.  An item

@@ -1061,6 +1061,19 @@ int sicp_map_elevation(sicp_map m, const double center[2], const sicp_map_elevat
   return abi_guard(m, [&]() -> int { return map_elevation(m, center, p, out, h, which, qt, info); });
 }
 
+int sicp_default_map_distance_params(sicp_map_distance_params* p) {
+  return abi_guard([&]() -> int {
+    if (!p) return SICP_ERR_INVALID_ARGUMENT;
+    map_default_distance_params(p);
+    return SICP_OK;
+  });
+}
+
+int sicp_map_distance(sicp_map m, const double center[3], const sicp_map_distance_params* p, const sicp_map_distance_out* out,
+                      sicp_handle h, int which, const double qt[7], sicp_map_distance_info* info) {
+  return abi_guard(m, [&]() -> int { return map_distance(m, center, p, out, h, which, qt, info); });
+}
+
 int sicp_map_extract(sicp_map m, const sicp_map_extract_params* p, sicp_handle dst, int dst_which, int32_t capacity, float* x,
                      float* y, float* z, uint32_t* label, uint32_t* count, uint32_t* hist, sicp_map_extract_info* info) {
   return abi_guard(m, [&]() -> int {
